@@ -9,6 +9,11 @@ slowest-rank clock use torch.distributed, the training extra's gradient exchange
 
 Prints ONE compact JSON line (rank 0, < 4 KB: compact_line()); the full result object goes to bench_full.json (write_full()).
 `--gpus N` with no launcher around it starts its own N ranks (launch_ranks()).
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line.  Everything else it can measure or check (clock and
+power under load, the host-buffer rate, the other scorer arithmetic, recall vs brute force, the CPU oracle baseline and its
+comparison, the other BASELINE configurations, training, Deep-Retrieval, the latency timers) runs only with `--full`; the
+per-extra switches below apply there.  `--dump-outputs DIR` writes what the last timed step returned (dump_outputs()).
 """
 import argparse
 import ctypes as C
@@ -145,9 +150,18 @@ def parse():
     ap.add_argument("--jtm-rows", type=int, default=4, help="training rows per item of the full JTM.optimize extra")
     ap.add_argument("--trained-recall-steps", type=int, default=6000, help="TDMTrainer steps (1024 tree-consistent targets each) before recall@topk vs brute force is measured again on the 1M-item tree; 0 = skip")
     ap.add_argument("--otm64", type=int, default=1, help="also time OTM serving and one OTM training iteration in the reference's fp64 (BASELINE configs[2]); 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra measurement and check (the switches above); without it only the headline steps run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the ids, scores and counts the last timed step returned (a fixed, seeded sample of its users) as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.big is not None:
         a.small = a.big
+    if not a.full:                # a plain run: the headline steps only
+        a.cpu_users = a.recall_users = a.host_buffer_steps = a.trained_recall_steps = 0
+        a.train = a.small = a.dr = a.other_scorer = a.diverse = a.long_history = a.jtm_full = a.otm64 = 0
     from dismember_amd import conf as dmconf
     a.params = dmconf.task_params("TDMTrainDeepModel", a.conf)
     a.embed = a.embed or a.params["embed_size"]
@@ -458,6 +472,29 @@ def write_full(full):
     return name
 
 
+DUMP_USERS = 16384
+DUMP_BYTES = 48_000_000
+
+
+def dump_outputs(out_dir, eng, U, topk, d_ids, d_sc, d_cnt):
+    """--dump-outputs: what the last timed step handed back (dm_tdm_beam_search_dev's device buffers: item ids [U, topk], scores
+    [U, topk], counts [U]) for a fixed, seeded sample of the step's users, so that two builds run with the same arguments can be
+    compared output for output.  Files: users.npy (row indices of the sample), item_ids.npy, scores.npy, counts.npy; integers as
+    float64 (exact), scores as the float32 the path computes; at most DUMP_BYTES in all."""
+    from dismember_amd import synth
+    ids = np.empty((U, topk), np.int32)
+    sc = np.empty((U, topk), np.float32)
+    cnt = np.empty(U, np.int32)
+    eng.d2h(ids, d_ids); eng.d2h(sc, d_sc); eng.d2h(cnt, d_cnt)
+    n = max(1, min(U, DUMP_USERS, DUMP_BYTES // (12 * topk + 16)))
+    pick = np.sort(np.random.default_rng(synth.SEED + 4242).choice(U, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "users.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "item_ids.npy"), ids[pick].astype(np.float64))
+    np.save(os.path.join(out_dir, "scores.npy"), sc[pick])
+    np.save(os.path.join(out_dir, "counts.npy"), cnt[pick].astype(np.float64))
+
+
 def launch_ranks(a):
     """`python bench.py --gpus N` as typed (no torchrun around it): start N ranks of this same command, one per GPU, with the launcher
     environment init_distributed() reads; rank 0 prints the line.  Fails loudly when the node has fewer than N devices (unless
@@ -593,10 +630,12 @@ def main():
     n_launch, kernel_ms = eng.timing_get_kind(0)                # the search kernel proper (HIP events on the library's stream)
     n_defer, defer_ms = eng.timing_get_kind(1)                  # second pass over deferred users (one-wave kernel only)
     kern_name = eng.last_beam_kernel()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng, U, a.topk, d_ids, d_sc, d_cnt)
     # the clock the kernel actually runs at (it holds the package at its power limit): sampled over a SECOND, untimed run of the same steps
     # so that the sampler's host thread cannot touch the timed region
     clk_mhz = pw_w = None
-    if rank == 0:
+    if rank == 0 and a.full:
         with ClockSampler(int(os.environ.get("DM_FORCE_DEVICE", local))) as cs_:
             for i in range(max(a.steps, 12)):
                 eng.tdm_beam_search_dev(d_seqs[i % NSH], U, L, a.beam, a.topk, d_ids, d_sc, d_cnt)
@@ -606,12 +645,13 @@ def main():
     rows = sum(shard_rows[i % NSH] for i in range(a.steps)) / float(a.steps)     # scored (node, user) rows per step, averaged over the timed steps
 
     # results of shard 0 (recall, the CPU oracle's comparison and the other-scorer comparison all use shard 0)
-    eng.tdm_beam_search_dev(d_seq, U, L, a.beam, a.topk, d_ids, d_sc, d_cnt)
-    sync()
-    ids = np.empty((U, a.topk), np.int32)
-    sc = np.empty((U, a.topk), np.float32)
-    cnt = np.empty(U, np.int32)
-    eng.d2h(ids, d_ids); eng.d2h(sc, d_sc); eng.d2h(cnt, d_cnt)
+    if a.full:
+        eng.tdm_beam_search_dev(d_seq, U, L, a.beam, a.topk, d_ids, d_sc, d_cnt)
+        sync()
+        ids = np.empty((U, a.topk), np.int32)
+        sc = np.empty((U, a.topk), np.float32)
+        cnt = np.empty(U, np.int32)
+        eng.d2h(ids, d_ids); eng.d2h(sc, d_sc); eng.d2h(cnt, d_cnt)
 
     # the same step through the HOST-buffer entry point (dm_tdm_beam_search: the request goes up and ids / scores / counts come down
     # over PCIe inside the call) — reported beside `value`, never as `value`

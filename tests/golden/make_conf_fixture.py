@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Fixture generator (BUILD container only; needs /root/reference): the KEY LISTS of the reference's configs/*.conf per
 prefix, read with the product's own reader (dismember_amd/conf.py), and the typed values of the keys the hot path consumes.
-Output: tests/golden/conf_keys.json.  No reference file travels: the fixture holds key names and a handful of scalar values."""
+Output: tests/golden/conf_keys.json (key names and a handful of scalar values) and tests/golden/reference_configs/ (the four
+settings files, copied verbatim, which tests/test_conf.py reads back)."""
 import json
 import os
+import shutil
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -21,8 +23,10 @@ HOT = ["seq_len", "embed_size", "beam_size", "topk_number", "layer_negative_coun
 
 def main():
     out = {}
+    os.makedirs(os.path.join(HERE, "reference_configs"), exist_ok=True)
     for name, prefixes in FILES.items():
         path = os.path.join(REF, "configs", name + ".conf")
+        shutil.copyfile(path, os.path.join(HERE, "reference_configs", name + ".conf"))
         out[name] = {}
         for p in prefixes:
             c = conf.read_conf(path, p)

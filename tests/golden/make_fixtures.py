@@ -11,6 +11,7 @@ tests can run on a box that has no /root/reference:
   data/otm/example_model.bin   -> din_f64.npy    (same layout, f64; OTM)
   data/otm/example_mapping.txt -> otm_mapping.npy (item -> leaf node id)
   data/example_data.csv        -> example_data.npz (interactions in time order + distinct items with category)
+                                  and example_data.csv.xz (the file itself, xz-compressed, for the tree-initialisation test)
   data/dr/example_mapping.bin  -> dr_mapping.npz  (item, id, paths[J][D]; Deep-Retrieval)
 
 Formats decoded here:
@@ -222,6 +223,10 @@ def main():
             seen.add(it); ui.append(it); uc.append(c)
     np.savez_compressed(os.path.join(OUT, "example_data.npz"), user=np.array(us, np.int16)[order],
                         item=np.array(its, np.int16)[order], uniq_item=np.array(ui, np.int16), uniq_cat=np.array(uc, np.int8))
+    import lzma
+    with open(os.path.join(REF, "data/example_data.csv"), "rb") as f_in, \
+            lzma.open(os.path.join(OUT, "example_data.csv.xz"), "wb", preset=9 | lzma.PRESET_EXTREME) as f_out:
+        f_out.write(f_in.read())
     dr = read_dr_mapping(os.path.join(REF, "data/dr/example_mapping.bin"))
     assert dr["paths"].shape == (3325, 2, 3) and dr["paths"].max() < 100
     np.savez_compressed(os.path.join(OUT, "dr_mapping.npz"), **dr)

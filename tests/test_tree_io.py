@@ -2,6 +2,7 @@
 bundled tree file, known answers for the integer logic."""
 import hashlib
 import json
+import lzma
 import os
 
 import numpy as np
@@ -83,9 +84,9 @@ def test_read_interactions_and_sequences():
     assert tree_io.user_sequences(s) == {1: [11, 10], 2: [10]}
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/example_data.csv"), reason="needs the reference's bundled csv")
 def test_pipeline_on_bundled_csv():
-    lines = open("/root/reference/data/example_data.csv").read().splitlines()
+    with lzma.open(os.path.join(GOLD, "example_data.csv.xz"), "rt") as f:         # the reference's data/example_data.csv, verbatim
+        lines = f.read().splitlines()
     b, ids, codes, split = tree_io.initialize_tree(lines, 10, 2, True, 0.8)      # configs/tdm.conf
     r = tree_io.read_tree_bytes(b)
     assert len(ids) == 3325 and r["max_level"] == 12 and len(r["leaf_ids"]) == 3325
