@@ -46,6 +46,16 @@ class SearchOpts(C.Structure):
     _fields_ = [("beam", C.c_int), ("topk", C.c_int), ("use_mask", C.c_int), ("widen_consumed", C.c_int)]
 
 
+class ClusterTrace(C.Structure):
+    _fields_ = [("node_cap", C.c_int64), ("level_cap", C.c_int32), ("centroid0", f32p), ("seeds", i32p), ("iters", i32p),
+                ("distortion", C.POINTER(C.c_double)), ("dist", f32p), ("perm", i32p)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [("levels_streamed", C.c_int32), ("levels_lds", C.c_int32), ("lloyd_passes", C.c_int64), ("bytes_streamed", C.c_int64),
+                ("seeding_s", C.c_double), ("lloyd_s", C.c_double), ("split_s", C.c_double), ("lds_s", C.c_double)]
+
+
 # name -> (restype, argtypes); also the list of symbols include/dismember_hip.h declares
 SIGNATURES = {
     "dm_version": (C.c_int, []),
@@ -155,6 +165,11 @@ SIGNATURES = {
     "dm_last_beam_kernel": (C.c_char_p, [C.c_void_p]),
     "dm_kernel_timing_get_kind": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "dm_last_scored_rows": (C.c_int, [C.c_void_p, i64p]),
+    "dm_cluster_tree": (C.c_int, [C.c_void_p, f32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, i32p,
+                                  C.POINTER(ClusterTrace), C.POINTER(ClusterStats)]),
+    "dm_cluster_tree_model": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_uint64, i32p,
+                                        C.POINTER(ClusterTrace), C.POINTER(ClusterStats)]),
+    "dm_get_leaf_embeddings": (C.c_int, [C.c_void_p, i32p, C.c_int64, f32p]),
 }
 
 

@@ -138,6 +138,70 @@ class Engine:
         """TDM.saveModel (T/model/TDM.scala:32-41): weights + index in one flat file (dm_save_model)."""
         self._chk(N.lib().dm_save_model(self._h, os.fsencode(path)))
 
+    @staticmethod
+    def checkpoint_leaf_ids(path):
+        """(item ids, leaf codes) of a dm_save_model checkpoint (layout: csrc/checkpoint.hip.inc); empty when it holds no id map."""
+        import struct
+        with open(path, "rb") as f:
+            hd = f.read(72)
+            _, _, _, _, has_tree, has_ids, _, _ = struct.unpack("<8i", hd[8:40])
+            _, _, n_nodes, n_leaf = struct.unpack("<4q", hd[40:72])
+            if not has_ids:
+                return np.zeros(0, np.int32), np.zeros(0, np.int32)
+            if has_tree:
+                f.seek(72 + 8 * n_nodes + (n_nodes + 7) // 8 * 8)
+            both = np.frombuffer(f.read(8 * n_leaf), dtype="<i4")
+        return both[:n_leaf].astype(np.int32), both[n_leaf:].astype(np.int32)
+
+    # ---- TDMClusterTree (csrc/cluster.hip.inc)
+    def leaf_embeddings(self, item_ids):
+        """dm_get_leaf_embeddings: the loaded table's rows at the items' current leaf codes, [n, E] float32."""
+        ids = _i32(item_ids).ravel()
+        if self.E is None:
+            raise DismemberError(-3, "leaf_embeddings: no weights loaded through this Engine")
+        out = np.empty((ids.size, int(self.E)), np.float32)
+        self._chk(N.lib().dm_get_leaf_embeddings(self._h, _p(ids, N.i32p), ids.size, _p(out, N.f32p)))
+        return out
+
+    def cluster_tree(self, embeddings=None, item_ids=None, restarts=10, max_iter=100, tol=1e-4, seed=0, trace=False):
+        """dm_cluster_tree (embeddings: [n, E] float32 on the host) or dm_cluster_tree_model (item_ids: the rows of the loaded
+        table at the items' leaf codes, gathered on the device) -> (codes [n] before flattenLeaves, stats dict, trace dict | None).
+        max_level = ceil(log2 n); the trace arrays are indexed as include/dismember_hip.h says."""
+        if (embeddings is None) == (item_ids is None):
+            raise ValueError("cluster_tree: give either embeddings or item_ids")
+        if embeddings is not None:
+            x = np.ascontiguousarray(embeddings, dtype=np.float32)
+            if x.ndim != 2:
+                raise ValueError("cluster_tree: embeddings must be [n, E]")
+            n, E = x.shape
+        else:
+            ids = _i32(item_ids).ravel()
+            n, E = ids.size, int(self.E or 0)
+        codes = np.empty(max(n, 1), np.int32)
+        stats = N.ClusterStats()
+        tr, bufs = None, None
+        if trace:
+            max_level = max(0, int(n - 1).bit_length()) if n > 1 else 0
+            nodes = (1 << max_level) - 1
+            bufs = dict(centroid0=np.full((max(nodes, 1), max(E, 1)), np.nan, np.float32), seeds=np.full((max(nodes, 1), 2), -1, np.int32),
+                        iters=np.zeros(max(nodes, 1), np.int32), distortion=np.full(max(nodes, 1), np.nan, np.float64),
+                        dist=np.full((max(max_level, 1), max(n, 1)), np.nan, np.float32), perm=np.zeros(max(n, 1), np.int32))
+            tr = N.ClusterTrace(nodes, max_level, _p(bufs["centroid0"], N.f32p), _p(bufs["seeds"], N.i32p), _p(bufs["iters"], N.i32p),
+                                bufs["distortion"].ctypes.data_as(C.POINTER(C.c_double)), _p(bufs["dist"], N.f32p), _p(bufs["perm"], N.i32p))
+        trp = C.byref(tr) if tr is not None else None
+        if embeddings is not None:
+            rc = N.lib().dm_cluster_tree(self._h, _p(x, N.f32p), n, E, int(restarts), int(max_iter), float(tol), int(seed) & (2 ** 64 - 1),
+                                         _p(codes, N.i32p), trp, C.byref(stats))
+        else:
+            rc = N.lib().dm_cluster_tree_model(self._h, _p(ids, N.i32p), n, int(restarts), int(max_iter), float(tol), int(seed) & (2 ** 64 - 1),
+                                               _p(codes, N.i32p), trp, C.byref(stats))
+        self._chk(rc)
+        st = {k: getattr(stats, k) for k, _ in N.ClusterStats._fields_}
+        if bufs is not None:
+            bufs.update(max_level=max_level, centroid0=bufs["centroid0"][:nodes], seeds=bufs["seeds"][:nodes], iters=bufs["iters"][:nodes],
+                        distortion=bufs["distortion"][:nodes], dist=bufs["dist"][:max_level], perm=bufs["perm"][:n])
+        return codes[:n], st, bufs
+
     def load_model(self, path):
         """TDM.loadModel: replaces the handle's tree, id maps and weights with the checkpoint's."""
         self._chk(N.lib().dm_load_model(self._h, os.fsencode(path)))

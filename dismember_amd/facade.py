@@ -47,9 +47,16 @@ class TDM:
         out = [list(zip(ids[u, :cnt[u]].tolist(), prob[u, :cnt[u]].tolist())) for u in range(ids.shape[0])]
         return out[0] if single else out
 
-    def save_model(self, model_path):
-        """TDM.saveModel (TDM.scala:32-41): one flat checkpoint instead of a Java-serialised module graph."""
+    def save_model(self, model_path, embed_path=None):
+        """TDM.saveModel (TDM.scala:32-41): one flat checkpoint instead of a Java-serialised module graph; with `embed_path` also the
+        leaf embeddings file TDMClusterTree reads (Serialization.saveEmbeddings, tdm/.../utils/Serialization.scala:15-58): item ids
+        ascending, one line `id, v1, ..., vE` each."""
         self.engine.save_model(model_path)
+        if embed_path is not None:
+            from .cluster import write_embeddings
+            ids, _ = self.engine.checkpoint_leaf_ids(model_path)
+            ids = np.sort(ids)
+            write_embeddings(embed_path, ids, self.engine.leaf_embeddings(ids))
 
     @classmethod
     def load_model(cls, engine, path, model_name="din"):

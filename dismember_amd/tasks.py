@@ -9,9 +9,11 @@ Each function is the body of the reference's `CommandApp` of the same name (exam
 the conf file is read by dismember_amd.conf (same keys, same defaults, same "failed to find <key>" stop), the steps are the
 reference's, and every hot step is a library call — tree index + DIN weights in HBM, level-wise negative sampling, forward /
 backward / Adam, the batched evaluator, `JTM.optimize` in one call.  What is NOT carried over: Java serialisation (the model file
-is `dm_save_model`'s flat checkpoint), HDFS paths, the DeepFM graph and the k-means `TDMClusterTree` (out of scope).
+is `dm_save_model`'s flat checkpoint), HDFS paths, the DeepFM graph and spectral clustering in `TDMClusterTree`.
 
   tdm_initialize_tree   tdm/TDMInitializeTree.scala:14-48  -> TreeInit.generate (tdm/.../tree/TreeInit.scala:33-66)
+  tdm_cluster_tree      tdm/TDMClusterTree.scala           -> RecursiveCluster.run on the device (dismember_amd/cluster.py; also
+                        `python -m dismember_amd.cluster --tdmConfFile FILE`; `main` here still answers 3 for the task name)
   tdm_train_deep_model  tdm/TDMTrainDeepModel.scala:20-83  -> LocalDataSet + LocalOptimizer.optimize (tdm/.../optim/LocalOptimizer.scala:58-126),
                         TDM.saveModel (:32-41), package.recommend (tdm/package.scala:114-124)
   jtm_tree_learning     jtm/JTMTreeLearning.scala:17-48    -> JTM.optimize (jtm/.../optim/JTM.scala:26-73), TreeUtil.writeTree
@@ -139,7 +141,7 @@ def tdm_train_deep_model(conf_path, quiet=True, engine=None, seed=2024, max_iter
             order = rng.permutation(len(ttgt)); pos, count, t_epoch = 0, 0, 0.0
     _mkdir_for(p["model_path"], p["embed_path"])
     tdm = TDM(eng, p["deep_model"])
-    tdm.save_model(p["model_path"])
+    tdm.save_model(p["model_path"], p["embed_path"])
     out = dict(losses=losses, eval=evals, params=p, engine=eng)
     query = [0, 0, 2126, 204, 3257, 3439, 996, 1681, 3438, 1882][-L:] if L <= 10 else [0] * (L - 10) + [0, 0, 2126, 204, 3257, 3439, 996, 1681, 3438, 1882]
     rec = tdm.recommend(query, 3, 20)
@@ -322,6 +324,9 @@ def otm_construct_tree(conf_path, quiet=True, engine=None):
         print("OTM tree construction time: %.4fs" % dt)
     od.save_mapping(p["mapping_path"], result)
     return dict(mapping=result, old_mapping=mapping, seconds=dt, params=p, engine=eng)
+
+
+from .cluster import tdm_cluster_tree  # noqa: E402,F401  (reachable as tasks.tdm_cluster_tree; not in TASK_FUNCS: see README.md)
 
 
 TASK_FUNCS = {

@@ -402,4 +402,20 @@ class JTM {
   std::vector<int64_t> rowOff_;
 };
 
+// RecursiveCluster.run (tdm/.../cluster/RecursiveCluster.scala:34-60): embeddings [n x E] row-major -> leaf code per row (before
+// TreeBuilder.flattenLeaves); clusterIterNum is the restart count.  The overload without embeddings clusters the loaded model's rows
+// at the items' current leaf codes (gathered on the device).
+inline std::vector<int32_t> clusterTree(Engine &e, const std::vector<float> &embeddings, int64_t n, int E, int clusterIterNum = 10,
+                                        uint64_t seed = 2024, dm_cluster_stats *stats = nullptr) {
+  std::vector<int32_t> codes((size_t)(n > 0 ? n : 0));
+  e.check(dm_cluster_tree(e.handle(), embeddings.data(), n, E, clusterIterNum, 100, 1e-4, seed, codes.data(), nullptr, stats));
+  return codes;
+}
+inline std::vector<int32_t> clusterTree(Engine &e, const std::vector<int32_t> &itemIds, int clusterIterNum = 10, uint64_t seed = 2024,
+                                        dm_cluster_stats *stats = nullptr) {
+  std::vector<int32_t> codes(itemIds.size());
+  e.check(dm_cluster_tree_model(e.handle(), itemIds.data(), (int64_t)itemIds.size(), clusterIterNum, 100, 1e-4, seed, codes.data(), nullptr, stats));
+  return codes;
+}
+
 }  // namespace dm

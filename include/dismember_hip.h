@@ -497,6 +497,47 @@ int dm_load_weights_din_dev(dm_handle_t h, int E, int64_t num_index, float *d_co
 /* the same for an fp64 model (dm_load_weights_din(DM_F64): the reference's OTM scorer is DIN[Double]) */
 int dm_load_weights_din_dev_f64(dm_handle_t h, int E, int64_t num_index, double *d_compact, int64_t n_elems);
 
+/* ---- TDMClusterTree: the balanced recursive 2-means tree rebuild ----------------
+ * RecursiveCluster.run (T/cluster/RecursiveCluster.scala:34-60,141-198, ForkJoinProcess.scala): every node fits 2-means on its
+ * items' embeddings (k-means++ seeds, Lloyd, `restarts` independent restarts, the lowest distortion wins — smile's
+ * PartitionClustering.run), takes every item's squared distance to centroid 0 — here the cluster seeded FIRST; smile's order is as
+ * arbitrary — and sends the n/2 nearest to child 2c+1 and the other n - n/2 to 2c+2, down to single items.  A node of two items
+ * puts its first left and its second right.  The reference is unseeded; here the result is a pure function of (embeddings, seed).
+ * Lloyd's stopping rule, the tie rules and the empty-cluster rule are stated in dismember_amd/csrc/cluster.hip.inc and restated
+ * in tests/cluster_ref.py.  max_level = ceil(log2 n); leaf codes come out on levels max_level - 1 and max_level (before
+ * TreeBuilder.flattenLeaves).  1 <= n <= 2^30, 1 <= E <= 128, 1 <= restarts <= 32.  n = 1 gives code 0. */
+
+/* Optional diagnostics, host buffers owned by the caller (any pointer may be NULL).  Per-node arrays are indexed by the internal
+ * node's code c < 2^max_level - 1; nodes that were never fitted (fewer than three items) keep NaN / -1 / 0. */
+typedef struct {
+  int64_t node_cap;    /* entries the per-node arrays hold: >= 2^max_level - 1 */
+  int32_t level_cap;   /* rows `dist` holds: >= max_level */
+  float *centroid0;    /* [node_cap, E] centroid 0 of the winning restart */
+  int32_t *seeds;      /* [node_cap, 2] row numbers (into the embeddings given) of the winning restart's two seeds */
+  int32_t *iters;      /* [node_cap] its Lloyd iterations */
+  double *distortion;  /* [node_cap] its final distortion */
+  float *dist;         /* [level_cap, n] by row: the distance the item had at the node of that level where it was split; NaN where
+                          it was a leaf already or the node had two items */
+  int32_t *perm;       /* [n] rows in final leaf order: the items of node (level l, index j) are one contiguous run of it */
+} dm_cluster_trace;
+
+typedef struct {
+  int32_t levels_streamed, levels_lds;  /* levels split by passes over the table / finished inside the LDS */
+  int64_t lloyd_passes, bytes_streamed; /* Lloyd iterations summed over the streamed levels; bytes of embeddings read by all passes */
+  double seeding_s, lloyd_s, split_s, lds_s; /* wall seconds per phase */
+} dm_cluster_stats;
+
+/* emb: host, [n, E] row-major.  codes_out [n]: leaf code of row i. */
+int dm_cluster_tree(dm_handle_t h, const float *emb, int64_t n, int E, int restarts, int max_iter, double tol, uint64_t seed,
+                    int32_t *codes_out, const dm_cluster_trace *trace, dm_cluster_stats *stats);
+/* The embeddings are the loaded DIN table's rows at the items' CURRENT leaf codes in the loaded tree (what TDM.saveModel writes to
+ * embed_path, T/utils/Serialization.scala:15-58), gathered on the device.  DM_ERR_STATE without a tree or weights, DM_ERR_INVALID
+ * for an id that is not a leaf of the tree. */
+int dm_cluster_tree_model(dm_handle_t h, const int32_t *item_ids, int64_t n, int restarts, int max_iter, double tol, uint64_t seed,
+                          int32_t *codes_out, const dm_cluster_trace *trace, dm_cluster_stats *stats);
+/* the same rows read back: out [n, E] with E the model's embed size */
+int dm_get_leaf_embeddings(dm_handle_t h, const int32_t *item_ids, int64_t n, float *out);
+
 /* ---- measurement ----------------------------------------------------------- */
 /* HIP events on the handle's stream around every beam-search kernel launched since the last
  * reset: number of launches and their summed duration. */

@@ -34,6 +34,19 @@ STRUCTS = {      # option structs flattened into scalars: (field, C type) in dec
     "dm_otm_train_opts": [("beam", "int"), ("leaf_level", "int"), ("use_mask", "int"), ("target_mode", "int")],
     "dm_sample_opts": [("start_level", "int"), ("with_prob", "int"), ("tolerance", "int"), ("use_mask", "int"), ("seed", "uint64_t")],
 }
+# structs of optional host OUTPUT arrays plus capacity scalars: (field, C type, is pointer, minimum length | None); flattened like STRUCTS,
+# the arrays pinned (null allowed) and copied back
+PTR_STRUCTS = {
+    "dm_cluster_trace": [("node_cap", "int64_t", False, None), ("level_cap", "int32_t", False, None),
+                         ("centroid0", "float", True, "trace_node_cap * {E}"), ("seeds", "int32_t", True, "trace_node_cap * 2"),
+                         ("iters", "int32_t", True, "trace_node_cap"), ("distortion", "double", True, "trace_node_cap"),
+                         ("dist", "float", True, "trace_level_cap * n"), ("perm", "int32_t", True, "n")],
+}
+PTR_STRUCT_E = {"dm_cluster_tree": "E", "dm_cluster_tree_model": "128"}     # {E} of the extents: the argument, or the library's largest
+# plain result structs: returned through an Array[Double] holding the fields in declaration order (null allowed)
+OUT_STRUCTS = {
+    "dm_cluster_stats": ["levels_streamed", "levels_lds", "lloyd_passes", "bytes_streamed", "seeding_s", "lloyd_s", "split_s", "lds_s"],
+}
 SCALAR = {"int": ("jint", "Int"), "int32_t": ("jint", "Int"), "int64_t": ("jlong", "Long"), "uint64_t": ("jlong", "Long"),
           "size_t": ("jlong", "Long"), "float": ("jfloat", "Float"), "double": ("jdouble", "Double")}
 ARRAY = {"int32_t": ("jintArray", "jint", "Array[Int]"), "int": ("jintArray", "jint", "Array[Int]"),
@@ -102,6 +115,9 @@ EXTENTS = {
     "dm_tdm_sample_train_batch_dev": {"neg_counts": "n_counts", "n_rows": "1"},
     "dm_dr_load_path_items": {"item_off": "n_paths + 1"},
     "dm_allreduce_grads": {"hs": "n"},
+    "dm_cluster_tree": {"emb": "n * E", "codes_out": "n", "stats": "8"},
+    "dm_cluster_tree_model": {"item_ids": "n", "codes_out": "n", "stats": "8"},
+    "dm_get_leaf_embeddings": {"item_ids": "n"},
 }
 
 
@@ -160,6 +176,7 @@ def gen(protos):
     c, sc = [], []
     for meth, cname, ret, args, voids in expand(protos):
         jparams, sparams, pre, post, call = [], [], [], [], []
+        after, xchecks = [], []    # statements between the call and the releases; extent checks of flattened struct arrays
         pinned = []            # host arrays acquired from the JVM: a NULL for a non-null array means a pending OutOfMemoryError
         handle_expr, comm_expr = "0", None
         for i, a in enumerate(args):
@@ -184,6 +201,31 @@ def gen(protos):
                     jparams.append("%s %s_%s" % (SCALAR[ct][0], an, f)); sparams.append("%s%s: %s" % (an, f.title().replace("_", ""), SCALAR[ct][1]))
                 pre.append("  %s s_%s = { %s };" % (base, an, ", ".join("(%s)%s_%s" % (ct, an, f) for f, ct in fields)))
                 call.append("&s_%s" % an)
+            elif base in PTR_STRUCTS and ptr == "*":
+                inits = []
+                for f, ct, isptr, need in PTR_STRUCTS[base]:
+                    nm = "%s_%s" % (an, f)
+                    if isptr:
+                        jt, je, st = ARRAY[ct]
+                        jparams.append("%s %s" % (jt, nm)); sparams.append("%s%s: %s" % (an, f.title().replace("_", ""), st))
+                        a_, r_ = pin(cname, je, nm, False)
+                        pre.append(a_); post.append(r_); pinned.append(nm)
+                        inits.append("(%s *)p_%s" % (ct, nm))
+                        need = need.replace("{E}", PTR_STRUCT_E[cname])
+                        xchecks.append('  if (%s && (jlong)(*e)->GetArrayLength(e, %s) < (jlong)(%s)) { raise_msg(e, DM_ERR_INVALID, "%s: array `%s` is shorter than %s"); (void)cls; return; }'
+                                       % (nm, nm, need, meth, nm, need))
+                    else:
+                        jparams.append("%s %s" % (SCALAR[ct][0], nm)); sparams.append("%s%s: %s" % (an, f.title().replace("_", ""), SCALAR[ct][1]))
+                        inits.append("(%s)%s" % (ct, nm))
+                pre.append("  %s s_%s = { %s };" % (base, an, ", ".join(inits)))
+                call.append("&s_%s" % an)
+            elif base in OUT_STRUCTS and ptr == "*":
+                jparams.append("jdoubleArray %s" % an); sparams.append("%s: Array[Double]" % an)
+                a_, r_ = pin(cname, "jdouble", an, False)
+                pre.append(a_); post.append(r_); pinned.append(an)
+                pre.append("  %s s_%s = { 0 };" % (base, an))
+                call.append("&s_%s" % an)
+                after.append("  if (p_%s) { %s }" % (an, " ".join("p_%s[%d] = (jdouble)s_%s.%s;" % (an, k, an, f) for k, f in enumerate(OUT_STRUCTS[base]))))
             elif base == "char" and ptr == "*":
                 jparams.append("jstring %s" % an); sparams.append("%s: String" % an)
                 pre.append("  const char *p_%s = %s ? (*e)->GetStringUTFChars(e, %s, 0) : 0;" % (an, an, an))
@@ -225,7 +267,7 @@ def gen(protos):
             need = re.sub(r"\bopts_(\w+)", r"opts_\1", expr)
             checks.append('  if (%s && (jlong)(*e)->GetArrayLength(e, %s) < (jlong)(%s)) { raise_msg(e, DM_ERR_INVALID, "%s: array `%s` is shorter than %s"); (void)cls; return; }'
                           % (an, an, need, meth, an, expr.replace("(jlong)", "")))
-        body = [sig] + checks + pre
+        body = [sig] + checks + xchecks + pre
         if pinned:
             # the JVM could not hand out one of the arrays (an exception is already pending): give back what was acquired and
             # return to Java without calling into the library or throwing on top of it
@@ -242,6 +284,7 @@ def gen(protos):
             body.append("  (void)e; (void)cls; return %s;" % callexpr)
         else:
             body.append("  const int rc_ = %s;" % callexpr)
+            body += after
             body += post[::-1]
             if comm_expr or (cname.startswith("dm_comm_create") or cname == "dm_comm_unique_id"):
                 body.append("  (void)cls; if (rc_) raise_comm(e, %s, rc_);" % (comm_expr or "0"))     # communicator calls: dm_comm_last_error
