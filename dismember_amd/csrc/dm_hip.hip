@@ -343,6 +343,8 @@ static int ensure_stage(dm_ctx *h) {
   return DM_OK;
 }
 
+#include "host_request.hip.inc"
+
 // Mask.scala:10 — scale = 1 / sqrt(embedSize) of the model as loaded (zero padding of the table does not change it)
 static double sm_scale64(const dm_ctx *h) { return 1.0 / sqrt((double)(h->embed_log > 0 ? h->embed_log : h->embed)); }
 static float sm_scale32(const dm_ctx *h) { return (float)sm_scale64(h); }
@@ -972,16 +974,8 @@ static int ensure_rows_split(dm_ctx *h) {
   return DM_OK;
 }
 
-static int next_events(dm_ctx *h, hipEvent_t *a, hipEvent_t *b);
 // HIP-event pair of kind 30 around a general-rows launch (dm_kernel_timing_get_kind: the roofline of JTM's scorer in bench.py)
-struct RowsTimer {
-  dm_ctx *h; hipEvent_t e0 = nullptr, e1 = nullptr; int rc = DM_OK;
-  explicit RowsTimer(dm_ctx *h_) : h(h_) {
-    const int k = h->ev_next_kind; h->ev_next_kind = 30; rc = next_events(h, &e0, &e1); h->ev_next_kind = k;
-    if (rc == DM_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "hipEventRecord failed");
-  }
-  int stop() { return (rc == DM_OK && hipEventRecord(e1, h->stream) != hipSuccess) ? fail(h, DM_ERR_HIP, "hipEventRecord failed") : rc; }
-};
+struct RowsTimer : LaunchTimer { explicit RowsTimer(dm_ctx *h_) : LaunchTimer(h_, 30) {} };
 
 template <int E, int LC>
 static int launch_rows_split_EL(dm_ctx *h, const RowsSplitParams &p, int64_t blocks) {
@@ -1144,19 +1138,15 @@ static bool long_history_pipeline(const dm_ctx *h, int max_beam, int L) {
   if (L <= DM_MAXL) return false;
   const char *e_ = getenv("DM_LONG_PIPELINE");          // read per call: the tests run both routes in one process
   if (e_ && e_[0] == '1') return true;
-  int cap = ((2 * max_beam + 15) / 16) * 16;
-  if (cap < 32) cap = 32;
-  int pcap = 16;
-  while (pcap < cap) pcap <<= 1;
+  int cap, pcap;
+  frontier_caps(max_beam, &cap, &pcap);
   // (sized for the split scorer's layout; the fp32-input layout of the same request is no larger)
   return dm_beam_lds(h->embed, 1, cap, pcap, 4, true, 2).total > 160 * 1024;
 }
 
 static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, bool tdm, SearchPlan *pl) {
-  int cap = ((2 * max_beam + 15) / 16) * 16;
-  if (cap < 32) cap = 32;
-  int pcap = 16;
-  while (pcap < cap) pcap <<= 1;
+  int cap, pcap;
+  frontier_caps(max_beam, &cap, &pcap);
   const int kt = L > DM_MAXL ? 2 : 1;          // histories of 17 .. 32 positions: the LDS-fed kernel's two-key-tile instance
   const int kq = kt > 1 ? 4 : (L + 3) / 4;
   int nteams = 0;
@@ -1216,33 +1206,22 @@ static int launch_beam_EK(dm_ctx *h, const BeamParams &p_in, const SearchPlan &p
     if (KT == 1) snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_kernel<%d, %d, %s>", E, KQ, SPLIT ? "true" : "false");
     else snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_kernel<%d, %d, %s, %d>", E, KQ, SPLIT ? "true" : "false", KT);
   }
-  if (h->ev_skip && !h->time_direct) {       // single-request path: the launch and nothing else
-    hipLaunchKernelGGL((dm_beam_kernel<E, KQ, SPLIT, KT>), dim3(pl.grid), dim3(DM_BLOCK), pl.lds, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return DM_OK;
-  }
-  hipEvent_t e0, e1;
-  int rc = next_events(h, &e0, &e1);
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipEventRecord(e0, h->stream));
+  LaunchTimer tm(h, LaunchTimer::KEEP, !(h->ev_skip && !h->time_direct));       // single-request path: the launch and nothing else
+  if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL((dm_beam_kernel<E, KQ, SPLIT, KT>), dim3(pl.grid), dim3(DM_BLOCK), pl.lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(e1, h->stream));
-  return DM_OK;
+  return tm.stop();
 }
 
 template <int E, int KQ>
 static int launch_beam_w_EK(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
   HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam_w_kernel<E, KQ>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
   snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_w_kernel<%d, %d>", E, KQ);
-  hipEvent_t e0, e1;
-  int rc = next_events(h, &e0, &e1);
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipEventRecord(e0, h->stream));
+  LaunchTimer tm(h);
+  if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL((dm_beam_w_kernel<E, KQ>), dim3(pl.grid), dim3(DMW_BLOCK), pl.lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(e1, h->stream));
-  return DM_OK;
+  return tm.stop();
 }
 template <int E>
 static int launch_beam_w_E(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
@@ -1565,7 +1544,8 @@ static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, con
     HIPCHK(h, hipMemsetAsync(d_ids, 0xFF, (size_t)U * o->topk * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)U * o->topk * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream));
-    const int cap_ = ((2 * max_beam + 15) / 16) * 16 < 32 ? 32 : ((2 * max_beam + 15) / 16) * 16;
+    int cap_;
+    frontier_caps(max_beam, &cap_, nullptr);
     return tdm_pipeline_dev(h, d_seq, U, L, o, max_beam, d_coff, d_cids, d_ids, d_scores, d_counts, trace_levels, cap_, d_tc, d_ts, d_tn);
   }
   int start, level;
@@ -1634,15 +1614,6 @@ static int host_pipe_plan(size_t bytes_per_user, int64_t U, int64_t *off /* [18]
   off[k] = rest; off[k + 1] = U;
   return k + 1;
 }
-static int host_pipe_ensure(dm_ctx *h, int n) {
-  if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-  while ((int)h->chunk_ev.size() < n) {
-    hipEvent_t e;
-    HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    h->chunk_ev.push_back(e);
-  }
-  return DM_OK;
-}
 
 static int host_max_beam(const dm_tdm_search_opts *o, const int64_t *coff, int64_t U) {
   int mb = o->beam;
@@ -1680,136 +1651,76 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
   if ((coff == nullptr) != (cids == nullptr) && coff && coff[U] > 0) return fail(h, DM_ERR_INVALID, "dm_tdm_beam_search: consumed_off / consumed_ids must both be given");
   HIPCHK(h, hipSetDevice(h->device));
   const int mb = host_max_beam(opts, coff, U);
-  const int cap = ((2 * mb + 15) / 16) * 16 < 32 ? 32 : ((2 * mb + 15) / 16) * 16;
-  int32_t *d_seq = nullptr, *d_cids = nullptr, *d_ids = nullptr, *d_counts = nullptr, *d_tc = nullptr, *d_tn = nullptr;
-  int64_t *d_coff = nullptr;
-  float *d_scores = nullptr, *d_ts = nullptr;
-  int rc = DM_OK;
-  const size_t nout = (size_t)U * opts->topk;
-  do {
-    // one arena for the request's device buffers, kept in the handle
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const int64_t nc = coff ? coff[U] : 0;
-    const size_t b_seq = al((size_t)U * L * 4), b_out = al(nout * 4), b_cnt = al((size_t)U * 4);
-    const size_t b_coff = coff ? al((size_t)(U + 1) * 8) : 0, b_cids = coff ? al((size_t)(nc > 0 ? nc : 1) * 4) : 0;
-    const size_t need = b_seq + 2 * b_out + b_cnt + b_coff + b_cids;
-    if (h->req_bytes < need) {
-      dm_free_ptr(h->d_req); h->d_req = nullptr; h->req_bytes = 0;
-      if ((rc = dm_alloc(h, &h->d_req, need + need / 2)) != DM_OK) break;
-      h->req_bytes = need + need / 2;
+  int cap;
+  frontier_caps(mb, &cap, nullptr);
+  const size_t topk = (size_t)opts->topk, b_seq = (size_t)U * L * 4;
+  const int64_t nc = coff ? coff[U] : 0;
+  // request arena: [seq | ids | scores | counts | consumed_off | consumed_ids]
+  ReqArena ar;
+  const size_t o_seq = ar.add(b_seq), o_ids = ar.add(U * topk * 4), o_sc = ar.add(U * topk * 4), o_cnt = ar.add((size_t)U * 4), o_end = ar.need;
+  const size_t o_coff = coff ? ar.add((size_t)(U + 1) * 8) : 0, o_cids = coff ? ar.add((size_t)(nc > 0 ? nc : 1) * 4) : 0;
+  int rc = ar.commit(h);
+  if (rc != DM_OK) return rc;
+  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_counts = ar.ptr<int32_t>(o_cnt), *d_cids = coff ? ar.ptr<int32_t>(o_cids) : nullptr;
+  int64_t *d_coff = coff ? ar.ptr<int64_t>(o_coff) : nullptr;
+  float *d_scores = ar.ptr<float>(o_sc);
+  HostOut outs[6] = {{out_ids, d_ids, topk * 4}, {out_scores, d_scores, topk * 4}, {out_counts, d_counts, 4}};
+  // small requests (the reference's one-user-per-call serving loop): the request goes up and the three result arrays come down
+  // through ONE pinned staging block — a pageable copy costs 10-15 us each, and a single-user search is 60 us of kernel
+  const bool staged = !coff && !tn && o_end <= (256u << 10);
+  if (staged && (rc = ensure_stage(h)) != DM_OK) return rc;
+  if (staged) memcpy(h->h_stage, seq, b_seq);
+  if (staged && h->direct_ok && U <= 8) {
+    // Single-request path (the reference's serving loop: one user per call, examples/.../tdm/package.scala:114-124).  The staging
+    // block is host-mapped: the kernel reads the request from it and writes the results into it; the host polls the counts.
+    volatile int32_t *m_cnt = (volatile int32_t *)(h->h_stage + o_cnt);
+    for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
+    bool direct = true;
+    rc = tdm_search_dev(h, (const int32_t *)h->d_stage, U, L, opts, mb, nullptr, nullptr, (int32_t *)(h->d_stage + o_ids),
+                        (float *)(h->d_stage + o_sc), (int32_t *)(h->d_stage + o_cnt), 0, nullptr, nullptr, nullptr, &direct);
+    if (rc != DM_OK) return rc;
+    if (direct) {
+      if ((rc = wait_host_direct(h, m_cnt, U, "tdm beam search")) == DM_OK) copy_from_stage(h, outs, 3, U);
+      return rc;
     }
-    char *base = (char *)h->d_req;
-    d_seq = (int32_t *)base; base += b_seq;
-    d_ids = (int32_t *)base; base += b_out;
-    d_scores = (float *)base; base += b_out;
-    d_counts = (int32_t *)base; base += b_cnt;
-    // small requests (the reference's one-user-per-call serving loop): the request goes up and the three result arrays come down
-    // through ONE pinned staging block — a pageable copy costs 10-15 us each, and a single-user search is 60 us of kernel
-    const size_t down = 2 * b_out + b_cnt;
-    const bool staged = !coff && !tn && b_seq + down <= (256u << 10);
-    if (staged && (rc = ensure_stage(h)) != DM_OK) break;
-    if (staged) memcpy(h->h_stage, seq, (size_t)U * L * 4);
-    if (staged && h->direct_ok && U <= 8) {
-      // Single-request path (the reference's serving loop: one user per call, examples/.../tdm/package.scala:114-124).  The staging
-      // block is host-mapped: the kernel reads the request from it and writes the results into it; the host polls the counts.
-      int32_t *m_ids = (int32_t *)(h->h_stage + b_seq);
-      float *m_sc = (float *)(h->h_stage + b_seq + b_out);
-      volatile int32_t *m_cnt = (volatile int32_t *)(h->h_stage + b_seq + 2 * b_out);
-      for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
-      bool direct = true;
-      rc = tdm_search_dev(h, (const int32_t *)h->d_stage, U, L, opts, mb, nullptr, nullptr, (int32_t *)(h->d_stage + b_seq),
-                          (float *)(h->d_stage + b_seq + b_out), (int32_t *)(h->d_stage + b_seq + 2 * b_out), 0, nullptr, nullptr, nullptr, &direct);
-      if (rc != DM_OK) break;
-      if (direct) {
-        bool done = false;
-        for (long spin = 0; !done; spin++) {
-          done = true;
-          for (int64_t u = 0; u < U; u++) done = done && m_cnt[u] >= 0;
-          if (!done && (spin & 0xFFF) == 0xFFF && hipStreamQuery(h->stream) != hipErrorNotReady) {
-            // the stream is idle (or failed) and the flags never came: a kernel fault
-            hipError_t e = hipStreamSynchronize(h->stream);
-            done = true;
-            for (int64_t u = 0; u < U; u++) done = done && m_cnt[u] >= 0;
-            if (!done) { rc = fail(h, DM_ERR_HIP, std::string("tdm beam search (single-request path): ") + (e != hipSuccess ? hipGetErrorString(e) : "kernel finished without results")); break; }
-          }
-        }
-        if (rc != DM_OK) break;
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        memcpy(out_ids, m_ids, nout * 4); memcpy(out_scores, m_sc, nout * 4);
-        for (int64_t u = 0; u < U; u++) out_counts[u] = m_cnt[u];
-        break;
-      }
-      // the plan did not allow it (one-wave-per-SIMD kernel, too many users for the grid): fall through to the staged path
-    }
-    if (hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "upload failed"); break; }
-    int64_t coff_[18];
-    const int n_chunks = (staged || coff || tn || long_history_pipeline(h, mb, L)) ? 1 : host_pipe_plan((size_t)opts->topk * 8, U, coff_);
-    if (n_chunks > 1) {
-      if ((rc = host_pipe_ensure(h, n_chunks)) != DM_OK) break;
-      int launched = 0;
-      for (int k = 0; k < n_chunks && rc == DM_OK; k++) {
-        const int64_t u0 = coff_[k], uk = coff_[k + 1] - u0;
-        if (uk <= 0) break;
-        h->rows_keep = k > 0;
-        rc = tdm_search_dev(h, d_seq + u0 * L, uk, L, opts, mb, nullptr, nullptr, d_ids + u0 * opts->topk, d_scores + u0 * opts->topk, d_counts + u0,
-                            0, nullptr, nullptr, nullptr);
-        h->rows_keep = false;
-        if (rc == DM_OK && hipEventRecord(h->chunk_ev[(size_t)k], h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "tdm beam search: event record failed");
-        if (rc == DM_OK) launched++;
-      }
-      hipError_t e = hipSuccess;
-      for (int k = 0; k < launched && e == hipSuccess; k++) {
-        const int64_t u0 = coff_[k], uk = coff_[k + 1] - u0;
-        e = hipStreamWaitEvent(h->copy_stream, h->chunk_ev[(size_t)k], 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_ids + u0 * opts->topk, d_ids + u0 * opts->topk, (size_t)uk * opts->topk * 4, hipMemcpyDeviceToHost, h->copy_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_scores + u0 * opts->topk, d_scores + u0 * opts->topk, (size_t)uk * opts->topk * 4, hipMemcpyDeviceToHost, h->copy_stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(out_counts + u0, d_counts + u0, (size_t)uk * 4, hipMemcpyDeviceToHost, h->copy_stream);
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
-      const hipError_t e2 = hipStreamSynchronize(h->stream);
-      if (rc == DM_OK && (e != hipSuccess || e2 != hipSuccess)) rc = fail(h, DM_ERR_HIP, std::string("tdm beam search (pipelined download): ") + hipGetErrorString(e != hipSuccess ? e : e2));
-      break;
-    }
-    if (coff) {
-      d_coff = (int64_t *)base; base += b_coff;
-      d_cids = (int32_t *)base; base += b_cids;
-      if (hipMemcpyAsync(d_coff, coff, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "upload failed"); break; }
-      if (nc > 0 && hipMemcpyAsync(d_cids, cids, (size_t)nc * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "upload failed"); break; }
-    }
-    if (tn) {
-      const size_t nt = (size_t)U * max_levels;
-      if ((rc = dm_alloc(h, (void **)&d_tc, nt * cap * 4)) != DM_OK) break;
-      if ((rc = dm_alloc(h, (void **)&d_ts, nt * cap * 4)) != DM_OK) break;
-      if ((rc = dm_alloc(h, (void **)&d_tn, nt * 4)) != DM_OK) break;
-      if (hipMemsetAsync(d_tn, 0, nt * 4, h->stream) != hipSuccess || hipMemsetAsync(d_tc, 0, nt * cap * 4, h->stream) != hipSuccess ||
-          hipMemsetAsync(d_ts, 0, nt * cap * 4, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "memset failed"); break; }
-    }
-    rc = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tc, d_ts, d_tn);
-    if (rc != DM_OK) break;
-    hipError_t e = hipSuccess;
-    if (staged) {
-      e = hipMemcpyAsync(h->h_stage + b_seq, d_ids, down, hipMemcpyDeviceToHost, h->stream);       // ids | scores | counts are one block of the arena
-    } else {
-      e = hipMemcpyAsync(out_ids, d_ids, nout * 4, hipMemcpyDeviceToHost, h->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_scores, d_scores, nout * 4, hipMemcpyDeviceToHost, h->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_counts, d_counts, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream);
-    }
-    if (e == hipSuccess && tn) {
-      const size_t nt = (size_t)U * max_levels;
-      e = hipMemcpyAsync(tc, d_tc, nt * cap * 4, hipMemcpyDeviceToHost, h->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(ts, d_ts, nt * cap * 4, hipMemcpyDeviceToHost, h->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(tn, d_tn, nt * 4, hipMemcpyDeviceToHost, h->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, std::string("tdm beam search: ") + hipGetErrorString(e)); break; }
-    if (staged) {
-      memcpy(out_ids, h->h_stage + b_seq, nout * 4);
-      memcpy(out_scores, h->h_stage + b_seq + b_out, nout * 4);
-      memcpy(out_counts, h->h_stage + b_seq + 2 * b_out, (size_t)U * 4);
-    }
-  } while (0);
-  dm_free_ptr(d_tc); dm_free_ptr(d_tn); dm_free_ptr(d_ts);      // trace buffers (parity instrumentation) are per call
-  return rc;
+    // the plan did not allow it (one-wave-per-SIMD kernel, too many users for the grid): fall through to the staged path
+  }
+  if (hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq, b_seq, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
+  int64_t off[18];
+  const int n_chunks = (staged || coff || tn || long_history_pipeline(h, mb, L)) ? 1 : host_pipe_plan(topk * 8, U, off);
+  if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
+    int launched;
+    rc = launch_chunks(h, n_chunks, off, [&](int, int64_t u0, int64_t uk) {
+      return tdm_search_dev(h, d_seq + u0 * L, uk, L, opts, mb, nullptr, nullptr, d_ids + u0 * topk, d_scores + u0 * topk, d_counts + u0, 0, nullptr, nullptr, nullptr);
+    }, &launched);
+    const hipError_t e = download_chunks(h, outs, 3, off, launched);
+    if (rc == DM_OK && e != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string("tdm beam search (pipelined download): ") + hipGetErrorString(e));
+    return rc;
+  }
+  if (coff) {
+    if (hipMemcpyAsync(d_coff, coff, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
+    if (nc > 0 && hipMemcpyAsync(d_cids, cids, (size_t)nc * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
+  }
+  struct TraceBufs {      // trace buffers (parity instrumentation) are per call
+    int32_t *tc = nullptr, *tn = nullptr; float *ts = nullptr;
+    ~TraceBufs() { dm_free_ptr(tc); dm_free_ptr(tn); dm_free_ptr(ts); }
+  } d_tr;
+  if (tn) {
+    const size_t nt = (size_t)U * max_levels;
+    if ((rc = dm_alloc(h, (void **)&d_tr.tc, nt * cap * 4)) != DM_OK) return rc;
+    if ((rc = dm_alloc(h, (void **)&d_tr.ts, nt * cap * 4)) != DM_OK) return rc;
+    if ((rc = dm_alloc(h, (void **)&d_tr.tn, nt * 4)) != DM_OK) return rc;
+    if (hipMemsetAsync(d_tr.tn, 0, nt * 4, h->stream) != hipSuccess || hipMemsetAsync(d_tr.tc, 0, nt * cap * 4, h->stream) != hipSuccess ||
+        hipMemsetAsync(d_tr.ts, 0, nt * cap * 4, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "memset failed");
+    outs[3] = {tc, d_tr.tc, (size_t)max_levels * cap * 4}; outs[4] = {ts, d_tr.ts, (size_t)max_levels * cap * 4}; outs[5] = {tn, d_tr.tn, (size_t)max_levels * 4};
+  }
+  rc = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tr.tc, d_tr.ts, d_tr.tn);
+  if (rc != DM_OK) return rc;
+  hipError_t e = staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("tdm beam search: ") + hipGetErrorString(e));
+  if (staged) copy_from_stage(h, outs, 3, U);
+  return DM_OK;
 }
 
 int dm_tdm_beam_search(dm_handle_t h, const int32_t *seq_item_ids, int64_t U, int L, const dm_tdm_search_opts *opts,
@@ -1905,66 +1816,36 @@ static int otm_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L
   level_start_int(beam, &start, &level);
   SearchPlan pl;
   if ((rc = plan_search(h, beam, U, L, leaf_level - level, false, &pl)) != DM_OK) return rc;
-  const size_t stride = (size_t)2 * beam;
-  // request arena (grow only): no hipMalloc / hipFree on the request path
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t nt = tn ? (size_t)U * max_levels : 0;
-  const size_t o_seq = 0, o_ids = o_seq + up((size_t)U * L * 4), o_sc = o_ids + up(U * stride * 4), o_cnt = o_sc + up(U * stride * 4);
-  const size_t o_tc = o_cnt + up((size_t)U * 4), o_ts = o_tc + up(nt * pl.cap * 4), o_tn = o_ts + up(nt * pl.cap * 4);
-  const size_t need = o_tn + up(nt * 4);
-  if (h->req_bytes < need) {
-    dm_free_ptr(h->d_req); h->d_req = nullptr; h->req_bytes = 0;
-    if ((rc = dm_alloc(h, &h->d_req, need + need / 2)) != DM_OK) return rc;
-    h->req_bytes = need + need / 2;
-  }
-  char *base = (char *)h->d_req;
-  int32_t *d_seq = (int32_t *)(base + o_seq), *d_ids = (int32_t *)(base + o_ids), *d_counts = (int32_t *)(base + o_cnt);
-  float *d_scores = (float *)(base + o_sc);
-  int32_t *d_tc = tn ? (int32_t *)(base + o_tc) : nullptr, *d_tn = tn ? (int32_t *)(base + o_tn) : nullptr;
-  float *d_ts = tn ? (float *)(base + o_ts) : nullptr;
+  const size_t stride = (size_t)2 * beam, nt = tn ? (size_t)U * max_levels : 0;
+  // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
+  ReqArena ar;
+  const size_t o_seq = ar.add((size_t)U * L * 4), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * 4), o_cnt = ar.add((size_t)U * 4);
+  const size_t o_tc = ar.add(nt * pl.cap * 4), o_ts = ar.add(nt * pl.cap * 4), o_tn = ar.add(nt * 4);
+  if ((rc = ar.commit(h)) != DM_OK) return rc;
+  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_counts = ar.ptr<int32_t>(o_cnt);
+  float *d_scores = ar.ptr<float>(o_sc);
+  int32_t *d_tc = tn ? ar.ptr<int32_t>(o_tc) : nullptr, *d_tn = tn ? ar.ptr<int32_t>(o_tn) : nullptr;
+  float *d_ts = tn ? ar.ptr<float>(o_ts) : nullptr;
+  const HostOut outs[6] = {{out_node_ids, d_ids, stride * 4}, {out_scores, d_scores, stride * 4}, {out_counts, d_counts, 4},
+                           {tc, d_tc, (size_t)max_levels * pl.cap * 4}, {ts, d_ts, (size_t)max_levels * pl.cap * 4}, {tn, d_tn, (size_t)max_levels * 4}};
   HIPCHK(h, hipMemcpyAsync(d_seq, seq_codes, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream));
-  int64_t coff_[18];
-  const int n_chunks = tn ? 1 : host_pipe_plan(stride * 8, U, coff_);
+  int64_t off[18];
+  const int n_chunks = tn ? 1 : host_pipe_plan(stride * 8, U, off);
   if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
-    if ((rc = host_pipe_ensure(h, n_chunks)) != DM_OK) return rc;
-    int launched = 0;
-    for (int k = 0; k < n_chunks && rc == DM_OK; k++) {
-      const int64_t u0 = coff_[k], uk = coff_[k + 1] - u0;
-      if (uk <= 0) break;
+    int launched;
+    rc = launch_chunks(h, n_chunks, off, [&](int, int64_t u0, int64_t uk) {
       SearchPlan plk;
-      if ((rc = plan_search(h, beam, uk, L, leaf_level - level, false, &plk)) != DM_OK) break;
-      h->rows_keep = k > 0;
-      rc = otm_search_dev(h, d_seq + u0 * L, uk, L, beam, leaf_level, d_ids + u0 * stride, d_scores + u0 * stride, d_counts + u0, 0, nullptr, nullptr, nullptr, plk);
-      h->rows_keep = false;
-      if (rc == DM_OK && hipEventRecord(h->chunk_ev[(size_t)k], h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "dm_otm_beam_search: event record failed");
-      if (rc == DM_OK) launched++;
-    }
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < launched && e == hipSuccess; k++) {
-      const int64_t u0 = coff_[k], uk = coff_[k + 1] - u0;
-      e = hipStreamWaitEvent(h->copy_stream, h->chunk_ev[(size_t)k], 0);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_node_ids + u0 * stride, d_ids + u0 * stride, (size_t)uk * stride * 4, hipMemcpyDeviceToHost, h->copy_stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_scores + u0 * stride, d_scores + u0 * stride, (size_t)uk * stride * 4, hipMemcpyDeviceToHost, h->copy_stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(out_counts + u0, d_counts + u0, (size_t)uk * 4, hipMemcpyDeviceToHost, h->copy_stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
-    if (rc != DM_OK) { (void)hipStreamSynchronize(h->stream); return rc; }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(h->stream); return fail(h, DM_ERR_HIP, std::string("dm_otm_beam_search (pipelined download): ") + hipGetErrorString(e)); }
-    HIPCHK(h, hipMemcpyAsync(&h->h_rows, h->d_rows, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->last_rows = (int64_t)h->h_rows;
-    return DM_OK;
+      const int rc_ = plan_search(h, beam, uk, L, leaf_level - level, false, &plk);
+      return rc_ != DM_OK ? rc_ : otm_search_dev(h, d_seq + u0 * L, uk, L, beam, leaf_level, d_ids + u0 * stride, d_scores + u0 * stride, d_counts + u0, 0, nullptr, nullptr, nullptr, plk);
+    }, &launched);
+    const hipError_t e = download_chunks(h, outs, 3, off, launched);
+    if (rc == DM_OK && e != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string("dm_otm_beam_search (pipelined download): ") + hipGetErrorString(e));
+    if (rc != DM_OK) return rc;
+  } else {
+    if (tn) HIPCHK(h, hipMemsetAsync(d_tn, 0, nt * 4, h->stream));
+    if ((rc = otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts, max_levels, d_tc, d_ts, d_tn, pl)) != DM_OK) return rc;
+    HIPCHK(h, download_all(h, outs, tn ? 6 : 3, U, h->stream));
   }
-  if (tn) HIPCHK(h, hipMemsetAsync(d_tn, 0, nt * 4, h->stream));
-  if ((rc = otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts, max_levels, d_tc, d_ts, d_tn, pl)) != DM_OK) return rc;
-  if (tn) {
-    HIPCHK(h, hipMemcpyAsync(tc, d_tc, nt * pl.cap * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ts, d_ts, nt * pl.cap * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(tn, d_tn, nt * 4, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(h, hipMemcpyAsync(out_node_ids, d_ids, U * stride * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_scores, d_scores, U * stride * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_counts, d_counts, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(&h->h_rows, h->d_rows, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->last_rows = (int64_t)h->h_rows;

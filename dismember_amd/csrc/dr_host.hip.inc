@@ -59,16 +59,11 @@ template <typename T>
 static int dr_launch_gemm(dm_ctx *h, const DrGemmParams<T> &p, bool timed = true) {
   if (p.M <= 0 || p.N <= 0) return DM_OK;
   dim3 grid((unsigned)((p.N + DR_TN - 1) / DR_TN), (unsigned)((p.M + DR_TM - 1) / DR_TM));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (timed) {
-    int rc = next_events(h, &e0, &e1);
-    if (rc != DM_OK) return rc;
-    HIPCHK(h, hipEventRecord(e0, h->stream));
-  }
+  LaunchTimer tm(h, LaunchTimer::KEEP, timed);
+  if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL(dr_gemm_kernel<T>, grid, dim3(256), 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
-  if (timed) HIPCHK(h, hipEventRecord(e1, h->stream));
-  return DM_OK;
+  return tm.stop();
 }
 // A search is several launches (history GEMM, layer 0, statistics and cut per layer).  An event pair around EACH of them (what
 // dm_kernel_timing_get_kind reports by kind) drains the GPU between two kernels: measured 0.39 -> 0.32 ms per 1 024 users, 0.63 -> 0.55 per
@@ -348,18 +343,12 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
       // every launch gets its own event pair; dm_kernel_timing_get_kind: 11 = layer 0, 10 + 2d = statistics of layer d, 11 + 2d = its cut,
       // 21 + 2d = the block version's pass over the users the one-wave cut flagged
       // (10 = the history GEMM of a sliced search)
-      struct Kind { dm_ctx *h; ~Kind() { h->ev_next_kind = 0; } } kind_{h};
       auto timed = [&](int kind, auto launch) -> int {
-        if (!detail) { launch(); HIPCHK(h, hipGetLastError()); return DM_OK; }
-        h->ev_next_kind = kind;
-        hipEvent_t a, b;
-        const int rc_ = next_events(h, &a, &b);
-        if (rc_ != DM_OK) return rc_;
-        HIPCHK(h, hipEventRecord(a, h->stream));
+        LaunchTimer tm(h, kind, detail);
+        if (tm.rc != DM_OK) return tm.rc;
         launch();
         HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipEventRecord(b, h->stream));
-        return DM_OK;
+        return tm.stop();
       };
       {
         const char *e_ = getenv("DM_DR_LAYER0_BLOCK");          // A/B switch: the block version (dr_beam_layer<T, 0>) for everybody
@@ -506,13 +495,11 @@ static int dr_recommend_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int be
   p.K = s->K; p.D = s->D; p.E = E; p.beam = beam; p.topk = topk; p.n2k = n2k; p.cap = cap; p.U = U;
   p.cand = (int32_t *)s->d_cand; p.score = (T *)((char *)s->d_cand + al((size_t)grid * cap * 4));
   p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_ncand = nullptr;
-  hipEvent_t e0, e1;
-  if ((rc = next_events(h, &e0, &e1)) != DM_OK) return rc;
-  HIPCHK(h, hipEventRecord(e0, h->stream));
+  LaunchTimer tm(h);
+  if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL(dr_rerank_kernel<T>, dim3((unsigned)grid), dim3(DR_NT), lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(e1, h->stream));
-  return DM_OK;
+  return tm.stop();
 }
 
 // scratch for the intermediate paths of a recommend call

@@ -1,0 +1,128 @@
+// Host-request layer (host code only): the mechanisms the host-buffer beam-search front ends share (tdm_search_host, otm_search_host in
+// dm_hip.hip, otm64_search_host in otm64.hip.inc) and the event pair around one launch.  A front end states its own policy — which
+// requests are staged, served in place or cut into chunks — and calls these.
+
+static int next_events(dm_ctx *h, hipEvent_t *a, hipEvent_t *b);
+
+// ---- frontier sizing of a beam search: cap = slots of a level's candidate list (2 * beam in whole 16-row tiles, at least two tiles),
+// pcap = the sort's power of two above it
+static void frontier_caps(int max_beam, int *cap, int *pcap) {
+  int c = ((2 * max_beam + 15) / 16) * 16;
+  if (c < 32) c = 32;
+  int p = 32;
+  while (p < c) p <<= 1;
+  *cap = c;
+  if (pcap) *pcap = p;
+}
+
+// ---- HIP-event pair around one launch on the handle's stream (dm_kernel_timing_get[_kind]).  kind: what the pair is recorded as
+// (KEEP = the handle's current ev_next_kind); on = false: no pair at all, rc stays DM_OK and stop() does nothing.
+struct LaunchTimer {
+  static constexpr int KEEP = -1;
+  dm_ctx *h; hipEvent_t e0 = nullptr, e1 = nullptr; int rc = DM_OK; bool on;
+  explicit LaunchTimer(dm_ctx *h_, int kind = KEEP, bool on_ = true) : h(h_), on(on_) {
+    if (!on) return;
+    const int k = h->ev_next_kind;
+    if (kind != KEEP) h->ev_next_kind = kind;
+    rc = next_events(h, &e0, &e1);
+    h->ev_next_kind = k;
+    if (rc == DM_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "hipEventRecord failed");
+  }
+  int stop() { return (on && rc == DM_OK && hipEventRecord(e1, h->stream) != hipSuccess) ? fail(h, DM_ERR_HIP, "hipEventRecord failed") : rc; }
+};
+
+// ---- request arena: the device buffers of one host-buffer request, laid out in h->d_req (grow only: no hipMalloc / hipFree on the
+// request path once the handle has seen its largest request).  add() every buffer, commit(), then ptr<T>(offset).
+struct ReqArena {
+  size_t need = 0; char *base = nullptr;
+  size_t add(size_t bytes) { const size_t off = need; need += (bytes + 255) & ~(size_t)255; return off; }
+  int commit(dm_ctx *h) {
+    if (h->req_bytes < need) {
+      const size_t grown = need + need / 2;
+      dm_free_ptr(h->d_req); h->d_req = nullptr;
+      const int rc = dm_alloc(h, &h->d_req, grown);
+      h->req_bytes = rc == DM_OK ? grown : 0;
+      if (rc != DM_OK) return rc;
+    }
+    base = (char *)h->d_req;
+    return DM_OK;
+  }
+  template <typename T> T *ptr(size_t off) const { return (T *)(base + off); }
+};
+
+// ---- one result array of a request: `bytes_per_user` bytes per user at `dev` (in the arena, or a per-call buffer) go to `host`
+struct HostOut { void *host; const void *dev; size_t bytes_per_user; };
+
+// plain download: every array on `stream`; the caller synchronizes
+static hipError_t download_all(dm_ctx *h, const HostOut *outs, int n, int64_t U, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; i++) e = hipMemcpyAsync(outs[i].host, outs[i].dev, outs[i].bytes_per_user * (size_t)U, hipMemcpyDeviceToHost, stream);
+  return e;
+}
+
+// The pinned staging block (ensure_stage) mirrors the head of the arena: a buffer at arena offset o is staged at h_stage + o, and the
+// single-request kernels address it as d_stage + o.
+static char *stage_of(const dm_ctx *h, const void *dev) { return h->h_stage + ((const char *)dev - (const char *)h->d_req); }
+static void copy_from_stage(const dm_ctx *h, const HostOut *outs, int n, int64_t U) {
+  for (int i = 0; i < n; i++) memcpy(outs[i].host, stage_of(h, outs[i].dev), outs[i].bytes_per_user * (size_t)U);
+}
+// staged download: outs[0] .. outs[n - 1] are adjacent in the arena and come down as ONE block; the caller synchronizes, then copy_from_stage()
+static hipError_t download_staged(dm_ctx *h, const HostOut *outs, int n, int64_t U) {
+  const char *first = (const char *)outs[0].dev, *end = (const char *)outs[n - 1].dev + outs[n - 1].bytes_per_user * (size_t)U;
+  return hipMemcpyAsync(stage_of(h, first), first, (size_t)(end - first), hipMemcpyDeviceToHost, h->stream);
+}
+
+// ---- single-request path: the kernel writes whole result rows into the host-mapped staging block and publishes each user's count
+// last; the caller has set the counts to -1 and launched.  Polls the counts; every 4096 spins a look at the stream: idle (or failed)
+// with counts still missing is a kernel fault.
+static int wait_host_direct(dm_ctx *h, volatile int32_t *m_cnt, int64_t U, const char *who) {
+  auto all_in = [&] { bool ok = true; for (int64_t u = 0; u < U; u++) ok = ok && m_cnt[u] >= 0; return ok; };
+  for (long spin = 0; !all_in(); spin++)
+    if ((spin & 0xFFF) == 0xFFF && hipStreamQuery(h->stream) != hipErrorNotReady) {
+      const hipError_t e = hipStreamSynchronize(h->stream);
+      if (!all_in()) return fail(h, DM_ERR_HIP, std::string(who) + " (single-request path): " + (e != hipSuccess ? hipGetErrorString(e) : "kernel finished without results"));
+    }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  return DM_OK;
+}
+
+// ---- pipelined download of a request cut into chunks of users (host_pipe_plan in dm_hip.hip says why and how).
+// fn(k, u0, uk) enqueues the search of chunk k = users [u0, u0 + uk).  Chunks after the first keep the scored-rows counter counting
+// (rows_keep); the first failure stops the launches.  *launched = the chunks whose event was recorded.
+template <typename Fn>
+static int launch_chunks(dm_ctx *h, int n_chunks, const int64_t *off, Fn fn, int *launched) {
+  *launched = 0;
+  if (!h->copy_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+  while ((int)h->chunk_ev.size() < n_chunks) {
+    hipEvent_t e;
+    HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    h->chunk_ev.push_back(e);
+  }
+  int rc = DM_OK;
+  for (int k = 0; k < n_chunks && rc == DM_OK; k++) {
+    const int64_t u0 = off[k], uk = off[k + 1] - u0;
+    if (uk <= 0) break;
+    h->rows_keep = k > 0;
+    rc = fn(k, u0, uk);
+    h->rows_keep = false;
+    if (rc == DM_OK && hipEventRecord(h->chunk_ev[(size_t)k], h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "host-buffer search: event record failed");
+    if (rc == DM_OK) ++*launched;
+  }
+  return rc;
+}
+
+// downloads the launched chunks, then synchronizes BOTH streams whatever happened; the first HIP error, if any
+static hipError_t download_chunks(dm_ctx *h, const HostOut *outs, int n, const int64_t *off, int launched) {
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < launched && e == hipSuccess; k++) {
+    const int64_t u0 = off[k], uk = off[k + 1] - u0;
+    e = hipStreamWaitEvent(h->copy_stream, h->chunk_ev[(size_t)k], 0);
+    for (int i = 0; i < n && e == hipSuccess; i++) {
+      const size_t b = outs[i].bytes_per_user;
+      e = hipMemcpyAsync((char *)outs[i].host + (size_t)u0 * b, (const char *)outs[i].dev + (size_t)u0 * b, (size_t)uk * b, hipMemcpyDeviceToHost, h->copy_stream);
+    }
+  }
+  const hipError_t e1 = h->copy_stream ? hipStreamSynchronize(h->copy_stream) : hipSuccess;
+  const hipError_t e2 = hipStreamSynchronize(h->stream);
+  return e != hipSuccess ? e : e1 != hipSuccess ? e1 : e2;
+}

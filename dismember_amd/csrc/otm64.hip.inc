@@ -248,19 +248,11 @@ static int launch_beam64_EK(dm_ctx *h, const Beam64Params &p, int grid, int lds)
   HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam64_kernel<E, KQ, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   if (KT == 1) snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam64_kernel<%d, %d>", E, KQ);
   else snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam64_kernel<%d, %d, %d>", E, KQ, KT);
-  if (p.host_direct && !h->time_direct) {       // single-request path: the launch and nothing else
-    hipLaunchKernelGGL((dm_beam64_kernel<E, KQ, KT>), dim3(grid), dim3(DM64_BLOCK), lds, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return DM_OK;
-  }
-  hipEvent_t e0, e1;
-  int rc = next_events(h, &e0, &e1);
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipEventRecord(e0, h->stream));
+  LaunchTimer tm(h, LaunchTimer::KEEP, !(p.host_direct && !h->time_direct));       // single-request path: the launch and nothing else
+  if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL((dm_beam64_kernel<E, KQ, KT>), dim3(grid), dim3(DM64_BLOCK), lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipEventRecord(e1, h->stream));
-  return DM_OK;
+  return tm.stop();
 }
 template <int E>
 static int launch_beam64_E(dm_ctx *h, const Beam64Params &p, int grid, int lds) {
@@ -286,10 +278,8 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   { const char *e_ = getenv("DM_LONG_PIPELINE"); if (L > DM_MAXL && e_ && e_[0] == '1') return DM_OK; }      // (A/B: 17 .. 32 positions on the per-level pipeline)
   const int kt = L > DM_MAXL ? 2 : 1;         // key tiles of 16 history positions
   const int E = h->embed;
-  int fcap = ((2 * beam + 15) / 16) * 16;
-  if (fcap < 32) fcap = 32;
-  int pcap = 32;
-  while (pcap < fcap) pcap <<= 1;
+  int fcap, pcap;
+  frontier_caps(beam, &fcap, &pcap);
   if (pcap > 32768) return DM_OK;          // sort positions are 16-bit
   int nteams = 0, lds = 0, b_global = 0, v_global = 0;
   // Team shapes, best first.  Small frontiers (OTM.recommend's default beam 20): twelve one-wave teams with everything in LDS.  Up to 512
@@ -479,88 +469,49 @@ static int otm64_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int
   for (int64_t i = 0; i < U * L; i++)
     if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_otm_beam_search: history code outside the embedding table");
   HIPCHK(h, hipSetDevice(h->device));
-  const int cap = ((2 * beam + 15) / 16) * 16 < 32 ? 32 : ((2 * beam + 15) / 16) * 16;
-  const size_t stride = (size_t)2 * beam, ssz = out_sc64 ? 8 : 4, tsz = ts64 ? 8 : 4;
-  const size_t nt = tn ? (size_t)U * max_levels : 0;
-  // one request arena kept in the handle (grow only: no hipMalloc / hipFree on the request path): [seq | ids | scores | counts | trace]
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_seq = 0, o_ids = o_seq + up((size_t)U * L * 4), o_sc = o_ids + up(U * stride * 4), o_cnt = o_sc + up(U * stride * ssz);
-  const size_t o_tc = o_cnt + up((size_t)U * 4), o_ts = o_tc + up(nt * cap * 4), o_tn = o_ts + up(nt * cap * tsz), need = o_tn + up(nt * 4);
-  if (h->req_bytes < need) {
-    dm_free_ptr(h->d_req); h->d_req = nullptr; h->req_bytes = 0;
-    if ((rc = dm_alloc(h, &h->d_req, need + need / 2)) != DM_OK) return rc;
-    h->req_bytes = need + need / 2;
-  }
-  char *base = (char *)h->d_req;
-  int32_t *d_seq = (int32_t *)(base + o_seq), *d_ids = (int32_t *)(base + o_ids), *d_cnt = (int32_t *)(base + o_cnt);
-  void *d_sc = base + o_sc;
-  int32_t *d_tc = tn ? (int32_t *)(base + o_tc) : nullptr, *d_tn = tn ? (int32_t *)(base + o_tn) : nullptr;
-  void *d_ts = tn ? (void *)(base + o_ts) : nullptr;
+  int cap;
+  frontier_caps(beam, &cap, nullptr);
+  const size_t stride = (size_t)2 * beam, ssz = out_sc64 ? 8 : 4, tsz = ts64 ? 8 : 4, b_seq = (size_t)U * L * 4, nt = tn ? (size_t)U * max_levels : 0;
+  // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
+  ReqArena ar;
+  const size_t o_seq = ar.add(b_seq), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * ssz), o_cnt = ar.add((size_t)U * 4), o_end = ar.need;
+  const size_t o_tc = ar.add(nt * cap * 4), o_ts = ar.add(nt * cap * tsz), o_tn = ar.add(nt * 4);
+  if ((rc = ar.commit(h)) != DM_OK) return rc;
+  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_cnt = ar.ptr<int32_t>(o_cnt);
+  void *d_sc = ar.ptr<char>(o_sc);
+  int32_t *d_tc = tn ? ar.ptr<int32_t>(o_tc) : nullptr, *d_tn = tn ? ar.ptr<int32_t>(o_tn) : nullptr;
+  void *d_ts = tn ? ar.ptr<char>(o_ts) : nullptr;
+  const HostOut outs[6] = {{out_node_ids, d_ids, stride * 4}, {out_sc64 ? (void *)out_sc64 : (void *)out_sc32, d_sc, stride * ssz}, {out_counts, d_cnt, 4},
+                           {tc, d_tc, (size_t)max_levels * cap * 4}, {ts64 ? (void *)ts64 : (void *)ts32, d_ts, (size_t)max_levels * cap * tsz}, {tn, d_tn, (size_t)max_levels * 4}};
   // small requests (OTM.recommend's one-user-per-call loop, examples/.../otm/package.scala:101-105): the request goes up and the
   // results come down through ONE pinned staging block
-  const size_t down = o_tc - o_ids;
-  const bool staged = !tn && up((size_t)U * L * 4) + down <= (256u << 10);
+  const bool staged = !tn && o_end <= (256u << 10);
   if (staged && (rc = ensure_stage(h)) != DM_OK) return rc;
-  if (staged) memcpy(h->h_stage, seq_codes, (size_t)U * L * 4);
+  if (staged) memcpy(h->h_stage, seq_codes, b_seq);
   if (staged && h->direct_ok && U <= 8) {
     // Single-request path (OTM.recommend's serving loop): the staging block is host-mapped — the fused kernel reads the request from
     // it and writes ids / scores / counts into it (whole rows, then a system-scope fence, then the count as the flag); the host polls.
-    char *hs = h->h_stage + up((size_t)U * L * 4);
-    int32_t *m_ids = (int32_t *)hs;
-    void *m_sc = hs + (o_sc - o_ids);
-    volatile int32_t *m_cnt = (volatile int32_t *)(hs + (o_cnt - o_ids));
+    volatile int32_t *m_cnt = (volatile int32_t *)(h->h_stage + o_cnt);
     for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
     bool done = false;
-    char *ds = h->d_stage + up((size_t)U * L * 4);          // the same block as the kernel addresses it
-    void *k_sc = ds + (o_sc - o_ids);
-    rc = beam64_search_dev(h, (const int32_t *)h->d_stage, U, L, beam, leaf_level, (int32_t *)ds, out_sc64 ? (double *)k_sc : nullptr,
-                           out_sc64 ? nullptr : (float *)k_sc, (int32_t *)(ds + (o_cnt - o_ids)), 0, cap, nullptr, nullptr, nullptr, nullptr, &done, true);
+    void *k_sc = h->d_stage + o_sc;          // the same block as the kernel addresses it
+    rc = beam64_search_dev(h, (const int32_t *)h->d_stage, U, L, beam, leaf_level, (int32_t *)(h->d_stage + o_ids), out_sc64 ? (double *)k_sc : nullptr,
+                           out_sc64 ? nullptr : (float *)k_sc, (int32_t *)(h->d_stage + o_cnt), 0, cap, nullptr, nullptr, nullptr, nullptr, &done, true);
     if (rc != DM_OK) return rc;
     if (done) {
-      bool ok = false;
-      for (long spin = 0; !ok; spin++) {
-        ok = true;
-        for (int64_t u = 0; u < U; u++) ok = ok && m_cnt[u] >= 0;
-        if (!ok && (spin & 0xFFF) == 0xFFF && hipStreamQuery(h->stream) != hipErrorNotReady) {
-          hipError_t e = hipStreamSynchronize(h->stream);        // the stream is idle (or failed) and the flags never came: a kernel fault
-          ok = true;
-          for (int64_t u = 0; u < U; u++) ok = ok && m_cnt[u] >= 0;
-          if (!ok) return fail(h, DM_ERR_HIP, std::string("fp64 OTM beam search (single-request path): ") + (e != hipSuccess ? hipGetErrorString(e) : "kernel finished without results"));
-        }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      memcpy(out_node_ids, m_ids, U * stride * 4);
-      memcpy(out_sc64 ? (void *)out_sc64 : (void *)out_sc32, m_sc, U * stride * ssz);
-      for (int64_t u = 0; u < U; u++) out_counts[u] = m_cnt[u];
-      return DM_OK;
+      if ((rc = wait_host_direct(h, m_cnt, U, "fp64 OTM beam search")) == DM_OK) copy_from_stage(h, outs, 3, U);
+      return rc;
     }
     // the fused kernel did not take it (pipeline fallback): the staged path below
   }
-  HIPCHK(h, hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq_codes, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream));
-  if (tn) {
-    HIPCHK(h, hipMemsetAsync(d_tc, 0, o_tn + up(nt * 4) - o_tc, h->stream));   // trace codes, scores and counts are adjacent
-  }
+  HIPCHK(h, hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq_codes, b_seq, hipMemcpyHostToDevice, h->stream));
+  if (tn) HIPCHK(h, hipMemsetAsync(d_tc, 0, ar.need - o_tc, h->stream));   // trace codes, scores and counts are adjacent
   rc = otm64_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, out_sc64 ? (double *)d_sc : nullptr, out_sc64 ? nullptr : (float *)d_sc,
                         d_cnt, max_levels, cap, d_tc, ts64 ? (double *)d_ts : nullptr, (tn && !ts64) ? (float *)d_ts : nullptr, d_tn);
   if (rc != DM_OK) return rc;
-  if (staged) {
-    char *hs = h->h_stage + up((size_t)U * L * 4);
-    HIPCHK(h, hipMemcpyAsync(hs, d_ids, down, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(out_node_ids, hs, U * stride * 4);
-    memcpy(out_sc64 ? (void *)out_sc64 : (void *)out_sc32, hs + (o_sc - o_ids), U * stride * ssz);
-    memcpy(out_counts, hs + (o_cnt - o_ids), (size_t)U * 4);
-    return DM_OK;
-  }
-  HIPCHK(h, hipMemcpyAsync(out_node_ids, d_ids, U * stride * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_sc64 ? (void *)out_sc64 : (void *)out_sc32, d_sc, U * stride * ssz, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_counts, d_cnt, (size_t)U * 4, hipMemcpyDeviceToHost, h->stream));
-  if (tn) {
-    HIPCHK(h, hipMemcpyAsync(tc, d_tc, nt * cap * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ts64 ? (void *)ts64 : (void *)ts32, d_ts, nt * cap * tsz, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(tn, d_tn, nt * 4, hipMemcpyDeviceToHost, h->stream));
-  }
+  HIPCHK(h, staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (staged) copy_from_stage(h, outs, 3, U);
   return DM_OK;
 }
 

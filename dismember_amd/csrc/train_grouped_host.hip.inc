@@ -38,17 +38,12 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   double *grad = (double *)h->d_grad;
   // every launch gets an event pair (dm_kernel_timing_get_kind: 40 = per-user setup, 41 = the row kernel, 42 = dW1a + per-user sums,
   // 43 = per-user backward, 44 = dW1b / datt.W): bench.py prices the row kernel against the fp64 matrix peak from these
-  struct Kind { dm_ctx *h; ~Kind() { h->ev_next_kind = 0; } } kind_{h};
   auto timed = [&](int kind, auto launch) -> int {
-    h->ev_next_kind = kind;
-    hipEvent_t ea, eb;
-    const int rc_ = next_events(h, &ea, &eb);
-    if (rc_ != DM_OK) return rc_;
-    HIPCHK(h, hipEventRecord(ea, h->stream));
+    LaunchTimer tm(h, kind);
+    if (tm.rc != DM_OK) return tm.rc;
     launch();
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(eb, h->stream));
-    return DM_OK;
+    return tm.stop();
   };
   // ---- per-user setup
   TgSetupParams sp{};

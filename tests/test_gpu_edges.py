@@ -1033,7 +1033,7 @@ def test_clone_of_an_f64_model_serves_the_fp64_search(oracle):
 
 def test_host_buffer_searches_pipeline_their_downloads_and_equal_the_device_resident_path():
     """Large host-buffer requests (dm_tdm_beam_search / dm_otm_beam_search) are cut into chunks of users whose result downloads run
-    under the kernels of the chunks behind them (host_pipe_chunks, dm_hip.hip).  Same ids, scores and counts as ONE launch over the
+    under the kernels of the chunks behind them (host_pipe_plan, dm_hip.hip).  Same ids, scores and counts as ONE launch over the
     device-resident request (dm_*_beam_search_dev), for a user count that does not divide into the chunks; the scored-rows counter
     covers the whole request."""
     from dismember_amd import Engine
