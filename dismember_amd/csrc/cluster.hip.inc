@@ -748,13 +748,8 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
 
 static int cluster_dispatch(dm_ctx *h, const float *d_X, int EP, int64_t n, int E, int R, int max_iter, double tol, uint64_t seed, int32_t *codes_out,
                             const dm_cluster_trace *trace, dm_cluster_stats *stats) {
-  switch (EP) {
-    case 16: return cluster_run<16>(h, d_X, n, E, R, max_iter, tol, seed, codes_out, trace, stats);
-    case 32: return cluster_run<32>(h, d_X, n, E, R, max_iter, tol, seed, codes_out, trace, stats);
-    case 64: return cluster_run<64>(h, d_X, n, E, R, max_iter, tol, seed, codes_out, trace, stats);
-    case 128: return cluster_run<128>(h, d_X, n, E, R, max_iter, tol, seed, codes_out, trace, stats);
-  }
-  return fail(h, DM_ERR_UNSUPPORTED, "dm_cluster_tree: embed size");
+  return dispatch_E(h, EP, "dm_cluster_tree: embed size",
+                    [&](auto e) { return cluster_run<decltype(e)::value>(h, d_X, n, E, R, max_iter, tol, seed, codes_out, trace, stats); });
 }
 
 static int cluster_check(dm_ctx *h, const char *who, int64_t n, int restarts, int max_iter, double tol, const void *codes_out) {

@@ -20,15 +20,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
-
-// Development builds (tools/build_probe.sh DM_DEV_LIGHT ...): only the E = 128 instances of the kernel templates are compiled — a third of
-// the compile time while iterating on one kernel.  Never the product build: models of other embedding sizes fail with "unsupported".
-#ifdef DM_DEV_LIGHT
-#define DM_IF_ALL_E(...)
-#else
-#define DM_IF_ALL_E(...) __VA_ARGS__
-#endif
 
 #include "beam_kernel.hip.inc"
 #include "beam_kernel_w.hip.inc"
@@ -213,6 +206,21 @@ static std::string g_create_err;
 static int fail(dm_ctx *h, int code, const std::string &msg) {
   if (h) h->err = msg; else g_create_err = msg;
   return code;
+}
+
+// The one embed-size dispatch of the kernel templates: f(std::integral_constant<int, E>) for E = 16 / 32 / 64 / 128, from MIN_E up
+// (the split-fp16 kernels start at 32: no smaller instance exists, none is instantiated here); any other size fails with the caller's
+// message.  Development builds (tools/build_probe.sh DM_DEV_LIGHT ...) compile the E = 128 instances only — a third of the compile
+// time while iterating on one kernel.  Never the product build: models of other embedding sizes fail with "unsupported".
+template <int MIN_E = 16, typename F>
+static int dispatch_E(dm_ctx *h, int E, const char *unsupported, F &&f) {
+#ifndef DM_DEV_LIGHT
+  if constexpr (MIN_E <= 16) { if (E == 16) return f(std::integral_constant<int, 16>{}); }
+  if (E == 32) return f(std::integral_constant<int, 32>{});
+  if (E == 64) return f(std::integral_constant<int, 64>{});
+#endif
+  if (E == 128) return f(std::integral_constant<int, 128>{});
+  return fail(h, DM_ERR_UNSUPPORTED, unsupported);
 }
 
 // ------------------------------------------------------------ small kernels
@@ -629,69 +637,6 @@ int dm_tdm_id_to_code(dm_handle_t h, const int32_t *item_ids, int n, int32_t *co
   return DM_OK;
 }
 
-// derived, fragment-ordered copies of the small matrices (att.W, l1.W, l1.b, l2.W, l2.b) from the
-// host copy of the tail of the compact vector
-template <typename T>
-static int upload_derived(dm_ctx *h, int E, const T *att_w) {
-  const T *l1_w = att_w + (int64_t)E * E, *l1_b = l1_w + (int64_t)E * 2 * E;
-  const T *l2_w = l1_b + E, *l2_b = l2_w + E;
-  const int NJ = E / 16, NT = E / 16;
-  std::vector<float> wfrag((size_t)NJ * NT * 64 * 4), afrag(wfrag.size()), bfrag(wfrag.size()), b1(E), w2(E);
-  for (int jc = 0; jc < NJ; jc++)
-    for (int nt = 0; nt < NT; nt++)
-      for (int ln = 0; ln < 64; ln++)
-        for (int t = 0; t < 4; t++) {
-          int g = ln >> 4, n = ln & 15;
-          const size_t fi = (((size_t)jc * NT + nt) * 64 + ln) * 4 + t;
-          const int k = 16 * jc + 4 * g + t, o = 16 * nt + n;
-          wfrag[fi] = (float)l1_w[(size_t)o * 2 * E + k];        // B[k][o] = W1a[o][k]
-          afrag[fi] = (float)att_w[(size_t)o * E + k];            // B[k][o] = att_w[o][k]
-          bfrag[fi] = (float)l1_w[(size_t)o * 2 * E + E + k];    // B[k][o] = W1b[o][k]
-        }
-  for (int o = 0; o < E; o++) { b1[o] = (float)l1_b[o]; w2[o] = (float)l2_w[o]; }
-  h->b2 = (float)l2_b[0];
-  // A-fragment order for the transposed products of the rows kernel: [mt][jc][lane] float4,
-  // element t = W[16mt + (lane&15)][16jc + 4(lane>>4) + t]
-  std::vector<float> attA(wfrag.size()), w1aA(wfrag.size()), w1bA(wfrag.size());
-  for (int mt = 0; mt < NT; mt++)
-    for (int jc = 0; jc < NJ; jc++)
-      for (int ln = 0; ln < 64; ln++)
-        for (int t = 0; t < 4; t++) {
-          const size_t fi = (((size_t)mt * NJ + jc) * 64 + ln) * 4 + t;
-          const int o = 16 * mt + (ln & 15), k = 16 * jc + 4 * (ln >> 4) + t;
-          attA[fi] = (float)att_w[(size_t)o * E + k];
-          w1aA[fi] = (float)l1_w[(size_t)o * 2 * E + k];
-          w1bA[fi] = (float)l1_w[(size_t)o * 2 * E + E + k];
-        }
-  ALLOC(h, h->d_attA, attA.size() * 4);
-  ALLOC(h, h->d_w1aA, w1aA.size() * 4);
-  ALLOC(h, h->d_w1bA, w1bA.size() * 4);
-  HIPCHK(h, hipMemcpy(h->d_attA, attA.data(), attA.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_w1aA, w1aA.data(), w1aA.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_w1bA, w1bA.data(), w1bA.size() * 4, hipMemcpyHostToDevice));
-  ALLOC(h, h->d_wfrag, wfrag.size() * 4);
-  ALLOC(h, h->d_afrag, afrag.size() * 4);
-  ALLOC(h, h->d_bfrag, bfrag.size() * 4);
-  ALLOC(h, h->d_b1, E * 4);
-  ALLOC(h, h->d_w2, E * 4);
-  HIPCHK(h, hipMemcpy(h->d_wfrag, wfrag.data(), wfrag.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_afrag, afrag.data(), afrag.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_bfrag, bfrag.data(), bfrag.size() * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_b1, b1.data(), E * 4, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_w2, w2.data(), E * 4, hipMemcpyHostToDevice));
-  // transposes in the loaded dtype for the general forward
-  std::vector<T> attT_t((size_t)E * E), l1T_t((size_t)2 * E * E);
-  for (int o = 0; o < E; o++) {
-    for (int k = 0; k < E; k++) attT_t[(size_t)k * E + o] = att_w[(size_t)o * E + k];
-    for (int k = 0; k < 2 * E; k++) l1T_t[(size_t)k * E + o] = l1_w[(size_t)o * 2 * E + k];
-  }
-  ALLOC(h, h->d_att_wT_t, attT_t.size() * sizeof(T));
-  ALLOC(h, h->d_l1T_t, l1T_t.size() * sizeof(T));
-  HIPCHK(h, hipMemcpy(h->d_att_wT_t, attT_t.data(), attT_t.size() * sizeof(T), hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_l1T_t, l1T_t.data(), l1T_t.size() * sizeof(T), hipMemcpyHostToDevice));
-  return DM_OK;
-}
-
 // Embedding sizes the kernels are built for; any other size up to 128 is zero-padded to the next one at load (S/nn/Attention.scala,
 // T/model/DIN.scala take any embedSize).  Zero columns / rows change no product: q.k, att.W k, W1 [q ; att] and w2 . h keep their
 // values, the padded hidden units are relu(0) = 0, and training leaves the padding at zero (its gradients are products with zero
@@ -730,101 +675,7 @@ static void unpad_compact(const T *src, int E, int Ep, int64_t NI, T *dst) {    
   d_w2[E] = s_w2[Ep];
 }
 
-template <typename T>
-static int load_weights_t(dm_ctx *h, int E, int64_t num_index, const T *w, int64_t n_elems) {
-  const int64_t need = num_index * E + (int64_t)E * E + (int64_t)E * 2 * E + E + E + 1;
-  if (need != n_elems) return fail(h, DM_ERR_INVALID, "dm_load_weights_din: n_elems does not match the DIN layout for (E, num_index)");
-  free_weights(h);
-  ALLOC(h, h->d_compact, (size_t)n_elems * sizeof(T));
-  HIPCHK(h, hipMemcpy(h->d_compact, w, (size_t)n_elems * sizeof(T), hipMemcpyHostToDevice));
-  // f32 table for the beam kernels
-  if (sizeof(T) == 4) { h->d_emb32 = (float *)h->d_compact; h->emb32_owned = false; }
-  else {
-    ALLOC(h, h->d_emb32, (size_t)num_index * E * 4);
-    h->emb32_owned = true;
-    hipLaunchKernelGGL(dm_f64_to_f32_kernel, dim3(2048), dim3(256), 0, h->stream, (const double *)h->d_compact,
-                       h->d_emb32, num_index * E);
-    HIPCHK(h, hipGetLastError());
-  }
-  int rc = upload_derived<T>(h, E, w + num_index * E);
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->embed = E; h->embed_log = E; h->num_index = num_index; h->w_loaded = true; h->split_dirty = true; h->table_dense_change = true;
-  return DM_OK;
-}
-template <typename T>
-static int load_weights_any_t(dm_ctx *h, int E, int64_t num_index, const T *w, int64_t n_elems) {
-  const int Ep = native_embed(E);
-  if (Ep == E) return load_weights_t<T>(h, E, num_index, w, n_elems);
-  if (n_elems != compact_len_for(num_index, E)) return fail(h, DM_ERR_INVALID, "dm_load_weights_din: n_elems does not match the DIN layout for (E, num_index)");
-  std::vector<T> padded((size_t)compact_len_for(num_index, Ep));
-  pad_compact<T>(w, E, Ep, num_index, padded.data());
-  const int rc = load_weights_t<T>(h, Ep, num_index, padded.data(), (int64_t)padded.size());
-  if (rc == DM_OK) h->embed_log = E;
-  return rc;
-}
-
-int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, const void *compact, int64_t n_elems) {
-  if (!h) return DM_ERR_INVALID;
-  DM_OWNER_ONLY(h, "dm_load_weights_din");
-  if (!compact || num_index <= 0) return fail(h, DM_ERR_INVALID, "dm_load_weights_din: bad arguments");
-  if (E < 1 || E > 128)
-    return fail(h, DM_ERR_UNSUPPORTED, "dm_load_weights_din: embed size must be 1 .. 128 (sizes other than 16 / 32 / 64 / 128 are zero-padded to the next of them; at E = 256 the "
-                "fp16 hi / lo planes of W1a are 256 KB against 64 KB of AccVGPRs per wave and 160 KB of LDS per CU: the weights would have to stream "
-                "per 128-column slab, ~4.3 x the E = 128 time per scored row — DESIGN.md, not built)");
-  if (dtype != DM_F32 && dtype != DM_F64) return fail(h, DM_ERR_INVALID, "dm_load_weights_din: dtype");
-  HIPCHK(h, hipSetDevice(h->device));
-  h->dtype = dtype;
-  return dtype == DM_F32 ? load_weights_any_t<float>(h, E, num_index, (const float *)compact, n_elems)
-                         : load_weights_any_t<double>(h, E, num_index, (const double *)compact, n_elems);
-}
-
-int dm_load_weights_din_dev(dm_handle_t h, int E, int64_t num_index, float *d_compact, int64_t n_elems) {
-  if (!h) return DM_ERR_INVALID;
-  DM_OWNER_ONLY(h, "dm_load_weights_din_dev");
-  if (!d_compact || num_index <= 0) return fail(h, DM_ERR_INVALID, "dm_load_weights_din_dev: bad arguments");
-  if (E != 16 && E != 32 && E != 64 && E != 128) return fail(h, DM_ERR_UNSUPPORTED, "dm_load_weights_din_dev: embed size must be 16, 32, 64 or 128");
-  const int64_t need = num_index * E + (int64_t)E * E + (int64_t)E * 2 * E + E + E + 1;
-  if (need != n_elems) return fail(h, DM_ERR_INVALID, "dm_load_weights_din_dev: n_elems does not match the DIN layout for (E, num_index)");
-  HIPCHK(h, hipSetDevice(h->device));
-  free_weights(h);
-  h->dtype = DM_F32;
-  h->d_compact = d_compact; h->d_emb32 = d_compact; h->emb32_owned = false;
-  const int64_t tail = n_elems - num_index * E;
-  std::vector<float> t((size_t)tail);
-  HIPCHK(h, hipMemcpy(t.data(), d_compact + num_index * E, (size_t)tail * 4, hipMemcpyDeviceToHost));
-  int rc = upload_derived<float>(h, E, t.data());
-  if (rc != DM_OK) return rc;
-  h->embed = E; h->embed_log = E; h->num_index = num_index; h->w_loaded = true; h->split_dirty = true; h->table_dense_change = true;
-  return DM_OK;
-}
-
-// the fp64 counterpart (the reference's OTM model is DIN[Double]): same ownership rule; the f32 copy of the table that the
-// throughput-mode beam kernels read is made here
-int dm_load_weights_din_dev_f64(dm_handle_t h, int E, int64_t num_index, double *d_compact, int64_t n_elems) {
-  if (!h) return DM_ERR_INVALID;
-  DM_OWNER_ONLY(h, "dm_load_weights_din_dev_f64");
-  if (!d_compact || num_index <= 0) return fail(h, DM_ERR_INVALID, "dm_load_weights_din_dev_f64: bad arguments");
-  if (E != 16 && E != 32 && E != 64 && E != 128) return fail(h, DM_ERR_UNSUPPORTED, "dm_load_weights_din_dev_f64: embed size must be 16, 32, 64 or 128");
-  const int64_t need = num_index * E + (int64_t)E * E + (int64_t)E * 2 * E + E + E + 1;
-  if (need != n_elems) return fail(h, DM_ERR_INVALID, "dm_load_weights_din_dev_f64: n_elems does not match the DIN layout for (E, num_index)");
-  HIPCHK(h, hipSetDevice(h->device));
-  free_weights(h);
-  h->dtype = DM_F64;
-  h->d_compact = d_compact;
-  ALLOC(h, h->d_emb32, (size_t)num_index * E * 4);
-  h->emb32_owned = true;
-  hipLaunchKernelGGL(dm_f64_to_f32_kernel, dim3(4096), dim3(256), 0, h->stream, (const double *)d_compact, h->d_emb32, num_index * E);
-  HIPCHK(h, hipGetLastError());
-  const int64_t tail = n_elems - num_index * E;
-  std::vector<double> t((size_t)tail);
-  HIPCHK(h, hipMemcpy(t.data(), d_compact + num_index * E, (size_t)tail * 8, hipMemcpyDeviceToHost));
-  int rc = upload_derived<double>(h, E, t.data());
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->embed = E; h->embed_log = E; h->num_index = num_index; h->w_loaded = true; h->split_dirty = true; h->table_dense_change = true;
-  return DM_OK;
-}
+#include "model_weights.hip.inc"
 
 template <typename T>
 __global__ void dm_fill_normal_kernel(T *out, int64_t n, float mean, float std, unsigned long long seed) {
@@ -1027,23 +878,13 @@ static int din_rows_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs
     q.emb_scale = ldexpf(1.0f, h->sh_e); q.out_unscale = ldexpf(1.0f, -(h->sh_e + h->sh_r));
     q.num_index = h->num_index; q.codes = d_codes; q.seqs = d_seqs; q.rowmask = d_rowmask; q.B = B; q.L = L; q.out = d_out;
     q.sm_scale = sm_scale32(h); q.seq_div = seq_div;
-    switch (h->embed) {
-      DM_IF_ALL_E(case 32: return launch_rows_split_E<32>(h, q);)
-      DM_IF_ALL_E(case 64: return launch_rows_split_E<64>(h, q);)
-      case 128: return launch_rows_split_E<128>(h, q);
-    }
+    return dispatch_E<32>(h, h->embed, "unsupported embed size", [&](auto e) { return launch_rows_split_E<decltype(e)::value>(h, q); });
   }
   RowsParams p;
   p.emb = h->d_emb32; p.attA = h->d_attA; p.w1aA = h->d_w1aA; p.w1bA = h->d_w1bA; p.b1 = h->d_b1; p.w2 = h->d_w2;
   p.b2 = h->b2; p.num_index = h->num_index; p.codes = d_codes; p.seqs = d_seqs; p.rowmask = d_rowmask; p.B = B; p.L = L;
   p.out = d_out; p.sm_scale = sm_scale32(h); p.seq_div = seq_div;
-  switch (h->embed) {
-    DM_IF_ALL_E(case 16: return launch_rows_E<16>(h, p);)
-    DM_IF_ALL_E(case 32: return launch_rows_E<32>(h, p);)
-    DM_IF_ALL_E(case 64: return launch_rows_E<64>(h, p);)
-    case 128: return launch_rows_E<128>(h, p);
-  }
-  return fail(h, DM_ERR_UNSUPPORTED, "unsupported embed size");
+  return dispatch_E(h, h->embed, "unsupported embed size", [&](auto e) { return launch_rows_E<decltype(e)::value>(h, p); });
 }
 
 int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, const int32_t *pad_flat_idx,
@@ -1438,12 +1279,8 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       HIPCHK(h, hipMemsetAsync(h->d_defer, 0, 16, h->stream));
       p.defer_count = (unsigned long long *)h->d_defer;
       p.defer_users = (int32_t *)((char *)h->d_defer + 16);
-      int rc = DM_OK;
-      switch (h->embed) {
-        DM_IF_ALL_E(case 32: rc = launch_beam_w_E<32>(h, p, pl); break;)
-        DM_IF_ALL_E(case 64: rc = launch_beam_w_E<64>(h, p, pl); break;)
-        default: rc = launch_beam_w_E<128>(h, p, pl); break;
-      }
+      const char *const no_split = "the split-fp16 scorer needs an embedding size of 32, 64 or 128";
+      int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
       if (rc != DM_OK) return rc;
       // second pass (an empty list costs one launch): same parameters, the list as the work queue, its own frontier layout
       SearchPlan pl2;
@@ -1469,28 +1306,14 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       p2.next_user = (unsigned long long *)((char *)h->d_defer + 8);
       p2.defer_count = nullptr; p2.defer_users = nullptr;
       h->ev_next_kind = 1;
-      switch (h->embed) {
-        DM_IF_ALL_E(case 32: rc = launch_beam_E<32, true>(h, p2, pl2); break;)
-        DM_IF_ALL_E(case 64: rc = launch_beam_E<64, true>(h, p2, pl2); break;)
-        default: rc = launch_beam_E<128, true>(h, p2, pl2); break;
-      }
+      rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p2, pl2); });
       h->ev_next_kind = 0;
       return rc;
     }
-    switch (h->embed) {
-      DM_IF_ALL_E(case 32: return launch_beam_E<32, true>(h, p, pl);)
-      DM_IF_ALL_E(case 64: return launch_beam_E<64, true>(h, p, pl);)
-      case 128: return launch_beam_E<128, true>(h, p, pl);
-    }
-    return fail(h, DM_ERR_UNSUPPORTED, "the split-fp16 scorer needs an embedding size of 32, 64 or 128");
+    return dispatch_E<32>(h, h->embed, "the split-fp16 scorer needs an embedding size of 32, 64 or 128",
+                          [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p, pl); });
   }
-  switch (h->embed) {
-    DM_IF_ALL_E(case 16: return launch_beam_E<16, false>(h, p, pl);)
-    DM_IF_ALL_E(case 32: return launch_beam_E<32, false>(h, p, pl);)
-    DM_IF_ALL_E(case 64: return launch_beam_E<64, false>(h, p, pl);)
-    case 128: return launch_beam_E<128, false>(h, p, pl);
-  }
-  return fail(h, DM_ERR_UNSUPPORTED, "unsupported embed size");
+  return dispatch_E(h, h->embed, "unsupported embed size", [&](auto e) { return launch_beam_E<decltype(e)::value, false>(h, p, pl); });
 }
 
 int dm_set_scorer_mode(dm_handle_t h, int mode) {

@@ -169,12 +169,7 @@ static int otm_pl_launch_attn_ne(dm_ctx *h, const Otm64Attn<T> &a) {
 }
 template <typename T>
 static int otm_pl_launch_attn(dm_ctx *h, const Otm64Attn<T> &a) {
-  switch (a.E) {
-    case 16: return otm_pl_launch_attn_ne<T, 1>(h, a);
-    case 32: return otm_pl_launch_attn_ne<T, 2>(h, a);
-    case 64: return otm_pl_launch_attn_ne<T, 4>(h, a);
-    default: return otm_pl_launch_attn_ne<T, 8>(h, a);
-  }
+  return dispatch_E(h, a.E, "unsupported embed size", [&](auto e) { return otm_pl_launch_attn_ne<T, decltype(e)::value / 16>(h, a); });
 }
 
 template <typename T>
@@ -327,12 +322,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   p.out_ids = d_ids; p.out_sc64 = d_sc64; p.out_sc32 = d_sc32; p.out_counts = d_counts; p.out_stride = 2 * beam;
   p.tr_codes = d_tc; p.tr_sc64 = d_ts64; p.tr_sc32 = d_ts32; p.tr_counts = d_tn; p.tr_levels = d_tn ? max_levels : 0; p.tr_cap = cap;
   p.scratch = (double *)h->d_scratch64; p.next_user = h->d_rows + 1; p.scored_rows = (p.static_users && U <= 64) ? h->d_rows + 3 : h->d_rows;
-  switch (E) {
-    DM_IF_ALL_E(case 16: rc = launch_beam64_E<16>(h, p, grid, lds); break;)
-    DM_IF_ALL_E(case 32: rc = launch_beam64_E<32>(h, p, grid, lds); break;)
-    DM_IF_ALL_E(case 64: rc = launch_beam64_E<64>(h, p, grid, lds); break;)
-    default: rc = launch_beam64_E<128>(h, p, grid, lds); break;
-  }
+  rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) { return launch_beam64_E<decltype(e)::value>(h, p, grid, lds); });
   if (rc == DM_OK) *done = true;
   return rc;
 }

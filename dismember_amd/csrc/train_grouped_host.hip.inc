@@ -153,13 +153,8 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
     }
   }
   HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 16, h->stream));
-  int rc;
-  switch (h->embed) {
-    DM_IF_ALL_E(case 16: rc = tg_launch_E<16>(h, d_seq, d_umask, d_codes, d_labels, U, n, L); break;)
-    DM_IF_ALL_E(case 32: rc = tg_launch_E<32>(h, d_seq, d_umask, d_codes, d_labels, U, n, L); break;)
-    DM_IF_ALL_E(case 64: rc = tg_launch_E<64>(h, d_seq, d_umask, d_codes, d_labels, U, n, L); break;)
-    default: rc = tg_launch_E<128>(h, d_seq, d_umask, d_codes, d_labels, U, n, L); break;
-  }
+  int rc = dispatch_E(h, h->embed, "unsupported embed size",
+                      [&](auto e) { return tg_launch_E<decltype(e)::value>(h, d_seq, d_umask, d_codes, d_labels, U, n, L); });
   if (rc != DM_OK) return rc;
   // rows the gradient reached: the candidates and the users' histories (each history once, not once per row)
   hipLaunchKernelGGL(dm_mark_touched_kernel, dim3(256), dim3(256), 0, h->stream, d_codes, (const int32_t *)nullptr, B, 0, h->d_touch_bits,

@@ -12,85 +12,26 @@ static int64_t compact_len(const dm_ctx *h) {
 }
 static size_t elem_size(const dm_ctx *h) { return h->dtype == DM_F64 ? 8 : 4; }
 
-template <int E>
-static int refresh_fragments_E(dm_ctx *h) {
-  if (h->dtype == DM_F64) {
-    // fp64 model: the training kernels' A fragments (six E x E blocks in d_tr64) and the transposes of the general forward; the
-    // fp64 beam kernel's fragments and the f32 mirror of the throughput modes are rebuilt lazily by their users
-    const double *att_w = (const double *)h->d_compact + h->num_index * E;
-    const double *l1_w = att_w + (int64_t)E * E;
-    double *f = (double *)h->d_tr64;
-    const size_t n = (size_t)E * E;
-    hipLaunchKernelGGL((dm_refresh_fragments_kernel<double, E>), dim3(64), dim3(256), 0, h->stream, att_w, l1_w, (double *)nullptr,
-                       (double *)nullptr, (double *)nullptr, f, f + n, f + 2 * n, f + 3 * n, f + 4 * n, f + 5 * n,
-                       (double *)h->d_att_wT_t, (double *)h->d_l1T_t);
-    HIPCHK(h, hipGetLastError());
-    return DM_OK;
-  }
-  const float *att_w = (const float *)h->d_compact + h->num_index * E;
-  const float *l1_w = att_w + (int64_t)E * E;
-  hipLaunchKernelGGL((dm_refresh_fragments_kernel<float, E>), dim3(64), dim3(256), 0, h->stream, att_w, l1_w, (float *)h->d_wfrag,
-                     (float *)h->d_afrag, (float *)h->d_bfrag, (float *)h->d_attA, (float *)h->d_w1aA, (float *)h->d_w1bA,
-                     (float *)h->d_attTA, (float *)h->d_w1aTA, (float *)h->d_w1bTA, (float *)h->d_att_wT_t, (float *)h->d_l1T_t);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
-}
+// The weights moved (dm_adam_step) or training state was just allocated (dm_train_init): the derived copies in the model's own type
+// follow at once; an f64 model's f32 mirror is left to ensure_f32_mirror
 static int refresh_fragments(dm_ctx *h) {
-  int rc;
   model_changed(h);      // (clones re-mirror: the lazily rebuilt copies are stale)
   h->split_dirty = true;   // the fp16 planes and scales of the split scorer follow the weights
   h->frag64_dirty = true;  // so do the fp64 beam kernel's fragments
-  switch (h->embed) {
-    DM_IF_ALL_E(case 16: rc = refresh_fragments_E<16>(h); break;)
-    DM_IF_ALL_E(case 32: rc = refresh_fragments_E<32>(h); break;)
-    DM_IF_ALL_E(case 64: rc = refresh_fragments_E<64>(h); break;)
-    default: rc = refresh_fragments_E<128>(h); break;
-  }
-  if (rc != DM_OK) return rc;
-  if (h->dtype == DM_F64) { h->f32_mirror_dirty = true; return DM_OK; }
-  const int E = h->embed;
-  const float *tail = (const float *)h->d_compact + h->num_index * E + 3 * (int64_t)E * E;   // l1.b ; l2.W ; l2.b
-  HIPCHK(h, hipMemcpyAsync(h->d_b1, tail, E * 4, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_w2, tail + E, E * 4, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&h->b2, tail + 2 * E, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return DM_OK;
+  const int rc = derive_small(h, DERIVE_OWN);
+  if (rc == DM_OK && h->dtype == DM_F64) h->f32_mirror_dirty = true;
+  return rc;
 }
 
 // f64 model whose weights moved (dm_adam_step): bring the f32 copies the throughput-mode beam kernels read up to date
 // (table, fragment-ordered small matrices, b1 / w2 / b2).  No-op for f32 models and while nothing changed.
-template <int E>
-static int f32_mirror_frags_E(dm_ctx *h, const float *tail32) {
-  hipLaunchKernelGGL((dm_refresh_fragments_kernel<float, E>), dim3(64), dim3(256), 0, h->stream, tail32, tail32 + (size_t)E * E,
-                     (float *)h->d_wfrag, (float *)h->d_afrag, (float *)h->d_bfrag, (float *)h->d_attA, (float *)h->d_w1aA,
-                     (float *)h->d_w1bA, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr, (float *)nullptr);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
-}
 static int ensure_f32_mirror(dm_ctx *h) {
   std::lock_guard<std::recursive_mutex> lk_(h->mu);
   if (h->dtype != DM_F64 || !h->f32_mirror_dirty) return DM_OK;
   model_changed(h);
-  const int E = h->embed;
-  const int64_t nt = 3 * (int64_t)E * E + 2 * E + 1;
-  hipLaunchKernelGGL(dm_f64_to_f32_kernel, dim3(4096), dim3(256), 0, h->stream, (const double *)h->d_compact, h->d_emb32, h->num_index * (int64_t)E);
-  HIPCHK(h, hipGetLastError());
-  if (!h->d_tail32) ALLOC(h, h->d_tail32, (size_t)nt * 4);
-  hipLaunchKernelGGL(dm_f64_to_f32_kernel, dim3(64), dim3(256), 0, h->stream, (const double *)h->d_compact + h->num_index * E, (float *)h->d_tail32, nt);
-  HIPCHK(h, hipGetLastError());
-  int rc;
-  switch (E) {
-    DM_IF_ALL_E(case 16: rc = f32_mirror_frags_E<16>(h, (const float *)h->d_tail32); break;)
-    DM_IF_ALL_E(case 32: rc = f32_mirror_frags_E<32>(h, (const float *)h->d_tail32); break;)
-    DM_IF_ALL_E(case 64: rc = f32_mirror_frags_E<64>(h, (const float *)h->d_tail32); break;)
-    default: rc = f32_mirror_frags_E<128>(h, (const float *)h->d_tail32); break;
-  }
+  int rc = mirror_table32(h);
+  if (rc == DM_OK) rc = derive_small(h, DERIVE_F32_MIRROR);
   if (rc != DM_OK) return rc;
-  const float *tail = (const float *)h->d_tail32 + 3 * (int64_t)E * E;
-  HIPCHK(h, hipMemcpyAsync(h->d_b1, tail, E * 4, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_w2, tail + E, E * 4, hipMemcpyDeviceToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&h->b2, tail + 2 * E, 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
   h->f32_mirror_dirty = false; h->split_dirty = true; h->table_dense_change = true;
   return DM_OK;
 }
@@ -231,12 +172,7 @@ static int train_fb_launch(dm_ctx *h, const int32_t *d_codes, const int32_t *d_s
   wg.emb = base; wg.codes = d_codes; wg.DZ = p.DZ; wg.AT = p.AT; wg.DA = p.DA; wg.CB = p.CB; wg.B = B;
   wg.num_index = h->num_index; wg.grad = (T *)h->d_grad;
   wg.chunk = 256;
-  switch (E) {
-    DM_IF_ALL_E(case 16: return launch_train_E<T, 16>(h, p, wg);)
-    DM_IF_ALL_E(case 32: return launch_train_E<T, 32>(h, p, wg);)
-    DM_IF_ALL_E(case 64: return launch_train_E<T, 64>(h, p, wg);)
-    default: return launch_train_E<T, 128>(h, p, wg);
-  }
+  return dispatch_E(h, E, "unsupported embed size", [&](auto e) { return launch_train_E<T, decltype(e)::value>(h, p, wg); });
 }
 
 // The general-rows forward of an f64 model on the matrix pipe: the forward half of dm_train_rows_kernel<double> (same fragments, same
@@ -268,15 +204,7 @@ static bool fwd64_ready(dm_ctx *h, int L) {
   std::lock_guard<std::recursive_mutex> lk_(h->mu);
   if (h->d_tr64) return true;
   if (dm_alloc(h, &h->d_tr64, 6 * (size_t)h->embed * h->embed * 8) != DM_OK) { h->d_tr64 = nullptr; return false; }
-  int rc = DM_ERR_UNSUPPORTED;
-  switch (h->embed) {
-    DM_IF_ALL_E(case 16: rc = refresh_fragments_E<16>(h); break;)
-    DM_IF_ALL_E(case 32: rc = refresh_fragments_E<32>(h); break;)
-    DM_IF_ALL_E(case 64: rc = refresh_fragments_E<64>(h); break;)
-    case 128: rc = refresh_fragments_E<128>(h); break;
-    default: break;
-  }
-  if (rc != DM_OK) { dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; return false; }
+  if (derive_small(h, DERIVE_OWN) != DM_OK) { dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; return false; }
   return true;
 }
 static int rows_fwd64(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, const unsigned *d_rowmask, int64_t B, int L, double *d_out) {
@@ -296,12 +224,7 @@ static int rows_fwd64(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, 
   HIPCHK(h, hipStreamSynchronize(h->stream));
   p.b2 = b2;
   p.codes = d_codes; p.seqs = d_seqs; p.rowmask = d_rowmask; p.B = B; p.L = L; p.sm_scale = sm_scale64(h); p.logits = d_out;
-  switch (E) {
-    DM_IF_ALL_E(case 16: return rows_fwd64_E<16>(h, p);)
-    DM_IF_ALL_E(case 32: return rows_fwd64_E<32>(h, p);)
-    DM_IF_ALL_E(case 64: return rows_fwd64_E<64>(h, p);)
-    default: return rows_fwd64_E<128>(h, p);
-  }
+  return dispatch_E(h, E, "unsupported embed size", [&](auto e) { return rows_fwd64_E<decltype(e)::value>(h, p); });
 }
 
 // all pointers device; accumulates this batch's gradients (mean BCE over the B rows) into the handle's gradient

@@ -606,8 +606,8 @@ __global__ void dm_adam_rows_kernel_f64(double *w, double *g, double *s, double 
 }
 
 // Rebuild every fragment-ordered copy of the three small matrices from the (updated) compact vector.  The fp32 beam kernels'
-// B-fragment copies (wfrag / afrag / bfrag) exist for float only; null pointers skip a group (the f32 mirror of an f64 model
-// has no transposed fragments and no plain transposes).
+// B-fragment copies (wfrag / afrag / bfrag) exist for float only.  Each group is skipped when its first pointer is null: wfrag, attA
+// (an f64 model without d_tr64), attTA (no training state), att_wT (the f32 mirror of an f64 model has no transposes of its own).
 template <typename T, int E>
 __global__ void dm_refresh_fragments_kernel(const T *att_w, const T *l1_w, T *wfrag, T *afrag, T *bfrag,
                                             T *attA, T *w1aA, T *w1bA, T *attTA, T *w1aTA, T *w1bTA,
@@ -629,7 +629,7 @@ __global__ void dm_refresh_fragments_kernel(const T *att_w, const T *l1_w, T *wf
       const int k = 16 * hi + 4 * (ln >> 4) + t, o = 16 * lo + col;
       wfrag[fi] = l1_w[o * 2 * E + k]; afrag[fi] = att_w[o * E + k]; bfrag[fi] = l1_w[o * 2 * E + E + k];
     }
-    {   // A-fragment order [mt = hi][jc = lo], k in the element type's feature map
+    if (attA) {   // A-fragment order [mt = hi][jc = lo], k in the element type's feature map
       const int o = 16 * hi + col, k = TR::feat(lo, ln >> 4, t);
       attA[fi] = att_w[o * E + k]; w1aA[fi] = l1_w[o * 2 * E + k]; w1bA[fi] = l1_w[o * 2 * E + E + k];
       if (attTA) { attTA[fi] = att_w[k * E + o]; w1aTA[fi] = l1_w[k * 2 * E + o]; w1bTA[fi] = l1_w[k * 2 * E + E + o]; }

@@ -6,7 +6,6 @@
 #include <cstdint>
 #include <type_traits>
 #include <utility>
-#define DM_IF_ALL_E(...)
 #include "../dismember_amd/csrc/beam_kernel.hip.inc"
 #include "../dismember_amd/csrc/beam_kernel_w.hip.inc"
 template __global__ void dm_beam_w_kernel<128, 3>(BeamParams);

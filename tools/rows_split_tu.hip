@@ -4,7 +4,6 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
-#define DM_IF_ALL_E(...)
 #include "../dismember_amd/csrc/beam_kernel.hip.inc"
 #include "../dismember_amd/csrc/rows_kernel.hip.inc"
 template __global__ void dm_din_rows_split_kernel<128>(RowsSplitParams);

@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#define DM_IF_ALL_E(...)
 #include "../dismember_amd/csrc/beam_kernel.hip.inc"
 #include "../dismember_amd/csrc/beam_kernel_w.hip.inc"
 #include "../dismember_amd/csrc/beam_kernel_f64.hip.inc"
