@@ -34,6 +34,8 @@
 
 #define DM_VERSION 100
 
+#define DM_LAZY_COPIES_PART 1      // struct LazyCopies
+#include "lazy_copies.hip.inc"
 // ------------------------------------------------------------------ context
 struct dm_dr_state;
 static void dm_dr_free(dm_dr_state *s);
@@ -91,31 +93,13 @@ struct dm_ctx {
   f32x4 *d_attA = nullptr, *d_w1aA = nullptr, *d_w1bA = nullptr;   // A-fragment order (rows kernel)
   float *d_b1 = nullptr, *d_w2 = nullptr;
   float b2 = 0.f;
-  // split-fp16 scorer (dm_set_scorer_mode): fp16 hi/lo planes of W1a and the power-of-two scales, rebuilt lazily
-  int scorer_mode = DM_SCORER_AUTO;
-  bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
-  bool split_dirty = true;
-  void *d_wsplit = nullptr;
-  double jtm_score_s = 0, jtm_rebal_s = 0;   // dm_jtm_last_step_seconds
-  void *d_rows_split = nullptr;   // general-rows split kernel: fp16 hi / lo planes of W1a and M = W1b att.W, then M in fp32
-  int sh_r = 0; bool rows_split_dirty = true;
-  bool emb_split_dirty = true;   // the pre-split copy of the table lags the scales (ensure_split_scales / ensure_split)
-  bool call_split = false;       // scorer arithmetic of the search being planned (split_for_call)
-  // incremental refresh inside a training loop (ensure_split_scales): the table changed only in the ACTIVE rows of the Adam step
-  bool table_dense_change = true;   // ... unless something rewrote it wholesale since the last full scan (load, dense Adam step, f64 -> f32 mirror)
-  bool sh_e_valid = false;          // sh_e comes from a full scan of the current table lineage
-  bool emb_split_need_full = true;  // d_emb_split is not (scale sh_e, stale in active rows only)
-  bool emb_split_patch = false;
-  unsigned long long active_rows_host = 0;   // length of the active-row list at the last Adam step
-  void *d_emb_split = nullptr;     // pre-split table of the W kernel (beam_kernel_w.hip.inc)
-  size_t emb_split_bytes = 0;
-  unsigned *d_maxabs = nullptr;
-  int sh_e = 0, sh_w = 0;
   void *d_att_wT_t = nullptr, *d_l1T_t = nullptr;  // transposes in the loaded dtype (general forward)
-  // fp64 beam kernel (beam_kernel_f64.hip.inc): A / B fragments of att.W, W1a, W1b; per-team K / G fragment scratch
-  void *d_frag64 = nullptr, *d_scratch64 = nullptr;
-  bool frag64_dirty = true;
-  double b2_64 = 0.0;            // l2.b of the f64 model (read back when the fragments are built)
+  LazyCopies lazy;             // the copies rebuilt on first use after a weight change, and their stale flags (lazy_copies.hip.inc)
+  int scorer_mode = DM_SCORER_AUTO;      // dm_set_scorer_mode
+  bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
+  bool call_split = false;     // scorer arithmetic of the search being planned (split_for_call)
+  double jtm_score_s = 0, jtm_rebal_s = 0;   // dm_jtm_last_step_seconds
+  void *d_scratch64 = nullptr; // fp64 beam kernel (beam_kernel_f64.hip.inc): per-team K / G fragment scratch
   size_t scratch64_bytes = 0;
   // training state (dm_train_init)
   bool train_ready = false;
@@ -124,7 +108,6 @@ struct dm_ctx {
   void *d_grad = nullptr, *d_adam_s = nullptr, *d_adam_r = nullptr, *d_loss = nullptr;   // in the loaded dtype
   void *d_tr64 = nullptr;        // f64 model: A fragments of att.W, W1a, W1b and of their transposes for the training kernels
   void *d_tail32 = nullptr;      // f64 model: f32 copy of the small matrices (source of the f32 mirror's fragments)
-  bool f32_mirror_dirty = false; // f64 model whose weights moved: the f32 copies the throughput beam kernels read are stale
   double last_loss = 0.0;
   f32x4 *d_attTA = nullptr, *d_w1aTA = nullptr, *d_w1bTA = nullptr;
   unsigned *d_touch_bits = nullptr;
@@ -428,11 +411,8 @@ static void free_weights(dm_ctx *h) {
   if (h->emb32_owned) dm_free_ptr(h->d_emb32);
   dm_free_ptr(h->d_compact); dm_free_ptr(h->d_wfrag); dm_free_ptr(h->d_afrag); dm_free_ptr(h->d_bfrag); dm_free_ptr(h->d_attA); dm_free_ptr(h->d_w1aA); dm_free_ptr(h->d_w1bA);
   dm_free_ptr(h->d_b1); dm_free_ptr(h->d_w2); dm_free_ptr(h->d_att_wT_t); dm_free_ptr(h->d_l1T_t);
-  dm_free_ptr(h->d_wsplit); dm_free_ptr(h->d_maxabs); h->d_wsplit = nullptr; h->d_maxabs = nullptr; h->split_dirty = true; h->table_dense_change = true; h->sh_e_valid = false; h->emb_split_need_full = true;
-  dm_free_ptr(h->d_rows_split); h->d_rows_split = nullptr; h->rows_split_dirty = true;
-  dm_free_ptr(h->d_emb_split); h->d_emb_split = nullptr; h->emb_split_bytes = 0;
-  dm_free_ptr(h->d_frag64); h->d_frag64 = nullptr; h->frag64_dirty = true;
-  dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; dm_free_ptr(h->d_tail32); h->d_tail32 = nullptr; h->f32_mirror_dirty = false;
+  h->lazy.released();
+  dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; dm_free_ptr(h->d_tail32); h->d_tail32 = nullptr;
   h->d_compact = nullptr; h->d_emb32 = nullptr; h->emb32_owned = false; h->d_wfrag = nullptr;
   dm_free_ptr(h->d_grad); dm_free_ptr(h->d_adam_s); dm_free_ptr(h->d_adam_r); dm_free_ptr(h->d_loss); dm_free_ptr(h->d_attTA);
   dm_free_ptr(h->d_w1aTA); dm_free_ptr(h->d_w1bTA); dm_free_ptr(h->d_touch_bits); dm_free_ptr(h->d_touch_list); dm_free_ptr(h->d_touch_cnt);
@@ -447,9 +427,8 @@ static void free_weights(dm_ctx *h) {
 #define DM_SHARED_FIELDS(X)                                                                                                              \
   X(tree_loaded) X(ids_loaded) X(leaves_at_max_only) X(max_level) X(n_slots) X(n_leaf_nodes) X(d_exists) X(d_leaf) X(d_node_id)          \
   X(d_id_to_code) X(d_leaf_codes) X(non_leaf_offset) X(max_code) X(w_loaded) X(dtype) X(embed) X(embed_log) X(num_index) X(d_compact)    \
-  X(d_emb32) X(d_wfrag) X(d_afrag) X(d_bfrag) X(d_attA) X(d_w1aA) X(d_w1bA) X(d_b1) X(d_w2) X(b2) X(d_wsplit) X(d_rows_split) X(sh_r)    \
-  X(d_emb_split) X(emb_split_bytes) X(d_maxabs) X(sh_e) X(sh_w) X(d_att_wT_t) X(d_l1T_t) X(d_frag64) X(b2_64) X(d_tail32)                \
-  X(d_lv_codes) X(d_lv_cdf) X(d_lv_start)
+  X(d_emb32) X(d_wfrag) X(d_afrag) X(d_bfrag) X(d_attA) X(d_w1aA) X(d_w1bA) X(d_b1) X(d_w2) X(b2) X(d_att_wT_t) X(d_l1T_t) X(d_tail32)   \
+  X(lazy) X(d_lv_codes) X(d_lv_cdf) X(d_lv_start)
 
 static void clone_mirror(dm_ctx *c, dm_ctx *p) {
 #define X(f) c->f = p->f;
@@ -461,9 +440,7 @@ static void clone_mirror(dm_ctx *c, dm_ctx *p) {
     c->seen_ids_epoch = p->ids_epoch;
   }
   c->emb32_owned = false;
-  // the parent's copies were brought up to date before the mirror was taken: nothing is stale for the clone, and nothing is rebuilt by it
-  c->split_dirty = false; c->emb_split_dirty = false; c->rows_split_dirty = false; c->frag64_dirty = false; c->f32_mirror_dirty = false;
-  c->table_dense_change = false; c->sh_e_valid = p->sh_e_valid; c->emb_split_need_full = false; c->emb_split_patch = false;
+  c->lazy.clone_view();
   c->seen_epoch = p->model_epoch.load();
 }
 static void clone_forget(dm_ctx *c) {         // the clone owns none of it
@@ -472,53 +449,6 @@ static void clone_forget(dm_ctx *c) {         // the clone owns none of it
   DM_SHARED_FIELDS(X)
 #undef X
   c->emb32_owned = false;
-}
-
-static bool use_split(const dm_ctx *h);
-static bool use_f64_beam(const dm_ctx *h);
-static int ensure_split(dm_ctx *h);
-static int ensure_rows_split(dm_ctx *h);
-static int ensure_f32_mirror(dm_ctx *h);
-static int ensure_frags64(dm_ctx *h);
-
-// A clone's read-only entry points start here.  Fast path: the parent's model has not changed since the mirror was taken (one atomic
-// load).  Otherwise, under the parent's lock: the copies this clone's scorer needs are brought up to date ON THE PARENT (its stream,
-// its buffers; no-ops when clean), the parent's stream is drained, and the mirror is retaken.  Weight updates through the parent must
-// not overlap a clone's search in flight — the reference's workers wait for each other the same way (LocalOptimizer.scala:73-80).
-static int clone_enter(dm_ctx *c) {
-  dm_ctx *p = c->parent;
-  if (c->seen_epoch == p->model_epoch.load()) return DM_OK;
-  std::lock_guard<std::recursive_mutex> lock(p->mu);
-  if (hipSetDevice(p->device) != hipSuccess) return fail(c, DM_ERR_HIP, "dm_clone: hipSetDevice failed");
-  for (int pass = 0; pass < 2; pass++) {
-    clone_mirror(c, p);                         // (first pass: the model's shape, so that the scorer choice below is this clone's)
-    if (!p->w_loaded) break;
-    int rc = DM_OK;
-    if (use_f64_beam(c)) rc = ensure_frags64(p);        // (decided on the clone: the parent's model with the clone's own scorer setting)
-    else {
-      rc = ensure_f32_mirror(p);
-      if (rc == DM_OK && use_split(c)) { rc = ensure_split(p); if (rc == DM_OK) rc = ensure_rows_split(p); }
-    }
-    if (rc != DM_OK) { c->err = p->err; return rc; }
-    if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(c, DM_ERR_HIP, "dm_clone: the parent's stream failed");
-  }
-  return DM_OK;
-}
-
-int dm_clone(dm_handle_t h, dm_handle_t *out) {
-  if (!h || !out) return DM_ERR_INVALID;
-  *out = nullptr;
-  dm_ctx *root = h->parent ? h->parent : h;      // a clone of a clone shares the same owner
-  dm_handle_t c = nullptr;
-  int rc = dm_create(root->device, &c);
-  if (rc != DM_OK) return fail(h, rc, g_create_err);
-  c->parent = root;
-  c->scorer_mode = h->scorer_mode;
-  root->n_clones.fetch_add(1);
-  rc = clone_enter(c);
-  if (rc != DM_OK) { h->err = c->err; root->n_clones.fetch_sub(1); c->parent = nullptr; dm_destroy(c); return rc; }
-  *out = c;
-  return DM_OK;
 }
 
 int dm_destroy(dm_handle_t h) {
@@ -676,6 +606,48 @@ static void unpad_compact(const T *src, int E, int Ep, int64_t NI, T *dst) {    
 }
 
 #include "model_weights.hip.inc"
+#define DM_LAZY_COPIES_PART 2      // predicates, build kernels, ensure_*
+#include "lazy_copies.hip.inc"
+
+// A clone's read-only entry points start here.  Fast path: the parent's model has not changed since the mirror was taken (one atomic
+// load).  Otherwise, under the parent's lock: the copies this clone's scorer needs are brought up to date ON THE PARENT (its stream,
+// its buffers; no-ops when clean), the parent's stream is drained, and the mirror is retaken.  Weight updates through the parent must
+// not overlap a clone's search in flight — the reference's workers wait for each other the same way (LocalOptimizer.scala:73-80).
+static int clone_enter(dm_ctx *c) {
+  dm_ctx *p = c->parent;
+  if (c->seen_epoch == p->model_epoch.load()) return DM_OK;
+  std::lock_guard<std::recursive_mutex> lock(p->mu);
+  if (hipSetDevice(p->device) != hipSuccess) return fail(c, DM_ERR_HIP, "dm_clone: hipSetDevice failed");
+  for (int pass = 0; pass < 2; pass++) {
+    clone_mirror(c, p);                         // (first pass: the model's shape, so that the scorer choice below is this clone's)
+    if (!p->w_loaded) break;
+    int rc = DM_OK;
+    if (use_f64_beam(c)) rc = ensure_frags64(p);        // (decided on the clone: the parent's model with the clone's own scorer setting)
+    else {
+      rc = ensure_f32_mirror(p);
+      if (rc == DM_OK && use_split(c)) { rc = ensure_split(p); if (rc == DM_OK) rc = ensure_rows_split(p); }
+    }
+    if (rc != DM_OK) { c->err = p->err; return rc; }
+    if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(c, DM_ERR_HIP, "dm_clone: the parent's stream failed");
+  }
+  return DM_OK;
+}
+
+int dm_clone(dm_handle_t h, dm_handle_t *out) {
+  if (!h || !out) return DM_ERR_INVALID;
+  *out = nullptr;
+  dm_ctx *root = h->parent ? h->parent : h;      // a clone of a clone shares the same owner
+  dm_handle_t c = nullptr;
+  int rc = dm_create(root->device, &c);
+  if (rc != DM_OK) return fail(h, rc, g_create_err);
+  c->parent = root;
+  c->scorer_mode = h->scorer_mode;
+  root->n_clones.fetch_add(1);
+  rc = clone_enter(c);
+  if (rc != DM_OK) { h->err = c->err; root->n_clones.fetch_sub(1); c->parent = nullptr; dm_destroy(c); return rc; }
+  *out = c;
+  return DM_OK;
+}
 
 template <typename T>
 __global__ void dm_fill_normal_kernel(T *out, int64_t n, float mean, float std, unsigned long long seed) {
@@ -796,35 +768,6 @@ static int launch_rows_E(dm_ctx *h, const RowsParams &p) {
   return DM_OK;
 }
 
-static bool use_split(const dm_ctx *h);
-static int ensure_split_scales(dm_ctx *h);
-static int split_shift(unsigned maxbits);
-static bool weights_in_motion(const dm_ctx *h);
-// fp16 planes of the general-rows split kernel (rows_kernel.hip.inc): follow the weights like the beam kernels' planes
-static int ensure_rows_split(dm_ctx *h) {
-  std::lock_guard<std::recursive_mutex> lk_(h->mu);
-  int rc = ensure_split_scales(h);     // sh_e = the table's scale: one read of the table per weight change, shared with the beam kernels
-  if (rc != DM_OK) return rc;
-  if (!h->rows_split_dirty && h->d_rows_split) return DM_OK;
-  const int E = h->embed;
-  const size_t plane_bytes = (size_t)4 * E * E * 2;
-  if (!h->d_rows_split) ALLOC(h, h->d_rows_split, plane_bytes + (size_t)E * E * 4);
-  float *Mbuf = (float *)((char *)h->d_rows_split + plane_bytes);
-  HIPCHK(h, hipMemsetAsync(h->d_maxabs, 0, 8, h->stream));
-  hipLaunchKernelGGL(dm_rows_m_kernel, dim3(64), dim3(256), 0, h->stream, h->d_attA, h->d_w1aA, h->d_w1bA, E, Mbuf, h->d_maxabs);
-  HIPCHK(h, hipGetLastError());
-  unsigned mb[2];
-  HIPCHK(h, hipMemcpyAsync(mb, h->d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  model_changed(h);
-  h->sh_r = split_shift(mb[0] > mb[1] ? mb[0] : mb[1]);
-  hipLaunchKernelGGL(dm_build_rows_planes_kernel, dim3(64), dim3(256), 0, h->stream, h->d_w1aA, (const float *)Mbuf, E, ldexpf(1.0f, h->sh_r),
-                     (_Float16 *)h->d_rows_split);
-  HIPCHK(h, hipGetLastError());
-  h->rows_split_dirty = false;
-  return DM_OK;
-}
-
 // HIP-event pair of kind 30 around a general-rows launch (dm_kernel_timing_get_kind: the roofline of JTM's scorer in bench.py)
 struct RowsTimer : LaunchTimer { explicit RowsTimer(dm_ctx *h_) : LaunchTimer(h_, 30) {} };
 
@@ -874,8 +817,8 @@ static int din_rows_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs
     int rc = ensure_rows_split(h);
     if (rc != DM_OK) return rc;
     RowsSplitParams q;
-    q.emb = h->d_emb32; q.planes = (const dm_h8 *)h->d_rows_split; q.b1 = h->d_b1; q.w2 = h->d_w2; q.b2 = h->b2;
-    q.emb_scale = ldexpf(1.0f, h->sh_e); q.out_unscale = ldexpf(1.0f, -(h->sh_e + h->sh_r));
+    q.emb = h->d_emb32; q.planes = (const dm_h8 *)h->lazy.d_rows_split; q.b1 = h->d_b1; q.w2 = h->d_w2; q.b2 = h->b2;
+    q.emb_scale = ldexpf(1.0f, h->lazy.sh_e); q.out_unscale = ldexpf(1.0f, -(h->lazy.sh_e + h->lazy.sh_r));
     q.num_index = h->num_index; q.codes = d_codes; q.seqs = d_seqs; q.rowmask = d_rowmask; q.B = B; q.L = L; q.out = d_out;
     q.sm_scale = sm_scale32(h); q.seq_div = seq_div;
     return dispatch_E<32>(h, h->embed, "unsupported embed size", [&](auto e) { return launch_rows_split_E<decltype(e)::value>(h, q); });
@@ -944,32 +887,17 @@ struct SearchPlan {
   bool wkernel;        // the one-wave-per-SIMD kernel with W1a in the AccVGPRs (beam_kernel_w.hip.inc)
 };
 
-// the scorer arithmetic the beam kernels will use for this handle's model (dm_set_scorer_mode)
-static bool use_split(const dm_ctx *h) {
-  return (h->scorer_mode == DM_SCORER_SPLIT_F16 || h->scorer_mode == DM_SCORER_AUTO) && h->embed % 32 == 0;
-}
-
-// AUTO mode inside a training loop: the split scorer's scales / fp16 copies are stale after every Adam step, and refreshing them is a
-// pass (or three) over the whole table.  A request that is small next to that takes the fp32-input kernels, which read the fp32
-// table as it is; both arithmetics meet the same tolerance.  An explicit DM_SCORER_SPLIT_F16 is always honoured.
-static bool weights_in_motion(const dm_ctx *h) {
-  return h->scorer_mode == DM_SCORER_AUTO && h->train_ready && (h->split_dirty || h->f32_mirror_dirty);
-}
+// AUTO mode inside a training loop (weights_in_motion): a search small next to the split copies' refresh keeps the fp32-input kernel
 static bool split_for_call(const dm_ctx *h, int64_t U, int max_beam) {
   if (!use_split(h)) return false;
-  if (weights_in_motion(h) || (h->scorer_mode == DM_SCORER_AUTO && h->train_ready && h->emb_split_dirty)) {
-    const bool patchable = h->sh_e_valid && !h->table_dense_change && h->dtype == DM_F32;                       // only the Adam step's active rows are stale
-    const double rows_ = patchable ? (double)h->active_rows_host : (double)h->num_index;
+  if (split_refresh_pending(h)) {
+    const bool patchable = split_patchable(h);                       // only the Adam step's active rows are stale
+    const double rows_ = (double)split_refresh_rows(h);
     const double rebuild_s = 3.0e-5 + 3.0 * rows_ * h->embed * 4 / (patchable ? 1.0e12 : 3.0e12);   // launches + read-back, then scan + read + write
     const double extra_s = (double)U * max_beam * 7.0e-9;                             // fp32-input kernel: ~7 ns more per (user, beam slot)
     if (extra_s < rebuild_s) return false;
   }
   return true;
-}
-
-// fp64 parity mode of the OTM search (otm64.hip.inc): in effect when f64 weights are loaded and the scorer mode is AUTO or F64
-static bool use_f64_beam(const dm_ctx *h) {
-  return h->dtype == DM_F64 && (h->scorer_mode == DM_SCORER_AUTO || h->scorer_mode == DM_SCORER_F64);
 }
 
 // Histories of 17 .. 32 positions run inside the fused LDS-fed kernel (two key tiles, beam_kernel.hip.inc) whenever its frontier fits
@@ -985,6 +913,16 @@ static bool long_history_pipeline(const dm_ctx *h, int max_beam, int L) {
   return dm_beam_lds(h->embed, 1, cap, pcap, 4, true, 2).total > 160 * 1024;
 }
 
+// The LDS-fed kernel runs teams of 8 / nteams waves: the largest team count, halving from `from`, whose dm_beam_lds layout fits the
+// 160 KB of a CU (*lds: that layout's size), or 0 when not even one team fits
+static int beam_teams_that_fit(int E, int from, int cap, int pcap, int kq, bool split, int kt, int *lds) {
+  for (int cand = from; cand >= 1; cand >>= 1) {
+    const BeamLds l = dm_beam_lds(E, cand, cap, pcap, kq, split, kt);
+    if (l.total <= 160 * 1024) { *lds = l.total; return cand; }
+  }
+  return 0;
+}
+
 static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, bool tdm, SearchPlan *pl) {
   int cap, pcap;
   frontier_caps(max_beam, &cap, &pcap);
@@ -998,14 +936,10 @@ static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, 
     BeamWLds l = dm_beamw_lds(h->embed, cap, pcap, kq);
     if (l.total <= 160 * 1024) { nteams = DMW_NWAVES; pl->lds = l.total; pl->wkernel = true; }
   }
-  // LDS-fed kernel: teams of 8 / nteams waves.  A frontier of at most 256 slots fits ONE wave's register sort, so small beams
+  // LDS-fed kernel.  A frontier of at most 256 slots fits ONE wave's register sort, so small beams
   // (the reference's serving default is candidateNum 20) run as eight one-wave teams: no team barriers at all on the latency
   // chain sort -> expand -> gather -> score of a level, and eight users per CU in flight instead of four
-  if (!nteams)
-  for (int cand = (pcap <= 256 ? 8 : 4); cand >= 1; cand >>= 1) {
-    BeamLds l = dm_beam_lds(h->embed, cand, cap, pcap, kq, h->call_split, kt);
-    if (l.total <= 160 * 1024) { nteams = cand; pl->lds = l.total; break; }
-  }
+  if (!nteams) nteams = beam_teams_that_fit(h->embed, pcap <= 256 ? 8 : 4, cap, pcap, kq, h->call_split, kt, &pl->lds);
   if (!nteams) return fail(h, DM_ERR_UNSUPPORTED, "beam too large for the LDS frontier (about 2*beam*28 bytes + weights must fit 160 KiB)");
   int64_t groups = (U + nteams - 1) / nteams;
   int grid = (int)(groups < h->n_cu ? groups : h->n_cu);
@@ -1085,178 +1019,14 @@ static int launch_beam_E(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
   }
 }
 
-// ---- split-fp16 scorer: scales and the fp16 planes of W1a -------------------------------------------------------
-__global__ void dm_maxabs_kernel(const float *x, int64_t n, unsigned *out) {
-  unsigned m = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned b = __float_as_uint(x[i]) & 0x7fffffffu;      // |x| as an ordered integer (NaN / inf sort highest)
-    m = b > m ? b : m;
-  }
-  for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)m, o); m = t > m ? t : m; }
-  if ((threadIdx.x & 63) == 0) atomicMax(out, m);
-}
-
-// planes[p][s][nt][lane][i], lane = (g, m): W1a[16nt + m][32s + 16(i>>2) + 4g + (i&3)] * 2^sh_w split into fp16 hi (p=0) and
-// lo (p=1); the column order is the one the beam kernel's gathered rows have inside a lane (two float4 per k-step)
-__global__ void dm_build_wsplit_kernel(const float *wfrag, int E, float scale, _Float16 *planes) {
-  const int NT = E / 16, NS = E / 32;
-  const int n = NS * NT * 64 * 8;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-    const int i = t & 7, lane = (t >> 3) & 63, nt = (t >> 9) % NT, s = (t >> 9) / NT;
-    const int jc = 2 * s + (i >> 2);
-    const float x = wfrag[(((size_t)jc * NT + nt) * 64 + lane) * 4 + (i & 3)] * scale;
-    const _Float16 hi = (_Float16)x;
-    const _Float16 lo = (_Float16)(x - (float)hi);
-    planes[t] = hi;
-    planes[(size_t)n + t] = lo;
-  }
-}
-
-// The table as the one-wave-per-SIMD kernel gathers it: every fp32 value x already split into hi = RNE16(x 2^s) and
-// lo = RNE16(x 2^s - hi), laid out so that the lane group g of a tile finds, per row and k-step, its two MFMA B operands as 32
-// contiguous bytes: out[row][s][g][0..7] = hi of columns 32s + 16(i>>2) + 4g + (i&3), out[row][s][g][8..15] = lo of the same.
-// Same bytes per row as the fp32 table (E * 4); identical values to the split the LDS-fed kernel does per tile.
-__global__ void dm_build_emb_split_kernel(const float *emb, int64_t num_index, int E, float scale, _Float16 *out) {
-  const int64_t n8 = num_index * (int64_t)(E / 8);        // groups of 8 values = one (row, s, g)
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n8; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t row = t / (E / 8);
-    const int sg = (int)(t % (E / 8)), s_ = sg >> 2, g = sg & 3;
-    const float *src = emb + row * E + 32 * s_ + 4 * g;
-    _Float16 *dst = out + row * (int64_t)(2 * E) + (int64_t)sg * 16;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const float x = src[16 * (i >> 2) + (i & 3)] * scale;
-      const _Float16 hi = (_Float16)x;
-      dst[i] = hi;
-      dst[8 + i] = (_Float16)(x - (float)hi);
-    }
-  }
-}
-
-// the same two passes over a LIST of rows (the rows an Adam step can have moved: ensure_split_scales / ensure_split inside a training loop)
-__global__ void dm_maxabs_rows_kernel(const float *emb, const int32_t *rows, int64_t n_rows, int E, unsigned *out) {
-  unsigned m = 0;
-  const int64_t n = n_rows * E;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned b = __float_as_uint(emb[(int64_t)rows[t / E] * E + (t % E)]) & 0x7fffffffu;
-    m = b > m ? b : m;
-  }
-  for (int o = 32; o > 0; o >>= 1) { const unsigned t = (unsigned)__shfl_xor((int)m, o); m = t > m ? t : m; }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
-__global__ void dm_build_emb_split_rows_kernel(const float *emb, const int32_t *rows, int64_t n_rows, int E, float scale, _Float16 *out) {
-  const int64_t n8 = n_rows * (int64_t)(E / 8);
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n8; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t row = rows[t / (E / 8)];
-    const int sg = (int)(t % (E / 8)), s_ = sg >> 2, g = sg & 3;
-    const float *src = emb + row * E + 32 * s_ + 4 * g;
-    _Float16 *dst = out + row * (int64_t)(2 * E) + (int64_t)sg * 16;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const float x = src[16 * (i >> 2) + (i & 3)] * scale;
-      const _Float16 hi = (_Float16)x;
-      dst[i] = hi;
-      dst[8 + i] = (_Float16)(x - (float)hi);
-    }
-  }
-}
-
-// power-of-two shift that puts max|x| into [2^13, 2^14): every scaled value and every rounding of it stays below the fp16
-// maximum, and fp16 subnormals only start 2^27 below the largest element
-static int split_shift(unsigned maxbits) {
-  if (maxbits == 0 || maxbits >= 0x7f800000u) return 0;
-  float m;
-  memcpy(&m, &maxbits, 4);
-  int e;
-  frexpf(m, &e);               // m = f * 2^e, f in [0.5, 1)
-  int sh = 14 - e;
-  if (sh > 40) sh = 40;
-  if (sh < -40) sh = -40;
-  return sh;
-}
-
-// scales (2^sh_e from max|emb|: one read of the table; 2^sh_w from max|W1a|) and the fp16 planes of W1a: what every split kernel
-// needs.  The pre-split copy of the table (ensure_split) is a second, larger step only the beam kernels take.
-static int ensure_split_scales(dm_ctx *h) {
-  std::lock_guard<std::recursive_mutex> lk_(h->mu);
-  if (!h->split_dirty && h->d_wsplit) return DM_OK;
-  model_changed(h);
-  const int E = h->embed;
-  if (E % 32 != 0) return fail(h, DM_ERR_UNSUPPORTED, "the split-fp16 scorer needs an embedding size that is a multiple of 32");
-  if (!h->d_wsplit) ALLOC(h, h->d_wsplit, (size_t)E * E * 4);
-  if (!h->d_maxabs) ALLOC(h, h->d_maxabs, 8);
-  // Inside a training loop whose Adam steps visit the active rows only, nothing else of the table has moved since the last full
-  // scan: the scale 2^sh_e stays (a power of two: exact) as long as the active rows still fit it, and only those rows are re-split.
-  bool patch = h->train_ready && h->sh_e_valid && !h->table_dense_change && h->d_active_list && h->dtype == DM_F32;
-  unsigned mb[2];
-  for (;;) {
-    HIPCHK(h, hipMemsetAsync(h->d_maxabs, 0, 8, h->stream));
-    if (patch) {
-      if (h->active_rows_host)
-        hipLaunchKernelGGL(dm_maxabs_rows_kernel, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->d_active_list, (int64_t)h->active_rows_host, E, h->d_maxabs);
-    } else
-      hipLaunchKernelGGL(dm_maxabs_kernel, dim3(4096), dim3(256), 0, h->stream, h->d_emb32, h->num_index * (int64_t)E, h->d_maxabs);
-    hipLaunchKernelGGL(dm_maxabs_kernel, dim3(16), dim3(256), 0, h->stream, (const float *)h->d_wfrag, (int64_t)E * E, h->d_maxabs + 1);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(mb, h->d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (patch && mb[0] != 0 && split_shift(mb[0]) < h->sh_e) { patch = false; continue; }    // an active row outgrew the scale: full scan
-    break;
-  }
-  if (!patch) {
-    h->sh_e = split_shift(mb[0]);
-    h->sh_e_valid = true; h->table_dense_change = false; h->emb_split_need_full = true;
-  }
-  h->emb_split_patch = patch;
-  h->sh_w = split_shift(mb[1]);
-  hipLaunchKernelGGL(dm_build_wsplit_kernel, dim3(64), dim3(256), 0, h->stream, (const float *)h->d_wfrag, E, ldexpf(1.0f, h->sh_w),
-                     (_Float16 *)h->d_wsplit);
-  HIPCHK(h, hipGetLastError());
-  h->split_dirty = false;
-  h->emb_split_dirty = true;
-  h->rows_split_dirty = true;
-  return DM_OK;
-}
-
-static int ensure_split(dm_ctx *h) {
-  std::lock_guard<std::recursive_mutex> lk_(h->mu);
-  int rc = ensure_split_scales(h);
-  if (rc != DM_OK) return rc;
-  if (!h->emb_split_dirty && h->d_emb_split) return DM_OK;
-  model_changed(h);
-  const int E = h->embed;
-  // the beam kernels gather pre-split rows: a second copy of the table (same size), refreshed whenever the weights change — as a whole,
-  // or in the active rows only when nothing else can have moved
-  const size_t bytes = (size_t)h->num_index * E * 4;
-  if (h->emb_split_bytes != bytes) {
-    dm_free_ptr(h->d_emb_split); h->d_emb_split = nullptr; h->emb_split_bytes = 0;
-    ALLOC(h, h->d_emb_split, bytes);
-    h->emb_split_bytes = bytes;
-    h->emb_split_need_full = true;
-  }
-  if (h->emb_split_need_full || !h->emb_split_patch) {
-    hipLaunchKernelGGL(dm_build_emb_split_kernel, dim3(8192), dim3(256), 0, h->stream, h->d_emb32, h->num_index, E, ldexpf(1.0f, h->sh_e),
-                       (_Float16 *)h->d_emb_split);
-    h->emb_split_need_full = false;
-  } else if (h->active_rows_host) {
-    hipLaunchKernelGGL(dm_build_emb_split_rows_kernel, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->d_active_list, (int64_t)h->active_rows_host,
-                       E, ldexpf(1.0f, h->sh_e), (_Float16 *)h->d_emb_split);
-  }
-  HIPCHK(h, hipGetLastError());
-  h->emb_split_dirty = false;
-  return DM_OK;
-}
-
-static int ensure_f32_mirror(dm_ctx *h);
 static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
   // the host-polled epilogue (results, system-scope fence, count as the flag) exists for the TDM final selection only: the mode-1 (OTM)
   // epilogue stores its counts before the ids and without a fence
   if (p.host_direct && p.mode != 0) return fail(h, DM_ERR_STATE, "launch_beam: the host-mapped single-request path is a mode-0 (TDM) path");
-  {   // f64 model trained since the f32 copies were made: refresh them (and the scorer parameters fill_common took from them)
-    const bool was = h->f32_mirror_dirty;
-    int rc_ = ensure_f32_mirror(h);
+  {   // f64 model trained since the f32 copies were made: refresh them, then take b2 again (fill_common read it before the rebuild)
+    const int rc_ = ensure_f32_mirror(h);
     if (rc_ != DM_OK) return rc_;
-    if (was) p.b2 = h->b2;
+    p.b2 = h->b2;
   }
   // the brute-force recall oracle (mode 2) always scores with the fp32-input MFMA
   if (h->scorer_mode == DM_SCORER_SPLIT_F16 && h->embed % 32 != 0)
@@ -1264,10 +1034,9 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
   if (h->call_split && p.mode != 2) {
     int rc = ensure_split(h);
     if (rc != DM_OK) return rc;
-    p.wsplit = (const dm_h8 *)h->d_wsplit;
-    p.emb_split = (const dm_h8 *)h->d_emb_split;
-    p.emb_scale = ldexpf(1.0f, h->sh_e); p.score_unscale = ldexpf(1.0f, -2 * h->sh_e);
-    p.acc_scale = ldexpf(1.0f, h->sh_e + h->sh_w); p.out_unscale = ldexpf(1.0f, -(h->sh_e + h->sh_w));
+    p.wsplit = (const dm_h8 *)h->lazy.d_wsplit;
+    p.emb_split = (const dm_h8 *)h->lazy.d_emb_split;
+    fill_split_scales(h, p);
     if (pl.wkernel) {
       // users the W kernel cannot score in fp16 throughout are queued in [count | next | ids ...] and scored by the LDS-fed kernel
       const size_t need = 16 + (size_t)p.U * 4;
@@ -1283,22 +1052,13 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
       if (rc != DM_OK) return rc;
       // second pass (an empty list costs one launch): same parameters, the list as the work queue, its own frontier layout
-      SearchPlan pl2;
-      {
-        const int kq = (p.L + 3) / 4;
-        int nteams = 0;
-        for (int cand = 4; cand >= 1; cand >>= 1) {
-          BeamLds l = dm_beam_lds(h->embed, cand, pl.cap, pl.pcap, kq, true);
-          if (l.total <= 160 * 1024) { nteams = cand; pl2.lds = l.total; break; }
-        }
-        if (!nteams) return fail(h, DM_ERR_UNSUPPORTED, "beam too large for the LDS frontier");
-        pl2 = pl; pl2.nteams = nteams; pl2.wkernel = false;
-        BeamLds l = dm_beam_lds(h->embed, nteams, pl.cap, pl.pcap, kq, true);
-        pl2.lds = l.total;
-        // the workspace was sized for grid x 4 one-wave teams; the second pass may use at most as many (block, team) slots
-        if (pl2.grid * pl2.nteams > pl.grid * pl.nteams) pl2.grid = pl.grid * pl.nteams / pl2.nteams;
-        if (pl2.grid < 1) pl2.grid = 1;
-      }
+      SearchPlan pl2 = pl;
+      pl2.wkernel = false;
+      pl2.nteams = beam_teams_that_fit(h->embed, 4, pl.cap, pl.pcap, (p.L + 3) / 4, true, 1, &pl2.lds);
+      if (!pl2.nteams) return fail(h, DM_ERR_UNSUPPORTED, "beam too large for the LDS frontier");
+      // the workspace was sized for grid x 4 one-wave teams; the second pass may use at most as many (block, team) slots
+      if (pl2.grid * pl2.nteams > pl.grid * pl.nteams) pl2.grid = pl.grid * pl.nteams / pl2.nteams;
+      if (pl2.grid < 1) pl2.grid = 1;
       BeamParams p2 = p;
       p2.nteams = pl2.nteams;
       p2.user_count = (const unsigned long long *)h->d_defer;
@@ -1332,8 +1092,8 @@ int dm_get_scorer_mode(dm_handle_t h, int *mode, int *effective, int *shift_emb,
   if (!h || !mode) return DM_ERR_INVALID;
   *mode = h->scorer_mode;
   if (effective) *effective = (h->w_loaded && use_f64_beam(h)) ? DM_SCORER_F64 : (h->w_loaded && use_split(h)) ? DM_SCORER_SPLIT_F16 : DM_SCORER_F32;
-  if (shift_emb) *shift_emb = h->sh_e;
-  if (shift_w) *shift_w = h->sh_w;
+  if (shift_emb) *shift_emb = h->lazy.sh_e;
+  if (shift_w) *shift_w = h->lazy.sh_w;
   return DM_OK;
 }
 
@@ -1715,11 +1475,8 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
   const int cap = chunk < 32 ? 32 : chunk;
   const int kt = L > DM_MAXL ? 2 : 1;
   const int kq = kt > 1 ? 4 : (L + 3) / 4;
-  int nteams = 0, lds = 0;
-  for (int cand = 4; cand >= 1; cand >>= 1) {
-    BeamLds l = dm_beam_lds(h->embed, cand, cap, pcap, kq, false, kt);
-    if (l.total <= 160 * 1024) { nteams = cand; lds = l.total; break; }
-  }
+  int lds = 0;
+  const int nteams = beam_teams_that_fit(h->embed, 4, cap, pcap, kq, false, kt, &lds);
   if (!nteams) return fail(h, DM_ERR_UNSUPPORTED, "dm_tdm_bruteforce_topk: LDS budget exceeded");
   // enough (user, slice) work items to fill every team a few times over
   int64_t slices = (4 * (int64_t)h->n_cu * nteams + U - 1) / U;

@@ -135,13 +135,13 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
   }
   if (sizeof(T) == 4 && E % 64 == 0) {       // (the split GEMM stages 64-column tiles: a tile never straddles an embedding row)
     // split-fp16 history GEMM (dm_set_scorer_mode): scales from the largest magnitudes, W planes built once
-    if (!h->d_maxabs) ALLOC(h, h->d_maxabs, 8);
-    HIPCHK(h, hipMemsetAsync(h->d_maxabs, 0, 8, h->stream));
-    hipLaunchKernelGGL(dm_maxabs_kernel, dim3(4096), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, n_emb, h->d_maxabs);
-    hipLaunchKernelGGL(dm_maxabs_kernel, dim3(256), dim3(256), 0, h->stream, (const float *)s->d_wseq, (int64_t)D * K * L * E, h->d_maxabs + 1);
+    if (!h->lazy.d_maxabs) ALLOC(h, h->lazy.d_maxabs, 8);
+    HIPCHK(h, hipMemsetAsync(h->lazy.d_maxabs, 0, 8, h->stream));
+    hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, nullptr, n_emb, 0, h->lazy.d_maxabs);
+    hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(256), dim3(256), 0, h->stream, (const float *)s->d_wseq, nullptr, (int64_t)D * K * L * E, 0, h->lazy.d_maxabs + 1);
     HIPCHK(h, hipGetLastError());
     unsigned mb[2];
-    HIPCHK(h, hipMemcpyAsync(mb, h->d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(mb, h->lazy.d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s->sh_a = split_shift(mb[0]); s->sh_b = split_shift(mb[1]);
     ALLOC(h, s->d_wseq_split, (size_t)2 * D * K * L * E * 2);

@@ -80,7 +80,8 @@ static int install_weights(dm_ctx *h, int dtype, int E, int E_model, int64_t num
   } else h->d_emb32 = (float *)d_compact;
   const int rc = derive_small(h, DERIVE_ALL);      // (ends with the stream drained)
   if (rc != DM_OK) return rc;
-  h->w_loaded = true; h->split_dirty = true; h->table_dense_change = true;
+  h->w_loaded = true;
+  h->lazy.loaded();
   return DM_OK;
 }
 

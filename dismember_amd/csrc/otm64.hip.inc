@@ -220,24 +220,6 @@ __global__ void otm64_emit_kernel(Otm64Out<T> p) {
 // [U][max_levels][cap]).  Exactly one of d_sc64 / d_sc32 (and of d_ts64 / d_ts32 when tracing) is non-null.
 // ---- the fused persistent kernel (beam_kernel_f64.hip.inc): the default; the per-level pipeline below stays for frontiers that
 // outgrow LDS, for searches with no level to score, and as a cross-check (DM_OTM64_PIPELINE=1 in the environment)
-static int ensure_frags64(dm_ctx *h) {
-  std::lock_guard<std::recursive_mutex> lk_(h->mu);
-  const int E = h->embed;
-  const size_t n = (size_t)E * E;
-  if (!h->d_frag64) { ALLOC(h, h->d_frag64, 3 * n * 8); h->frag64_dirty = true; }
-  if (!h->frag64_dirty) return DM_OK;
-  model_changed(h);
-  const double *base = (const double *)h->d_compact;
-  const double *att_w = base + h->num_index * E, *l1_w = att_w + n;
-  double *f = (double *)h->d_frag64;
-  hipLaunchKernelGGL(dm_build_frags64_kernel, dim3(64), dim3(256), 0, h->stream, att_w, l1_w, E, f, f + n, f + 2 * n);
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(&h->b2_64, l1_w + 2 * n + 2 * E, 8, hipMemcpyDeviceToHost, h->stream));      // l2.b: a kernel argument
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->frag64_dirty = false;
-  return DM_OK;
-}
-
 template <int E, int KQ, int KT = 1>
 static int launch_beam64_EK(dm_ctx *h, const Beam64Params &p, int grid, int lds) {
   HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam64_kernel<E, KQ, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
@@ -306,7 +288,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   const double *base = (const double *)h->d_compact;
   const size_t n = (size_t)E * E;
   const double *l1_b = base + h->num_index * E + 3 * n, *l2_w = l1_b + E;
-  const double b2 = h->b2_64;
+  const double b2 = h->lazy.b2_64;
   Beam64Params p{};
   p.static_users = U <= (int64_t)grid * nteams ? 1 : 0;
   p.b_global = b_global; p.v_global = v_global;
@@ -316,7 +298,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   p.sm_scale = sm_scale64(h);
   p.phase_cycles = h->d_phase;
   if (!p.static_users || U > 64) HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));       // queue head + scored-row counter
-  const double *f = (const double *)h->d_frag64;
+  const double *f = (const double *)h->lazy.d_frag64;
   p.emb = base; p.num_index = h->num_index; p.w1aA = (const f64x2 *)f; p.attA = f + n; p.w1bB = f + 2 * n; p.b1 = l1_b; p.w2 = l2_w; p.b2 = b2;
   p.seq = d_seq; p.U = U; p.L = L; p.beam = beam; p.leaf_level = leaf_level; p.nteams = nteams; p.cap = fcap; p.pcap = pcap;
   p.out_ids = d_ids; p.out_sc64 = d_sc64; p.out_sc32 = d_sc32; p.out_counts = d_counts; p.out_stride = 2 * beam;

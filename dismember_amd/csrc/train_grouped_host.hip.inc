@@ -33,7 +33,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   const size_t n2 = (size_t)E * E;
   const double *base = (const double *)h->d_compact;
   const double *att_w = base + h->num_index * E, *l1_w = att_w + n2, *b1 = l1_w + 2 * n2, *w2 = b1 + E;
-  const double *f64f = (const double *)h->d_frag64;          // w1aA, attA, w1bB
+  const double *f64f = (const double *)h->lazy.d_frag64;          // w1aA, attA, w1bB
   const double *tr = (const double *)h->d_tr64;              // attA, w1aA, w1bA, attTA, w1aTA, w1bTA (training fragment order)
   double *grad = (double *)h->d_grad;
   // every launch gets an event pair (dm_kernel_timing_get_kind: 40 = per-user setup, 41 = the row kernel, 42 = dW1a + per-user sums,
@@ -51,7 +51,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   if ((rc = timed(40, [&] { hipLaunchKernelGGL((tg_setup_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, sp); })) != DM_OK) return rc;
   // ---- rows: forward + backward
   TgRowsParams rp{};
-  rp.emb = base; rp.num_index = h->num_index; rp.l1_w = l1_w; rp.w2 = w2; rp.b2 = h->b2_64;
+  rp.emb = base; rp.num_index = h->num_index; rp.l1_w = l1_w; rp.w2 = w2; rp.b2 = h->lazy.b2_64;
   rp.codes = d_codes; rp.labels = d_labels; rp.umask = d_umask; rp.U = U; rp.n = n; rp.L = L;
   rp.tiles_per_user = (n + 15) / 16;
   {

@@ -6,35 +6,8 @@ static int train_check(dm_ctx *h, const char *who) {
   return DM_OK;
 }
 
-static int64_t compact_len(const dm_ctx *h) {
-  const int64_t E = h->embed;
-  return h->num_index * E + 3 * E * E + 2 * E + 1;
-}
+static int64_t compact_len(const dm_ctx *h) { return compact_len_for(h->num_index, h->embed); }
 static size_t elem_size(const dm_ctx *h) { return h->dtype == DM_F64 ? 8 : 4; }
-
-// The weights moved (dm_adam_step) or training state was just allocated (dm_train_init): the derived copies in the model's own type
-// follow at once; an f64 model's f32 mirror is left to ensure_f32_mirror
-static int refresh_fragments(dm_ctx *h) {
-  model_changed(h);      // (clones re-mirror: the lazily rebuilt copies are stale)
-  h->split_dirty = true;   // the fp16 planes and scales of the split scorer follow the weights
-  h->frag64_dirty = true;  // so do the fp64 beam kernel's fragments
-  const int rc = derive_small(h, DERIVE_OWN);
-  if (rc == DM_OK && h->dtype == DM_F64) h->f32_mirror_dirty = true;
-  return rc;
-}
-
-// f64 model whose weights moved (dm_adam_step): bring the f32 copies the throughput-mode beam kernels read up to date
-// (table, fragment-ordered small matrices, b1 / w2 / b2).  No-op for f32 models and while nothing changed.
-static int ensure_f32_mirror(dm_ctx *h) {
-  std::lock_guard<std::recursive_mutex> lk_(h->mu);
-  if (h->dtype != DM_F64 || !h->f32_mirror_dirty) return DM_OK;
-  model_changed(h);
-  int rc = mirror_table32(h);
-  if (rc == DM_OK) rc = derive_small(h, DERIVE_F32_MIRROR);
-  if (rc != DM_OK) return rc;
-  h->f32_mirror_dirty = false; h->split_dirty = true; h->table_dense_change = true;
-  return DM_OK;
-}
 
 int dm_train_init(dm_handle_t h, const dm_adam_opts *o) {
   if (!h) return DM_ERR_INVALID;
@@ -71,12 +44,9 @@ int dm_train_init(dm_handle_t h, const dm_adam_opts *o) {
   HIPCHK(h, hipMemsetAsync(h->d_touch_bits, 0, (size_t)((h->num_index + 31) / 32 + 1) * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_touch_cnt, 0, 8, h->stream));
   h->adam = *o; h->adam_t = 0; h->touch_cap = 0; h->touch_ub = 0; h->train_ready = true; h->last_loss = 0.0;
-  h->active_rows_host = 0;
-  if (h->split_dirty || h->emb_split_dirty) h->table_dense_change = true;   // changes of an earlier training run not yet in the split copies
-  const bool mirror_was_dirty = h->f32_mirror_dirty;
-  int rc = refresh_fragments(h);
-  h->f32_mirror_dirty = mirror_was_dirty;      // the weights did not move
-  return rc;
+  model_changed(h);      // (clones re-mirror: the lazily rebuilt copies are stale)
+  h->lazy.training_started();
+  return derive_small(h, DERIVE_OWN);      // d_tr64 / the transposed fragments were just allocated
 }
 
 __global__ void dm_mark_touched_kernel(const int32_t *codes, const int32_t *seqs, int64_t B, int L, unsigned *bits,
@@ -357,8 +327,7 @@ int dm_adam_step(dm_handle_t h, float grad_scale) {
   const bool force_dense = fd_ && fd_[0] == '1';
   const bool sparse = !force_dense && o.eps > 0 && (int64_t)act * 4 < h->num_index;
   h->adam_last_sparse = sparse ? 1 : 0; h->adam_last_rows = sparse ? act : (unsigned long long)h->num_index;
-  h->active_rows_host = act;
-  if (!sparse) h->table_dense_change = true;         // the split scorer's copies can no longer be refreshed row by row
+  h->lazy.adam_stepped(sparse, act, h->dtype == DM_F64);      // before the first launch: a step that fails half-way has still moved weights
   if (h->dtype == DM_F64) {
     double *w = (double *)h->d_compact, *g = (double *)h->d_grad, *s_ = (double *)h->d_adam_s, *r_ = (double *)h->d_adam_r;
     if (sparse) {
@@ -388,7 +357,9 @@ int dm_adam_step(dm_handle_t h, float grad_scale) {
   }
   HIPCHK(h, hipMemsetAsync(h->d_touch_cnt, 0, 8, h->stream));
   h->touch_ub = 0;
-  return refresh_fragments(h);
+  // the weights moved: the derived copies in the model's own type follow at once, the lazy ones were marked stale above
+  model_changed(h);      // (clones re-mirror)
+  return derive_small(h, DERIVE_OWN);
 }
 
 // measurement: embedding rows the last dm_adam_step visited (== num_index when it streamed the whole table) and whether it took the
