@@ -26,6 +26,10 @@
 // D_t = sum of the squared distances to the assigned centroid, new centroid = mean of its items; an empty cluster is re-seeded
 // at the item farthest from the other centroid (lowest position on ties).  A restart stops after iteration t when the summed
 // squared movement of its two centroids is <= tol^2, or t >= 2 and |D_{t-1} - D_t| <= tol, or t = max_iter.  Its distortion is D_t.
+//
+// Input contract: finite float32 rows.  Every comparison above is false for a NaN distance (no farthest item, no rank), so both
+// entry points refuse a NaN or an infinity with DM_ERR_INVALID before the first clustering kernel runs: dm_cluster_tree scans the
+// host array, dm_cluster_tree_model checks the gathered rows on the device (cl_nonfinite_kernel).
 #define CL_TB 256
 #define CL_TILE 1024
 #define CL_RMAX 32
@@ -95,6 +99,13 @@ __global__ void cl_gather_rows_kernel(const float *tab, int stride, int cols, co
     const int64_t r = i / ocols; const int e = (int)(i % ocols);
     out[i] = e < cols ? tab[(int64_t)rows[r] * stride + e] : 0.f;
   }
+}
+
+// lowest row of X [n][cols] that holds a NaN or an infinity -> *first (the caller sets it to INT32_MAX: no such row)
+__global__ void cl_nonfinite_kernel(const float *X, int64_t n, int cols, int32_t *first) {
+  const int64_t tot = n * cols;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (int64_t)gridDim.x * blockDim.x)
+    if ((__float_as_uint(X[i]) & 0x7f800000u) == 0x7f800000u) atomicMin(first, (int32_t)(i / cols));
 }
 
 // ---- seeding -----------------------------------------------------------------------------------------------------------------
@@ -323,7 +334,10 @@ __global__ __launch_bounds__(CL_TB) void cl_lloyd_reduce_kernel(ClLevel L) {
       D += dsh[i]; c1 += csh[i];
       if (fdsh[i] > bd || (fdsh[i] == bd && fpsh[i] < bp)) { bd = fdsh[i]; bp = fpsh[i]; }
     }
-    tot_dist = D; tot_c1 = c1; far_pos = bp;
+    // no farthest item was found (no distance compared greater than -1: non-finite rows, which the entry points refuse): the
+    // segment's first position, so that the sentinel can never become an address
+    const int sb = L.seg_off[s], se = L.seg_off[s + 1];
+    tot_dist = D; tot_c1 = c1; far_pos = bp >= sb && bp < se ? bp : sb;
   }
   __syncthreads();
   const int size = L.seg_off[s + 1] - L.seg_off[s];
@@ -767,6 +781,22 @@ static void cluster_single(int32_t *codes_out, const dm_cluster_trace *trace, dm
   if (stats) *stats = dm_cluster_stats{};
 }
 
+// the finite-input scan of the host array: one pass, branch-free inside a row (an OR of "exponent all ones" over its columns, which
+// the compiler vectorises), so it runs at the speed of one core reading memory; -1 = every value finite
+static int64_t cluster_first_nonfinite_row(const float *emb, int64_t n, int E) {
+  for (int64_t i = 0; i < n; i++) {
+    const float *row = emb + i * E;
+    uint32_t bad = 0;
+    for (int e = 0; e < E; e++) {
+      uint32_t u;
+      memcpy(&u, row + e, 4);
+      bad |= (u & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    }
+    if (bad) return i;
+  }
+  return -1;
+}
+
 int dm_cluster_tree(dm_handle_t h, const float *emb, int64_t n, int E, int restarts, int max_iter, double tol, uint64_t seed, int32_t *codes_out,
                     const dm_cluster_trace *trace, dm_cluster_stats *stats) {
   if (!h) return DM_ERR_INVALID;
@@ -774,6 +804,13 @@ int dm_cluster_tree(dm_handle_t h, const float *emb, int64_t n, int E, int resta
   if (E < 1 || E > 128) return fail(h, DM_ERR_UNSUPPORTED, "dm_cluster_tree: embed size must be 1 .. 128");
   const int rc = cluster_check(h, "dm_cluster_tree", n, restarts, max_iter, tol, codes_out);
   if (rc != DM_OK) return rc;
+  const int64_t bad_row = cluster_first_nonfinite_row(emb, n, E);
+  if (bad_row >= 0) {
+    int e = 0;
+    while (e < E - 1 && std::isfinite(emb[bad_row * E + e])) e++;
+    return fail(h, DM_ERR_INVALID, "dm_cluster_tree: row " + std::to_string(bad_row) + " holds a non-finite value (column " + std::to_string(e) +
+                                       "); the embeddings must be finite");
+  }
   if (n == 1) { cluster_single(codes_out, trace, stats); return DM_OK; }
   HIPCHK(h, hipSetDevice(h->device));
   const int EP = native_embed(E);
@@ -823,6 +860,19 @@ int dm_cluster_tree_model(dm_handle_t h, const int32_t *item_ids, int64_t n, int
   float *d_X = nullptr;
   const int rg = cluster_gather_model(h, "dm_cluster_tree_model", item_ids, n, h->embed, arena, &d_X);
   if (rg != DM_OK) return rg;
+  {                                                   // the finite-input contract, before any clustering kernel
+    int32_t *d_first, first = 0x7fffffff;
+    CL_GET(d_first, 1);
+    HIPCHK(h, hipMemcpy(d_first, &first, 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(cl_nonfinite_kernel, dim3((unsigned)std::min<int64_t>((n * h->embed + 255) / 256, 8192)), dim3(256), 0, h->stream,
+                       (const float *)d_X, n, h->embed, d_first);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&first, d_first, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (first != 0x7fffffff)
+      return fail(h, DM_ERR_INVALID, "dm_cluster_tree_model: row " + std::to_string(first) + " (item id " + std::to_string(item_ids[first]) +
+                                         ") holds a non-finite value; the embeddings must be finite");
+  }
   if (n == 1) { cluster_single(codes_out, trace, stats); return DM_OK; }
   return cluster_dispatch(h, d_X, h->embed, n, h->embed_log > 0 ? h->embed_log : h->embed, restarts, max_iter, tol, seed, codes_out, trace, stats);
 }

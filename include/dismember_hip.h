@@ -527,7 +527,8 @@ typedef struct {
   double seeding_s, lloyd_s, split_s, lds_s; /* wall seconds per phase */
 } dm_cluster_stats;
 
-/* emb: host, [n, E] row-major.  codes_out [n]: leaf code of row i. */
+/* emb: host, [n, E] row-major, every value finite: a NaN or an infinity is refused with DM_ERR_INVALID (the message names the first
+ * such row) before any kernel runs, by this entry point and by dm_cluster_tree_model alike.  codes_out [n]: leaf code of row i. */
 int dm_cluster_tree(dm_handle_t h, const float *emb, int64_t n, int E, int restarts, int max_iter, double tol, uint64_t seed,
                     int32_t *codes_out, const dm_cluster_trace *trace, dm_cluster_stats *stats);
 /* The embeddings are the loaded DIN table's rows at the items' CURRENT leaf codes in the loaded tree (what TDM.saveModel writes to

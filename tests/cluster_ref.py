@@ -17,15 +17,20 @@ def sqdist(x, c):
     return (d * d).sum(axis=-1)
 
 
-def lloyd(x, s0, s1, max_iter=100, tol=1e-4):
-    """x [n, E]; s0, s1: seed positions -> (c0, c1, assign, distortion, iterations)."""
+def lloyd(x, s0, s1, max_iter=100, tol=1e-4, margin=False):
+    """x [n, E]; s0, s1: seed positions -> (c0, c1, assign, distortion, iterations) and, with margin=True, a sixth value: the minimum
+    over iterations and items of |d0 - d1| / (d0 + d1), how far the nearest item ever was from the bisecting boundary (1 where both
+    distances are zero: such an item sits on both centroids and the tie rule decides in every arithmetic)."""
     x = np.asarray(x, np.float64)
     c0, c1 = x[s0].copy(), x[s1].copy()
-    prev, it = 0.0, 0
+    prev, it, mg = 0.0, 0, 1.0
     while True:
         it += 1
         d0, d1 = sqdist(x, c0), sqdist(x, c1)
         a = d1 < d0
+        if margin:
+            tot = d0 + d1
+            mg = min(mg, float(np.where(tot > 0, np.abs(d0 - d1) / np.where(tot > 0, tot, 1.0), 1.0).min()))
         dm = np.where(a, d1, d0)
         D = float(dm.sum())
         far = x[int(np.argmax(dm))]
@@ -34,7 +39,7 @@ def lloyd(x, s0, s1, max_iter=100, tol=1e-4):
         moved = float(((n0 - c0) ** 2).sum() + ((n1 - c1) ** 2).sum())
         c0, c1 = n0, n1
         if moved <= tol * tol or (it >= 2 and abs(prev - D) <= tol) or it >= max_iter:
-            return c0, c1, a, D, it
+            return (c0, c1, a, D, it, mg) if margin else (c0, c1, a, D, it)
         prev = D
 
 
@@ -183,3 +188,226 @@ def f32_mean_error(x):
     """max absolute error of a plain float32 column mean against fp64"""
     x32 = np.asarray(x, np.float32)
     return float(np.abs(x32.mean(axis=0, dtype=np.float32).astype(np.float64) - x32.astype(np.float64).mean(axis=0)).max())
+
+
+# ---- the library's counter RNG (dismember_amd/csrc/sampler.hip.inc, cluster.hip.inc), restated with Python integers mod 2^64 ----
+M64 = (1 << 64) - 1
+
+
+def splitmix(z):
+    """dm_dev_splitmix"""
+    z = (z + 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def sample_draw(seed, t, level, ctr, stream):
+    """dm_sample_draw(seed, t, level, ctr, stream)"""
+    inner = splitmix(((t & M64) * 64 + level + (stream << 40)) & M64)
+    return splitmix((seed & M64) ^ inner ^ ((ctr * 0xD6E8FEB86659FD93) & M64))
+
+
+def cl_uniform(seed, node, restart, ctr):
+    """cl_uniform: stream 9, the top 53 bits as a double in [0, 1)"""
+    return float(sample_draw(seed, node, restart, ctr, 9) >> 11) * 2.0 ** -53
+
+
+def cl_first_seed(seed, node, restart, size):
+    return min(int(cl_uniform(seed, node, restart, 0) * float(size)), size - 1)
+
+
+def predict_seeds(x, seed, node, restart):
+    """x: the node's rows in the node's position order -> (s0, candidate positions of the second seed).
+    s0 is cl_first_seed.  The second seed is the D^2-weighted pick at u1 * total: d^2 to row s0 in float32 (float32 accumulation over
+    E, as the device's distances are), accumulated in fp64 in position order; the device's fmaf order and numpy's differ by float32
+    roundings, so every position whose cumulative interval comes within 1e-6 * total of the target is a candidate (normally one).
+    total == 0 (every row on the first seed): the next position."""
+    x32 = np.asarray(x, np.float32)
+    size = len(x32)
+    s0 = cl_first_seed(seed, node, restart, size)
+    d = ((x32 - x32[s0]) ** 2).sum(axis=1, dtype=np.float32).astype(np.float64)
+    cum = np.cumsum(d)
+    total = float(cum[-1])
+    if not total > 0.0:
+        return s0, [(s0 + 1) % size]
+    target = cl_uniform(seed, node, restart, 1) * total
+    lo, eps = cum - d, 1e-6 * total
+    cand = np.flatnonzero((d > 0) & (lo - eps <= target) & (target <= cum + eps))
+    if cand.size == 0:                                            # the target beyond the last positive interval: the last such position
+        cand = np.flatnonzero(d > 0)[-1:]
+    return s0, [int(c) for c in cand]
+
+
+def nodes(n, perm):
+    """(code, level, items in final order) of every internal node"""
+    level, sizes = 0, [n]
+    while max(sizes) > 1:
+        off = 0
+        for j, s in enumerate(sizes):
+            if s > 1:
+                yield (1 << level) - 1 + j, level, perm[off:off + s]
+            off += s
+        sizes = [v for s in sizes for v in (s // 2, s - s // 2)]
+        level += 1
+
+
+def check_split_rule(x, tr, rel_bound, label="G2"):
+    """the split rule on the device's own numbers: at every traced node the left child is a set of the n/2 smallest traced distances,
+    and every traced distance is the squared distance to the traced centroid 0 within rel_bound -> nodes checked"""
+    n = len(x)
+    worst, checked = 0.0, 0
+    for code, level, items in nodes(n, tr["perm"]):
+        if len(items) < 3:
+            assert np.isnan(tr["dist"][level, items]).all()
+            continue
+        d = tr["dist"][level, items].astype(np.float64)
+        h = len(items) // 2
+        assert d[:h].max() <= d[h:].min(), (code, "the left child is not a set of the n/2 smallest distances")
+        want = sqdist(x[items], tr["centroid0"][code])
+        err = np.abs(d - want) / np.maximum(want, 1e-300)
+        err = err[want > 0]
+        worst = max(worst, float(err.max()) if err.size else 0.0)
+        checked += 1
+    print("%s: %d nodes, worst relative distance error %.3g (bound %.3g)" % (label, checked, worst, rel_bound))
+    assert worst <= rel_bound
+    return checked
+
+
+# ---- which nodes the multi-tile Lloyd comparison (G8) looks at, and the condition it puts on its input ----------------------------
+_PATH_BITS = [(0x9E37 * (k + 1)) & 0xFFFF for k in range(8)]
+
+
+def sampled_indices(level):
+    """node indices inside `level` that G8 compares: every node down to level 4, below that eight per level, one fixed root-to-leaf
+    path under each node of level 3 (so the set is closed under taking the parent)"""
+    if level <= 4:
+        return set(range(1 << level))
+    d = level - 3
+    return set((k << d) | (_PATH_BITS[k] >> (16 - d)) for k in range(8))
+
+
+def margin_survey(x, restarts, seed, max_iter=100, tol=1e-4, device_rng=False):
+    """The restatement's own tree over x, followed through the sampled nodes only -> [(level, size, margin)] of every sampled node of
+    three items or more, margin being that of the winning restart's Lloyd run (see lloyd).  The seeds of a node come from a numpy
+    generator seeded with `seed`, or with device_rng from the library's counter RNG keyed by (seed, node code, restart) as
+    predict_seeds restates it: the tree the device is predicted to build for that seed."""
+    x = np.asarray(x, np.float64)
+    rng = np.random.default_rng(seed)
+    out, stack = [], [(0, 0, np.arange(len(x)))]
+    while stack:
+        level, j, idx = stack.pop()
+        if len(idx) < 3:
+            continue
+        best = None
+        for r in range(restarts):
+            if device_rng:
+                s0, cand = predict_seeds(x[idx], seed, (1 << level) - 1 + j, r)
+                s1 = cand[0]
+            else:
+                s0, s1 = seed_pair(x[idx], rng)
+            c0, _, _, D, it, mg = lloyd(x[idx], s0, s1, max_iter, tol, margin=True)
+            if best is None or D < best[0]:
+                best = (D, c0, mg, it)
+        out.append((level, len(idx), best[2], best[0], best[3]))
+        order = split_order(sqdist(x[idx], best[1]))
+        h = len(idx) // 2
+        nxt = sampled_indices(level + 1)
+        for cj, part in ((2 * j, idx[order[:h]]), (2 * j + 1, idx[order[h:]])):
+            if cj in nxt:
+                stack.append((level + 1, cj, part))
+    return out
+
+
+def margin_floor(E):
+    """an item closer to the bisecting boundary than this (relative) may be assigned differently by float32 distances of E terms"""
+    return 64 * E * 2.0 ** -24
+
+
+def hierarchy(n, E, seed, top=4, ratio=0.1, below=0.6, scale=2.0 ** 20):
+    """A planted hierarchy over n rows whose planted nodes have the sizes of the balanced recursion (n/2 | n - n/2), shuffled.  Planted
+    level l adds +- (a random vector of length s_l per planted node).  Down to level `top`, s_l = scale * ratio^l and the vector lies
+    in the first E/2 columns: every node of levels 0 .. top - 1 is two tight, far-apart blobs, so no item comes near a bisecting
+    boundary whatever the two seeds are.  Under it, s_l = s_top * ratio * below^(l - top - 1) and the vector lies in the last E/2
+    columns: blobs that overlap enough for Lloyd to need several iterations.  The two column sets keep float32 out of the way: the
+    members of a node under `top` agree exactly in the first columns, so their mean is exact there and the rounding of a float32
+    centroid (2^-24 of each coordinate) is relative to the small coordinates only.  scale = 2^20 puts the smallest distortion (a
+    three-item node at the deepest level, 2 s_12^2 = 0.16) three orders above the default tol = 1e-4, so the distortion and
+    iteration checks of G8 bind at every compared node (tests/test_cluster_host.py asserts it).  -> x float32 [n, E]."""
+    rng = np.random.default_rng(seed)
+    x = np.zeros((n, E))
+    half = max(E // 2, 1)
+    segs, level = [(0, n)], 0
+    while max(s for _, s in segs) > 1:
+        level += 1
+        sl = scale * (ratio ** level if level <= top else ratio ** (top + 1) * below ** (level - top - 1))
+        nxt = []
+        for st, sz in segs:
+            if sz < 2:
+                nxt.append((st, sz))
+                continue
+            u = np.zeros(E)
+            if level <= top:
+                u[:half] = rng.standard_normal(half)
+            else:
+                u[E - half:] = rng.standard_normal(half)
+            u *= sl / np.linalg.norm(u)
+            h = sz // 2
+            x[st:st + h] -= u
+            x[st + h:st + sz] += u
+            nxt += [(st, h), (st + h, sz - h)]
+        segs = nxt
+    return x[rng.permutation(n)].astype(np.float32)
+
+
+def blobs(n, E, seed, k=12, sigma=0.01):
+    """k tight Gaussian blobs (N(0, sigma) around N(0, 1) centres) of unequal sizes, rows interleaved at random: 2-means has many local
+    optima on it (which blobs go together), far apart in distortion, and no item near a boundary.  -> x float32 [n, E]."""
+    rng = np.random.default_rng(seed)
+    centres = rng.standard_normal((k, E))
+    which = rng.choice(k, size=n, p=np.arange(1, k + 1) / (k * (k + 1) / 2.0))
+    return (centres[which] + rng.standard_normal((n, E)) * sigma).astype(np.float32)
+
+
+def predict_winner(x, seed, node, restarts, max_iter=100, tol=1e-4):
+    """every restart's predicted seed pair run through lloyd -> (winning restart, its (s0, s1), its distortion, the runner-up's
+    distortion, True when every restart had a single second-seed candidate); lowest distortion wins, lowest index on ties"""
+    runs, single = [], True
+    for r in range(restarts):
+        s0, cand = predict_seeds(x, seed, node, r)
+        single = single and len(cand) == 1
+        runs.append((lloyd(x, s0, cand[0], max_iter, tol)[3], r, s0, cand[0]))
+    order = sorted(runs)
+    D, r, s0, s1 = order[0]
+    return r, (s0, s1), D, (order[1][0] if len(order) > 1 else np.inf), single
+
+
+def distortion_tol(E, D, tol=1e-4):
+    """G3's rule: the device sums float32 distances of E sequential terms (relative error <= E * 2^-24 each, twice that allowed), and
+    the two may stop one iteration apart where |D_{t-1} - D_t| straddles the tolerance"""
+    return tol + 2 * E * 2.0 ** -24 * D
+
+
+def balanced_codes(n):
+    """the codes of the balanced recursion over the identity order: row i is position i at every level"""
+    out, stack = np.zeros(n, np.int64), [(0, 0, n)]
+    while stack:
+        code, st, sz = stack.pop()
+        if sz == 1:
+            out[st] = code
+        else:
+            stack += [(2 * code + 1, st, sz // 2), (2 * code + 2, st + sz // 2, sz - sz // 2)]
+    return out
+
+
+# ---- the cases of tests/test_gpu_cluster_edges.py whose input conditions tests/test_cluster_host.py proves on the CPU ---------------
+N8, DATA_SEED, G8_SEED = 2500, {16: 9, 32: 5, 64: 1, 128: 20}, 30      # G8: g8_data(E) clustered with seed G8_SEED
+
+
+def g8_data(E):
+    return hierarchy(N8, E, DATA_SEED[E])
+
+
+G9_SHAPES = [(200, 16), (300, 16), (1500, 16), (1500, 128)]
+G9_WINNER_SEEDS = {(200, 16): [1, 3, 5, 11, 13, 23], (300, 16): [1, 5, 8, 26, 38, 39], (1500, 16): [3, 14, 18, 27, 35, 37],
+                   (1500, 128): [2, 10, 12, 14, 16, 23]}   # G9 at 32 restarts, on blobs(n, E, 3)

@@ -95,3 +95,87 @@ def test_spectral_is_refused_and_dispatcher_line_stays(tmp_path):
     from test_tasks import _conf
     assert tasks.main(["TDMClusterTree", "--tdmConfFile", _conf(tmp_path)]) == 3
     assert cluster.main([]) == 2
+
+
+def test_rng_restatement():
+    """cluster_ref restates the library's counter RNG (csrc/sampler.hip.inc) with Python integers.  dm_dev_splitmix is SplitMix64's
+    output function (Steele, Lea, Flood 2014), whose published first outputs from state 0 pin the constants; the oracle library
+    keeps its own draw static (orc_draw), so the pin of dm_sample_draw against the device is G9 in test_gpu_cluster_edges.py."""
+    assert R.splitmix(0) == 0xE220A8397B1DCDAF and R.splitmix(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
+    assert R.splitmix(2 * 0x9E3779B97F4A7C15 & R.M64) == 0x06C45D188009454F
+    assert R.sample_draw(2 ** 64 - 1, 2 ** 40, 31, 2 ** 63, 9) < 2 ** 64                       # everything wraps mod 2^64
+    u = [R.cl_uniform(s, node, r, c) for s in range(20) for node in (0, 1, 1000) for r in (0, 31) for c in (0, 1)]
+    assert all(0.0 <= v < 1.0 for v in u) and len(set(u)) == len(u) and 0.4 < np.mean(u) < 0.6
+    for size in (3, 257, 2500):
+        p = [R.cl_first_seed(s, 0, 0, size) for s in range(200)]
+        assert min(p) >= 0 and max(p) < size and len(set(p)) > min(size, 200) // 2
+        assert R.cl_first_seed(7, 0, 0, size) == int(R.cl_uniform(7, 0, 0, 0) * size)
+
+
+def test_predict_seeds_and_margin():
+    x = np.tile(np.float32([1.0, -2.0, 0.0, 3.0]), (7, 1))
+    for seed in range(5):
+        s0, cand = R.predict_seeds(x, seed, 0, 0)
+        assert cand == [(s0 + 1) % 7]                                                           # every row on the first seed
+    x = np.random.default_rng(2).random((50, 4), dtype=np.float32)
+    picks = [R.predict_seeds(x, seed, 0, 0) for seed in range(300)]
+    assert all(len(c) >= 1 and s0 not in c for s0, c in picks) and sum(len(c) == 1 for _, c in picks) >= 298
+    far = np.vstack([x, x[:1] + 1000.0])                                                       # one row holds nearly all of the D^2 mass
+    assert sum(R.predict_seeds(far, seed, 0, 0)[1] == [50] for seed in range(100)) >= 90
+    out = R.lloyd(x, 0, 1, margin=True)
+    plain = R.lloyd(x, 0, 1)
+    assert len(out) == 6 and out[4] == plain[4] and out[3] == plain[3] and np.array_equal(out[0], plain[0]) and 0.0 <= out[5] <= 1.0
+    y = np.float64([[0.0], [1.0], [0.5 + 1e-9]])
+    assert R.lloyd(y, 0, 1, max_iter=1, margin=True)[5] == pytest.approx(2e-9 / (0.25 + 0.25), rel=1e-3)
+    assert np.array_equal(R.balanced_codes(5), [3, 4, 5, 13, 14]) and R.sampled_indices(3) == set(range(8))
+    for level in range(5, 12):
+        assert len(R.sampled_indices(level)) == 8 and {j >> 1 for j in R.sampled_indices(level)} <= R.sampled_indices(level - 1)
+
+
+@pytest.mark.parametrize("E", [16, 32, 64, 128])
+def test_g8_input_keeps_its_items_off_the_boundaries(E):
+    """the condition G8 puts on its input: over the restatement's own tree, for 20 generator seeds and for the tree predicted for
+    the device's seed, no item of a node of levels 0-3 ever comes within 64 E 2^-24 of the bisecting boundary, and of the sampled
+    nodes below (all of level 4, eight per deeper level: the ones G8 compares) at most a tenth do.  The data is scaled against the
+    default tol = 1e-4: the distortion tolerance is under a hundredth of the distortion at every node, and in the tree predicted for
+    the device some streamed node and some LDS node take three iterations or more"""
+    x = R.g8_data(E)
+    surveys = [R.margin_survey(x, 4, seed) for seed in range(20)] + [R.margin_survey(x, 4, R.G8_SEED, device_rng=True)]
+    for sv in surveys:
+        top = [m for level, _, m, _, _ in sv if level <= 3]
+        low = [m for level, _, m, _, _ in sv if level > 3]
+        assert len(top) == 15 and min(top) >= R.margin_floor(E), (E, min(top))
+        assert len(low) >= 48 and sum(m < R.margin_floor(E) for m in low) <= 0.1 * len(low)
+        assert all(R.distortion_tol(E, D) <= 0.01 * D for _, _, _, D, _ in sv)                   # the distortion check binds at every node
+    predicted = surveys[-1]                                                                    # and so does the iteration check: real Lloyd work
+    assert max(it for level, _, _, _, it in predicted if level <= 3) >= 3 and max(it for level, _, _, _, it in predicted if level > 3) >= 3
+
+
+@pytest.mark.parametrize("n,E", R.G9_SHAPES)
+def test_g9_seed_conditions(n, E):
+    x = R.g8_data(E)[:n]
+    assert sum(len(R.predict_seeds(x, seed, 0, 0)[1]) == 1 for seed in range(1, 33)) >= 30
+    x = R.blobs(n, E, 3)
+    high = 0
+    for seed in R.G9_WINNER_SEEDS[(n, E)]:
+        r, _, D, runner_up, single = R.predict_winner(x, seed, 0, 32)
+        assert single and runner_up - D > 2 * R.distortion_tol(E, D), (seed, r, D, runner_up)
+        high += r >= 16
+    assert len(R.G9_WINNER_SEEDS[(n, E)]) == 6 and high >= 2
+
+
+def test_edge_tolerances_are_what_numpy_gives():
+    t = json.load(open(os.path.join(ROOT, "tests", "golden", "cluster_tolerances.json")))
+    for E in (16, 32, 64, 128):
+        x = R.g8_data(E)
+        c = t["centroid_multi_tile"]["hierarchy_2500x%d" % E]
+        assert c["measured_f32_mean_abs"] == pytest.approx(R.f32_mean_error(x), rel=1e-6)
+        assert c["f32_rounding_abs"] == pytest.approx(float(np.abs(x).max()) * 2.0 ** -24)      # half an ulp of the largest coordinate
+        assert c["bound_abs"] == pytest.approx(4 * (c["measured_f32_mean_abs"] + c["f32_rounding_abs"]))
+    cases = {"uniform_600x%d" % E: np.random.default_rng(40 + E).random((600, E), dtype=np.float32) for E in (1, 24, 48, 100)}
+    cases["hierarchy_2500x16"] = R.g8_data(16)
+    assert sorted(cases) == sorted(t["distance_edges"])
+    for name, x in cases.items():
+        d = t["distance_edges"][name]
+        assert d["measured_rel"] == pytest.approx(R.f32_distance_error(x, x.mean(axis=0)), rel=1e-6) and d["bound_rel"] == pytest.approx(4 * d["measured_rel"])
+        assert d["measured_rel"] >= 2.0 ** -25                                                  # the device rounds its fp64 distance to float32 once

@@ -46,37 +46,7 @@ def test_g1_structure(eng, n, E):
         assert st["levels_streamed"] == 0
 
 
-def _nodes(n, perm):
-    """(code, level, items in final order) of every internal node"""
-    level, sizes = 0, [n]
-    while max(sizes) > 1:
-        off = 0
-        for j, s in enumerate(sizes):
-            if s > 1:
-                yield (1 << level) - 1 + j, level, perm[off:off + s]
-            off += s
-        sizes = [v for s in sizes for v in (s // 2, s - s // 2)]
-        level += 1
-
-
-def _check_split_rule(x, tr, rel_bound):
-    n = len(x)
-    worst, checked = 0.0, 0
-    for code, level, items in _nodes(n, tr["perm"]):
-        if len(items) < 3:
-            assert np.isnan(tr["dist"][level, items]).all()
-            continue
-        d = tr["dist"][level, items].astype(np.float64)
-        h = len(items) // 2
-        assert d[:h].max() <= d[h:].min(), (code, "the left child is not a set of the n/2 smallest distances")
-        want = R.sqdist(x[items], tr["centroid0"][code])
-        err = np.abs(d - want) / np.maximum(want, 1e-300)
-        err = err[want > 0]
-        worst = max(worst, float(err.max()) if err.size else 0.0)
-        checked += 1
-    print("G2: %d nodes, worst relative distance error %.3g (bound %.3g)" % (checked, worst, rel_bound))
-    assert worst <= rel_bound
-    return checked
+_nodes, _check_split_rule = R.nodes, R.check_split_rule      # (shared with test_gpu_cluster_edges.py)
 
 
 @pytest.mark.parametrize("case", ["planted_1024x16", "uniform_5000x16", "uniform_1000x128"])
@@ -200,6 +170,17 @@ def test_g7_argument_errors(eng):
     assert L.dm_cluster_tree_model(fresh._h, bad.ctypes.data_as(N.i32p), 2, 3, 100, 1e-4, 1, cp, None, None) == -1
     assert b"not a leaf" in L.dm_last_error(fresh._h)
     assert L.dm_get_leaf_embeddings(fresh._h, None, 2, xp) == -1
+    for v in (np.nan, -np.inf):                                   # a non-finite row is refused by both entry points, the row named
+        bad_x = x.copy()
+        bad_x[4, 2] = v
+        assert call(bad_x.ctypes.data_as(N.f32p), 10, 16, 3, 100, 1e-4, 1, cp, None, None) == -1
+        assert b"dm_cluster_tree: row 4 " in L.dm_last_error(eng._h)
+        w = np.load(os.path.join(GOLDEN, "din_f32.npy")).copy()
+        two = t["leaf_ids"][:2].astype(np.int32)
+        w[int(t["leaf_codes"][1]) * 16 + 7] = v
+        fresh.load_weights_din(w, 16, 8191)
+        assert L.dm_cluster_tree_model(fresh._h, two.ctypes.data_as(N.i32p), 2, 3, 100, 1e-4, 1, cp, None, None) == -1
+        assert b"dm_cluster_tree_model: row 1 (item id %d)" % two[1] in L.dm_last_error(fresh._h)
     fresh.close()
     good, _, _ = eng.cluster_tree(x, restarts=3, seed=1)          # the handle still works after the refused calls
     R.check_structure(good, 10)

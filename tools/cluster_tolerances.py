@@ -7,6 +7,8 @@ float32 numpy evaluation against fp64 on the tests' own data (never from what th
   centroid  absolute error of a float32 column mean over the members of every node of the restatement's tree, plus one float32
             rounding of the largest coordinate (the centroid is handed back as float32: 2^-24 of its magnitude is the format's own
             precision); the device is allowed 4 x the sum.
+  centroid_multi_tile, distance_edges  the bounds of tests/test_gpu_cluster_edges.py (G8, G10, G11), the same two rules measured on
+            each case's whole data.
 """
 import json
 import os
@@ -51,6 +53,17 @@ def main():
         if name == "planted_1024x16":
             fmt = float(np.abs(x).max()) * 2.0 ** -24
             out["centroid"] = {"measured_f32_mean_abs": m, "f32_rounding_abs": fmt, "bound_abs": 4 * (m + fmt)}
+    # tests/test_gpu_cluster_edges.py: the same two rules on each case's whole data (tests/test_cluster_host.py recomputes these)
+    out["centroid_multi_tile"], out["distance_edges"] = {}, {}
+    for E in (16, 32, 64, 128):
+        x = R.g8_data(E)
+        m, fmt = R.f32_mean_error(x), float(np.abs(x).max()) * 2.0 ** -24
+        out["centroid_multi_tile"]["hierarchy_2500x%d" % E] = {"measured_f32_mean_abs": m, "f32_rounding_abs": fmt, "bound_abs": 4 * (m + fmt)}
+    edges = {"uniform_600x%d" % E: rng_u(600, E, 40 + E) for E in (1, 24, 48, 100)}
+    edges["hierarchy_2500x16"] = R.g8_data(16)
+    for name, x in edges.items():
+        d = R.f32_distance_error(x, x.mean(axis=0))
+        out["distance_edges"][name] = {"measured_rel": d, "bound_rel": 4 * d}
     with open(os.path.join(ROOT, "tests", "golden", "cluster_tolerances.json"), "w") as f:
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
