@@ -229,8 +229,76 @@ constexpr int dmw_sm_pos(int npos, int k) {
 constexpr int dmw_sp_slot(int nslot, int gps, int s, int piece) { const int b = 3 * gps * (s + 1) + piece; return b < nslot ? b : nslot - 1; }
 constexpr int dmw_ep_slot(int nb, int j) { const int last = 3 * (j / nb) - 1, first = 3 * (j / nb - 1); return first + ((j % nb) * (last - first + 1)) / nb; }
 
-template <int E, int KQ>
+// ---- the FOLDED attention-combine (L <= 10): H^T += (G + b1)^T P^T in ONE v_mfma_f32_16x16x32_f16 per feature tile.
+// The product has three terms per history position — p_hi G_hi, p_hi G_lo, p_lo G_hi — so 3 L <= 30 of the 32 contraction
+// slots of one MFMA.  Lane group g of the tile holds p of positions g, g + 4, g + 8 (i = 0, 1, 2) and owns k-slots 8 g .. 8 g + 7;
+// positions 8 and 9 (groups 0, 1) would need nine slots, so their p_lo G_hi term lives in slot 2 of group g + 2, whose own third
+// position (10, 11) does not exist.  This function is THE slot map: the per-user setup writes the (G + b1) fragment through its
+// inverse, the tile code packs the P operand by it (dmw_fold_p_item states what the packing puts into every slot).
+enum { DMW_HH = 0, DMW_HL = 1, DMW_LH = 2 };          // p_hi G_hi, p_hi G_lo, p_lo G_hi
+#define DMW_FOLD_MAXL 10
+struct DmwSlot { int grp, k; };
+constexpr DmwSlot dmw_fold_slot(int pos, int term) {
+  const int g = pos & 3, i = pos >> 2;
+  if (term == DMW_HH) return DmwSlot{g, i};
+  if (term == DMW_HL) return DmwSlot{g, 4 + i};
+  return i == 0 ? DmwSlot{g, 3} : i == 1 ? DmwSlot{g, 7} : DmwSlot{g + 2, 2};
+}
+// inverse: the (position, term) of slot (grp, k) as 4 * pos + term, -1 for a slot no term owns
+constexpr int dmw_fold_src(int grp, int k) {
+  for (int pos = 0; pos < DMW_FOLD_MAXL; pos++)
+    for (int term = 0; term < 3; term++) {
+      const DmwSlot s = dmw_fold_slot(pos, term);
+      if (s.grp == grp && s.k == k) return 4 * pos + term;
+    }
+  return -1;
+}
+// the G part of k-slot k — hi, or lo for a p_hi G_lo term — is the same in every lane group that uses the slot (the G writer
+// converts by slot, not by lane)
+constexpr bool dmw_fold_g_lo(int k) { return k >= 4 && k < 7; }
+// what the tile code packs into slot (grp, k) of the P operand: item j (0, 1) as 2 * pos + (1 = the lo part), -1 for none.
+// Slots 0-2 / 4-6 carry p_hi of the lane's own positions, 3 / 7 p_lo of its first two, and slot 2 is OR-ed with p_lo of the
+// third position of the lane 32 further (group grp ^ 2): of the two halves OR-ed there one is always +0
+constexpr int dmw_fold_p_item(int grp, int k, int j) {
+  if (j == 0) return k == 3 ? 2 * grp + 1 : k == 7 ? 2 * (grp + 4) + 1 : 2 * (grp + 4 * (k & 3));
+  return k == 2 ? 2 * ((grp ^ 2) + 8) + 1 : -1;
+}
+// for every L <= 10: every (position < L, term) owns exactly one slot, no slot has two owners, and what the P operand holds in
+// a slot is the owner's p part or — a position >= L has p = +0 in both parts — zero: every unused slot multiplies a zero
+constexpr bool dmw_fold_map_ok() {
+  for (int L = 1; L <= DMW_FOLD_MAXL; L++) {
+    int owners[4][8] = {};
+    for (int pos = 0; pos < L; pos++)
+      for (int term = 0; term < 3; term++) {
+        const DmwSlot s = dmw_fold_slot(pos, term);
+        if (s.grp < 0 || s.grp > 3 || s.k < 0 || s.k > 7) return false;
+        if (++owners[s.grp][s.k] > 1) return false;
+        if (dmw_fold_src(s.grp, s.k) != 4 * pos + term || dmw_fold_g_lo(s.k) != (term == DMW_HL)) return false;
+      }
+    for (int grp = 0; grp < 4; grp++)
+      for (int k = 0; k < 8; k++) {
+        const int src = dmw_fold_src(grp, k);
+        const int want = src >= 0 && (src >> 2) < L ? 2 * (src >> 2) + ((src & 3) == DMW_LH ? 1 : 0) : -1;
+        for (int j = 0; j < 2; j++) {
+          const int it = dmw_fold_p_item(grp, k, j);
+          if (it >= 0 && (it >> 1) < L && it != want) return false;          // a live p part in a slot that is not its own
+        }
+        if (want >= 0 && dmw_fold_p_item(grp, k, 0) != want && dmw_fold_p_item(grp, k, 1) != want) return false;
+      }
+  }
+  return true;
+}
+static_assert(dmw_fold_map_ok(), "folded attention-combine: the slot map and the P packing disagree");
+// position whose (G + b1) value slot k of lane group grp holds, per k as one nibble per group (15 = none: the half is zero)
+constexpr unsigned dmw_fold_pos_nibbles(int k) {
+  unsigned w = 0;
+  for (int grp = 0; grp < 4; grp++) { const int s = dmw_fold_src(grp, k); w |= (unsigned)(s < 0 ? 15 : s >> 2) << (4 * grp); }
+  return w;
+}
+
+template <int E, int KQ, bool FOLD>
 __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
+  static_assert(!FOLD || KQ <= 3, "the folded attention-combine holds 10 history positions");
   constexpr int NJ = E / 16, NT = E / 16, NS = E / 32;
   constexpr int KCOLS = KQ >= 4 ? 16 : 12;
   constexpr int NB = NT < 4 ? NT : 4;          // MFMAs per batch (independent accumulators issued back to back)
@@ -497,7 +565,40 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
       }
       constexpr int NENT = NT * 64;           // one dm_h8 per (feature tile, lane)
       constexpr int NQ = (NENT + 63) / 64;
-      if (sp != DM_G32) {
+      if constexpr (FOLD) {
+        // the folded layout: half k of lane group g_ is the G part of the (position, term) that owns slot (g_, k) — dmw_fold_slot
+        if (sp != DM_G32) {
+          const float gs = __uint_as_float((unsigned)(S - sp + 127) << 23);
+          float gv[NQ][8];
+#pragma unroll
+          for (int q = 0; q < NQ; q++) {
+            const int idx = lane + 64 * q;
+            const int nt_ = (idx >> 6) % NT, m_ = idx & 15, g_ = (idx >> 4) & 3;
+            DMW_FOR(8, k)
+              const int pos = (int)((dmw_fold_pos_nibbles(k) >> (4 * g_)) & 15u);
+              const int posc = pos < 4 * KQ ? pos : 0;
+              const float v = Gfw[((posc >> 2) * NT + nt_) * 64 + (posc & 3) * 16 + m_] * gs;
+              gv[q][k] = pos < 4 * KQ ? v : 0.0f;
+            DMW_END
+          }
+          wsync();   // every fp32 value has been read: the planes overwrite the region
+          typedef float f32x2_ __attribute__((ext_vector_type(2)));
+#pragma unroll
+          for (int q = 0; q < NQ; q++) {
+            float x[8];
+            DMW_FOR(8, k)     // a G_lo slot holds what the fp16 hi part leaves of the value
+              x[k] = dmw_fold_g_lo(k) ? gv[q][k] - (float)(_Float16)gv[q][k] : gv[q][k];
+            DMW_END
+            const dm_h2 h01 = __builtin_convertvector((f32x2_){x[0], x[1]}, dm_h2), h23 = __builtin_convertvector((f32x2_){x[2], x[3]}, dm_h2);
+            const dm_h2 h45 = __builtin_convertvector((f32x2_){x[4], x[5]}, dm_h2), h67 = __builtin_convertvector((f32x2_){x[6], x[7]}, dm_h2);
+            dm_h8 o;
+            o[0] = h01[0]; o[1] = h01[1]; o[2] = h23[0]; o[3] = h23[1]; o[4] = h45[0]; o[5] = h45[1]; o[6] = h67[0]; o[7] = h67[1];
+            ((dm_h8 *)Gfw)[lane + 64 * q] = o;
+          }
+        } else {
+          for (int i = lane; i < KQ * NT * 64; i += 64) Gfw[i] *= p.acc_scale;
+        }
+      } else if (sp != DM_G32) {
         const float gs = __uint_as_float((unsigned)(S - sp + 127) << 23);
         float gv[NQ][4];
 #pragma unroll
@@ -809,6 +910,8 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
           float xl = 0.f;        // a cross-lane exchange in flight: issued behind one MFMA, consumed >= 4 MFMAs later (LDS crossbar latency)
           typedef float f32x2_ __attribute__((ext_vector_type(2)));
           dm_h2 p01, p23, q01, q23;
+          typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
+          unsigned xq = 0u;      // folded product: the p_lo half received from the lane 32 further
           // Mask.scala:17-35, SoftMax.scala:28-42 in the base-2 domain (4 positions in the lane, 12 in lanes r+16, r+32, r+48),
           // cut into 18 items of 1-4 VALU instructions; item k rides behind the MFMA at position dmw_sm_pos(k) of the chain
           auto softmax_item = [&](auto kc) {
@@ -829,6 +932,14 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
             else if constexpr (k == 16) {
               q01 = __builtin_convertvector((f32x2_){pr[0] - (float)p01[0], pr[1] - (float)p01[1]}, dm_h2);
               q23 = __builtin_convertvector((f32x2_){pr[2] - (float)p23[0], pr[3] - (float)p23[1]}, dm_h2);
+              // folded product: p_lo of positions 8, 9 goes to the lane 32 further (slot 2 of group g + 2, dmw_fold_slot)
+              if constexpr (FOLD && KQ >= 3) xq = (unsigned)__shfl_xor((int)__builtin_bit_cast(unsigned, q23), 32);
+            } else if constexpr (FOLD) {
+              // [ph0 ph1 ph2|X pl0 | ph0 ph1 ph2 pl1]: of ph2 and the received X = pl2 one is +0 in every lane (dmw_fold_p_item)
+              const unsigned u01 = __builtin_bit_cast(unsigned, p01), u23 = __builtin_bit_cast(unsigned, p23), v01 = __builtin_bit_cast(unsigned, q01);
+              const unsigned lo2 = u23 & 0xffffu;
+              const u32x4_ pu = {u01, (lo2 | (xq & 0xffffu)) | (v01 << 16), u01, lo2 | (v01 & 0xffff0000u)};
+              pb0 = __builtin_bit_cast(dm_h8, pu);
             } else {
               pb0 = (dm_h8){p01[0], p01[1], p23[0], p23[1], p01[0], p01[1], p23[0], p23[1]};
               pb1 = (dm_h8){q01[0], q01[1], q23[0], q23[1], 0, 0, 0, 0};
@@ -891,7 +1002,26 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
           DMW_END
           // ---- H^T += (G + b1)^T P^T.  Behind its MFMAs: the split of the last k-step of the next tile, and — behind the LAST
           //      group — the epilogue elements of this tile's first EPG accumulators (final since the group before)
-          {
+          if constexpr (FOLD) {
+            // one MFMA per feature tile: the three terms of every position share its 32 contraction slots (dmw_fold_slot)
+            asm volatile("s_nop 1" : "+v"(pb0));
+            load_keys();                 // the next tile's score MFMAs open with these: a whole product of slack
+            DMW_FOR(GPS, gg)
+              constexpr int nb0 = gg * NB;
+              DMW_FOR(NB, ii)
+                dmw_mfma_vv(acc[nb0 + ii], gvv[nb0 + ii], pb0);
+                DMW_PIN();
+#ifndef DMW_DBG_NO_GATHER
+                if constexpr (gg == 0 && ii == 1 % NB) dmw_gather16<128 * (NS - 1)>(bh[NS - 1], nsrc);
+                if constexpr (gg == 0 && ii == 2 % NB) dmw_gather16<128 * (NS - 1) + 16>(bl[NS - 1], nsrc);
+#endif
+                if constexpr (EPG > 0 && gg == GPS - 1) {
+                  DMW_FOR(4 * EPG, el) if constexpr ((el * NB) / (4 * EPG) == ii) epi_elem(el / 4, el % 4); DMW_END
+                }
+                DMW_PIN();
+              DMW_END
+            DMW_END
+          } else {
             asm volatile("s_nop 1" : "+v"(pb0), "+v"(pb1));
             load_keys();                 // the next tile's score MFMAs open with these: a whole product of slack
             constexpr int NGAP = 2 * GPS;
@@ -926,10 +1056,23 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
         //      attention-combine product.  The 32 epilogue elements of tile t: pieces 0..3 (accumulators final half way through
         //      t's last product) behind t's last ten MFMAs and the next tile's score MFMAs; pieces 4..7 behind every third
         //      MFMA of the next tile's first accumulator group.
+        //      FOLD: the attention-combine product is 8 MFMAs (gaps 108..115, 116 gaps per tile) and pieces 0..3 are final after
+        //      its first four.  Their elements keep the distance (in gaps) they had behind the MFMA that finalises their
+        //      accumulator: five behind this tile's last MFMAs, nine behind the next tile's score MFMAs, the last two in the
+        //      free gaps 1 and 2 of its W1a chain (accumulator 3 is rewritten at chain position 3); pieces 4..7 follow at chain
+        //      positions 3, 6, .. 45 and 46 (the elements run in order: each piece fetches the next one's w2 vector).
         typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        u32x4_ pbu0 = {0u, 0u, 0u, 0u}, pbu1 = {0u, 0u, 0u, 0u};       // the P operands; pbu1 lanes 2, 3 stay zero
+        u32x4_ pbu0 = {0u, 0u, 0u, 0u}, pbu1 = {0u, 0u, 0u, 0u};       // the P operands; pbu1 lanes 2, 3 stay zero (FOLD: pbu0 alone)
         constexpr int FG_S = 3 * NS, FG_W = 3 * NS + 3 * NGRP * NB;          // 12, 108
+        constexpr int FG_N = FG_W + (FOLD ? 1 : 2) * GPS * NB;               // gaps per tile: 124, FOLD 116
         constexpr auto el_gap = [](int el) constexpr -> int {
+          if constexpr (FOLD) {
+            // accumulator n is final four MFMAs earlier than unfolded, so its elements sit four gaps earlier, counted on from the
+            // product's first MFMA: 2 3 4 6 | 7 8 10 11 | 13 14 15 17 | 18 19 21 22 for pieces 0 | 1 | 2 | 3
+            if (el >= 16) return el < 31 ? FG_S + 3 + 3 * (el - 16) : FG_S + 46;
+            const int pos = 2 + (el * 22) / 16;
+            return pos < FG_N - FG_W ? FG_W + pos : pos - (FG_N - FG_W);
+          }
           if (el >= 16) return FG_S + 3 * (el - 16);
           const int slot = (el * 22) / 16;
           return slot < 10 ? FG_W + 6 + slot : slot - 10;
@@ -945,11 +1088,12 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
           float ma = 0.f, mb = 0.f, mx = 0.f, sum = 0.f, sb = 0.f, xl = 0.f;
           dm_h8 gvv[NT];
           unsigned pu01 = 0u, pu23 = 0u;
+          unsigned xt = 0u, xq = 0u;        // FOLD: p_lo of the lane's third position, sent to / received from the lane 32 further
           typedef float f32x2_ __attribute__((ext_vector_type(2)));
           auto gap = [&](auto g_c) {
             constexpr int G = decltype(g_c)::value;
             constexpr int w = G - FG_S;                   // position in the W1a chain
-            // ---- epilogue elements (of the previous tile below FG_W + 6, of this one from there)
+            // ---- epilogue elements (of the previous tile below FG_W + 6 — FOLD: FG_W + 2 —, of this one from there)
 #ifndef DMW_DBG_F_NOEPI
             DMW_FOR(4 * NT, el) if constexpr (el_gap(el) == G) epi_elem(el / 4, el % 4); DMW_END
 #endif
@@ -984,14 +1128,32 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
               pu01 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){pr[0], pr[1]}, dm_h2));
               pu23 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_){pr[2], pr[3]}, dm_h2));
             }
-            if constexpr (w == 56) { pbu0[0] = pu01; pbu0[1] = pu23; }
-            if constexpr (w == 58) { pbu0[2] = pu01; pbu0[3] = pu23; }
+            if constexpr (FOLD) {
+              // the single operand [ph0 ph1 | ph2+X pl0 | ph0 ph1 | ph2 pl1] (dmw_fold_slot; ph3 = 0 rides in the upper halves of
+              // dwords 1 and 3 until the low parts overwrite it).  X = pl2 of the lane 32 further: one exchange of a dword, issued
+              // behind its own MFMA and OR-ed in eight gaps later — of ph2 and X one is +0 in every lane
+              constexpr int K0 = dmw_fold_slot(0, DMW_LH).k, K1 = dmw_fold_slot(4, DMW_LH).k, K2 = dmw_fold_slot(8, DMW_LH).k;
+              static_assert(K0 == 3 && K1 == 7 && K2 == 2 && dmw_fold_slot(8, DMW_LH).grp == 2, "the packing below places p_lo by hand");
+              if constexpr (w == 56) { pbu0[0] = pu01; pbu0[2] = pu01; }
+              if constexpr (w == 58) { pbu0[K0 >> 1] = pu23; pbu0[K1 >> 1] = pu23; }
+              if constexpr (w == 59) {
+                asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "+v"(pbu0[K0 >> 1]) : "v"(pu01), "v"(pr[0]));
+                asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(pbu0[K1 >> 1]) : "v"(pu01), "v"(pr[1]));
+              }
+              if constexpr (KQ >= 3) {
+                if constexpr (w == 61) asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(xt) : "v"(pu23), "v"(pr[2]));
+                if constexpr (w == 62) xq = (unsigned)__shfl_xor((int)xt, 32);
+                if constexpr (w == 70) pbu0[K2 >> 1] |= xq & 0xffffu;
+              }
+            }
+            if constexpr (!FOLD && w == 56) { pbu0[0] = pu01; pbu0[1] = pu23; }
+            if constexpr (!FOLD && w == 58) { pbu0[2] = pu01; pbu0[3] = pu23; }
             // the low parts p - fp16(p): one mixed-precision fma per element, rounded once like the subtraction it replaces
-            if constexpr (w == 59) {
+            if constexpr (!FOLD && w == 59) {
               asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(pbu1[0]) : "v"(pu01), "v"(pr[0]));
               asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(pbu1[1]) : "v"(pu23), "v"(pr[2]));
             }
-            if constexpr (w == 61) {
+            if constexpr (!FOLD && w == 61) {
               asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(pbu1[0]) : "v"(pu01), "v"(pr[1]));
               asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(pbu1[1]) : "v"(pu23), "v"(pr[3]));
             }
@@ -1055,7 +1217,15 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
             TMARK(1 + gg);
           DMW_END
           // ---- H^T += (G + b1)^T P^T
-          {
+          if constexpr (FOLD) {
+            const dm_h8 pbf = __builtin_bit_cast(dm_h8, pbu0);
+            DMW_FOR(GPS, gg)
+              DMW_FOR(NB, i)
+                dmw_mfma_vv(acc[gg * NB + i], gvv[gg * NB + i], pbf);
+                DMW_PIN(); gap(std::integral_constant<int, FG_W + gg * NB + i>{}); DMW_PIN();
+              DMW_END
+            DMW_END
+          } else {
             const dm_h8 pb0 = __builtin_bit_cast(dm_h8, pbu0), pb1 = __builtin_bit_cast(dm_h8, pbu1);
             DMW_FOR(GPS, gg)
               constexpr int nb0 = gg * NB;
@@ -1093,7 +1263,10 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
           DMW_PIN();
           asm volatile("s_nop 7\n\ts_nop 7");          // MFMA results -> VALU readers
           DMW_PIN();
-          DMW_FOR(NT - EPG, nn) DMW_FOR(4, rr) epi_elem(EPG + nn, rr); DMW_END DMW_END
+          // (the elements the tile ran behind its own last MFMAs are done: whole pieces, or — hand-placed FOLD tile — the first five)
+          constexpr int EL_IN = (E == 128 && FOLD) ? 5 : 4 * EPG;
+          static_assert(E != 128 || (el_gap(EL_IN - 1) >= FG_W && el_gap(EL_IN) < FG_W), "elements placed behind the tile's own product");
+          DMW_FOR(4 * NT - EL_IN, j) epi_elem((EL_IN + j) / 4, (EL_IN + j) % 4); DMW_END
           epi_finish(tot - 1, 0); epi_finish(tot - 1, 1); epi_finish(tot - 1, 2);
         }
       }

@@ -988,23 +988,27 @@ static int launch_beam_EK(dm_ctx *h, const BeamParams &p_in, const SearchPlan &p
   return tm.stop();
 }
 
-template <int E, int KQ>
+// FOLD: the attention-combine product in one MFMA per feature tile — its three terms per history position fit the 32 contraction
+// slots of v_mfma_f32_16x16x32_f16 exactly when 3 L <= 32 (beam_kernel_w.hip.inc, dmw_fold_slot)
+template <int E, int KQ, bool FOLD>
 static int launch_beam_w_EK(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam_w_kernel<E, KQ>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
-  snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_w_kernel<%d, %d>", E, KQ);
+  HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam_w_kernel<E, KQ, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
+  snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_w_kernel<%d, %d, %s>", E, KQ, FOLD ? "true" : "false");
   LaunchTimer tm(h);
   if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dm_beam_w_kernel<E, KQ>), dim3(pl.grid), dim3(DMW_BLOCK), pl.lds, h->stream, p);
+  hipLaunchKernelGGL((dm_beam_w_kernel<E, KQ, FOLD>), dim3(pl.grid), dim3(DMW_BLOCK), pl.lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
   return tm.stop();
 }
 template <int E>
 static int launch_beam_w_E(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
+  const bool fold = 3 * p.L <= 32;
+  static_assert(3 * DMW_FOLD_MAXL <= 32 && 3 * (DMW_FOLD_MAXL + 1) > 32, "the slot map covers exactly the lengths that fold");
   switch ((p.L + 3) / 4) {
-    case 1: return launch_beam_w_EK<E, 1>(h, p, pl);
-    case 2: return launch_beam_w_EK<E, 2>(h, p, pl);
-    case 3: return launch_beam_w_EK<E, 3>(h, p, pl);
-    default: return launch_beam_w_EK<E, 4>(h, p, pl);
+    case 1: return launch_beam_w_EK<E, 1, true>(h, p, pl);
+    case 2: return launch_beam_w_EK<E, 2, true>(h, p, pl);
+    case 3: return fold ? launch_beam_w_EK<E, 3, true>(h, p, pl) : launch_beam_w_EK<E, 3, false>(h, p, pl);
+    default: return launch_beam_w_EK<E, 4, false>(h, p, pl);
   }
 }
 

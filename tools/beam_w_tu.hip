@@ -8,4 +8,6 @@
 #include <utility>
 #include "../dismember_amd/csrc/beam_kernel.hip.inc"
 #include "../dismember_amd/csrc/beam_kernel_w.hip.inc"
-template __global__ void dm_beam_w_kernel<128, 3>(BeamParams);
+// the headline instantiation (L <= 10: folded attention-combine) and the unfolded one of the same KQ (L = 11, 12)
+template __global__ void dm_beam_w_kernel<128, 3, true>(BeamParams);
+template __global__ void dm_beam_w_kernel<128, 3, false>(BeamParams);

@@ -35,7 +35,10 @@ n_waves = 256 * 4
 clk = v.sum() / n_waves / (ms * 1e-3) / 1e9
 print("shader clock under this kernel: %.3f GHz" % clk)
 tiles = rows / 16.0
-print("cycles per tile in the tile loop: %.0f (matrix pipe minimum 124 x 16 = 1984)" % (v[4] / tiles))
+kern = eng.last_beam_kernel()
+n_mfma = 116 if kern.rstrip(">").endswith("true") else 124      # FOLD instantiation: the attention-combine is 8 MFMAs, not 16
+print("kernel %s" % kern)
+print("cycles per tile in the tile loop: %.0f (matrix pipe minimum %d x 16 = %d)" % (v[4] / tiles, n_mfma, 16 * n_mfma))
 print("cycles per user outside the tile loop: %.0f" % ((v.sum() - v[4]) / U))
 tv = np.array(list(out)[8:16], dtype=np.float64)
 if tv.sum() > 0 and os.environ.get("DM_PROBE_SETUP"):

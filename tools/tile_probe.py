@@ -21,10 +21,19 @@ N.lib().dm_debug_phase_cycles(eng._h, out)
 eng.timing_reset()
 eng.tdm_beam_search_dev(d_seq, U, 10, 200, 200, d_ids, d_sc, d_cnt); eng.synchronize()
 N.lib().dm_debug_phase_cycles(eng._h, out)
-v = np.array(list(out)[:5], dtype=np.float64)
+kern = eng.last_beam_kernel()
 rows = eng.last_scored_rows()
 tiles = rows / 16.0
-names = ["S^T MFMAs + next-tile gather issue", "softmax", "main chain (256 MFMAs)", "P x G (24 MFMAs)", "epilogue + store"]
-print("kernel ms", eng.timing_get(), "tiles", tiles)
+if kern.startswith("dm_beam_w_kernel"):
+    # the one-wave kernel (DM_SCORER=split_f16) reports its tile sections behind the phase slots; the attention-combine
+    # is 8 MFMAs in the FOLD instantiation (dm_beam_w_kernel<E, KQ, true>, L <= 10) and 16 otherwise
+    fold = kern.rstrip(">").endswith("true")
+    v = np.array(list(out)[8:13], dtype=np.float64)
+    names = ["scores (12 MFMAs)", "W1a chain, accumulators 0-3 (48 MFMAs)", "W1a chain, accumulators 4-7 (48 MFMAs)",
+             "attention-combine (%d MFMAs)" % (8 if fold else 16), "tail"]
+else:
+    v = np.array(list(out)[:5], dtype=np.float64)
+    names = ["S^T MFMAs + next-tile gather issue", "softmax", "main chain (256 MFMAs)", "P x G (24 MFMAs)", "epilogue + store"]
+print("kernel", kern, "ms", eng.timing_get(), "tiles", tiles)
 for n, x in zip(names, v): print("%-40s %6.2f%%  %8.0f clock64 ticks / tile" % (n, 100 * x / v.sum(), x / tiles))
 print("total ticks / tile %.0f" % (v.sum() / tiles))
