@@ -71,6 +71,9 @@ SIGNATURES = {
     "dm_tdm_id_to_code": (C.c_int, [C.c_void_p, i32p, C.c_int, i32p, i32p, C.POINTER(C.c_int)]),
     "dm_level_start": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dm_load_weights_din": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "dm_load_weights_deepfm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
+    "dm_get_scorer_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dm_deepfm_forward": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, f32p]),
     "dm_din_forward": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "dm_tdm_beam_search": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, C.POINTER(SearchOpts), i64p, i32p, i32p,
                                      f32p, i32p]),

@@ -5,11 +5,12 @@
 // the reference's format it holds no optimizer state (Adam.buffer is transient, scalann/.../optim/Adam.scala:85-88).
 //
 //   char     magic[8] = "DMHIPCK1"
-//   int32    version (1), dtype (DM_F32 | DM_F64), embed, max_level, has_tree, has_ids, reserved[2]
+//   int32    version (1), dtype (DM_F32 | DM_F64), embed, max_level, has_tree, has_ids,
+//            reserved[0] = scorer kind (0 DIN, 1 DeepFM), reserved[1] = DeepFM's seq_len (0 for DIN): a DIN file has both words 0, as ever
 //   int64    num_index, n_elems, n_nodes, n_leaf_ids
 //   [has_tree] int32 codes[n_nodes]; int32 node_ids[n_nodes]; uint8 is_leaf[n_nodes] (+ padding to 8 bytes)
 //   [has_ids]  int32 leaf_item_ids[n_leaf_ids]; int32 leaf_codes[n_leaf_ids]
-//   elem     compact[n_elems]
+//   elem     compact[n_elems]      (DIN: SURVEY.md row A0; DeepFM: deepfm.hip.inc; always the MODEL's embed size, never the padded one)
 
 #include <sys/stat.h>
 
@@ -36,7 +37,9 @@ static int save_model_body(dm_ctx *h, const char *path) {
   hd.has_tree = h->tree_loaded ? 1 : 0; hd.has_ids = h->ids_loaded ? 1 : 0;
   hd.num_index = h->num_index;
   const int64_t E = h->embed_log;
-  hd.n_elems = h->num_index * E + 3 * E * E + 2 * E + 1;
+  const bool dfm = h->scorer_kind == DM_KIND_DEEPFM;
+  hd.n_elems = dfm ? deepfm_len_for(h->num_index, E, h->dfm_L) : h->num_index * E + 3 * E * E + 2 * E + 1;
+  if (dfm) { hd.reserved[0] = DM_KIND_DEEPFM; hd.reserved[1] = h->dfm_L; }
   std::vector<int32_t> codes, nids, lids, lcodes;
   std::vector<uint8_t> isleaf;
   if (h->tree_loaded) {
@@ -59,7 +62,11 @@ static int save_model_body(dm_ctx *h, const char *path) {
   std::vector<char> lv;
   if (h->embed_log != h->embed) {
     lv.resize((size_t)hd.n_elems * (h->dtype == DM_F64 ? 8 : 4));
-    const int rc_ = dm_train_download(h, 0, lv.data(), hd.n_elems);
+    int rc_;
+    if (dfm) {
+      std::vector<float> m;
+      if ((rc_ = dfm_download_model(h, m)) == DM_OK) memcpy(lv.data(), m.data(), lv.size());
+    } else rc_ = dm_train_download(h, 0, lv.data(), hd.n_elems);
     if (rc_ != DM_OK) return rc_;
   }
   // written next to the target and renamed over it on success: a failed save leaves the previous checkpoint intact (the reference
@@ -124,7 +131,12 @@ static int load_model_body(dm_ctx *h, FILE *f) {
   if (hd.num_index <= 0 || (uint64_t)hd.num_index > fsize / es || hd.n_nodes < 0 || (uint64_t)hd.n_nodes > fsize / 9 ||
       hd.n_leaf_ids < 0 || (uint64_t)hd.n_leaf_ids > fsize / 8 || (!hd.has_tree && hd.n_nodes) || (!hd.has_ids && hd.n_leaf_ids))
     return fail(h, DM_ERR_INVALID, "dm_load_model: header counts exceed the file");
-  if (hd.n_elems != hd.num_index * E + 3 * E * E + 2 * E + 1) return fail(h, DM_ERR_INVALID, "dm_load_model: inconsistent header");
+  const int kind = hd.reserved[0], seq_len = hd.reserved[1];
+  if ((kind != DM_KIND_DIN && kind != DM_KIND_DEEPFM) || (kind == DM_KIND_DIN && seq_len != 0) ||
+      (kind == DM_KIND_DEEPFM && (seq_len < 1 || seq_len > DFM_MAXL || hd.dtype != DM_F32)))
+    return fail(h, DM_ERR_INVALID, "dm_load_model: unknown scorer in the header (kind / seq_len words)");
+  if (hd.n_elems != (kind == DM_KIND_DEEPFM ? deepfm_len_for(hd.num_index, E, seq_len) : hd.num_index * E + 3 * E * E + 2 * E + 1))
+    return fail(h, DM_ERR_INVALID, "dm_load_model: inconsistent header");
   const uint64_t tree_bytes = hd.has_tree ? (uint64_t)hd.n_nodes * 8 + (((uint64_t)hd.n_nodes + 7) & ~(uint64_t)7) : 0;
   const uint64_t ids_bytes = hd.has_ids ? (uint64_t)hd.n_leaf_ids * 8 : 0;
   const uint64_t total = (uint64_t)hd.n_elems * es;
@@ -149,10 +161,11 @@ static int load_model_body(dm_ctx *h, FILE *f) {
       if (lids[(size_t)i] < 0 || lcodes[(size_t)i] < 0) return fail(h, DM_ERR_INVALID, "dm_load_model: negative entry in the id map");
   }
   int rc = DM_OK;
-  if (native_embed(hd.embed) != hd.embed) {          // an embed size the kernels pad: through the host loader
+  if (kind == DM_KIND_DEEPFM || native_embed(hd.embed) != hd.embed) {          // DeepFM, or an embed size the kernels pad: through the host loader
     std::vector<char> lv((size_t)total);
     if (!ckpt_read(f, lv.data(), lv.size())) return fail(h, DM_ERR_INVALID, "dm_load_model: truncated file (weights)");
-    rc = dm_load_weights_din(h, hd.dtype, hd.embed, hd.num_index, lv.data(), hd.n_elems);
+    rc = kind == DM_KIND_DEEPFM ? dm_load_weights_deepfm(h, hd.dtype, hd.embed, seq_len, hd.num_index, lv.data(), hd.n_elems)
+                                : dm_load_weights_din(h, hd.dtype, hd.embed, hd.num_index, lv.data(), hd.n_elems);
   } else {
     // weights: straight into a device buffer the handle then owns (no host copy of the table's size)
     if (hipSetDevice(h->device) != hipSuccess) return fail(h, DM_ERR_HIP, "hipSetDevice failed");

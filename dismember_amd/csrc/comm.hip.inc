@@ -589,6 +589,7 @@ int dm_train_sync_stats(dm_handle_t h, uint64_t *out8) {
 
 int dm_train_sync_gradients(dm_handle_t h) {
   if (!h) return DM_ERR_INVALID;
+  DM_DIN_ONLY(h, "dm_train_sync_gradients");
   dm_ctx *one[1] = {h};
   return sync_gradients_impl(one, 1);
 }

@@ -1,0 +1,380 @@
+// DeepFM node scorer (tdm/src/main/scala/com/mass/tdm/model/DeepFM.scala:11-45), serving half: the row forward and the scorer of the
+// TDM level pipeline (tdm_pipeline.hip.inc).  fp32 only; the training step is not here.
+//
+// Model (T = L + 1 features of E values: the item row e, then the history rows k_1 .. k_L; -1 / padding = a zero row):
+//   x      = [e ; k_1 ; .. ; k_L]                                            Concat(itemFlatten, seqFlatten), DeepFM.scala:26-34
+//   fm     = (|sum_i x_i|^2 - sum_i |x_i|^2) / 2                              scalann/.../nn/FM.scala:24-37
+//   logit  = fm + l2.W relu(l1.W x + l1.b) + l2.b                             Linear(T E, T), ReLU, Linear(T, 1), Add; DeepFM.scala:35-42
+// Compact vector in Graph.parameters order (scalann/.../nn/graphnn/Graph.scala:37-48 walks the nodes in forward order: EmbeddingShare,
+// DeepFM.scala:18; Linear, :35; Linear, :39 — FM, Reshape, Concat, ReLU and Add hold no parameters):
+//   [emb num_index x E ; l1.W T x (T E) ; l1.b T ; l2.W 1 x T ; l2.b 1]       n = num_index E + T T E + 2 T + 1
+// On the device every E-wide block (the table's rows, the T column blocks of every l1.W row) is zero-padded to Ep = 16 / 32 / 64 / 128
+// like the DIN loader's: zero columns add nothing to a dot product, to |s|^2 or to sum |k|^2.
+//
+// Per user (shared by every row scored for that user): W1a = l1.W[:, :E], W1s = l1.W[:, E:]
+//   s = sum_j k_j          c = (|s|^2 - sum_j |k_j|^2) / 2 + l2.b          a = W1s vec(K) + l1.b   (T values)
+//   logit(e) = e.s + c + sum_t l2.W[t] relu(W1a[t].e + a[t])
+// since |e + s|^2 - |e|^2 - sum |k_j|^2 = 2 e.s + |s|^2 - sum |k_j|^2.  A level of the search is therefore ONE product per user,
+// [children x E] . [E x (T + 1)]: column 0 is the user's s, columns 1 .. T are W1a (shared by all users), padded to 16 / 32 / 48.
+//
+// Summation orders (fixed; no atomics on floats; two runs give the same bits):
+//   s[e], sum_j k_j[e]^2   history order j = 0 .. L-1, one thread per feature
+//   c                      d[e] = s[e]^2 - sum_j k_j[e]^2 per feature (the cancellation happens per feature, on small numbers), then the
+//                          xor-shuffle tree over the 64 lanes of each wave and wave 0 + wave 1
+//   a[t]                   lane-strided partial sums over vec(K) in index order, then the xor-shuffle tree
+//   level kernel           v_mfma_f32_16x16x4_f32 over k = 0 .. Ep-1 in steps of 4 (exact fp32 fma chain per output), the epilogue per column,
+//                          column tiles added in order, then the xor-shuffle tree over the 16 lanes that hold a row's columns
+
+#define DFM_MAXL 32
+
+static int64_t deepfm_len_for(int64_t num_index, int64_t E, int64_t L) { const int64_t T = L + 1; return num_index * E + T * T * E + 2 * T + 1; }
+static int dfm_col_tiles(int L) { return (L + 2 + 15) / 16; }      // ceil((T + 1) / 16): 1 for L <= 14, 2 for L <= 30, 3 up to 32
+
+// ---- derived copies, from the compact vector on the device: W1a (and the zero column 0 / padding columns) as MFMA B fragments
+// frag[ct][jc][lane = (g, r)][t] = M[col 16 ct + r][feature 16 jc + 4 g + t], M[0] = 0 (the user's s goes there), M[n] = W1a[n - 1] for
+// n = 1 .. T, 0 beyond; w2p[n] = l2.W[n - 1] for n = 1 .. T, 0 elsewhere.
+__global__ void dfm_derive_kernel(const float *l1_w, const float *l2_w, int E, int T, int NCT, float *frag, float *w2p) {
+  const int NJ = E / 16, n = NCT * NJ * 256;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int t = i & 3, lane = (i >> 2) & 63, jc = (i >> 8) % NJ, ct = (i >> 8) / NJ;
+    const int col = 16 * ct + (lane & 15), e = 16 * jc + 4 * (lane >> 4) + t;
+    frag[i] = (col >= 1 && col <= T) ? l1_w[(int64_t)(col - 1) * T * E + e] : 0.0f;
+  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NCT * 16; i += gridDim.x * blockDim.x) w2p[i] = (i >= 1 && i <= T) ? l2_w[i - 1] : 0.0f;
+}
+
+// ---- per user: s [U][E], aux [U][NC]: aux[0] = c, aux[n] = a[n - 1] for n = 1 .. T, 0 beyond.  One workgroup of 256 per user.
+struct DfmUser {
+  const float *emb, *l1_w, *l1_b;      // l1_w [T][T E]
+  float b2;
+  const int32_t *kcode;                // [U][L], -1 = zero row
+  int E, L, NC;
+  int64_t num_index;
+  float *S, *aux;
+};
+
+__global__ __launch_bounds__(256) void dfm_user_kernel(DfmUser p) {
+  __shared__ float K[DFM_MAXL * 128];
+  __shared__ float red[2];
+  const int64_t u = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int E = p.E, L = p.L, T = L + 1, n = L * E;
+  for (int i = tid; i < n; i += 256) {
+    const int32_t c = p.kcode[u * L + i / E];
+    K[i] = (c >= 0 && c < p.num_index) ? p.emb[(int64_t)c * E + i % E] : 0.0f;
+  }
+  __syncthreads();
+  if (tid < 128) {                     // E <= 128: waves 0 and 1
+    float d = 0.0f;
+    if (tid < E) {
+      float s = 0.0f, q = 0.0f;
+      for (int j = 0; j < L; j++) { const float v = K[j * E + tid]; s += v; q = fmaf(v, v, q); }
+      p.S[u * E + tid] = s;
+      d = fmaf(s, s, -q);
+    }
+    d = dm_wave_sum(d);
+    if (lane == 0) red[wave] = d;
+  }
+  for (int t = wave; t < T; t += 4) {
+    const float *w = p.l1_w + (int64_t)t * T * E + E;      // W1s[t]: the L history blocks of row t
+    float part = 0.0f;
+    for (int i = lane; i < n; i += 64) part = fmaf(w[i], K[i], part);
+    part = dm_wave_sum(part);
+    if (lane == 0) p.aux[u * p.NC + 1 + t] = part + p.l1_b[t];
+  }
+  for (int i = T + 1 + tid; i < p.NC; i += 256) p.aux[u * p.NC + i] = 0.0f;
+  __syncthreads();
+  if (tid == 0) p.aux[u * p.NC] = 0.5f * (red[0] + red[1]) + p.b2;
+}
+
+// ---- one level: sc[u][row] for the rows < counts[u] of cur[u][stride].  One wave per (user, 16-row tile); the children's rows go
+// HBM -> VGPR straight into A-fragment layout (lane (g, r): row r, features 16 jc + 4 g .. + 3 as one float4 per jc: k-step (jc, t) of
+// the MFMA takes feature 16 jc + 4 g + t from lane group g — the B fragments above follow the same map); W1a's fragments are staged once
+// per workgroup in LDS (NCT E 64 bytes: 24 KB at E = 128, L = 32) and read back as one conflict-free ds_read_b128 per lane and (ct, jc);
+// column 0 of tile 0 is the user's s, held by the lanes r = 0.
+// C layout: lane (g, r) holds rows 4 g .. 4 g + 3 of column 16 ct + r.
+struct DfmLevel {
+  const float *emb;
+  const f32x4 *frag;                   // [NCT][E / 16][64]
+  const float *w2p;                    // [NCT * 16]
+  const float *S, *aux;                // [U][E], [U][NCT * 16]
+  const int32_t *codes, *counts;       // [U][stride], [U]
+  float *sc;                           // [U][stride]
+  int stride;
+  int64_t U, num_index;
+};
+
+template <int E, int NCT>
+__global__ __launch_bounds__(256) void dfm_level_kernel(DfmLevel p) {
+  constexpr int NJ = E / 16, NC = NCT * 16;
+  extern __shared__ __attribute__((aligned(16))) char smem_dfm[];
+  f32x4 *wl = (f32x4 *)smem_dfm;
+  for (int i = threadIdx.x; i < NCT * NJ * 64; i += 256) wl[i] = p.frag[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  const int tpu = p.stride / 16;
+  const int64_t total = p.U * tpu;
+  for (int64_t w = (int64_t)blockIdx.x * 4 + wave; w < total; w += (int64_t)gridDim.x * 4) {
+    const int64_t u = w / tpu;
+    const int row0 = (int)(w % tpu) * 16;
+    const int n = min(p.counts[u], p.stride);
+    if (row0 >= n) continue;           // (wave-uniform) rows at or past counts[u] are neither gathered nor stored
+    int32_t code = row0 + r < n ? p.codes[u * p.stride + row0 + r] : -1;
+    if (code >= p.num_index) code = -1;
+    f32x4 qa[NJ], sf[NJ];
+#pragma unroll
+    for (int jc = 0; jc < NJ; jc++) {
+      qa[jc] = code >= 0 ? *(const f32x4 *)(p.emb + (int64_t)code * E + 16 * jc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      sf[jc] = r == 0 ? *(const f32x4 *)(p.S + u * E + 16 * jc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    float tot[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int jc = 0; jc < NJ; jc++) {
+        f32x4 b = wl[(ct * NJ + jc) * 64 + lane];
+        if (ct == 0) b = r == 0 ? sf[jc] : b;
+#pragma unroll
+        for (int t = 0; t < 4; t++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[jc][t], b[t], acc, 0, 0, 0);
+      }
+      const int col = 16 * ct + r;
+      const float av = p.aux[u * NC + col], wv = p.w2p[col];
+#pragma unroll
+      for (int rr = 0; rr < 4; rr++) {
+        const float x = acc[rr] + av;
+        tot[rr] += col == 0 ? x : wv * fmaxf(x, 0.0f);
+      }
+    }
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) tot[rr] += __shfl_xor(tot[rr], o);
+    }
+    if (r == 0) {
+#pragma unroll
+      for (int rr = 0; rr < 4; rr++)
+        if (row0 + 4 * g + rr < n) p.sc[u * p.stride + row0 + 4 * g + rr] = tot[rr];
+    }
+  }
+}
+
+// ---- Module.forward(Table(item, seq)) for rows that each carry their own history: one wave per row, the direct formulation
+// (FM over the T rows, then the two Linears), every sum lane-strided in index order + the xor-shuffle tree.
+struct DfmFwd {
+  const float *emb, *l1_w, *l1_b, *l2_w;
+  float b2;
+  const int32_t *codes, *seqs;
+  int E, L;
+  int64_t B;
+  float *out;
+};
+
+__global__ __launch_bounds__(256) void dfm_forward_kernel(DfmFwd p) {
+  extern __shared__ __attribute__((aligned(16))) char smem_dff[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int E = p.E, T = p.L + 1, n = T * E;
+  float *x = (float *)smem_dff + (size_t)wave * n;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < p.B; row += (int64_t)gridDim.x * 4) {
+    for (int i = lane; i < n; i += 64) {
+      const int f = i / E;
+      const int32_t c = f == 0 ? p.codes[row] : p.seqs[row * p.L + f - 1];
+      x[i] = c >= 0 ? p.emb[(int64_t)c * E + i % E] : 0.0f;
+    }
+    __builtin_amdgcn_wave_barrier();
+    float d = 0.0f;
+    for (int e = lane; e < E; e += 64) {
+      float s = 0.0f, q = 0.0f;
+      for (int f = 0; f < T; f++) { const float v = x[f * E + e]; s += v; q = fmaf(v, v, q); }
+      d += fmaf(s, s, -q);
+    }
+    float logit = 0.5f * dm_wave_sum(d) + p.b2;
+    for (int t = 0; t < T; t++) {
+      const float *w = p.l1_w + (int64_t)t * n;
+      float part = 0.0f;
+      for (int i = lane; i < n; i += 64) part = fmaf(w[i], x[i], part);
+      const float hsum = dm_wave_sum(part) + p.l1_b[t];
+      logit += p.l2_w[t] * fmaxf(hsum, 0.0f);
+    }
+    if (lane == 0) p.out[row] = logit;
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+// kinds of dm_kernel_timing_get_kind
+enum { DFM_KIND_USER = 40, DFM_KIND_LEVEL = 41 };
+
+// device layout of the small blocks behind the table (padded E)
+struct DfmBlocks { const float *l1_w, *l1_b, *l2_w, *l2_b; };
+static DfmBlocks dfm_blocks(const dm_ctx *h) {
+  const int64_t E = h->embed, T = h->dfm_L + 1;
+  DfmBlocks b;
+  b.l1_w = (const float *)h->d_compact + h->num_index * E; b.l1_b = b.l1_w + T * T * E; b.l2_w = b.l1_b + T; b.l2_b = b.l2_w + T;
+  return b;
+}
+
+// model layout (E) <-> device layout (Ep): the table's rows and the T column blocks of every l1.W row
+static void dfm_repad(const float *src, int E_src, int E_dst, int64_t NI, int L, float *dst) {
+  const int64_t T = L + 1;
+  const int Ec = E_src < E_dst ? E_src : E_dst;
+  memset(dst, 0, (size_t)deepfm_len_for(NI, E_dst, L) * 4);
+  for (int64_t r = 0; r < NI; r++) memcpy(dst + r * E_dst, src + r * E_src, (size_t)Ec * 4);
+  const float *s_w = src + NI * E_src;
+  float *d_w = dst + NI * E_dst;
+  for (int64_t b = 0; b < T * T; b++) memcpy(d_w + b * E_dst, s_w + b * E_src, (size_t)Ec * 4);
+  memcpy(d_w + T * T * E_dst, s_w + T * T * E_src, (size_t)(2 * T + 1) * 4);
+}
+
+int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_index, const void *compact, int64_t n_elems) {
+  if (!h) return DM_ERR_INVALID;
+  DM_OWNER_ONLY(h, "dm_load_weights_deepfm");
+  if (dtype == DM_F64) return fail(h, DM_ERR_UNSUPPORTED, "dm_load_weights_deepfm: DM_F32 only (the reference's DeepFM[Double] belongs to OTM, which this library serves with DIN)");
+  if (dtype != DM_F32) return fail(h, DM_ERR_INVALID, "dm_load_weights_deepfm: dtype");
+  if (!compact || num_index <= 0 || E < 1 || E > 128 || L < 1 || L > DFM_MAXL)
+    return fail(h, DM_ERR_INVALID, "dm_load_weights_deepfm: bad arguments (E must be 1..128, L 1..32)");
+  if (n_elems != deepfm_len_for(num_index, E, L))
+    return fail(h, DM_ERR_INVALID, "dm_load_weights_deepfm: n_elems does not match the DeepFM layout for (E, L, num_index)");
+  HIPCHK(h, hipSetDevice(h->device));
+  const int Ep = native_embed(E);
+  const float *w = (const float *)compact;
+  std::vector<float> padded;
+  if (Ep != E) {
+    padded.resize((size_t)deepfm_len_for(num_index, Ep, L));
+    dfm_repad(w, E, Ep, num_index, L, padded.data());
+    w = padded.data();
+  }
+  const size_t bytes = (size_t)deepfm_len_for(num_index, Ep, L) * 4;
+  free_weights(h);      // (also switches the handle back to "no scorer": a failed load leaves no half-DIN, half-DeepFM state)
+  void *d = nullptr;
+  ALLOC(h, d, bytes);
+  if (hipMemcpy(d, w, bytes, hipMemcpyHostToDevice) != hipSuccess) { dm_free_ptr(d); return fail(h, DM_ERR_HIP, "dm_load_weights_deepfm: upload failed"); }
+  h->d_compact = d; h->d_emb32 = (float *)d; h->dtype = DM_F32; h->embed = Ep; h->embed_log = E; h->num_index = num_index;
+  h->scorer_kind = DM_KIND_DEEPFM; h->dfm_L = L;
+  const int NCT = dfm_col_tiles(L);
+  ALLOC(h, h->d_dfm_frag, (size_t)NCT * Ep * 64);
+  ALLOC(h, h->d_dfm_w2p, (size_t)NCT * 16 * 4);
+  const DfmBlocks b = dfm_blocks(h);
+  hipLaunchKernelGGL(dfm_derive_kernel, dim3(32), dim3(256), 0, h->stream, b.l1_w, b.l2_w, Ep, L + 1, NCT, h->d_dfm_frag, h->d_dfm_w2p);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(&h->b2, b.l2_b, 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->w_loaded = true;
+  return DM_OK;
+}
+
+int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len) {
+  if (!h || !kind) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  *kind = h->scorer_kind;
+  if (seq_len) *seq_len = h->scorer_kind == DM_KIND_DEEPFM ? h->dfm_L : 0;
+  return DM_OK;
+}
+
+// the model's own layout (unpadded E) on the host: the checkpoint's payload
+static int dfm_download_model(dm_ctx *h, std::vector<float> &out) {
+  const int64_t NI = h->num_index;
+  std::vector<float> dev((size_t)deepfm_len_for(NI, h->embed, h->dfm_L));
+  HIPCHK(h, hipMemcpy(dev.data(), h->d_compact, dev.size() * 4, hipMemcpyDeviceToHost));
+  out.resize((size_t)deepfm_len_for(NI, h->embed_log, h->dfm_L));
+  dfm_repad(dev.data(), h->embed, h->embed_log, NI, h->dfm_L, out.data());
+  return DM_OK;
+}
+
+int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, int64_t B, int L, float *logits) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_deepfm_forward: weights not loaded");
+  if (h->scorer_kind != DM_KIND_DEEPFM) return fail(h, DM_ERR_STATE, "dm_deepfm_forward: the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model)");
+  if (!codes || !seqs || !logits || B < 0) return fail(h, DM_ERR_INVALID, "dm_deepfm_forward: bad arguments");
+  if (L != h->dfm_L) return fail(h, DM_ERR_INVALID, "dm_deepfm_forward: L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
+  if (B == 0) return DM_OK;
+  // LookupTable.embeddingLookup validates every index first (LookupTable.scala:29-53)
+  for (int64_t i = 0; i < B; i++)
+    if (codes[i] != -1 && (codes[i] < 0 || codes[i] >= h->num_index)) {
+      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)i, codes[i]);
+      return fail(h, DM_ERR_INDEX, b);
+    }
+  for (int64_t i = 0; i < B * L; i++)
+    if (seqs[i] != -1 && (seqs[i] < 0 || seqs[i] >= h->num_index)) {
+      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)(i / L), seqs[i]);
+      return fail(h, DM_ERR_INDEX, b);
+    }
+  HIPCHK(h, hipSetDevice(h->device));
+  ReqArena ar;
+  const size_t o_codes = ar.add((size_t)B * 4), o_seqs = ar.add((size_t)B * L * 4), o_out = ar.add((size_t)B * 4);
+  int rc = ar.commit(h);
+  if (rc != DM_OK) return rc;
+  HIPCHK(h, hipMemcpyAsync(ar.ptr<int32_t>(o_codes), codes, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ar.ptr<int32_t>(o_seqs), seqs, (size_t)B * L * 4, hipMemcpyHostToDevice, h->stream));
+  const DfmBlocks b = dfm_blocks(h);
+  DfmFwd p;
+  p.emb = h->d_emb32; p.l1_w = b.l1_w; p.l1_b = b.l1_b; p.l2_w = b.l2_w; p.b2 = h->b2;
+  p.codes = ar.ptr<int32_t>(o_codes); p.seqs = ar.ptr<int32_t>(o_seqs); p.E = h->embed; p.L = L; p.B = B; p.out = ar.ptr<float>(o_out);
+  const size_t lds = (size_t)4 * (L + 1) * h->embed * 4;      // at most 4 x 33 x 128 floats = 66 KB
+  HIPCHK(h, hipFuncSetAttribute((const void *)dfm_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  int64_t blocks = (B + 3) / 4;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(dfm_forward_kernel, dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(logits, p.out, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DM_OK;
+}
+
+// ---- the level pipeline's scorer
+template <int E, int NCT>
+static int dfm_launch_level(dm_ctx *h, const DfmLevel &p) {
+  const size_t lds = (size_t)NCT * E * 64;
+  const int64_t waves = p.U * (p.stride / 16);
+  int64_t blocks = (waves + 3) / 4;
+  if (blocks > (int64_t)h->n_cu * 4) blocks = (int64_t)h->n_cu * 4;
+  if (blocks < 1) blocks = 1;
+  LaunchTimer tm(h, DFM_KIND_LEVEL);
+  if (tm.rc != DM_OK) return tm.rc;
+  hipLaunchKernelGGL((dfm_level_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
+  HIPCHK(h, hipGetLastError());
+  return tm.stop();
+}
+
+struct TdmPlDeepFM : TdmPlScorer {
+  int E, L, NCT, stride = 0;
+  float *S = nullptr, *aux = nullptr;
+  explicit TdmPlDeepFM(const dm_ctx *h) : E(h->embed), L(h->dfm_L), NCT(dfm_col_tiles(h->dfm_L)) {}
+  size_t ws_bytes(int64_t Uc, int, int) const override { return tdm_pl_up((size_t)Uc * E * 4) + tdm_pl_up((size_t)Uc * NCT * 16 * 4); }
+  int attach(dm_ctx *, char *w, int64_t Uc, int stride_, int) override {
+    stride = stride_;
+    S = (float *)w; w += tdm_pl_up((size_t)Uc * E * 4);
+    aux = (float *)w;
+    return DM_OK;
+  }
+  int setup(dm_ctx *h, const int32_t *kcode, int64_t Un) override {
+    const DfmBlocks b = dfm_blocks(h);
+    DfmUser p;
+    p.emb = h->d_emb32; p.l1_w = b.l1_w; p.l1_b = b.l1_b; p.b2 = h->b2; p.kcode = kcode; p.E = E; p.L = L; p.NC = NCT * 16;
+    p.num_index = h->num_index; p.S = S; p.aux = aux;
+    LaunchTimer tm(h, DFM_KIND_USER);
+    if (tm.rc != DM_OK) return tm.rc;
+    hipLaunchKernelGGL(dfm_user_kernel, dim3((unsigned)Un), dim3(256), 0, h->stream, p);
+    HIPCHK(h, hipGetLastError());
+    return tm.stop();
+  }
+  int score(dm_ctx *h, const int32_t *cur, const int32_t *ncur, float *sc, int64_t Un) override {
+    DfmLevel p;
+    p.emb = h->d_emb32; p.frag = (const f32x4 *)h->d_dfm_frag; p.w2p = h->d_dfm_w2p; p.S = S; p.aux = aux; p.codes = cur; p.counts = ncur;
+    p.sc = sc; p.stride = stride; p.U = Un; p.num_index = h->num_index;
+    return dispatch_E(h, E, "unsupported embed size", [&](auto e) {
+      constexpr int E_ = decltype(e)::value;
+      return NCT == 1 ? dfm_launch_level<E_, 1>(h, p) : NCT == 2 ? dfm_launch_level<E_, 2>(h, p) : dfm_launch_level<E_, 3>(h, p);
+    });
+  }
+};
+
+// TDM beam search with a DeepFM model: every history length takes the level pipeline
+static int dfm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
+                            const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
+                            int trace_levels, int cap, int32_t *d_tc, float *d_ts, int32_t *d_tn) {
+  snprintf(h->last_kernel, sizeof(h->last_kernel), "tdm level pipeline: dfm_level_kernel<%d, %d>", h->embed, dfm_col_tiles(h->dfm_L));
+  TdmPlDeepFM dfm(h);
+  return tdm_pl_fold(h, dfm, d_seq, U, L, o, max_beam, d_coff, d_cids, d_ids, d_scores, d_counts, trace_levels, cap, d_tc, d_ts, d_tn);
+}

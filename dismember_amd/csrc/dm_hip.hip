@@ -94,6 +94,12 @@ struct dm_ctx {
   float *d_b1 = nullptr, *d_w2 = nullptr;
   float b2 = 0.f;
   void *d_att_wT_t = nullptr, *d_l1T_t = nullptr;  // transposes in the loaded dtype (general forward)
+  // which scorer the loaded weights are (dm_get_scorer_kind).  DeepFM (deepfm.hip.inc): d_compact holds [emb ; l1.W ; l1.b ; l2.W ; l2.b]
+  // with every E-wide block padded to `embed`, none of the DIN copies above exists, and b2 is l2.b
+  int scorer_kind = DM_KIND_DIN;
+  int dfm_L = 0;               // DeepFM: the history length l1.W is sized by
+  float *d_dfm_frag = nullptr; // DeepFM: [0 ; W1a ; 0] as MFMA B fragments, and l2.W over the same padded columns
+  float *d_dfm_w2p = nullptr;
   LazyCopies lazy;             // the copies rebuilt on first use after a weight change, and their stale flags (lazy_copies.hip.inc)
   int scorer_mode = DM_SCORER_AUTO;      // dm_set_scorer_mode
   bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
@@ -394,6 +400,9 @@ int dm_create(int device_id, dm_handle_t *out) {
 
 static inline void model_changed(dm_ctx *h) { h->model_epoch.fetch_add(1); }
 static int clone_enter(dm_ctx *c);
+// entry points that evaluate DIN (after DM_CLONE_ENTER: a clone mirrors its owner's scorer): refused while a DeepFM model is loaded
+static const char *scorer_name(const dm_ctx *h) { return h->scorer_kind == DM_KIND_DEEPFM ? "DeepFM" : "DIN"; }
+#define DM_DIN_ONLY(h, who) do { if ((h)->scorer_kind != DM_KIND_DIN) return fail((h), DM_ERR_UNSUPPORTED, std::string(who) + ": the loaded scorer is " + scorer_name(h) + "; this entry point evaluates DIN (a DeepFM model serves dm_deepfm_forward and dm_tdm_beam_search*)"); } while (0)
 // entry points that replace the model or train it: the owning handle only
 #define DM_OWNER_ONLY(h, who) do { if ((h)->parent) return fail((h), DM_ERR_STATE, who ": not on a clone (dm_clone) - load and train through the owning handle"); } while (0)
 // read-only entry points: a clone first brings its mirror of the parent's model up to date
@@ -412,6 +421,7 @@ static void free_weights(dm_ctx *h) {
   dm_free_ptr(h->d_compact); dm_free_ptr(h->d_wfrag); dm_free_ptr(h->d_afrag); dm_free_ptr(h->d_bfrag); dm_free_ptr(h->d_attA); dm_free_ptr(h->d_w1aA); dm_free_ptr(h->d_w1bA);
   dm_free_ptr(h->d_b1); dm_free_ptr(h->d_w2); dm_free_ptr(h->d_att_wT_t); dm_free_ptr(h->d_l1T_t);
   h->lazy.released();
+  dm_free_ptr(h->d_dfm_frag); dm_free_ptr(h->d_dfm_w2p); h->d_dfm_frag = h->d_dfm_w2p = nullptr; h->scorer_kind = DM_KIND_DIN; h->dfm_L = 0;
   dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; dm_free_ptr(h->d_tail32); h->d_tail32 = nullptr;
   h->d_compact = nullptr; h->d_emb32 = nullptr; h->emb32_owned = false; h->d_wfrag = nullptr;
   dm_free_ptr(h->d_grad); dm_free_ptr(h->d_adam_s); dm_free_ptr(h->d_adam_r); dm_free_ptr(h->d_loss); dm_free_ptr(h->d_attTA);
@@ -428,7 +438,7 @@ static void free_weights(dm_ctx *h) {
   X(tree_loaded) X(ids_loaded) X(leaves_at_max_only) X(max_level) X(n_slots) X(n_leaf_nodes) X(d_exists) X(d_leaf) X(d_node_id)          \
   X(d_id_to_code) X(d_leaf_codes) X(non_leaf_offset) X(max_code) X(w_loaded) X(dtype) X(embed) X(embed_log) X(num_index) X(d_compact)    \
   X(d_emb32) X(d_wfrag) X(d_afrag) X(d_bfrag) X(d_attA) X(d_w1aA) X(d_w1bA) X(d_b1) X(d_w2) X(b2) X(d_att_wT_t) X(d_l1T_t) X(d_tail32)   \
-  X(lazy) X(d_lv_codes) X(d_lv_cdf) X(d_lv_start)
+  X(lazy) X(d_lv_codes) X(d_lv_cdf) X(d_lv_start) X(scorer_kind) X(dfm_L) X(d_dfm_frag) X(d_dfm_w2p)
 
 static void clone_mirror(dm_ctx *c, dm_ctx *p) {
 #define X(f) c->f = p->f;
@@ -621,6 +631,10 @@ static int clone_enter(dm_ctx *c) {
   for (int pass = 0; pass < 2; pass++) {
     clone_mirror(c, p);                         // (first pass: the model's shape, so that the scorer choice below is this clone's)
     if (!p->w_loaded) break;
+    if (p->scorer_kind == DM_KIND_DEEPFM) {      // no lazily rebuilt copies: what dm_load_weights_deepfm made is all there is
+      if (hipStreamSynchronize(p->stream) != hipSuccess) return fail(c, DM_ERR_HIP, "dm_clone: the parent's stream failed");
+      break;
+    }
     int rc = DM_OK;
     if (use_f64_beam(c)) rc = ensure_frags64(p);        // (decided on the clone: the parent's model with the clone's own scorer setting)
     else {
@@ -835,6 +849,7 @@ int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, con
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_din_forward: weights not loaded");
+  DM_DIN_ONLY(h, "dm_din_forward");
   if (!codes || !seqs || !logits || B < 0 || L <= 0 || L > 32 || n_pad < 0 || (n_pad > 0 && !pad_flat_idx))
     return fail(h, DM_ERR_INVALID, "dm_din_forward: bad arguments (L must be 1..32)");
   if (B == 0) return DM_OK;
@@ -1083,6 +1098,7 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
 int dm_set_scorer_mode(dm_handle_t h, int mode) {
   if (!h) return DM_ERR_INVALID;
   if (mode != DM_SCORER_F32 && mode != DM_SCORER_SPLIT_F16 && mode != DM_SCORER_AUTO && mode != DM_SCORER_F64) return fail(h, DM_ERR_INVALID, "dm_set_scorer_mode: unknown mode");
+  DM_DIN_ONLY(h, "dm_set_scorer_mode");      // (the DeepFM scorer has one arithmetic: fp32)
   if (mode == DM_SCORER_F64 && h->w_loaded && h->dtype != DM_F64)
     return fail(h, DM_ERR_UNSUPPORTED, "dm_set_scorer_mode: the fp64 scorer needs f64 weights");
   if (mode == DM_SCORER_SPLIT_F16 && h->w_loaded && h->embed % 32 != 0)
@@ -1116,6 +1132,14 @@ static void fill_common(dm_ctx *h, BeamParams &p) {
 static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
                             const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
                             int trace_levels, int cap, int32_t *d_tc, float *d_ts, int32_t *d_tn);
+static int dfm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
+                            const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
+                            int trace_levels, int cap, int32_t *d_tc, float *d_ts, int32_t *d_tn);
+// the searches that run level by level (tdm_pipeline.hip.inc) instead of inside one fused kernel: every search of a DeepFM model, and
+// DIN histories of 17 .. 32 positions whose frontier does not fit LDS beside two key tiles
+static bool level_pipeline(const dm_ctx *h, int max_beam, int L) {
+  return h->scorer_kind == DM_KIND_DEEPFM || long_history_pipeline(h, max_beam, L);
+}
 
 static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
                           const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
@@ -1125,15 +1149,17 @@ static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, con
   if (U == 0) return DM_OK;          // an empty batch is not an error
   if (h->n_slots > h->num_index) return fail(h, DM_ERR_INDEX, "tdm beam search: tree codes exceed the embedding table (embeddingLookup would fail)");
   if (h->max_code >= h->num_index) return fail(h, DM_ERR_INDEX, "tdm beam search: id map codes exceed the embedding table");
-  if (long_history_pipeline(h, max_beam, L)) {
-    // histories of 17 .. 32 positions whose frontier does not fit LDS beside two key tiles: the per-level pipeline (tdm_pipeline.hip.inc)
+  const bool dfm = h->scorer_kind == DM_KIND_DEEPFM;
+  if (dfm && o->use_mask) return fail(h, DM_ERR_INVALID, "tdm beam search: DeepFM has no mask (TDM.scala:26-29): use_mask must be 0");
+  if (dfm && L != h->dfm_L) return fail(h, DM_ERR_INVALID, "tdm beam search: L = " + std::to_string(L) + " but the DeepFM model was built for seq_len " + std::to_string(h->dfm_L));
+  if (level_pipeline(h, max_beam, L)) {
     if (direct) { *direct = false; return DM_OK; }          // (the caller takes the staged path and comes back)
     HIPCHK(h, hipMemsetAsync(d_ids, 0xFF, (size_t)U * o->topk * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)U * o->topk * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream));
     int cap_;
     frontier_caps(max_beam, &cap_, nullptr);
-    return tdm_pipeline_dev(h, d_seq, U, L, o, max_beam, d_coff, d_cids, d_ids, d_scores, d_counts, trace_levels, cap_, d_tc, d_ts, d_tn);
+    return (dfm ? dfm_pipeline_dev : tdm_pipeline_dev)(h, d_seq, U, L, o, max_beam, d_coff, d_cids, d_ids, d_scores, d_counts, trace_levels, cap_, d_tc, d_ts, d_tn);
   }
   int start, level;
   level_start_int(o->beam, &start, &level);
@@ -1274,7 +1300,7 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
   }
   if (hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq, b_seq, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
   int64_t off[18];
-  const int n_chunks = (staged || coff || tn || long_history_pipeline(h, mb, L)) ? 1 : host_pipe_plan(topk * 8, U, off);
+  const int n_chunks = (staged || coff || tn || level_pipeline(h, mb, L)) ? 1 : host_pipe_plan(topk * 8, U, off);
   if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
     int launched;
     rc = launch_chunks(h, n_chunks, off, [&](int, int64_t u0, int64_t uk) {
@@ -1361,6 +1387,7 @@ static int otm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, int
 
 static int otm_check(dm_ctx *h, int64_t U, int L, int beam, int leaf_level, const char *who) {
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": weights not loaded");
+  DM_DIN_ONLY(h, who);
   if (U < 0 || L <= 0 || L > DM_PIPE_MAXL || beam <= 0 || leaf_level <= 0 || leaf_level > 30)
     return fail(h, DM_ERR_INVALID, std::string(who) + ": bad arguments (L must be 1..32)");
   if ((((int64_t)1) << (leaf_level + 1)) - 1 > h->num_index) return fail(h, DM_ERR_INDEX, std::string(who) + ": leaf level exceeds the embedding table");
@@ -1469,6 +1496,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   if (!h->tree_loaded || !h->ids_loaded || !h->w_loaded) return fail(h, DM_ERR_STATE, "dm_tdm_bruteforce_topk: tree, id maps and weights must be loaded first");
+  DM_DIN_ONLY(h, "dm_tdm_bruteforce_topk");
   if (U == 0 && L > 0 && L <= DM_PIPE_MAXL && topk > 0 && topk <= 256) return DM_OK;          // an empty batch is not an error
   if (!seq_item_ids || !out_item_ids || !out_scores || !out_counts || U <= 0 || L <= 0 || L > DM_PIPE_MAXL || topk <= 0 || topk > 256)
     return fail(h, DM_ERR_INVALID, "dm_tdm_bruteforce_topk: bad arguments (L must be 1..32, topk 1..256)");
@@ -1553,6 +1581,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "dr_host.hip.inc"
 #include "otm64.hip.inc"
 #include "tdm_pipeline.hip.inc"
+#include "deepfm.hip.inc"
 #include "comm.hip.inc"
 #include "jtm_sharded.hip.inc"
 #include "train_grouped_host.hip.inc"

@@ -277,6 +277,7 @@ int dm_jtm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
                          float *weights) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
+  DM_DIN_ONLY(h, "dm_jtm_child_weights");
   return jtm_child_weights_impl(h, row_off, row_item_ids, false, 0, item_node, n_items, L, old_level, level, hierarchical, min_level, use_mask, weights);
 }
 
@@ -338,6 +339,7 @@ int dm_jtm_child_weights_cached(dm_handle_t h, const int32_t *item_node, int64_t
                                 int hierarchical, int min_level, int use_mask, float *weights) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
+  DM_DIN_ONLY(h, "dm_jtm_child_weights_cached");
   if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_child_weights_cached: call dm_jtm_cache_rows first");
   if (i_lo < 0 || n_items < 0 || i_lo + n_items > (int64_t)h->jtm_off.size() - 1) return fail(h, DM_ERR_INVALID, "dm_jtm_child_weights_cached: item range outside the cached catalogue");
   return jtm_child_weights_impl(h, h->jtm_off.data() + i_lo, nullptr, true, i_lo, item_node, n_items, h->jtm_L, old_level, level, hierarchical,
@@ -682,6 +684,7 @@ int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *o
                        int hierarchical, int min_level, int use_mask, int max_assign, int32_t *out_node) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
+  DM_DIN_ONLY(h, "dm_jtm_step_cached");
   if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_step_cached: call dm_jtm_cache_rows first");
   if (!item_node || !old_node || !out_node || n_items != (int64_t)h->jtm_off.size() - 1 || level <= old_level || level - old_level > 8 || max_assign < 0)
     return fail(h, DM_ERR_INVALID, "dm_jtm_step_cached: bad arguments (n_items must be the cached catalogue)");
@@ -759,6 +762,7 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_otm_child_weights: weights must be loaded first");
+  DM_DIN_ONLY(h, "dm_otm_child_weights");
   if (!row_off || !item_node || !weights || n_items < 0 || L <= 0 || L > 32 || level <= old_level || level - old_level > 8)
     return fail(h, DM_ERR_INVALID, "dm_otm_child_weights: bad arguments");
   if ((((int64_t)1) << (level + 1)) - 1 > h->num_index) return fail(h, DM_ERR_INDEX, "dm_otm_child_weights: level exceeds the embedding table");

@@ -107,6 +107,7 @@ static int jtm_rebalance_step(dm_ctx *h, const float *d_w, const int32_t *d_old,
 
 static int jtm_optimize_impl(dm_ctx *h, const int32_t *item_code, int64_t n_items, int max_level, int gap, int hierarchical, int min_level,
                              int use_mask, int32_t *out_proj, double *step_seconds) {
+  DM_DIN_ONLY(h, "dm_jtm_optimize_cached");
   if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_optimize_cached: call dm_jtm_cache_rows first");
   if (!item_code || !out_proj || n_items != (int64_t)h->jtm_off.size() - 1 || max_level < 1 || max_level > 30 || gap < 1 || gap > 8)
     return fail(h, DM_ERR_INVALID, "dm_jtm_optimize_cached: bad arguments (n_items must be the cached catalogue)");

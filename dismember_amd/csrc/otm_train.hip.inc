@@ -353,6 +353,7 @@ int dm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, in
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_otm_pseudo_targets: weights not loaded");
+  DM_DIN_ONLY(h, "dm_otm_pseudo_targets");
   if (!seq_codes || !target_off || !o || !out_nodes || !out_labels || !out_counts || U <= 0 || L <= 0 || L > DM_PIPE_MAXL)
     return fail(h, DM_ERR_INVALID, "dm_otm_pseudo_targets: bad arguments");
   int rc = otm_check(h, U, L, o->beam, o->leaf_level, "dm_otm_pseudo_targets");

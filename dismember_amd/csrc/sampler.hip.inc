@@ -218,6 +218,7 @@ int dm_tdm_set_node_probs(dm_handle_t h, const int32_t *codes, const float *prob
 
 static int sample_check(dm_ctx *h, int64_t T, int L, const int32_t *neg_counts, int n_counts, const dm_sample_opts *o, int64_t *per_target) {
   if (!h->tree_loaded || !h->ids_loaded) return fail(h, DM_ERR_STATE, "negative sampling: tree and id maps must be loaded first");
+  DM_DIN_ONLY(h, "negative sampling");      // (the rows it makes feed the DIN training step)
   if (!neg_counts || !o || T < 0 || L <= 0 || L > 32 || o->start_level < 1)
     return fail(h, DM_ERR_INVALID, "negative sampling: bad arguments (start_sample_level must be >= 1, seq_len <= 32)");
   // the sampled rows go straight to dm_train_forward_backward_dev, which does not range-check them: an id map or a tree that

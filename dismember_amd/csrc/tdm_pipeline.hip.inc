@@ -1,4 +1,5 @@
-// TDM beam search for history lengths 17 .. 32: the level fold as a short pipeline of kernels over a batch of users.
+// TDM beam search level by level: the level fold as a short pipeline of kernels over a batch of users, with the scorer as a parameter
+// (TdmPlScorer below).  Two scorers use it: DIN for history lengths 17 .. 32 (this file) and DeepFM for every length (deepfm.hip.inc).
 //
 // The fused beam kernels (beam_kernel*.hip.inc) hold ONE 16-position score tile per candidate tile (DM_MAXL = 16); the reference has no
 // such limit (scalann/.../nn/Attention.scala:34-53 takes any sequence length).  Longer histories therefore take this path: the same fold
@@ -214,31 +215,84 @@ __global__ __launch_bounds__(256) void tdm_pl_final_kernel(TdmPlFinal p) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
+// The scorer of the level fold: everything between "the users' history codes are known" and "sc[U][stride] holds the scores of
+// cur[U][stride] (ncur[U] rows per user)".  Two hooks — setup once per pass of users, score once per level — plus the scorer's share of
+// the pass's workspace.  The fold below owns the integer logic and never looks inside.
+struct TdmPlScorer {
+  virtual ~TdmPlScorer() {}
+  virtual size_t ws_bytes(int64_t Uc, int stride, int L) const = 0;
+  virtual int attach(dm_ctx *h, char *ws, int64_t Uc, int stride, int L) = 0;      // carve the workspace; once per call, before any pass
+  virtual int setup(dm_ctx *h, const int32_t *kcode, int64_t Un) = 0;              // kcode [Un][L]: history codes, -1 = a zero row
+  virtual int score(dm_ctx *h, const int32_t *cur, const int32_t *ncur, float *sc, int64_t Un) = 0;
+};
+
+static size_t tdm_pl_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The per-user restructured DIN of DESIGN.md §3 in plain fp32 (histories of 17 .. 32 positions): T1 = K att.W^T, G = T1 W1b^T + b1 per
+// user; per level H1 = Q W1a^T over the children (gather GEMM), then attention + epilogue per row (otm64_attn_kernel<float>)
+struct TdmPlDin : TdmPlScorer {
+  int use_mask, E, L = 0, stride = 0;
+  const float *base = nullptr, *att_w = nullptr, *l1_w = nullptr, *l1_b = nullptr, *l2_w = nullptr;
+  const int32_t *kcode = nullptr;
+  float *H1 = nullptr, *T1 = nullptr, *G = nullptr, *zero = nullptr;
+  TdmPlDin(const dm_ctx *h, int use_mask_) : use_mask(use_mask_), E(h->embed) {}
+  size_t ws_bytes(int64_t Uc, int stride_, int L_) const override {
+    return tdm_pl_up((size_t)Uc * stride_ * E * 4) + 2 * tdm_pl_up((size_t)Uc * L_ * E * 4) + 256;
+  }
+  int attach(dm_ctx *h, char *w, int64_t Uc, int stride_, int L_) override {
+    L = L_; stride = stride_;
+    base = (const float *)h->d_compact;
+    att_w = base + h->num_index * E; l1_w = att_w + (int64_t)E * E; l1_b = l1_w + (int64_t)2 * E * E; l2_w = l1_b + E;
+    H1 = (float *)w; w += tdm_pl_up((size_t)Uc * stride * E * 4);
+    T1 = (float *)w; w += tdm_pl_up((size_t)Uc * L * E * 4);
+    G = (float *)w; w += tdm_pl_up((size_t)Uc * L * E * 4);
+    zero = (float *)w;
+    HIPCHK(h, hipMemsetAsync(zero, 0, 256, h->stream));
+    return DM_OK;
+  }
+  int setup(dm_ctx *h, const int32_t *kcode_, int64_t Un) override {
+    kcode = kcode_;
+    int rc;
+    DrGemmParams<float> g{};
+    g.A = base; g.lda = E; g.gidx = kcode; g.Lg = 1; g.E = E; g.B = att_w; g.ldb = E; g.bias = nullptr; g.zero = zero;
+    g.C = T1; g.ldc = E; g.M = Un * L; g.N = E; g.Kd = E;
+    if ((rc = dr_launch_gemm<float>(h, g)) != DM_OK) return rc;
+    g.A = T1; g.gidx = nullptr; g.B = l1_w + E; g.ldb = 2 * E; g.bias = l1_b; g.C = G;
+    return dr_launch_gemm<float>(h, g);
+  }
+  int score(dm_ctx *h, const int32_t *cur, const int32_t *ncur, float *sc, int64_t Un) override {
+    int rc;
+    DrGemmParams<float> q{};
+    q.A = base; q.lda = E; q.gidx = cur; q.Lg = 1; q.E = E; q.B = l1_w; q.ldb = 2 * E; q.bias = nullptr; q.zero = zero;
+    q.C = H1; q.ldc = E; q.M = Un * stride; q.N = E; q.Kd = E;
+    if ((rc = dr_launch_gemm<float>(h, q)) != DM_OK) return rc;
+    Otm64Attn<float> a{};
+    a.emb = base; a.H1 = H1; a.G = G; a.w2 = l2_w; a.b2 = h->b2; a.scale = sm_scale32(h); a.codes = cur; a.seq = kcode; a.scores = sc;
+    a.n = stride; a.stride = stride; a.L = L; a.E = E; a.U = Un; a.counts = ncur; a.use_mask = use_mask;
+    return otm_pl_launch_attn<float>(h, a);
+  }
+};
+
+// The level fold (Recommender._recommend + TDM.recommend) over passes of users, scored by `scorer`.
 // d_seq [U][L] item ids on the device; outputs pre-filled by the caller (ids -1, scores 0, counts 0); trace [U][trace_levels][cap] or null
-static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
-                            const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
-                            int trace_levels, int cap, int32_t *d_tc, float *d_ts, int32_t *d_tn) {
-  if (h->dtype != DM_F32)
-    return fail(h, DM_ERR_UNSUPPORTED, "tdm beam search: history lengths 17..32 run in fp32 on an f32 model (an f64 model serves OTM searches of that length in fp64)");
-  snprintf(h->last_kernel, sizeof(h->last_kernel), "tdm level pipeline (L > 16)");
+static int tdm_pl_fold(dm_ctx *h, TdmPlScorer &scorer, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
+                       const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
+                       int trace_levels, int cap, int32_t *d_tc, float *d_ts, int32_t *d_tn) {
   const int E = h->embed;
-  const float *base = (const float *)h->d_compact;
-  const float *att_w = base + h->num_index * E, *l1_w = att_w + (int64_t)E * E, *l1_b = l1_w + (int64_t)2 * E * E, *l2_w = l1_b + E;
   int start, level0;
   level_start_int(o->beam, &start, &level0);
   int n_iter = h->max_level - level0 + 1;
   if (n_iter < 0) n_iter = 0;
   int stride = 2 * (max_beam > start + 1 ? max_beam : start + 1);
   stride = (stride + 15) / 16 * 16;
-  if ((size_t)stride * 16 > 128 * 1024) return fail(h, DM_ERR_UNSUPPORTED, "tdm beam search (L > 16): beam too large for the level pipeline");
+  if ((size_t)stride * 16 > 128 * 1024) return fail(h, DM_ERR_UNSUPPORTED, "tdm beam search (level pipeline): beam too large for the level pipeline");
   const int lcap = h->leaves_at_max_only ? stride : stride * (n_iter > 0 ? n_iter : 1);
   int64_t Uc = ((int64_t)1 << 30) / ((int64_t)stride * E * 4);
   if (Uc < 1) Uc = 1;
   if (Uc > U) Uc = U;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_k = up((size_t)Uc * L * 4), b_codes = up((size_t)Uc * stride * 4), b_cnt = up((size_t)Uc * 4);
-  const size_t b_h1 = up((size_t)Uc * stride * E * 4), b_t1 = up((size_t)Uc * L * E * 4), b_lf = up((size_t)Uc * lcap * 4);
-  const size_t need = b_k + 3 * b_codes + 3 * b_cnt + b_h1 + 2 * b_t1 + 5 * b_lf + 256;
+  const size_t b_k = tdm_pl_up((size_t)Uc * L * 4), b_codes = tdm_pl_up((size_t)Uc * stride * 4), b_cnt = tdm_pl_up((size_t)Uc * 4);
+  const size_t b_lf = tdm_pl_up((size_t)Uc * lcap * 4);
+  const size_t need = b_k + 3 * b_codes + 3 * b_cnt + 5 * b_lf + scorer.ws_bytes(Uc, stride, L);
   int rc = ensure_ws(h, need);
   if (rc != DM_OK) return rc;
   char *w = (char *)h->d_ws;
@@ -249,15 +303,11 @@ static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, c
   int32_t *n0 = (int32_t *)w; w += b_cnt;
   int32_t *n1 = (int32_t *)w; w += b_cnt;
   int32_t *lf_n = (int32_t *)w; w += b_cnt;
-  float *H1 = (float *)w; w += b_h1;
-  float *T1 = (float *)w; w += b_t1;
-  float *G = (float *)w; w += b_t1;
   int32_t *lf_code = (int32_t *)w; w += b_lf;
   float *lf_score = (float *)w; w += b_lf;
   int32_t *lf_pos = (int32_t *)w; w += b_lf;
   unsigned long long *lf_key = (unsigned long long *)w; w += 2 * b_lf;
-  float *zero = (float *)w;
-  HIPCHK(h, hipMemsetAsync(zero, 0, 256, h->stream));
+  if ((rc = scorer.attach(h, w, Uc, stride, L)) != DM_OK) return rc;
   HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));
   const size_t lds_step = (size_t)stride * 16;
   HIPCHK(h, hipFuncSetAttribute((const void *)tdm_pl_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
@@ -266,12 +316,7 @@ static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, c
     const int64_t Un = U - u0 < Uc ? U - u0 : Uc;
     hipLaunchKernelGGL(tdm_pl_keys_kernel, dim3(256), dim3(256), 0, h->stream, d_seq + u0 * L, Un * L, t, kcode);
     HIPCHK(h, hipGetLastError());
-    DrGemmParams<float> g{};
-    g.A = base; g.lda = E; g.gidx = kcode; g.Lg = 1; g.E = E; g.B = att_w; g.ldb = E; g.bias = nullptr; g.zero = zero;
-    g.C = T1; g.ldc = E; g.M = Un * L; g.N = E; g.Kd = E;
-    if ((rc = dr_launch_gemm<float>(h, g)) != DM_OK) return rc;
-    g.A = T1; g.gidx = nullptr; g.B = l1_w + E; g.ldb = 2 * E; g.bias = l1_b; g.C = G;
-    if ((rc = dr_launch_gemm<float>(h, g)) != DM_OK) return rc;
+    if ((rc = scorer.setup(h, kcode, Un)) != DM_OK) return rc;
     TdmPlStep sp{};
     sp.t = t; sp.lf_code = lf_code; sp.lf_score = lf_score; sp.lf_pos = lf_pos; sp.lf_n = lf_n;
     sp.consumed_off = d_coff ? d_coff + u0 : nullptr; sp.stride = stride; sp.lcap = lcap; sp.beam = o->beam; sp.topk = o->topk;
@@ -288,14 +333,7 @@ static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, c
       hipLaunchKernelGGL(tdm_pl_step_kernel, dim3((unsigned)Un), dim3(256), lds_step, h->stream, sp);
       HIPCHK(h, hipGetLastError());
       std::swap(cur, nxt); std::swap(ncur, nnxt);
-      DrGemmParams<float> q{};
-      q.A = base; q.lda = E; q.gidx = cur; q.Lg = 1; q.E = E; q.B = l1_w; q.ldb = 2 * E; q.bias = nullptr; q.zero = zero;
-      q.C = H1; q.ldc = E; q.M = Un * stride; q.N = E; q.Kd = E;
-      if ((rc = dr_launch_gemm<float>(h, q)) != DM_OK) return rc;
-      Otm64Attn<float> a{};
-      a.emb = base; a.H1 = H1; a.G = G; a.w2 = l2_w; a.b2 = h->b2; a.scale = sm_scale32(h); a.codes = cur; a.seq = kcode; a.scores = sc;
-      a.n = stride; a.stride = stride; a.L = L; a.E = E; a.U = Un; a.counts = ncur; a.use_mask = o->use_mask ? 1 : 0;
-      if ((rc = otm_pl_launch_attn<float>(h, a)) != DM_OK) return rc;
+      if ((rc = scorer.score(h, cur, ncur, sc, Un)) != DM_OK) return rc;
       if (d_tn && it < trace_levels) {
         hipLaunchKernelGGL(tdm_pl_trace_kernel, dim3(512), dim3(256), 0, h->stream, (const int32_t *)cur, (const float *)sc, (const int32_t *)ncur,
                            stride, Un, u0, it, trace_levels, cap, d_tc, d_ts, d_tn);
@@ -311,4 +349,15 @@ static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, c
     HIPCHK(h, hipStreamSynchronize(h->stream));      // the workspace is reused by the next pass
   }
   return DM_OK;
+}
+
+// the DIN route: histories of 17 .. 32 positions whose frontier does not fit the fused kernel's LDS
+static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
+                            const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
+                            int trace_levels, int cap, int32_t *d_tc, float *d_ts, int32_t *d_tn) {
+  if (h->dtype != DM_F32)
+    return fail(h, DM_ERR_UNSUPPORTED, "tdm beam search: history lengths 17..32 run in fp32 on an f32 model (an f64 model serves OTM searches of that length in fp64)");
+  snprintf(h->last_kernel, sizeof(h->last_kernel), "tdm level pipeline (L > 16)");
+  TdmPlDin din(h, o->use_mask ? 1 : 0);
+  return tdm_pl_fold(h, din, d_seq, U, L, o, max_beam, d_coff, d_cids, d_ids, d_scores, d_counts, trace_levels, cap, d_tc, d_ts, d_tn);
 }

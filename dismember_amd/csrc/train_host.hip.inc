@@ -2,6 +2,7 @@
 
 static int train_check(dm_ctx *h, const char *who) {
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": weights not loaded");
+  DM_DIN_ONLY(h, who);
   if (!h->train_ready) return fail(h, DM_ERR_STATE, std::string(who) + ": call dm_train_init first");
   return DM_OK;
 }
@@ -13,6 +14,7 @@ int dm_train_init(dm_handle_t h, const dm_adam_opts *o) {
   if (!h) return DM_ERR_INVALID;
   DM_OWNER_ONLY(h, "dm_train_init");
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_train_init: weights not loaded");
+  DM_DIN_ONLY(h, "dm_train_init");
   if (!o || o->lr <= 0) return fail(h, DM_ERR_INVALID, "dm_train_init: bad optimizer options");
   HIPCHK(h, hipSetDevice(h->device));
   const int64_t n = compact_len(h);
@@ -373,6 +375,7 @@ int dm_adam_last_step_rows(dm_handle_t h, uint64_t *rows, int *active_rows_only)
 int dm_train_download(dm_handle_t h, int what, void *out, int64_t n) {
   if (!h) return DM_ERR_INVALID;
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_train_download: weights not loaded");
+  DM_DIN_ONLY(h, "dm_train_download");
   const bool padded = h->embed_log != h->embed;
   if (!out || n != compact_len_for(h->num_index, h->embed_log)) return fail(h, DM_ERR_INVALID, "dm_train_download: n must be the compact vector length");
   const void *src = what == 0 ? h->d_compact : what == 1 ? h->d_grad : what == 2 ? h->d_adam_s : h->d_adam_r;

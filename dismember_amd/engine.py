@@ -90,6 +90,29 @@ class Engine:
         self._chk(N.lib().dm_load_weights_din(self._h, dt, int(E), int(num_index), w.ctypes.data_as(C.c_void_p), w.size))
         self.E, self.dtype, self.num_index = int(E), w.dtype, int(num_index)
 
+    def load_weights_deepfm(self, compact, E, L, num_index):
+        """dm_load_weights_deepfm: the reference's DeepFM graph (tdm/.../model/DeepFM.scala:11-45), float32 only, compact vector
+        [emb num_index x E ; l1.W T x (T E) ; l1.b T ; l2.W 1 x T ; l2.b 1] with T = L + 1.  L is part of the model."""
+        w = np.ascontiguousarray(compact)
+        if w.dtype == np.float32:
+            dt = 0
+        elif w.dtype == np.float64:
+            dt = 1                                     # (refused by the library: DM_ERR_UNSUPPORTED)
+        else:
+            raise TypeError("weights must be float32")
+        self._chk(N.lib().dm_load_weights_deepfm(self._h, dt, int(E), int(L), int(num_index), w.ctypes.data_as(C.c_void_p), w.size))
+        self.E, self.dtype, self.num_index = int(E), w.dtype, int(num_index)
+
+    def scorer_kind(self):
+        """(kind, seq_len) of the loaded scorer (dm_get_scorer_kind): ("din", 0) or ("deepfm", L)."""
+        k, sl = C.c_int(0), C.c_int(0)
+        self._chk(N.lib().dm_get_scorer_kind(self._h, C.byref(k), C.byref(sl)))
+        return ("deepfm" if k.value == 1 else "din"), sl.value
+
+    @property
+    def scorer(self):
+        return self.scorer_kind()[0]
+
     def load_weights_din_synthetic(self, E, num_index, seed, small=None, tree_depth=None, rho=0.0, std=0.05):
         """Build the compact DIN vector on the device (N(0, 0.05) table; `small` = host array holding
         [att.W ; l1.W ; l1.b ; l2.W ; l2.b], defaults to the reference init) and load it without a host copy."""
@@ -241,6 +264,18 @@ class Engine:
         out = np.empty(B, dtype=self.dtype)
         self._chk(N.lib().dm_din_forward(self._h, _p(codes, N.i32p), _p(seqs, N.i32p), _p(pad, N.i32p), pad.size, B, L,
                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def deepfm_forward(self, codes, seqs):
+        """dm_deepfm_forward: logits [B] float32 of the DeepFM graph for rows (code, history codes [L]); -1 = a zero row.  There is no
+        mask argument: the graph has none."""
+        codes = _i32(codes).ravel()
+        seqs = _i32(seqs)
+        B = codes.size
+        L = seqs.shape[-1] if seqs.ndim == 2 else seqs.size // max(B, 1)
+        seqs = seqs.ravel()
+        out = np.empty(B, dtype=np.float32)
+        self._chk(N.lib().dm_deepfm_forward(self._h, _p(codes, N.i32p), _p(seqs, N.i32p), B, int(L), _p(out, N.f32p)))
         return out
 
     # ---- beam search

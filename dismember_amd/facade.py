@@ -23,12 +23,18 @@ class TDM:
         self.engine = engine
         self.use_mask = model_name.lower() == "din"   # TDM.apply, TDM.scala:26-29
 
+    def _deepfm(self):
+        """The engine holds a DeepFM model (Engine.load_weights_deepfm / a DeepFM checkpoint): the graph has no mask, whatever the name says."""
+        return self.engine.scorer == "deepfm"
+
     def predict(self, sequence, target):
         """TDM.predict(sequence, target): Double (TDM.scala:10-15): the model's probability for ONE (history, target item) pair —
         idToCode over sequence ++ target, one forward, sigmoid in double.  (The reference hands the model a single [1, L + 1] tensor,
         which only its DeepFM graph accepts; for DIN the same row goes through Module.forward(Table(item, sequence, mask)).)"""
         seq = np.asarray(sequence, dtype=np.int32).ravel()
         codes, mask_pos = self.engine.id_to_code(np.concatenate([seq, np.asarray([target], np.int32)]))
+        if self._deepfm():
+            return float(sigmoid(np.float32(self.engine.deepfm_forward(codes[-1:], codes[None, :-1])[0])))
         pad = mask_pos[mask_pos < seq.size].astype(np.int32) if self.use_mask else np.zeros(0, np.int32)
         logit = self.engine.din_forward(codes[-1:], codes[None, :-1], pad)
         return float(sigmoid(np.float32(logit[0])))
@@ -42,7 +48,7 @@ class TDM:
         """TDM.recommend(sequence, topk, candidateNum): Array[(Int, Double)] (TDM.scala:17-22)."""
         seq = np.asarray(sequence, dtype=np.int32)
         single = seq.ndim == 1
-        ids, sc, cnt = self.engine.tdm_beam_search(seq, candidate_num, topk, use_mask=self.use_mask)
+        ids, sc, cnt = self.engine.tdm_beam_search(seq, candidate_num, topk, use_mask=self.use_mask and not self._deepfm())
         prob = sigmoid(sc)                                   # one vectorised pass, in double
         out = [list(zip(ids[u, :cnt[u]].tolist(), prob[u, :cnt[u]].tolist())) for u in range(ids.shape[0])]
         return out[0] if single else out
@@ -71,7 +77,7 @@ class TDM:
         consumed = None
         if consumed_items is not None:
             consumed = [consumed_items] if single else consumed_items
-        ids, _, cnt = self.engine.tdm_beam_search(seq, candidate_num, topk, use_mask=self.use_mask, consumed=consumed,
+        ids, _, cnt = self.engine.tdm_beam_search(seq, candidate_num, topk, use_mask=self.use_mask and not self._deepfm(), consumed=consumed,
                                                   widen_consumed=consumed is not None)
         out = [ids[u, :cnt[u]].copy() for u in range(ids.shape[0])]
         return out[0] if single else out

@@ -120,6 +120,23 @@ class Engine {
     check(dm_load_weights_din(h_, DM_F64, embedSize, numIndex, compact.data(), (int64_t)compact.size()));
     embed_ = embedSize;
   }
+  // the reference's DeepFM graph (tdm/.../model/DeepFM.scala:11-45), float only: [emb ; l1.W ; l1.b ; l2.W ; l2.b], T = seqLen + 1
+  void loadWeightsDeepFM(const std::vector<float> &compact, int embedSize, int seqLen, int64_t numIndex) {
+    check(dm_load_weights_deepfm(h_, DM_F32, embedSize, seqLen, numIndex, compact.data(), (int64_t)compact.size()));
+    embed_ = embedSize;
+  }
+  // Module.forward(Table(item, seq)) of a loaded DeepFM model: codes [B], seqs [B * seqLen] node codes (-1 = a zero row) -> logits [B]
+  std::vector<float> deepfmForward(const std::vector<int32_t> &codes, const std::vector<int32_t> &seqs, int seqLen) const {
+    std::vector<float> logits(codes.size());
+    check(dm_deepfm_forward(h_, codes.data(), seqs.data(), (int64_t)codes.size(), seqLen, logits.data()));
+    return logits;
+  }
+  // which scorer is loaded: DM_KIND_DIN or DM_KIND_DEEPFM (dm_get_scorer_kind)
+  int scorerKind() const {
+    int kind = DM_KIND_DIN, seqLen = 0;
+    check(dm_get_scorer_kind(h_, &kind, &seqLen));
+    return kind;
+  }
   // TDM.saveModel / TDM.loadModel (tdm/.../model/TDM.scala:32-54): weights + index in one flat file (dm_save_model)
   void saveModel(const std::string &path) const { check(dm_save_model(h_, path.c_str())); }
   void loadModel(const std::string &path) { check(dm_load_model(h_, path.c_str())); }
@@ -158,9 +175,13 @@ class TDM {
     std::vector<int32_t> codes(all.size()), maskPos(all.size());
     int nMask = 0;
     e_.check(dm_tdm_id_to_code(e_.handle(), all.data(), (int)all.size(), codes.data(), maskPos.data(), &nMask));
+    float logit = 0.f;
+    if (e_.scorerKind() == DM_KIND_DEEPFM) {          // the DeepFM graph has no mask input
+      e_.check(dm_deepfm_forward(e_.handle(), &codes.back(), codes.data(), 1, (int)sequence.size(), &logit));
+      return sigmoid((double)logit);
+    }
     std::vector<int32_t> pad;
     if (useMask_) for (int i = 0; i < nMask; i++) if (maskPos[(size_t)i] < (int32_t)sequence.size()) pad.push_back(maskPos[(size_t)i]);
-    float logit = 0.f;
     const int32_t dummy = 0;
     e_.check(dm_din_forward(e_.handle(), &codes.back(), codes.data(), pad.empty() ? &dummy : pad.data(), (int64_t)pad.size(), 1, (int)sequence.size(), &logit));
     return sigmoid((double)logit);

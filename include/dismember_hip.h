@@ -96,10 +96,31 @@ int dm_level_start(int candidate_num, int *start_code, int *level);
 int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, const void *compact,
                         int64_t n_elems);
 
+/* The reference's second node scorer, DeepFM (T/model/DeepFM.scala:11-45; `deep_model DeepFM` in the TDM conf files), serving half:
+ * compact vector in Graph.parameters order (S/nn/graphnn/Graph.scala:37-48; EmbeddingShare DeepFM.scala:18, Linear :35, Linear :39 —
+ * FM holds no parameters), T = L + 1:
+ *   [emb num_index x E ; l1.W T x (T E) ; l1.b T ; l2.W 1 x T ; l2.b 1]          n_elems = num_index E + T T E + 2 T + 1
+ * dtype: DM_F32 only (DM_F64 -> DM_ERR_UNSUPPORTED).  E 1..128, zero-padded on the device like DIN's.  L 1..32 is part of the model
+ * (l1.W is sized by it) and is kept on the handle; a wrong n_elems, L or E is DM_ERR_INVALID.  The handle records which scorer is
+ * loaded (dm_get_scorer_kind: *seq_len is DeepFM's L, 0 for DIN); loading DIN weights afterwards switches it back.  dm_clone clones
+ * serve the same model through the shared storage.
+ * With a DeepFM model loaded: dm_deepfm_forward and dm_tdm_beam_search / _trace / _dev serve it (the searches through the per-level
+ * pipeline for every L, use_mask must be 0 — the graph has no mask, T/model/TDM.scala:26-29 — and L must be the model's: DM_ERR_INVALID
+ * otherwise); dm_get_leaf_embeddings, dm_cluster_tree_model, dm_save_model / dm_load_model work as for DIN; every entry point that
+ * evaluates DIN (dm_din_forward, dm_otm_*, dm_tdm_bruteforce_topk, dm_jtm_*, dm_train_*, dm_adam_step, dm_tdm_make_train_batch,
+ * dm_tdm_sample_train_batch_dev, dm_set_scorer_mode) returns DM_ERR_UNSUPPORTED and leaves the handle usable. */
+enum { DM_KIND_DIN = 0, DM_KIND_DEEPFM = 1 };
+int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_index, const void *compact, int64_t n_elems);
+int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len);
+/* Module.forward(Table(item, seq)) of the DeepFM graph for rows that each carry their own history (call sites: T/model/Recommender.scala:
+ * 93-94 with SeqModelInputs, TDM.predict): codes [B], seqs [B*L] node codes, -1 = a zero row; an index outside [0, num_index) is
+ * DM_ERR_INDEX as in dm_din_forward; L must equal the model's seq_len; logits [B] float.  DM_ERR_STATE on a DIN model. */
+int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, int64_t B, int L, float *logits);
+
 /* Checkpoint (replaces TDM.saveModel / loadModel, T/utils/Serialization.scala:60-101 — a Java ObjectOutputStream of the module graph
  * there; tdm/src/test/scala/TdmModelTrainSpec.scala:85-96 pins save -> load -> identical recommendations): one flat little-endian
  * file with the compact parameter vector in the loaded dtype plus the tree nodes and the item id -> leaf code map when they are
- * loaded (layout: dismember_amd/csrc/checkpoint.hip.inc).  No optimizer state, like the reference.  dm_load_model replaces whatever
+ * loaded (layout: dismember_amd/csrc/checkpoint.hip.inc; the header names the scorer, DIN or DeepFM).  No optimizer state, like the reference.  dm_load_model replaces whatever
  * tree / id maps / weights the handle holds with the file's. */
 int dm_save_model(dm_handle_t h, const char *path);
 int dm_load_model(dm_handle_t h, const char *path);
@@ -550,7 +571,8 @@ int dm_kernel_timing_get(dm_handle_t h, int *launches, double *total_ms);
  * A Deep-Retrieval search is several launches: by default ONE pair brackets the whole search (kind 0); with
  * DM_DR_TIME_LAUNCHES=1 in the environment (read per call) every launch gets its own pair — kind 0 the history
  * GEMM, 11 layer 0, 10 + 2d / 11 + 2d the statistics / cut of layer d — at 2 - 14 % of the search's wall time.
- * Kind 30: the general-rows scorer (dm_din_forward, JTM child weights: dm_din_rows_split*_kernel), one pair per launch. */
+ * Kind 30: the general-rows scorer (dm_din_forward, JTM child weights: dm_din_rows_split*_kernel), one pair per launch.
+ * Kinds 40 / 41: a DeepFM search's user set-up (dfm_user_kernel, one per pass of users) / its level kernel (dfm_level_kernel, one per level). */
 int dm_kernel_timing_get_kind(dm_handle_t h, int kind, int *launches, double *total_ms);
 /* name (with template arguments) of the kernel that ran the last TDM / OTM beam search, as a profiler lists it
  * (owned by the handle, valid until the next search) */

@@ -9,8 +9,12 @@ class TDM(engine: HipEngine, useMask: Boolean) extends Serializable {
     val all = sequence :+ target
     val codes = new Array[Int](all.length); val maskPos = new Array[Int](all.length); val nMask = new Array[Int](1)
     Native.tdmIdToCode(engine.handle, all, all.length, codes, maskPos, nMask)
-    val pad = if (useMask) maskPos.take(nMask(0)).filter(_ < sequence.length) else Array.emptyIntArray
     val logit = new Array[Float](1)
+    if (TDM.isDeepFM(engine)) {          // the DeepFM graph has no mask input
+      Native.deepfmForward(engine.handle, Array(codes.last), codes.init, 1L, sequence.length, logit)
+      return TDM.sigmoid(logit(0))
+    }
+    val pad = if (useMask) maskPos.take(nMask(0)).filter(_ < sequence.length) else Array.emptyIntArray
     Native.dinForwardF32(engine.handle, Array(codes.last), codes.init, pad, pad.length.toLong, 1L, sequence.length, logit)
     TDM.sigmoid(logit(0))
   }
@@ -50,9 +54,17 @@ object TDM {
   def saveModel(modelPath: String, engine: HipEngine): Unit = Native.saveModel(engine.handle, modelPath)
   def loadModel(engine: HipEngine, modelPath: String, modelName: String): TDM = {
     val name = modelName.toLowerCase
-    require(name == "din", "the device scorer is DIN (DeepFM is outside the hot path)")
+    require(name == "din" || name == "deepfm", "DeepModel name should either be DeepFM or DIN")
     Native.loadModel(engine.handle, modelPath)
-    new TDM(engine, useMask = true)
+    require(isDeepFM(engine) == (name == "deepfm"), s"the checkpoint holds a ${if (isDeepFM(engine)) "DeepFM" else "DIN"} model, not $modelName")
+    new TDM(engine, useMask = name == "din")
+  }
+
+  /** The scorer the engine holds (dm_get_scorer_kind): 1 = DeepFM, served without a mask whatever the facade was built with. */
+  def isDeepFM(engine: HipEngine): Boolean = {
+    val kind = new Array[Int](1); val seqLen = new Array[Int](1)
+    Native.getScorerKind(engine.handle, kind, seqLen)
+    kind(0) == 1
   }
 
   /** TDM.loadTree(treePbPath) (TDM.scala:50-52 -> TDMOp.initTree): the reference's own tree file, parsed by the library. */

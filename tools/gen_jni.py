@@ -57,6 +57,7 @@ ARRAY = {"int32_t": ("jintArray", "jint", "Array[Int]"), "int": ("jintArray", "j
 VOID_HOST = {
     "dm_load_weights_din": {"compact": [("F32", "float"), ("F64", "double")]},     # dtype is fixed by the variant (FIXED below)
     "dm_din_forward": {"logits": [("F32", "float"), ("F64", "double")]},
+    "dm_load_weights_deepfm": {"compact": [("F32", "float")]},                     # DM_F32 only
     "dm_train_download": {"out": [("F32", "float"), ("F64", "double")]},               # the loaded dtype
     "dm_comm_unique_id": {"id128": [("", "uint8_t")]},
     "dm_comm_create_rccl": {"id128": [("", "uint8_t")]},
@@ -65,13 +66,14 @@ VOID_HOST = {
     "dm_memcpy_h2d": {"src": [("", "uint8_t"), ("I32", "int32_t"), ("F32", "float"), ("F64", "double")]},
     "dm_memcpy_d2h": {"dst": [("", "uint8_t"), ("I32", "int32_t"), ("F32", "float"), ("F64", "double")]},
 }
-FIXED = {("dm_load_weights_din", "F32"): {"dtype": "DM_F32"}, ("dm_load_weights_din", "F64"): {"dtype": "DM_F64"}}   # args the variant pins
+FIXED = {("dm_load_weights_din", "F32"): {"dtype": "DM_F32"}, ("dm_load_weights_din", "F64"): {"dtype": "DM_F64"},
+         ("dm_load_weights_deepfm", "F32"): {"dtype": "DM_F32"}}   # args the variant pins
 HANDWRITTEN = {"dm_dr_load_model"}          # struct with pointer arrays: written out below
 # entry points that neither wait on peers / the network nor run a long device job: the only ones allowed a Critical region
 # (not dm_create — HIP runtime and device initialisation can take seconds — and not dm_memcpy_h2d / _d2h: arbitrarily large
 # synchronous copies; both would hold the GC locker for their whole duration)
 CRITICAL_OK = {"dm_level_start", "dm_jtm_shard_range", "dm_tdm_id_to_code", "dm_kernel_timing_get",
-               "dm_kernel_timing_get_kind", "dm_get_scorer_mode", "dm_comm_rank", "dm_device_count", "dm_last_scored_rows",
+               "dm_kernel_timing_get_kind", "dm_get_scorer_mode", "dm_get_scorer_kind", "dm_comm_rank", "dm_device_count", "dm_last_scored_rows",
                "dm_train_last_loss", "dm_train_sync_stats", "dm_jtm_last_step_seconds", "dm_adam_last_step_rows", "dm_comm_unique_id", "dm_dev_alloc"}
 JTYPE = {"jint": "Int", "jlong": "Long", "jfloat": "Float", "jdouble": "Double", "jbyte": "Byte"}
 # Minimum lengths (in elements) of host arrays whose extent follows from the scalar arguments of the same call: checked with
@@ -85,6 +87,7 @@ EXTENTS = {
     "dm_load_id_maps": {"leaf_item_ids": "n", "leaf_codes": "n"},
     "dm_tdm_id_to_code": {"item_ids": "n", "codes": "n", "mask_pos": "n", "n_mask": "1"},
     "dm_din_forward": {"codes": "B", "seqs": "B * L", "pad_flat_idx": "n_pad", "logits": "B"},
+    "dm_deepfm_forward": {"codes": "B", "seqs": "B * L", "logits": "B"},
     "dm_tdm_beam_search": dict(_SEARCH_OUT, seq_item_ids="U * L", consumed_off="U + 1"),
     "dm_tdm_beam_search_trace": dict(_SEARCH_OUT, seq_item_ids="U * L", trace_counts="U * max_levels"),
     "dm_otm_beam_search": _OTM_OUT, "dm_otm_beam_search_f64": _OTM_OUT,
