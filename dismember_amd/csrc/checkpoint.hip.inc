@@ -178,10 +178,10 @@ static int load_model_body(dm_ctx *h, FILE *f) {
       const size_t n = total - off < slice ? (size_t)(total - off) : slice;
       ok = ckpt_read(f, buf.data(), n) && hipMemcpy((char *)d + off, buf.data(), n, hipMemcpyHostToDevice) == hipSuccess;
     }
-    if (!ok) { dm_free_ptr(d); return fail(h, DM_ERR_INVALID, "dm_load_model: truncated file (weights)"); }
+    if (!ok) { dm_release(d); return fail(h, DM_ERR_INVALID, "dm_load_model: truncated file (weights)"); }
     rc = hd.dtype == DM_F64 ? dm_load_weights_din_dev_f64(h, hd.embed, hd.num_index, (double *)d, hd.n_elems)
                             : dm_load_weights_din_dev(h, hd.embed, hd.num_index, (float *)d, hd.n_elems);
-    if (rc != DM_OK && h->d_compact != d) dm_free_ptr(d);
+    if (rc != DM_OK && h->d_compact != d) dm_release(d);
   }
   if (rc != DM_OK) return rc;
   if (hd.has_tree && (rc = dm_load_tree_tdm(h, codes.data(), nids.data(), isleaf.data(), hd.n_nodes, hd.max_level)) != DM_OK) return rc;

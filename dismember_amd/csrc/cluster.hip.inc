@@ -600,20 +600,7 @@ __global__ __launch_bounds__(CL_TB) void cl_lds_subtree_kernel(ClLds P) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-struct ClArena {                                   // device allocations of one call, freed together
-  std::vector<void *> ptrs;
-  ~ClArena() { for (void *p : ptrs) dm_free_ptr(p); }
-  template <typename T>
-  int get(dm_ctx *h, T **out, size_t count) {
-    void *p = nullptr;
-    const int rc = dm_alloc(h, &p, count * sizeof(T));
-    if (rc != DM_OK) return rc;
-    ptrs.push_back(p); *out = (T *)p;
-    return DM_OK;
-  }
-  void drop_from(size_t mark) { while (ptrs.size() > mark) { dm_free_ptr(ptrs.back()); ptrs.pop_back(); } }
-};
-#define CL_GET(ptr, count) do { const int rc_g_ = arena.get(h, &(ptr), (size_t)(count)); if (rc_g_ != DM_OK) return rc_g_; } while (0)
+#define CL_GET(ptr, count) do { const int rc_g_ = arena.alloc((ptr), (size_t)(count) * sizeof(*(ptr))); if (rc_g_ != DM_OK) return rc_g_; } while (0)   // device allocations of one call, freed together
 
 static int cl_max_level(int64_t n) { int l = 0; while (((int64_t)1 << l) < n) l++; return l; }
 static std::vector<int32_t> cl_level_sizes(int64_t n, int level) {
@@ -632,7 +619,7 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
   using clk = std::chrono::steady_clock;
   auto secs = [](clk::time_point a) { return std::chrono::duration<double>(clk::now() - a).count(); };
   dm_cluster_stats st{};
-  ClArena arena;
+  DevTemps arena(h);
   hipStream_t sm = h->stream;
   const int max_level = cl_max_level(n);
   const int64_t nodes = ((int64_t)1 << max_level) - 1;
@@ -663,7 +650,7 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
     const int S = (int)sizes.size();
     if (*std::max_element(sizes.begin(), sizes.end()) <= CUT) break;
     if (!keys[0]) { CL_GET(keys[0], n); CL_GET(keys[1], n); CL_GET(sort_tmp, dev_sort_scratch_bytes(n) / 4 + 1); }
-    const size_t mark = arena.ptrs.size();
+    const size_t mark = arena.owned.size();
     std::vector<int32_t> seg_off(S + 1, 0), tile_first(S + 1, 0), tile_seg, tile_start;
     for (int s = 0; s < S; s++) {
       seg_off[s + 1] = seg_off[s] + sizes[s];
@@ -814,7 +801,7 @@ int dm_cluster_tree(dm_handle_t h, const float *emb, int64_t n, int E, int resta
   if (n == 1) { cluster_single(codes_out, trace, stats); return DM_OK; }
   HIPCHK(h, hipSetDevice(h->device));
   const int EP = native_embed(E);
-  ClArena arena;
+  DevTemps arena(h);
   float *d_X;
   CL_GET(d_X, (size_t)n * EP);
   if (EP != E) HIPCHK(h, hipMemsetAsync(d_X, 0, (size_t)n * EP * 4, h->stream));
@@ -824,7 +811,7 @@ int dm_cluster_tree(dm_handle_t h, const float *emb, int64_t n, int E, int resta
 }
 
 // the loaded table's rows at the items' current leaf codes -> *d_out [n][ocols] on the device
-static int cluster_gather_model(dm_ctx *h, const char *who, const int32_t *item_ids, int64_t n, int ocols, ClArena &arena, float **d_out) {
+static int cluster_gather_model(dm_ctx *h, const char *who, const int32_t *item_ids, int64_t n, int ocols, DevTemps &arena, float **d_out) {
   if (!h->ids_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": no tree loaded (item id -> leaf code map)");
   if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": no weights loaded");
   std::vector<int32_t> codes((size_t)n);
@@ -856,7 +843,7 @@ int dm_cluster_tree_model(dm_handle_t h, const int32_t *item_ids, int64_t n, int
   if (!item_ids) return fail(h, DM_ERR_INVALID, "dm_cluster_tree_model: item_ids is null");
   const int rc = cluster_check(h, "dm_cluster_tree_model", n, restarts, max_iter, tol, codes_out);
   if (rc != DM_OK) return rc;
-  ClArena arena;
+  DevTemps arena(h);
   float *d_X = nullptr;
   const int rg = cluster_gather_model(h, "dm_cluster_tree_model", item_ids, n, h->embed, arena, &d_X);
   if (rg != DM_OK) return rg;
@@ -881,7 +868,7 @@ int dm_get_leaf_embeddings(dm_handle_t h, const int32_t *item_ids, int64_t n, fl
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   if (!item_ids || !out || n < 1) return fail(h, DM_ERR_INVALID, "dm_get_leaf_embeddings: bad arguments");
-  ClArena arena;
+  DevTemps arena(h);
   float *d_X = nullptr;
   const int E = h->embed_log > 0 ? h->embed_log : h->embed;
   const int rg = cluster_gather_model(h, "dm_get_leaf_embeddings", item_ids, n, E, arena, &d_X);

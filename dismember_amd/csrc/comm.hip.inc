@@ -157,9 +157,8 @@ static int host_all_gather_v(dm_comm *c, const void *send, size_t bytes, std::ve
 
 static int comm_stage(dm_comm *c, size_t bytes) {
   if (c->stage_bytes >= bytes) return DM_OK;
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  c->d_stage = nullptr; c->stage_bytes = 0;
-  CHIPCHK(c, hipMalloc(&c->d_stage, bytes + bytes / 2 + 256));
+  dm_release(c->d_stage); c->stage_bytes = 0;
+  if (dm_alloc(nullptr, &c->d_stage, bytes + bytes / 2 + 256) != DM_OK) { c->err = g_create_err; return DM_ERR_HIP; }
   c->stage_bytes = bytes + bytes / 2 + 256;
   return DM_OK;
 }
@@ -292,7 +291,7 @@ int dm_comm_destroy(dm_comm_t c) {
   if (c->kind == DM_COMM_RCCL) {
     if (c->device >= 0) (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->d_stage) (void)hipFree(c->d_stage);
+    dm_release(c->d_stage);
     if (c->nccl) (void)ncclCommDestroy(c->nccl);
   }
   comm_close_sockets(c);
@@ -384,11 +383,7 @@ __global__ void dm_sync_record_kernel(const unsigned long long *cnt, unsigned lo
 }
 
 static int sync_grow(dm_ctx *h, size_t bytes) {
-  if (h->sync_bytes >= bytes) return DM_OK;
-  dm_free_ptr(h->d_sync); h->d_sync = nullptr; h->sync_bytes = 0;
-  ALLOC(h, h->d_sync, bytes + bytes / 4 + 256);
-  h->sync_bytes = bytes + bytes / 4 + 256;
-  return DM_OK;
+  return h->sync.reserve(h, bytes, bytes / 4 + 256);
 }
 
 // what the last exchange moved (bench.py prints it) lives in the handle (dm_ctx::sync_stats: the reference's shape is N worker threads
@@ -428,7 +423,6 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
   const bool f64 = h0->dtype == DM_F64;
   const size_t es = f64 ? 8 : 4;
   const ncclDataType_t nty = f64 ? ncclDouble : ncclFloat;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // ---- (1) touched-row counts of every rank
   std::vector<uint64_t> cnt(W, 0), okf(W, 1);
   if (c0->kind == DM_COMM_RCCL) {
@@ -438,18 +432,18 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
       HIPCHK(h, hipSetDevice(h->device));
       int rc = sync_grow(h, 16 + 16 * (size_t)W);
       if (rc != DM_OK) return rc;
-      hipLaunchKernelGGL(dm_sync_record_kernel, dim3(1), dim3(64), 0, h->stream, h->d_touch_cnt, (unsigned long long)h->touch_cap, (unsigned long long *)h->d_sync);
+      hipLaunchKernelGGL(dm_sync_record_kernel, dim3(1), dim3(64), 0, h->stream, h->d_touch_cnt, (unsigned long long)h->touch_cap, (unsigned long long *)h->sync.p);
       HIPCHK(h, hipGetLastError());
     }
     ncclResult_t e = ncclGroupStart();
     for (int i = 0; i < nh && e == ncclSuccess; i++)
-      e = ncclAllGather(hs[i]->d_sync, (char *)hs[i]->d_sync + 16, 2, ncclUint64, hs[i]->comm->nccl, hs[i]->stream);
+      e = ncclAllGather(hs[i]->sync.p, (char *)hs[i]->sync.p + 16, 2, ncclUint64, hs[i]->comm->nccl, hs[i]->stream);
     ncclResult_t e2 = ncclGroupEnd();
     if (e != ncclSuccess || e2 != ncclSuccess)
       return fail(h0, DM_ERR_HIP, std::string("dm_train_sync_gradients: RCCL count exchange failed: ") + ncclGetErrorString(e != ncclSuccess ? e : e2));
     for (int i = 0; i < nh; i++) {
       HIPCHK(hs[i], hipSetDevice(hs[i]->device));
-      HIPCHK(hs[i], hipMemcpyAsync(rec[i].data(), (char *)hs[i]->d_sync + 16, 16 * (size_t)W, hipMemcpyDeviceToHost, hs[i]->stream));
+      HIPCHK(hs[i], hipMemcpyAsync(rec[i].data(), (char *)hs[i]->sync.p + 16, 16 * (size_t)W, hipMemcpyDeviceToHost, hs[i]->stream));
     }
     for (int i = 0; i < nh; i++) { HIPCHK(hs[i], hipSetDevice(hs[i]->device)); HIPCHK(hs[i], hipStreamSynchronize(hs[i]->stream)); }
     S.host_syncs++;
@@ -478,7 +472,7 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
   S.rows_total = total;
   // ---- per handle staging.  RCCL: [record area 256 B | own block | W blocks], block = [maxc row ids (padded to 256 B) | maxc x E
   // gradient elements]; HOST: [own rows | own grads | all rows | all grads | W dense blocks]
-  const size_t blk_rows = up(maxc * 4), blk = blk_rows + up(maxc * E * es);
+  const size_t blk_rows = DevArena::up(maxc * 4), blk = blk_rows + DevArena::up(maxc * E * es);
   struct Lay { char *mine; char *all; int32_t *my_rows; void *my_grads; int32_t *all_rows; char *all_grads; char *dense_all; };
   std::vector<Lay> lay(nh);
   for (int i = 0; i < nh; i++) {
@@ -486,19 +480,19 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
     HIPCHK(h, hipSetDevice(h->device));
     const uint64_t mine = cnt[h->comm->rank];
     const size_t need = c0->kind == DM_COMM_RCCL ? 256 + 16 * (size_t)W + (size_t)(W + 1) * blk
-                                                 : up(mine * 4) + up(mine * E * es) + up(total * 4) + up(total * E * es) + up((size_t)W * nd * es);
+                                                 : DevArena::up(mine * 4) + DevArena::up(mine * E * es) + DevArena::up(total * 4) + DevArena::up(total * E * es) + DevArena::up((size_t)W * nd * es);
     int rc = sync_grow(h, need);
     if (rc != DM_OK) return rc;
-    char *w = (char *)h->d_sync;
+    char *w = (char *)h->sync.p;
     if (c0->kind == DM_COMM_RCCL) {
-      w += up(16 + 16 * (size_t)W);
+      w += DevArena::up(16 + 16 * (size_t)W);
       lay[i].mine = w; lay[i].all = w + blk;
       lay[i].my_rows = (int32_t *)lay[i].mine; lay[i].my_grads = lay[i].mine + blk_rows;
     } else {
-      lay[i].my_rows = (int32_t *)w; w += up(mine * 4);
-      lay[i].my_grads = w; w += up(mine * E * es);
-      lay[i].all_rows = (int32_t *)w; w += up(total * 4);
-      lay[i].all_grads = w; w += up(total * E * es);
+      lay[i].my_rows = (int32_t *)w; w += DevArena::up(mine * 4);
+      lay[i].my_grads = w; w += DevArena::up(mine * E * es);
+      lay[i].all_rows = (int32_t *)w; w += DevArena::up(total * 4);
+      lay[i].all_grads = w; w += DevArena::up(total * E * es);
       lay[i].dense_all = w;
     }
     if (mine) { rc = launch_gather_rows(h, (int64_t)mine, lay[i].my_rows, lay[i].my_grads); if (rc != DM_OK) return rc; }

@@ -248,7 +248,7 @@ int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_i
   free_weights(h);      // (also switches the handle back to "no scorer": a failed load leaves no half-DIN, half-DeepFM state)
   void *d = nullptr;
   ALLOC(h, d, bytes);
-  if (hipMemcpy(d, w, bytes, hipMemcpyHostToDevice) != hipSuccess) { dm_free_ptr(d); return fail(h, DM_ERR_HIP, "dm_load_weights_deepfm: upload failed"); }
+  if (hipMemcpy(d, w, bytes, hipMemcpyHostToDevice) != hipSuccess) { dm_release(d); return fail(h, DM_ERR_HIP, "dm_load_weights_deepfm: upload failed"); }
   h->d_compact = d; h->d_emb32 = (float *)d; h->dtype = DM_F32; h->embed = Ep; h->embed_log = E; h->num_index = num_index;
   h->scorer_kind = DM_KIND_DEEPFM; h->dfm_L = L;
   const int NCT = dfm_col_tiles(L);
@@ -301,7 +301,7 @@ int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, 
       return fail(h, DM_ERR_INDEX, b);
     }
   HIPCHK(h, hipSetDevice(h->device));
-  ReqArena ar;
+  ReqArena ar(h);
   const size_t o_codes = ar.add((size_t)B * 4), o_seqs = ar.add((size_t)B * L * 4), o_out = ar.add((size_t)B * 4);
   int rc = ar.commit(h);
   if (rc != DM_OK) return rc;
@@ -341,11 +341,13 @@ struct TdmPlDeepFM : TdmPlScorer {
   int E, L, NCT, stride = 0;
   float *S = nullptr, *aux = nullptr;
   explicit TdmPlDeepFM(const dm_ctx *h) : E(h->embed), L(h->dfm_L), NCT(dfm_col_tiles(h->dfm_L)) {}
-  size_t ws_bytes(int64_t Uc, int, int) const override { return tdm_pl_up((size_t)Uc * E * 4) + tdm_pl_up((size_t)Uc * NCT * 16 * 4); }
-  int attach(dm_ctx *, char *w, int64_t Uc, int stride_, int) override {
+  size_t o_s = 0, o_aux = 0;
+  void layout(DevArena &ar, int64_t Uc, int stride_, int) override {
     stride = stride_;
-    S = (float *)w; w += tdm_pl_up((size_t)Uc * E * 4);
-    aux = (float *)w;
+    o_s = ar.add((size_t)Uc * E * 4); o_aux = ar.add((size_t)Uc * NCT * 16 * 4);
+  }
+  int attach(dm_ctx *, const DevArena &ar) override {
+    S = ar.ptr<float>(o_s); aux = ar.ptr<float>(o_aux);
     return DM_OK;
   }
   int setup(dm_ctx *h, const int32_t *kcode, int64_t Un) override {

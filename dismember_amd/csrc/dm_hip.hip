@@ -21,6 +21,7 @@
 #include <cstring>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "beam_kernel.hip.inc"
@@ -34,6 +35,7 @@
 
 #define DM_VERSION 100
 
+#include "dev_mem.hip.inc"
 #define DM_LAZY_COPIES_PART 1      // struct LazyCopies
 #include "lazy_copies.hip.inc"
 // ------------------------------------------------------------------ context
@@ -105,8 +107,7 @@ struct dm_ctx {
   bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
   bool call_split = false;     // scorer arithmetic of the search being planned (split_for_call)
   double jtm_score_s = 0, jtm_rebal_s = 0;   // dm_jtm_last_step_seconds
-  void *d_scratch64 = nullptr; // fp64 beam kernel (beam_kernel_f64.hip.inc): per-team K / G fragment scratch
-  size_t scratch64_bytes = 0;
+  DevGrow scratch64;           // fp64 beam kernel (beam_kernel_f64.hip.inc): per-team K / G fragment scratch
   // training state (dm_train_init)
   bool train_ready = false;
   dm_adam_opts adam{};
@@ -139,8 +140,7 @@ struct dm_ctx {
   // Deep-Retrieval model (dm_dr_load_model)
   dm_dr_state *dr = nullptr;
   // request arena of the host-buffer entry points (grow only: no hipMalloc / hipFree on the request path)
-  void *d_req = nullptr;
-  size_t req_bytes = 0;
+  DevGrow req;
   unsigned long long h_rows = 0;
   char *h_stage = nullptr;     // pinned staging block for small host-buffer requests (one upload, one download per call)
   char *d_stage = nullptr;     // the same block as the kernels address it (hipHostGetDevicePointer): single-request path
@@ -150,17 +150,14 @@ struct dm_ctx {
   std::vector<hipEvent_t> chunk_ev;
   bool rows_keep = false;      // a later chunk of one request: the scored-rows counter keeps counting
   // cached search workspace
-  void *d_ws = nullptr;
-  size_t ws_bytes = 0;
+  DevGrow ws;
   // device-side negative sampler (sampler.hip.inc): per-level code / cumulative-probability tables, per-call scratch
   int32_t *d_lv_codes = nullptr;
   double *d_lv_cdf = nullptr;
   int64_t *d_lv_start = nullptr;
-  void *d_samp = nullptr;
-  size_t samp_bytes = 0;
+  DevGrow samp;
   // multi-GPU exchange (comm.hip.inc): the attached communicator (not owned) and the staging area of dm_train_sync_gradients
-  void *d_defer = nullptr;       // users the W kernel hands to the LDS-fed kernel: [count u64 | queue head u64 | ids]
-  size_t defer_bytes = 0;
+  DevGrow defer;                 // users the W kernel hands to the LDS-fed kernel: [count u64 | queue head u64 | ids]
   // JTM: the catalogue's training rows kept on the device across gap steps (dm_jtm_cache_rows)
   int64_t *d_jtm_off = nullptr;
   int32_t *d_jtm_ritem = nullptr, *d_jtm_rids = nullptr;
@@ -175,8 +172,7 @@ struct dm_ctx {
   dm_sync_stats sync_stats{};
   dm_jtm_stats jtm_stats{};
   dm_otm_stats otm_stats{};
-  void *d_sync = nullptr;
-  size_t sync_bytes = 0;
+  DevGrow sync;
 };
 
 static std::string g_create_err;
@@ -312,7 +308,9 @@ __global__ __launch_bounds__(256) void dm_din_forward_kernel(DinFwdParams<T> p) 
 
 // ------------------------------------------------------------------ helpers
 static int dm_alloc(dm_ctx *h, void **p, size_t bytes) {
-  HIPCHK(h, hipMalloc(p, bytes ? bytes : 16));
+  const hipError_t e = hipMalloc(p, bytes ? bytes : 16);       // h == nullptr: an owner without a handle (the communicator's staging block)
+  if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("hipMalloc(") + std::to_string(bytes) + " bytes) failed: " + hipGetErrorString(e));
+  dm_live_add(*p, bytes ? bytes : 16);
   return DM_OK;
 }
 #define ALLOC(h, ptr, bytes)                                   \
@@ -320,7 +318,6 @@ static int dm_alloc(dm_ctx *h, void **p, size_t bytes) {
     int rc_ = dm_alloc((h), (void **)&(ptr), (bytes));         \
     if (rc_ != DM_OK) return rc_;                              \
   } while (0)
-static void dm_free_ptr(void *p) { if (p) (void)hipFree(p); }
 
 // The 256 KB pinned staging block of the small-request paths.  It is also what the single-request kernels read and write in place
 // and whose count words the host polls, so it is allocated COHERENT explicitly (fine-grained: device stores become visible to the
@@ -391,9 +388,9 @@ int dm_create(int device_id, dm_handle_t *out) {
   { const char *e_ = getenv("DM_NO_DIRECT"); if (e_ && e_[0] == '1') h->direct_ok = false; }
   { const char *e_ = getenv("DM_TIME_DIRECT"); if (e_ && e_[0] == '1') h->time_direct = true; }
   if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return fail(nullptr, DM_ERR_HIP, "hipStreamCreate failed"); }
-  if (hipMalloc((void **)&h->d_rows, 64) != hipSuccess) { delete h; return fail(nullptr, DM_ERR_HIP, "hipMalloc failed"); }
+  if (dm_alloc(h, (void **)&h->d_rows, 64) != DM_OK) { delete h; return fail(nullptr, DM_ERR_HIP, "hipMalloc failed"); }
   (void)hipMemset(h->d_rows, 0, 64);
-  if (hipMalloc((void **)&h->d_phase, 128) == hipSuccess) (void)hipMemset(h->d_phase, 0, 128);
+  if (dm_alloc(h, (void **)&h->d_phase, 128) == DM_OK) (void)hipMemset(h->d_phase, 0, 128);
   *out = h;
   return DM_OK;
 }
@@ -410,26 +407,25 @@ static const char *scorer_name(const dm_ctx *h) { return h->scorer_kind == DM_KI
 
 static void free_tree(dm_ctx *h) {
   model_changed(h);
-  dm_free_ptr(h->d_lv_codes); dm_free_ptr(h->d_lv_cdf); dm_free_ptr(h->d_lv_start);
-  h->d_lv_codes = nullptr; h->d_lv_cdf = nullptr; h->d_lv_start = nullptr;
-  dm_free_ptr(h->d_exists); dm_free_ptr(h->d_leaf); dm_free_ptr(h->d_node_id); dm_free_ptr(h->d_leaf_codes);
-  h->d_exists = h->d_leaf = nullptr; h->d_node_id = h->d_leaf_codes = nullptr; h->tree_loaded = false;
+  dm_release(h->d_lv_codes, h->d_lv_cdf, h->d_lv_start, h->d_exists, h->d_leaf, h->d_node_id, h->d_leaf_codes);
+  h->tree_loaded = false;
+}
+// the training state of dm_train_init: its buffers, and the flags that say they exist
+static void free_training(dm_ctx *h) {
+  dm_release(h->d_grad, h->d_adam_s, h->d_adam_r, h->d_loss, h->d_tr64, h->d_attTA, h->d_w1aTA, h->d_w1bTA);
+  dm_release(h->d_touch_bits, h->d_touch_list, h->d_touch_cnt, h->d_active_bits, h->d_active_list, h->d_active_cnt);
+  h->train_ready = false; h->touch_cap = 0; h->touch_ub = 0;
 }
 static void free_weights(dm_ctx *h) {
   model_changed(h);
-  if (h->emb32_owned) dm_free_ptr(h->d_emb32);
-  dm_free_ptr(h->d_compact); dm_free_ptr(h->d_wfrag); dm_free_ptr(h->d_afrag); dm_free_ptr(h->d_bfrag); dm_free_ptr(h->d_attA); dm_free_ptr(h->d_w1aA); dm_free_ptr(h->d_w1bA);
-  dm_free_ptr(h->d_b1); dm_free_ptr(h->d_w2); dm_free_ptr(h->d_att_wT_t); dm_free_ptr(h->d_l1T_t);
+  if (h->emb32_owned) dm_release(h->d_emb32);
+  h->d_emb32 = nullptr; h->emb32_owned = false;
+  dm_release(h->d_compact, h->d_wfrag, h->d_afrag, h->d_bfrag, h->d_attA, h->d_w1aA, h->d_w1bA, h->d_b1, h->d_w2, h->d_att_wT_t, h->d_l1T_t);
   h->lazy.released();
-  dm_free_ptr(h->d_dfm_frag); dm_free_ptr(h->d_dfm_w2p); h->d_dfm_frag = h->d_dfm_w2p = nullptr; h->scorer_kind = DM_KIND_DIN; h->dfm_L = 0;
-  dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; dm_free_ptr(h->d_tail32); h->d_tail32 = nullptr;
-  h->d_compact = nullptr; h->d_emb32 = nullptr; h->emb32_owned = false; h->d_wfrag = nullptr;
-  dm_free_ptr(h->d_grad); dm_free_ptr(h->d_adam_s); dm_free_ptr(h->d_adam_r); dm_free_ptr(h->d_loss); dm_free_ptr(h->d_attTA);
-  dm_free_ptr(h->d_w1aTA); dm_free_ptr(h->d_w1bTA); dm_free_ptr(h->d_touch_bits); dm_free_ptr(h->d_touch_list); dm_free_ptr(h->d_touch_cnt);
-  dm_free_ptr(h->d_active_bits); dm_free_ptr(h->d_active_list); dm_free_ptr(h->d_active_cnt); h->d_active_bits = nullptr; h->d_active_list = nullptr; h->d_active_cnt = nullptr;
-  h->d_grad = h->d_adam_s = h->d_adam_r = h->d_loss = nullptr; h->d_attTA = h->d_w1aTA = h->d_w1bTA = nullptr;
-  h->d_touch_bits = nullptr; h->d_touch_list = nullptr; h->d_touch_cnt = nullptr; h->train_ready = false; h->touch_cap = 0; h->touch_ub = 0;
-  h->d_afrag = h->d_bfrag = nullptr; h->d_attA = h->d_w1aA = h->d_w1bA = nullptr; h->d_b1 = h->d_w2 = nullptr; h->d_att_wT_t = h->d_l1T_t = nullptr; h->w_loaded = false;
+  dm_release(h->d_dfm_frag, h->d_dfm_w2p, h->d_tail32);
+  h->scorer_kind = DM_KIND_DIN; h->dfm_L = 0;
+  free_training(h);
+  h->w_loaded = false;
 }
 
 // Everything a clone mirrors from its parent: the tree, the id maps, the weights and every derived copy (fragment orders, split planes,
@@ -461,6 +457,7 @@ static void clone_forget(dm_ctx *c) {         // the clone owns none of it
   c->emb32_owned = false;
 }
 
+static void jtm_drop_cache(dm_ctx *h);
 int dm_destroy(dm_handle_t h) {
   if (!h) return DM_ERR_INVALID;
   if (h->n_clones.load() > 0) return fail(h, DM_ERR_STATE, "dm_destroy: the handle still has clones (dm_clone): destroy them first");
@@ -468,10 +465,10 @@ int dm_destroy(dm_handle_t h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->parent) { clone_forget(h); h->parent->n_clones.fetch_sub(1); h->parent = nullptr; }
   free_tree(h); free_weights(h); dm_dr_free(h->dr);
-  dm_free_ptr(h->d_id_to_code); dm_free_ptr(h->d_rows); dm_free_ptr(h->d_phase); dm_free_ptr(h->d_ws); dm_free_ptr(h->d_req); dm_free_ptr(h->d_sync);
+  dm_release(h->d_id_to_code, h->d_rows, h->d_phase);
+  for (DevGrow *g : {&h->ws, &h->req, &h->sync, &h->samp, &h->defer, &h->scratch64}) g->release();
   if (h->h_stage) (void)hipHostFree(h->h_stage);
-  dm_free_ptr(h->d_lv_codes); dm_free_ptr(h->d_lv_cdf); dm_free_ptr(h->d_lv_start); dm_free_ptr(h->d_samp); dm_free_ptr(h->d_defer); dm_free_ptr(h->d_scratch64);
-  dm_free_ptr(h->d_jtm_off); dm_free_ptr(h->d_jtm_ritem); dm_free_ptr(h->d_jtm_rids); dm_free_ptr(h->d_jtm_rseq); dm_free_ptr(h->d_jtm_rmask);
+  jtm_drop_cache(h);
   for (auto &pr : h->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
   for (auto &e_ : h->chunk_ev) (void)hipEventDestroy(e_);
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -551,7 +548,7 @@ int dm_load_id_maps(dm_handle_t h, const int32_t *leaf_item_ids, const int32_t *
   h->h_id_to_code.assign((size_t)h->non_leaf_offset, -1);
   for (int64_t i = 0; i < n; i++)
     if (leaf_item_ids[i] >= 0) h->h_id_to_code[leaf_item_ids[i]] = leaf_codes[i];
-  dm_free_ptr(h->d_id_to_code); h->d_id_to_code = nullptr;
+  dm_release(h->d_id_to_code);
   ALLOC(h, h->d_id_to_code, h->h_id_to_code.size() * 4);
   HIPCHK(h, hipMemcpy(h->d_id_to_code, h->h_id_to_code.data(), h->h_id_to_code.size() * 4, hipMemcpyHostToDevice));
   h->ids_loaded = true;
@@ -871,29 +868,25 @@ int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, con
   unsigned *d_mask = nullptr;
   void *d_out = nullptr;
   const size_t esz = h->dtype == DM_F32 ? 4 : 8;
-  int rc = DM_OK;
-  do {
-    if ((rc = dm_alloc(h, (void **)&d_codes, B * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_seqs, B * L * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_mask, B * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, &d_out, B * esz)) != DM_OK) break;
-    if (hipMemcpyAsync(d_codes, codes, B * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipMemcpyAsync(d_seqs, seqs, B * L * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipMemsetAsync(d_mask, 0, B * 4, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_din_forward: upload failed"); break; }
-    if (n_pad > 0) {
-      if (dm_alloc(h, (void **)&d_pad, n_pad * 4) != DM_OK) { rc = DM_ERR_HIP; break; }
-      if (hipMemcpyAsync(d_pad, pad_flat_idx, n_pad * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "upload failed"); break; }
-      hipLaunchKernelGGL(dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, h->stream, d_pad, n_pad, L, d_mask);
-    }
-    rc = h->dtype == DM_F32 ? (L <= DM_MAXL ? din_rows_dev(h, d_codes, d_seqs, d_mask, B, L, (float *)d_out)
-                                            : din_forward_t<float>(h, d_codes, d_seqs, d_mask, B, L, (float *)d_out))
-                            : din_forward_t<double>(h, d_codes, d_seqs, d_mask, B, L, (double *)d_out);
-    if (rc != DM_OK) break;
-    if (hipMemcpyAsync(logits, d_out, B * esz, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, std::string("dm_din_forward: ") + hipGetErrorString(hipGetLastError())); break; }
-  } while (0);
-  dm_free_ptr(d_codes); dm_free_ptr(d_seqs); dm_free_ptr(d_mask); dm_free_ptr(d_out); dm_free_ptr(d_pad);
-  return rc;
+  DevTemps t(h);
+  int rc;
+  if ((rc = t.alloc(d_codes, B * 4)) != DM_OK || (rc = t.alloc(d_seqs, B * L * 4)) != DM_OK || (rc = t.alloc(d_mask, B * 4)) != DM_OK ||
+      (rc = t.alloc(d_out, B * esz)) != DM_OK) return rc;
+  if (hipMemcpyAsync(d_codes, codes, B * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(d_seqs, seqs, B * L * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemsetAsync(d_mask, 0, B * 4, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "dm_din_forward: upload failed");
+  if (n_pad > 0) {
+    if (t.alloc(d_pad, n_pad * 4) != DM_OK) return DM_ERR_HIP;
+    if (hipMemcpyAsync(d_pad, pad_flat_idx, n_pad * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
+    hipLaunchKernelGGL(dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, h->stream, d_pad, n_pad, L, d_mask);
+  }
+  rc = h->dtype == DM_F32 ? (L <= DM_MAXL ? din_rows_dev(h, d_codes, d_seqs, d_mask, B, L, (float *)d_out)
+                                          : din_forward_t<float>(h, d_codes, d_seqs, d_mask, B, L, (float *)d_out))
+                          : din_forward_t<double>(h, d_codes, d_seqs, d_mask, B, L, (double *)d_out);
+  if (rc != DM_OK) return rc;
+  if (hipMemcpyAsync(logits, d_out, B * esz, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+      hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, std::string("dm_din_forward: ") + hipGetErrorString(hipGetLastError()));
+  return DM_OK;
 }
 
 // ------------------------------------------------------------ beam search
@@ -965,11 +958,7 @@ static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, 
 }
 
 static int ensure_ws(dm_ctx *h, size_t bytes) {
-  if (h->ws_bytes >= bytes) return DM_OK;
-  dm_free_ptr(h->d_ws); h->d_ws = nullptr; h->ws_bytes = 0;
-  ALLOC(h, h->d_ws, bytes);
-  h->ws_bytes = bytes;
-  return DM_OK;
+  return h->ws.reserve(h, bytes);
 }
 
 static int next_events(dm_ctx *h, hipEvent_t *a, hipEvent_t *b) {
@@ -1059,14 +1048,10 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
     if (pl.wkernel) {
       // users the W kernel cannot score in fp16 throughout are queued in [count | next | ids ...] and scored by the LDS-fed kernel
       const size_t need = 16 + (size_t)p.U * 4;
-      if (h->defer_bytes < need) {
-        dm_free_ptr(h->d_defer); h->d_defer = nullptr; h->defer_bytes = 0;
-        ALLOC(h, h->d_defer, need + need / 4);
-        h->defer_bytes = need + need / 4;
-      }
-      HIPCHK(h, hipMemsetAsync(h->d_defer, 0, 16, h->stream));
-      p.defer_count = (unsigned long long *)h->d_defer;
-      p.defer_users = (int32_t *)((char *)h->d_defer + 16);
+      { const int rc_d = h->defer.reserve(h, need, need / 4); if (rc_d != DM_OK) return rc_d; }
+      HIPCHK(h, hipMemsetAsync(h->defer.p, 0, 16, h->stream));
+      p.defer_count = (unsigned long long *)h->defer.p;
+      p.defer_users = (int32_t *)((char *)h->defer.p + 16);
       const char *const no_split = "the split-fp16 scorer needs an embedding size of 32, 64 or 128";
       int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
       if (rc != DM_OK) return rc;
@@ -1080,9 +1065,9 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       if (pl2.grid < 1) pl2.grid = 1;
       BeamParams p2 = p;
       p2.nteams = pl2.nteams;
-      p2.user_count = (const unsigned long long *)h->d_defer;
-      p2.user_list = (const int32_t *)((char *)h->d_defer + 16);
-      p2.next_user = (unsigned long long *)((char *)h->d_defer + 8);
+      p2.user_count = (const unsigned long long *)h->defer.p;
+      p2.user_list = (const int32_t *)((char *)h->defer.p + 16);
+      p2.next_user = (unsigned long long *)((char *)h->defer.p + 8);
       p2.defer_count = nullptr; p2.defer_users = nullptr;
       h->ev_next_kind = 1;
       rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p2, pl2); });
@@ -1177,8 +1162,8 @@ static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, con
   p.widen = (o->widen_consumed && d_coff) ? 1 : 0;
   p.consumed_off = d_coff; p.consumed_ids = d_cids; p.mode = 0; p.nteams = pl.nteams; p.cap = pl.cap; p.pcap = pl.pcap; p.leaf_fast = h->leaves_at_max_only ? 1 : 0;
   p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_stride = o->topk;
-  p.ws_code = (int32_t *)h->d_ws; p.ws_score = (float *)h->d_ws + per; p.ws_khi = (uint32_t *)h->d_ws + 2 * per;
-  p.ws_klo = (uint32_t *)h->d_ws + 3 * per; p.ws_cap = pl.ws_cap;
+  p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p + per; p.ws_khi = (uint32_t *)h->ws.p + 2 * per;
+  p.ws_klo = (uint32_t *)h->ws.p + 3 * per; p.ws_cap = pl.ws_cap;
   p.trace_codes = d_tc; p.trace_scores = d_ts; p.trace_counts = d_tn; p.trace_levels = trace_levels;
   if (direct) {
     // single-request path (tdm_search_host): request and results live in host-mapped pinned memory, one team per user without the
@@ -1269,7 +1254,7 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
   const size_t topk = (size_t)opts->topk, b_seq = (size_t)U * L * 4;
   const int64_t nc = coff ? coff[U] : 0;
   // request arena: [seq | ids | scores | counts | consumed_off | consumed_ids]
-  ReqArena ar;
+  ReqArena ar(h);
   const size_t o_seq = ar.add(b_seq), o_ids = ar.add(U * topk * 4), o_sc = ar.add(U * topk * 4), o_cnt = ar.add((size_t)U * 4), o_end = ar.need;
   const size_t o_coff = coff ? ar.add((size_t)(U + 1) * 8) : 0, o_cids = coff ? ar.add((size_t)(nc > 0 ? nc : 1) * 4) : 0;
   int rc = ar.commit(h);
@@ -1314,26 +1299,29 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
     if (hipMemcpyAsync(d_coff, coff, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
     if (nc > 0 && hipMemcpyAsync(d_cids, cids, (size_t)nc * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
   }
-  struct TraceBufs {      // trace buffers (parity instrumentation) are per call
-    int32_t *tc = nullptr, *tn = nullptr; float *ts = nullptr;
-    ~TraceBufs() { dm_free_ptr(tc); dm_free_ptr(tn); dm_free_ptr(ts); }
-  } d_tr;
-  if (tn) {
+  // the search and its download; d_tc / d_ts / d_tn: device trace buffers or null
+  auto finish = [&](int32_t *d_tc, float *d_ts, int32_t *d_tn) -> int {
+    int rc_f = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tc, d_ts, d_tn);
+    if (rc_f != DM_OK) return rc_f;
+    hipError_t e = staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("tdm beam search: ") + hipGetErrorString(e));
+    if (staged) copy_from_stage(h, outs, 3, U);
+    return DM_OK;
+  };
+  if (tn) {      // trace buffers (parity instrumentation) are per call; the guard exists on this path only
+    DevTemps trace(h);
+    int32_t *d_tc = nullptr, *d_tn = nullptr; float *d_ts = nullptr;
     const size_t nt = (size_t)U * max_levels;
-    if ((rc = dm_alloc(h, (void **)&d_tr.tc, nt * cap * 4)) != DM_OK) return rc;
-    if ((rc = dm_alloc(h, (void **)&d_tr.ts, nt * cap * 4)) != DM_OK) return rc;
-    if ((rc = dm_alloc(h, (void **)&d_tr.tn, nt * 4)) != DM_OK) return rc;
-    if (hipMemsetAsync(d_tr.tn, 0, nt * 4, h->stream) != hipSuccess || hipMemsetAsync(d_tr.tc, 0, nt * cap * 4, h->stream) != hipSuccess ||
-        hipMemsetAsync(d_tr.ts, 0, nt * cap * 4, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "memset failed");
-    outs[3] = {tc, d_tr.tc, (size_t)max_levels * cap * 4}; outs[4] = {ts, d_tr.ts, (size_t)max_levels * cap * 4}; outs[5] = {tn, d_tr.tn, (size_t)max_levels * 4};
+    if ((rc = trace.alloc(d_tc, nt * cap * 4)) != DM_OK) return rc;
+    if ((rc = trace.alloc(d_ts, nt * cap * 4)) != DM_OK) return rc;
+    if ((rc = trace.alloc(d_tn, nt * 4)) != DM_OK) return rc;
+    if (hipMemsetAsync(d_tn, 0, nt * 4, h->stream) != hipSuccess || hipMemsetAsync(d_tc, 0, nt * cap * 4, h->stream) != hipSuccess ||
+        hipMemsetAsync(d_ts, 0, nt * cap * 4, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "memset failed");
+    outs[3] = {tc, d_tc, (size_t)max_levels * cap * 4}; outs[4] = {ts, d_ts, (size_t)max_levels * cap * 4}; outs[5] = {tn, d_tn, (size_t)max_levels * 4};
+    return finish(d_tc, d_ts, d_tn);
   }
-  rc = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tr.tc, d_tr.ts, d_tr.tn);
-  if (rc != DM_OK) return rc;
-  hipError_t e = staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("tdm beam search: ") + hipGetErrorString(e));
-  if (staged) copy_from_stage(h, outs, 3, U);
-  return DM_OK;
+  return finish(nullptr, nullptr, nullptr);
 }
 
 int dm_tdm_beam_search(dm_handle_t h, const int32_t *seq_item_ids, int64_t U, int L, const dm_tdm_search_opts *opts,
@@ -1379,8 +1367,8 @@ static int otm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, int
   const size_t per = (size_t)pl.grid * pl.nteams * pl.ws_cap;
   p.seq = d_seq; p.U = U; p.L = L; p.use_mask = 1; p.beam = beam; p.topk = stride; p.mode = 1; p.otm_leaf_level = leaf_level;
   p.nteams = pl.nteams; p.cap = pl.cap; p.pcap = pl.pcap; p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_stride = stride;
-  p.ws_code = (int32_t *)h->d_ws; p.ws_score = (float *)h->d_ws + per; p.ws_khi = (uint32_t *)h->d_ws + 2 * per;
-  p.ws_klo = (uint32_t *)h->d_ws + 3 * per; p.ws_cap = pl.ws_cap;
+  p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p + per; p.ws_khi = (uint32_t *)h->ws.p + 2 * per;
+  p.ws_klo = (uint32_t *)h->ws.p + 3 * per; p.ws_cap = pl.ws_cap;
   p.trace_codes = d_tc; p.trace_scores = d_ts; p.trace_counts = d_tn; p.trace_levels = d_tn ? max_levels : 0;
   return launch_beam(h, p, pl);
 }
@@ -1432,7 +1420,7 @@ static int otm_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L
   if ((rc = plan_search(h, beam, U, L, leaf_level - level, false, &pl)) != DM_OK) return rc;
   const size_t stride = (size_t)2 * beam, nt = tn ? (size_t)U * max_levels : 0;
   // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
-  ReqArena ar;
+  ReqArena ar(h);
   const size_t o_seq = ar.add((size_t)U * L * 4), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * 4), o_cnt = ar.add((size_t)U * 4);
   const size_t o_tc = ar.add(nt * pl.cap * 4), o_ts = ar.add(nt * pl.cap * 4), o_tn = ar.add(nt * 4);
   if ((rc = ar.commit(h)) != DM_OK) return rc;
@@ -1524,53 +1512,51 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
   unsigned long long *d_keys = nullptr;
   int rc = DM_OK;
   std::vector<unsigned long long> keys((size_t)n_work * topk);
-  do {
-    if ((rc = ensure_ws(h, 1024)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_seq, (size_t)U * L * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_keys, keys.size() * 8)) != DM_OK) break;
-    hipError_t e = hipMemcpyAsync(d_seq, seq_item_ids, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_rows, 0, 16, h->stream);
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_tdm_bruteforce_topk: upload failed"); break; }
-    BeamParams p;
-    fill_common(h, p);
-    p.seq = d_seq; p.U = U; p.L = L; p.use_mask = use_mask; p.beam = 2; p.topk = topk; p.mode = 2;
-    p.nteams = nteams; p.cap = cap; p.pcap = pcap; p.out_stride = topk;
-    p.bf_leaf_codes = h->d_leaf_codes; p.bf_n_leaf = h->n_leaf_nodes; p.bf_slices = (int)slices; p.bf_chunk = chunk;
-    p.bf_per_slice = per; p.bf_out_keys = d_keys;
-    p.ws_code = (int32_t *)h->d_ws; p.ws_score = (float *)h->d_ws; p.ws_khi = (uint32_t *)h->d_ws; p.ws_klo = (uint32_t *)h->d_ws;
-    p.ws_cap = 0;
-    SearchPlan pl;
-    pl.nteams = nteams; pl.cap = cap; pl.pcap = pcap; pl.lds = lds; pl.ws_cap = 0; pl.wkernel = false;
-    int64_t groups = (n_work + nteams - 1) / nteams;
-    pl.grid = (int)(groups < h->n_cu ? groups : h->n_cu);
-    if ((rc = launch_beam(h, p, pl)) != DM_OK) break;
-    e = hipMemcpyAsync(keys.data(), d_keys, keys.size() * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, std::string("dm_tdm_bruteforce_topk: ") + hipGetErrorString(e)); break; }
-    std::vector<int32_t> nid((size_t)h->n_slots);
-    if (hipMemcpy(nid.data(), h->d_node_id, nid.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "node id download failed"); break; }
-    // merge the per-slice winners (keys are unique: descending-score key << 32 | leaf code)
-    std::vector<unsigned long long> row((size_t)slices * topk);
-    for (int64_t u = 0; u < U; u++) {
-      std::copy(keys.begin() + u * slices * topk, keys.begin() + (u + 1) * slices * topk, row.begin());
-      const size_t kk = std::min<size_t>(topk, row.size());
-      std::partial_sort(row.begin(), row.begin() + kk, row.end());
-      int n = 0;
-      for (size_t i = 0; i < kk; i++) {
-        if (row[i] == ~0ull) break;
-        const uint32_t code = (uint32_t)row[i], dk = (uint32_t)(row[i] >> 32);
-        const uint32_t asc = ~dk;
-        const uint32_t bits = (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
-        float sc; memcpy(&sc, &bits, 4);
-        out_item_ids[u * topk + n] = nid[code];
-        out_scores[u * topk + n] = sc;
-        n++;
-      }
-      for (int i = n; i < topk; i++) { out_item_ids[u * topk + i] = -1; out_scores[u * topk + i] = 0.f; }
-      out_counts[u] = n;
+  DevTemps t(h);
+  if ((rc = ensure_ws(h, 1024)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_seq, (size_t)U * L * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_keys, keys.size() * 8)) != DM_OK) return rc;
+  hipError_t e = hipMemcpyAsync(d_seq, seq_item_ids, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->d_rows, 0, 16, h->stream);
+  if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_tdm_bruteforce_topk: upload failed");
+  BeamParams p;
+  fill_common(h, p);
+  p.seq = d_seq; p.U = U; p.L = L; p.use_mask = use_mask; p.beam = 2; p.topk = topk; p.mode = 2;
+  p.nteams = nteams; p.cap = cap; p.pcap = pcap; p.out_stride = topk;
+  p.bf_leaf_codes = h->d_leaf_codes; p.bf_n_leaf = h->n_leaf_nodes; p.bf_slices = (int)slices; p.bf_chunk = chunk;
+  p.bf_per_slice = per; p.bf_out_keys = d_keys;
+  p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p; p.ws_khi = (uint32_t *)h->ws.p; p.ws_klo = (uint32_t *)h->ws.p;
+  p.ws_cap = 0;
+  SearchPlan pl;
+  pl.nteams = nteams; pl.cap = cap; pl.pcap = pcap; pl.lds = lds; pl.ws_cap = 0; pl.wkernel = false;
+  int64_t groups = (n_work + nteams - 1) / nteams;
+  pl.grid = (int)(groups < h->n_cu ? groups : h->n_cu);
+  if ((rc = launch_beam(h, p, pl)) != DM_OK) return rc;
+  e = hipMemcpyAsync(keys.data(), d_keys, keys.size() * 8, hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("dm_tdm_bruteforce_topk: ") + hipGetErrorString(e));
+  std::vector<int32_t> nid((size_t)h->n_slots);
+  if (hipMemcpy(nid.data(), h->d_node_id, nid.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DM_ERR_HIP, "node id download failed");
+  // merge the per-slice winners (keys are unique: descending-score key << 32 | leaf code)
+  std::vector<unsigned long long> row((size_t)slices * topk);
+  for (int64_t u = 0; u < U; u++) {
+    std::copy(keys.begin() + u * slices * topk, keys.begin() + (u + 1) * slices * topk, row.begin());
+    const size_t kk = std::min<size_t>(topk, row.size());
+    std::partial_sort(row.begin(), row.begin() + kk, row.end());
+    int n = 0;
+    for (size_t i = 0; i < kk; i++) {
+      if (row[i] == ~0ull) break;
+      const uint32_t code = (uint32_t)row[i], dk = (uint32_t)(row[i] >> 32);
+      const uint32_t asc = ~dk;
+      const uint32_t bits = (asc & 0x80000000u) ? (asc & 0x7fffffffu) : ~asc;
+      float sc; memcpy(&sc, &bits, 4);
+      out_item_ids[u * topk + n] = nid[code];
+      out_scores[u * topk + n] = sc;
+      n++;
     }
-  } while (0);
-  dm_free_ptr(d_seq); dm_free_ptr(d_keys);
+    for (int i = n; i < topk; i++) { out_item_ids[u * topk + i] = -1; out_scores[u * topk + i] = 0.f; }
+    out_counts[u] = n;
+  }
   return rc;
 }
 
@@ -1599,7 +1585,7 @@ int dm_dev_alloc(dm_handle_t h, size_t bytes, void **dptr) {
 int dm_dev_free(dm_handle_t h, void *dptr) {
   if (!h) return DM_ERR_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  if (dptr) HIPCHK(h, hipFree(dptr));
+  HIPCHK(h, dm_free_one(dptr));
   return DM_OK;
 }
 int dm_memcpy_h2d(dm_handle_t h, void *dst, const void *src, size_t bytes) {

@@ -19,7 +19,7 @@ struct dm_dr_state {
   void *d_etabs[DR_MAXD * (DR_MAXD - 1) / 2] = {};  // exp(T_{d,t}[node][k] - rowmax[node])
   bool sliced = true;                 // DM_DR_SLICED=0 at load time keeps the one-workgroup-per-user kernel
   int64_t sliced_min = 512;           // batches below this take the single launch (DM_DR_SLICED_MIN_USERS: tests run the sliced path on tiny batches)
-  void *d_state = nullptr; size_t state_bytes = 0;  // layer state + partial statistics of the sliced search
+  DevGrow state;                                     // layer state + partial statistics of the sliced search
   void *d_rr_emb = nullptr, *d_rr_w = nullptr, *d_rr_b = nullptr, *d_sm_w = nullptr, *d_sm_b = nullptr;
   // path -> items
   int64_t P = 0;
@@ -28,31 +28,17 @@ struct dm_dr_state {
   int64_t *d_item_off = nullptr;
   int32_t *d_items = nullptr;
   // scratch (grow only)
-  void *d_S = nullptr; size_t S_bytes = 0;
-  void *d_UV = nullptr; size_t UV_bytes = 0;
-  void *d_io = nullptr; size_t io_bytes = 0;        // seq ids + paths + probs + counts + outputs of one chunk
-  void *d_cand = nullptr; size_t cand_bytes = 0;
+  DevGrow S, UV, io, cand;                          // io: seq ids + paths + probs + counts + outputs of one chunk
 };
 
 static void dm_dr_free(dm_dr_state *s) {
   if (!s) return;
-  dm_free_ptr(s->d_layer_emb); dm_free_ptr(s->d_wseq); dm_free_ptr(s->d_sbias); dm_free_ptr(s->d_zero); dm_free_ptr(s->d_wseq_split); dm_free_ptr(s->d_wseq_stages); dm_free_ptr(s->d_emb_stages);
-  for (auto &t : s->d_tabs) dm_free_ptr(t);
-  for (auto &t : s->d_rowmax) dm_free_ptr(t);
-  for (auto &t : s->d_etabs) dm_free_ptr(t);
-  dm_free_ptr(s->d_state);
-  dm_free_ptr(s->d_rr_emb); dm_free_ptr(s->d_rr_w); dm_free_ptr(s->d_rr_b); dm_free_ptr(s->d_sm_w); dm_free_ptr(s->d_sm_b);
-  dm_free_ptr(s->d_codes); dm_free_ptr(s->d_item_off); dm_free_ptr(s->d_items);
-  dm_free_ptr(s->d_S); dm_free_ptr(s->d_UV); dm_free_ptr(s->d_io); dm_free_ptr(s->d_cand);
+  dm_release(s->d_layer_emb, s->d_wseq, s->d_sbias, s->d_zero, s->d_wseq_split, s->d_wseq_stages, s->d_emb_stages);
+  for (auto *v : {&s->d_tabs, &s->d_rowmax, &s->d_etabs})
+    for (auto &t : *v) dm_release(t);
+  dm_release(s->d_rr_emb, s->d_rr_w, s->d_rr_b, s->d_sm_w, s->d_sm_b, s->d_codes, s->d_item_off, s->d_items);
+  for (DevGrow *g : {&s->state, &s->S, &s->UV, &s->io, &s->cand}) g->release();
   delete s;
-}
-
-static int dr_grow(dm_ctx *h, void **p, size_t *have, size_t want) {
-  if (*have >= want) return DM_OK;
-  dm_free_ptr(*p); *p = nullptr; *have = 0;
-  int rc = dm_alloc(h, p, want);
-  if (rc == DM_OK) *have = want;
-  return rc;
 }
 
 template <typename T>
@@ -98,15 +84,12 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
   const size_t zero_bytes = (size_t)4 * E * esz > 4096 ? (size_t)4 * E * esz : 4096;   // the 256 x 256 split GEMM steps through a zero block as long as a
   ALLOC(h, s->d_zero, zero_bytes);                                                     // row's records (4 E bytes); the other GEMMs read one row of E values
   HIPCHK(h, hipMemsetAsync(s->d_zero, 0, zero_bytes, h->stream));
-  struct TmpBufs {                         // freed on every exit path
-    std::vector<void *> v;
-    explicit TmpBufs(int n) : v(n, nullptr) {}
-    ~TmpBufs() { for (void *w : v) dm_free_ptr(w); }
-    void *&operator[](int i) { return v[i]; }
-  } tmpw(D);
+  DevTemps tmp(h);
+  std::vector<void *> tmpw(D, nullptr);
   for (int d = 0; d < D; d++) {
     const size_t cols = (size_t)(L + d) * E;
-    if ((rc = dr_copy_in(h, &tmpw[d], m->layer_w[d], (size_t)K * cols * esz, dev)) != DM_OK) return rc;
+    if ((rc = tmp.alloc(tmpw[d], (size_t)K * cols * esz)) != DM_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(tmpw[d], m->layer_w[d], (size_t)K * cols * esz, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpy2DAsync((char *)s->d_wseq + (size_t)d * K * L * E * esz, (size_t)L * E * esz, tmpw[d], cols * esz,
                                (size_t)L * E * esz, K, hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync((char *)s->d_sbias + (size_t)d * K * esz, m->layer_b[d], K * esz,
@@ -164,10 +147,11 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
     { const char *e_ = getenv("DM_DR_GEMM_X_MIN_ROWS"); if (e_ && atoll(e_) > 0) s->x_min_rows = atoll(e_); }
     const char *x_ = getenv("DM_DR_GEMM_X");                   // "0": keep the 128 x 128 kernel (and save the second table copy)
     if (!(x_ && x_[0] == '0')) {
-      if (hipMalloc(&s->d_emb_stages, (size_t)n_emb * 4) != hipSuccess || hipMalloc(&s->d_wseq_stages, (size_t)D * K * L * E * 4) != hipSuccess) {
+      const std::string err0 = h->err;           // (an optimisation that does not fit leaves no trace, not even a last-error string)
+      if (dm_alloc(h, &s->d_emb_stages, (size_t)n_emb * 4) != DM_OK || dm_alloc(h, &s->d_wseq_stages, (size_t)D * K * L * E * 4) != DM_OK) {
         (void)hipGetLastError();
-        dm_free_ptr(s->d_emb_stages); dm_free_ptr(s->d_wseq_stages);
-        s->d_emb_stages = nullptr; s->d_wseq_stages = nullptr;
+        dm_release(s->d_emb_stages, s->d_wseq_stages);
+        h->err = err0;
       } else {
         hipLaunchKernelGGL(dr_split_rows_kernel, dim3(8192), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, n_emb / E, E,
                            ldexpf(1.0f, s->sh_a), (_Float16 *)s->d_emb_stages);
@@ -247,8 +231,8 @@ int dm_dr_load_path_items(dm_handle_t h, const int32_t *path_nodes, int64_t n_pa
     off[(size_t)i + 1] = off[(size_t)i] + c;
     if (c > mb) mb = c;
   }
-  dm_free_ptr(s->d_codes); dm_free_ptr(s->d_item_off); dm_free_ptr(s->d_items);
-  s->d_codes = nullptr; s->d_item_off = nullptr; s->d_items = nullptr; s->paths_loaded = false;
+  dm_release(s->d_codes, s->d_item_off, s->d_items);
+  s->paths_loaded = false;
   ALLOC(h, s->d_codes, (size_t)n_paths * 8);
   ALLOC(h, s->d_item_off, ((size_t)n_paths + 1) * 8);
   ALLOC(h, s->d_items, (size_t)n_items * 4);
@@ -273,7 +257,7 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
   HIPCHK(h, hipFuncSetAttribute((const void *)dr_beam_kernel<T, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIPCHK(h, hipFuncSetAttribute((const void *)dr_beam_kernel<T, DR_MAXD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t chunk = 32768;
-  int rc = dr_grow(h, &s->d_S, &s->S_bytes, ((size_t)(U < chunk ? U : chunk) * D * K + 64) * sizeof(T));      // + slack: the sliced search reads 8 columns at a time
+  int rc = s->S.reserve(h, ((size_t)(U < chunk ? U : chunk) * D * K + 64) * sizeof(T));      // + slack: the sliced search reads 8 columns at a time
   if (rc != DM_OK) return rc;
   if (sizeof(T) == 4 && !s->d_wseq_split && h->scorer_mode == DM_SCORER_SPLIT_F16)      // asked for by name: say so instead of quietly running fp32
     return fail(h, DM_ERR_UNSUPPORTED, "dm_dr_beam_search: the split-fp16 history GEMM needs embed_size % 64 == 0 (this model: fp32 GEMM; use DM_SCORER_AUTO or DM_SCORER_F32)");
@@ -289,12 +273,12 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
     DrGemmParams<T> g{};
     g.A = (const T *)s->d_layer_emb; g.lda = 0; g.gidx = d_seq + u0 * L; g.Lg = L; g.E = E;
     g.B = (const T *)s->d_wseq; g.ldb = (int64_t)L * E; g.bias = (const T *)s->d_sbias; g.zero = (const T *)s->d_zero;
-    g.C = (T *)s->d_S; g.ldc = (int64_t)D * K; g.M = n; g.N = D * K; g.Kd = L * E;
+    g.C = (T *)s->S.p; g.ldc = (int64_t)D * K; g.M = n; g.N = D * K; g.Kd = L * E;
     if (sizeof(T) == 4 && s->d_wseq_split && h->scorer_mode != DM_SCORER_F32) {
       DrGemmSplitParams q{};
       q.emb = (const float *)s->d_layer_emb; q.gidx = g.gidx; q.Lg = L; q.E = E;
       q.Bp = (const _Float16 *)s->d_wseq_split; q.bias = (const float *)s->d_sbias; q.zero = (const float *)s->d_zero;
-      q.C = (float *)s->d_S; q.ldc = g.ldc; q.M = n; q.N = D * K; q.Kd = L * E;
+      q.C = (float *)s->S.p; q.ldc = g.ldc; q.M = n; q.N = D * K; q.Kd = L * E;
       q.a_scale = ldexpf(1.0f, s->sh_a); q.c_unscale = ldexpf(1.0f, -(s->sh_a + s->sh_b));
       q.embp = (const _Float16 *)s->d_emb_stages; q.Bt = (const _Float16 *)s->d_wseq_stages; q.zeroh = (const _Float16 *)s->d_zero;
       const bool x = s->d_emb_stages && L <= DR_X_MAXL && (s->x_min_rows > 0 ? n >= s->x_min_rows : dr_gemm_x_pays(n, q.N, h->n_cu));
@@ -312,7 +296,7 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
       if (detail) HIPCHK(h, hipEventRecord(e1, h->stream));
     } else if ((rc = dr_launch_gemm<T>(h, g, detail)) != DM_OK) return rc;
     DrBeamParams<T> p{};
-    p.S = (const T *)s->d_S;
+    p.S = (const T *)s->S.p;
     for (int i = 0; i < DR_MAXD * (DR_MAXD - 1) / 2; i++) p.tabs[i] = (const T *)s->d_tabs[i];
     p.K = K; p.D = D; p.beam = beam; p.n2 = n2; p.U = n;
     p.fast = dr_beam_fast_ok(K, n2) && !s->exact_only ? 1 : 0; p.nl = dr_beam_nl(K, n2);
@@ -325,12 +309,11 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
     if (s->sliced && p.fast && K <= DRS_W * DRS_NS && n2 <= 64 && D <= DR_MAXD && n >= s->sliced_min) {      // (small batches: one launch beats five)
       // column-sliced search (dr_sliced.hip.inc): layer 0, then per layer a statistics launch over (user, path, slice) and a cut
       // launch over users; state and partial statistics in one grow-only block
-      auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-      const size_t b_nodes = up((size_t)n * beam * D * 4), b_prob = up((size_t)n * beam * sizeof(T)), b_np = up((size_t)n * 4);
-      const size_t b_smax = up((size_t)n * D * sizeof(T)), b_ps = up((size_t)n * beam * DRS_NS * sizeof(T)), b_pb = up((size_t)n * beam * 64 * sizeof(T));
-      const size_t b_es = up(((size_t)n * D * K + 64) * sizeof(T));
-      if ((rc = dr_grow(h, &s->d_state, &s->state_bytes, 2 * (b_nodes + b_prob + b_np) + b_smax + b_ps + b_pb + b_es + b_np)) != DM_OK) return rc;
-      char *w = (char *)s->d_state;
+      const size_t b_nodes = DevArena::up((size_t)n * beam * D * 4), b_prob = DevArena::up((size_t)n * beam * sizeof(T)), b_np = DevArena::up((size_t)n * 4);
+      const size_t b_smax = DevArena::up((size_t)n * D * sizeof(T)), b_ps = DevArena::up((size_t)n * beam * DRS_NS * sizeof(T)), b_pb = DevArena::up((size_t)n * beam * 64 * sizeof(T));
+      const size_t b_es = DevArena::up(((size_t)n * D * K + 64) * sizeof(T));
+      if ((rc = s->state.reserve(h, 2 * (b_nodes + b_prob + b_np) + b_smax + b_ps + b_pb + b_es + b_np)) != DM_OK) return rc;
+      char *w = (char *)s->state.p;
       int32_t *nodes[2]; T *pprob[2]; int32_t *npv[2];
       for (int i = 0; i < 2; i++) { nodes[i] = (int32_t *)w; w += b_nodes; pprob[i] = (T *)w; w += b_prob; npv[i] = (int32_t *)w; w += b_np; }
       DrsParams<T> q{};
@@ -448,13 +431,12 @@ int dm_dr_beam_search(dm_handle_t h, const int32_t *seq_ids, int64_t U, int beam
   if ((rc = dr_check_ids(h, seq_ids, U * s->L)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t b_seq = (size_t)U * s->L * 4, b_paths = (size_t)U * beam * s->D * 4, b_probs = (size_t)U * beam * 8, b_cnt = (size_t)U * 4;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  if ((rc = dr_grow(h, &s->d_io, &s->io_bytes, al(b_seq) + al(b_paths) + al(b_probs) + al(b_cnt))) != DM_OK) return rc;
-  char *base = (char *)s->d_io;
+  if ((rc = s->io.reserve(h, DevArena::up(b_seq) + DevArena::up(b_paths) + DevArena::up(b_probs) + DevArena::up(b_cnt))) != DM_OK) return rc;
+  char *base = (char *)s->io.p;
   int32_t *d_seq = (int32_t *)base;
-  double *d_probs = (double *)(base + al(b_seq));
-  int32_t *d_paths = (int32_t *)(base + al(b_seq) + al(b_probs));
-  int32_t *d_cnt = (int32_t *)(base + al(b_seq) + al(b_probs) + al(b_paths));
+  double *d_probs = (double *)(base + DevArena::up(b_seq));
+  int32_t *d_paths = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_probs));
+  int32_t *d_cnt = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_probs) + DevArena::up(b_paths));
   HIPCHK(h, hipMemcpyAsync(d_seq, seq_ids, b_seq, hipMemcpyHostToDevice, h->stream));
   if ((rc = dm_dr_beam_search_dev(h, d_seq, U, beam, d_paths, d_probs, d_cnt)) != DM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(out_paths, d_paths, b_paths, hipMemcpyDeviceToHost, h->stream));
@@ -471,11 +453,11 @@ static int dr_recommend_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int be
   int rc = dr_beam_dev_t<T>(h, d_seq, U, beam, d_paths, d_probs, d_pcounts);
   if (rc != DM_OK) return rc;
   const int E = s->E, L = s->L;
-  if ((rc = dr_grow(h, &s->d_UV, &s->UV_bytes, (size_t)U * E * sizeof(T))) != DM_OK) return rc;
+  if ((rc = s->UV.reserve(h, (size_t)U * E * sizeof(T))) != DM_OK) return rc;
   DrGemmParams<T> g{};                       // RerankModel.inferenceUserVector (RerankModel.scala:54-68)
   g.A = (const T *)s->d_rr_emb; g.lda = 0; g.gidx = d_seq; g.Lg = L; g.E = E;
   g.B = (const T *)s->d_rr_w; g.ldb = (int64_t)L * E; g.bias = (const T *)s->d_rr_b; g.zero = (const T *)s->d_zero;
-  g.C = (T *)s->d_UV; g.ldc = E; g.M = U; g.N = E; g.Kd = L * E;
+  g.C = (T *)s->UV.p; g.ldc = E; g.M = U; g.N = E; g.Kd = L * E;
   if ((rc = dr_launch_gemm<T>(h, g)) != DM_OK) return rc;
   const int n2k = dr_pow2_ge(topk);
   const size_t lds = dr_rerank_lds((int)sizeof(T), E, beam, n2k);
@@ -487,13 +469,12 @@ static int dr_recommend_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int be
   int64_t grid = (int64_t)h->n_cu * 8;
   if (grid > U) grid = U;
   while (grid > 1 && (size_t)grid * cap * (4 + sizeof(T)) > ((size_t)4 << 30)) grid /= 2;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  if ((rc = dr_grow(h, &s->d_cand, &s->cand_bytes, al((size_t)grid * cap * 4) + (size_t)grid * cap * sizeof(T))) != DM_OK) return rc;
+  if ((rc = s->cand.reserve(h, DevArena::up((size_t)grid * cap * 4) + (size_t)grid * cap * sizeof(T))) != DM_OK) return rc;
   DrRerankParams<T> p{};
   p.paths = d_paths; p.counts = d_pcounts; p.codes = s->d_codes; p.item_off = s->d_item_off; p.items = s->d_items; p.P = s->P;
-  p.UV = (const T *)s->d_UV; p.sm_w = (const T *)s->d_sm_w; p.sm_b = (const T *)s->d_sm_b;
+  p.UV = (const T *)s->UV.p; p.sm_w = (const T *)s->d_sm_w; p.sm_b = (const T *)s->d_sm_b;
   p.K = s->K; p.D = s->D; p.E = E; p.beam = beam; p.topk = topk; p.n2k = n2k; p.cap = cap; p.U = U;
-  p.cand = (int32_t *)s->d_cand; p.score = (T *)((char *)s->d_cand + al((size_t)grid * cap * 4));
+  p.cand = (int32_t *)s->cand.p; p.score = (T *)((char *)s->cand.p + DevArena::up((size_t)grid * cap * 4));
   p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_ncand = nullptr;
   LaunchTimer tm(h);
   if (tm.rc != DM_OK) return tm.rc;
@@ -506,13 +487,12 @@ static int dr_recommend_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int be
 static int dr_recommend_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, int topk, int32_t *d_ids, double *d_scores,
                             int32_t *d_counts) {
   dm_dr_state *s = h->dr;
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_paths = al((size_t)U * beam * s->D * 4), b_probs = al((size_t)U * beam * 8), b_cnt = al((size_t)U * 4);
+  const size_t b_paths = DevArena::up((size_t)U * beam * s->D * 4), b_probs = DevArena::up((size_t)U * beam * 8), b_cnt = DevArena::up((size_t)U * 4);
   int rc = ensure_ws(h, b_paths + b_probs + b_cnt);
   if (rc != DM_OK) return rc;
-  double *d_probs = (double *)h->d_ws;
-  int32_t *d_paths = (int32_t *)((char *)h->d_ws + b_probs);
-  int32_t *d_pc = (int32_t *)((char *)h->d_ws + b_probs + b_paths);
+  double *d_probs = (double *)h->ws.p;
+  int32_t *d_paths = (int32_t *)((char *)h->ws.p + b_probs);
+  int32_t *d_pc = (int32_t *)((char *)h->ws.p + b_probs + b_paths);
   return s->dtype == DM_F32 ? dr_recommend_dev_t<float>(h, d_seq, U, beam, topk, d_paths, d_probs, d_pc, d_ids, d_scores, d_counts)
                             : dr_recommend_dev_t<double>(h, d_seq, U, beam, topk, d_paths, d_probs, d_pc, d_ids, d_scores, d_counts);
 }
@@ -540,24 +520,23 @@ int dm_dr_recommend(dm_handle_t h, const int32_t *seq_ids, int64_t U, int beam, 
   dm_dr_state *s = h->dr;
   if ((rc = dr_check_ids(h, seq_ids, U * s->L)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t b_seq = (size_t)U * s->L * 4, b_ids = (size_t)U * topk * 4, b_sc = (size_t)U * topk * 8, b_cnt = (size_t)U * 4;
-  if ((rc = dr_grow(h, &s->d_io, &s->io_bytes, al(b_seq) + al(b_sc) + al(b_ids) + al(b_cnt))) != DM_OK) return rc;
-  char *base = (char *)s->d_io;
+  if ((rc = s->io.reserve(h, DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids) + DevArena::up(b_cnt))) != DM_OK) return rc;
+  char *base = (char *)s->io.p;
   int32_t *d_seq = (int32_t *)base;
-  double *d_sc = (double *)(base + al(b_seq));
-  int32_t *d_ids = (int32_t *)(base + al(b_seq) + al(b_sc));
-  int32_t *d_cnt = (int32_t *)(base + al(b_seq) + al(b_sc) + al(b_ids));
-  if (U <= 8 && h->direct_ok && al(b_seq) + al(b_sc) + al(b_ids) + al(b_cnt) <= (256u << 10)) {
+  double *d_sc = (double *)(base + DevArena::up(b_seq));
+  int32_t *d_ids = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_sc));
+  int32_t *d_cnt = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids));
+  if (U <= 8 && h->direct_ok && DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids) + DevArena::up(b_cnt) <= (256u << 10)) {
     // single requests (DeepRetrieval.recommend's serving loop, examples/.../dr/package.scala:107-111): request and results live in the
     // host-mapped pinned staging block — the kernels read and write it in place, no copy on either side of the three launches
     if ((rc = ensure_stage(h)) != DM_OK) return rc;
     char *hb = h->h_stage, *db = h->d_stage;      // the block as the host / the kernels address it
     memcpy(hb, seq_ids, b_seq);
-    double *m_sc = (double *)(hb + al(b_seq));
-    int32_t *m_ids = (int32_t *)(hb + al(b_seq) + al(b_sc)), *m_cnt = (int32_t *)(hb + al(b_seq) + al(b_sc) + al(b_ids));
-    if ((rc = dr_recommend_dev(h, (const int32_t *)db, U, beam, topk, (int32_t *)(db + al(b_seq) + al(b_sc)), (double *)(db + al(b_seq)),
-                               (int32_t *)(db + al(b_seq) + al(b_sc) + al(b_ids)))) != DM_OK) return rc;
+    double *m_sc = (double *)(hb + DevArena::up(b_seq));
+    int32_t *m_ids = (int32_t *)(hb + DevArena::up(b_seq) + DevArena::up(b_sc)), *m_cnt = (int32_t *)(hb + DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids));
+    if ((rc = dr_recommend_dev(h, (const int32_t *)db, U, beam, topk, (int32_t *)(db + DevArena::up(b_seq) + DevArena::up(b_sc)), (double *)(db + DevArena::up(b_seq)),
+                               (int32_t *)(db + DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids)))) != DM_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     memcpy(out_ids, m_ids, b_ids); memcpy(out_scores, m_sc, b_sc); memcpy(out_counts, m_cnt, b_cnt);
     return DM_OK;

@@ -31,23 +31,10 @@ struct LaunchTimer {
   int stop() { return (on && rc == DM_OK && hipEventRecord(e1, h->stream) != hipSuccess) ? fail(h, DM_ERR_HIP, "hipEventRecord failed") : rc; }
 };
 
-// ---- request arena: the device buffers of one host-buffer request, laid out in h->d_req (grow only: no hipMalloc / hipFree on the
-// request path once the handle has seen its largest request).  add() every buffer, commit(), then ptr<T>(offset).
-struct ReqArena {
-  size_t need = 0; char *base = nullptr;
-  size_t add(size_t bytes) { const size_t off = need; need += (bytes + 255) & ~(size_t)255; return off; }
-  int commit(dm_ctx *h) {
-    if (h->req_bytes < need) {
-      const size_t grown = need + need / 2;
-      dm_free_ptr(h->d_req); h->d_req = nullptr;
-      const int rc = dm_alloc(h, &h->d_req, grown);
-      h->req_bytes = rc == DM_OK ? grown : 0;
-      if (rc != DM_OK) return rc;
-    }
-    base = (char *)h->d_req;
-    return DM_OK;
-  }
-  template <typename T> T *ptr(size_t off) const { return (T *)(base + off); }
+// ---- request arena: the device buffers of one host-buffer request, laid out in h->req (grow only, by half again: no hipMalloc /
+// hipFree on the request path once the handle has seen its largest request).  add() every buffer, commit(), then ptr<T>(offset).
+struct ReqArena : DevArena {
+  explicit ReqArena(dm_ctx *h) : DevArena(h->req, 2) {}
 };
 
 // ---- one result array of a request: `bytes_per_user` bytes per user at `dev` (in the arena, or a per-call buffer) go to `host`
@@ -62,7 +49,7 @@ static hipError_t download_all(dm_ctx *h, const HostOut *outs, int n, int64_t U,
 
 // The pinned staging block (ensure_stage) mirrors the head of the arena: a buffer at arena offset o is staged at h_stage + o, and the
 // single-request kernels address it as d_stage + o.
-static char *stage_of(const dm_ctx *h, const void *dev) { return h->h_stage + ((const char *)dev - (const char *)h->d_req); }
+static char *stage_of(const dm_ctx *h, const void *dev) { return h->h_stage + ((const char *)dev - (const char *)h->req.p); }
 static void copy_from_stage(const dm_ctx *h, const HostOut *outs, int n, int64_t U) {
   for (int i = 0; i < n; i++) memcpy(outs[i].host, stage_of(h, outs[i].dev), outs[i].bytes_per_user * (size_t)U);
 }

@@ -165,28 +165,27 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
   float *d_out = nullptr, *d_w = nullptr;
   int *d_bad = nullptr;
   size_t cap_pairs = 0, cap_rows = 0, cap_items = 0;
-  int rc = DM_OK;
-  if ((rc = dm_alloc(h, (void **)&d_bad, 4)) != DM_OK) return rc;
+  // what this call allocates is t's; d_off / d_ritem / d_rids of a cached catalogue are the handle's and only pass through
+  DevTemps t(h);
+  int rc;
+  if ((rc = t.alloc(d_bad, 4)) != DM_OK) return rc;
   (void)hipMemsetAsync(d_bad, 0, 4, h->stream);
   // the cached catalogue's per-row history codes (non-hierarchical scoring): built once per cached catalogue and id map
   const bool per_row = cached && !hierarchical;
   if (per_row && (!h->d_jtm_rseq || h->jtm_rseq_ids_epoch != h->ids_epoch || h->jtm_rseq_num_index != h->num_index)) {      // (the codes were bounds-checked against THAT table)
     const int64_t Rall = h->jtm_off[(size_t)h->jtm_i_hi] - h->jtm_R_base;       // the rows on this device (dm_jtm_cache_rows_range)
-    dm_free_ptr(h->d_jtm_rseq); dm_free_ptr(h->d_jtm_rmask); h->d_jtm_rseq = nullptr; h->d_jtm_rmask = nullptr;
+    dm_release(h->d_jtm_rseq, h->d_jtm_rmask);
     if ((rc = dm_alloc(h, (void **)&h->d_jtm_rseq, (size_t)(Rall > 0 ? Rall : 1) * L * 4)) != DM_OK ||
-        (rc = dm_alloc(h, (void **)&h->d_jtm_rmask, (size_t)(Rall > 0 ? Rall : 1) * 4)) != DM_OK) { dm_free_ptr(d_bad); return rc; }
+        (rc = dm_alloc(h, (void **)&h->d_jtm_rmask, (size_t)(Rall > 0 ? Rall : 1) * 4)) != DM_OK) return rc;
     if (Rall > 0)
       hipLaunchKernelGGL(dm_jtm_rowseq_kernel, dim3((unsigned)((Rall + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->d_jtm_rids, Rall, L,
                          (const int32_t *)h->d_id_to_code, h->non_leaf_offset, h->max_code, h->num_index, h->d_jtm_rseq, h->d_jtm_rmask, d_bad);
     h->jtm_rseq_ids_epoch = h->ids_epoch; h->jtm_rseq_num_index = h->num_index;
   }
-  if (cached && n_items > 0 && (i_lo < h->jtm_i_lo || i_lo + n_items > h->jtm_i_hi)) {
-    dm_free_ptr(d_bad);
+  if (cached && n_items > 0 && (i_lo < h->jtm_i_lo || i_lo + n_items > h->jtm_i_hi))
     return fail(h, DM_ERR_STATE, "dm_jtm_child_weights: items outside the range whose rows this handle holds (dm_jtm_cache_rows_range)");
-  }
   const int64_t Rb = cached ? h->jtm_R_base : 0;          // row numbers are absolute, the cached arrays start at the range's first row
-  int64_t i0 = 0;
-  while (i0 < n_items && rc == DM_OK) {
+  for (int64_t i0 = 0; i0 < n_items;) {
     int64_t i1 = i0, pairs = 0;
     while (i1 < n_items) {
       const int64_t add = (row_off[i1 + 1] - row_off[i1]) * nchain;
@@ -194,29 +193,27 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
       pairs += add; i1++;
     }
     const int64_t ni = i1 - i0, R0 = row_off[i0], nrows = row_off[i1] - R0;
+    const size_t own_rows = cached ? 0 : (size_t)nrows;       // rows this call has to hold itself
     if ((size_t)ni > cap_items) {
-      if (!cached) { dm_free_ptr(d_off); d_off = nullptr; }
-      if (!resident) { dm_free_ptr(d_node); dm_free_ptr(d_w); }
-      d_node = nullptr; d_w = nullptr;
+      t.drop(d_off); t.drop(d_node); t.drop(d_w);
       cap_items = (size_t)ni;
-      if (!cached && (rc = dm_alloc(h, (void **)&d_off, (cap_items + 1) * 8)) != DM_OK) break;
-      if (!resident && (rc = dm_alloc(h, (void **)&d_node, cap_items * 4)) != DM_OK) break;
-      if (!resident && (rc = dm_alloc(h, (void **)&d_w, cap_items * nchild * 4)) != DM_OK) break;
+      if (!cached && (rc = t.alloc(d_off, (cap_items + 1) * 8)) != DM_OK) return rc;
+      if (!resident && (rc = t.alloc(d_node, cap_items * 4)) != DM_OK) return rc;
+      if (!resident && (rc = t.alloc(d_w, cap_items * nchild * 4)) != DM_OK) return rc;
     }
-    if (!cached && (size_t)nrows > cap_rows) {
-      dm_free_ptr(d_ritem); dm_free_ptr(d_rids); d_ritem = nullptr; d_rids = nullptr;
-      cap_rows = (size_t)nrows;
-      if ((rc = dm_alloc(h, (void **)&d_ritem, cap_rows * 4)) != DM_OK) break;
-      if ((rc = dm_alloc(h, (void **)&d_rids, cap_rows * L * 4)) != DM_OK) break;
+    if (own_rows > cap_rows) {
+      t.drop(d_ritem); t.drop(d_rids);
+      cap_rows = own_rows;
+      if ((rc = t.alloc(d_ritem, cap_rows * 4)) != DM_OK) return rc;
+      if ((rc = t.alloc(d_rids, cap_rows * L * 4)) != DM_OK) return rc;
     }
     if ((size_t)pairs > cap_pairs) {
-      dm_free_ptr(d_codes); dm_free_ptr(d_seqs); dm_free_ptr(d_mask); dm_free_ptr(d_out);
-      d_codes = d_seqs = nullptr; d_mask = nullptr; d_out = nullptr;
+      t.drop(d_codes); t.drop(d_seqs); t.drop(d_mask); t.drop(d_out);
       cap_pairs = (size_t)pairs;
-      if ((rc = dm_alloc(h, (void **)&d_codes, cap_pairs * 4)) != DM_OK) break;
-      if (!per_row && (rc = dm_alloc(h, (void **)&d_seqs, cap_pairs * L * 4)) != DM_OK) break;
-      if (!per_row && (rc = dm_alloc(h, (void **)&d_mask, cap_pairs * 4)) != DM_OK) break;
-      if ((rc = dm_alloc(h, (void **)&d_out, cap_pairs * 4)) != DM_OK) break;
+      if ((rc = t.alloc(d_codes, cap_pairs * 4)) != DM_OK) return rc;
+      if (!per_row && (rc = t.alloc(d_seqs, cap_pairs * L * 4)) != DM_OK) return rc;
+      if (!per_row && (rc = t.alloc(d_mask, cap_pairs * 4)) != DM_OK) return rc;
+      if ((rc = t.alloc(d_out, cap_pairs * 4)) != DM_OK) return rc;
     }
     hipError_t e = hipSuccess;
     if (cached) {
@@ -234,11 +231,11 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
     if (e == hipSuccess && !resident) e = hipMemcpyAsync(d_node, item_node + i0, (size_t)ni * 4, hipMemcpyHostToDevice, h->stream);
     const int32_t *d_node_use = resident ? d_item_node_all + i0 : d_node;
     float *d_w_use = resident ? d_weights_all + i0 * nchild : d_w;
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_jtm_child_weights: upload failed"); break; }
+    if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_jtm_child_weights: upload failed");
     if (pairs > 0 && per_row) {
       hipLaunchKernelGGL(dm_jtm_codes_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream, (const int64_t *)d_off, (const int32_t *)d_ritem,
                          (int32_t)(i_lo + i0), d_node_use, R0, nrows, gap, d_codes);
-      if ((rc = din_rows_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, use_mask ? h->d_jtm_rmask + (R0 - Rb) : nullptr, pairs, L, d_out, nchain)) != DM_OK) break;
+      if ((rc = din_rows_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, use_mask ? h->d_jtm_rmask + (R0 - Rb) : nullptr, pairs, L, d_out, nchain)) != DM_OK) return rc;
     } else if (pairs > 0) {
       JtmExpandParams p;
       p.row_off = d_off; p.row_item = d_ritem; p.item_base = cached ? (int32_t)(i_lo + i0) : 0; p.row_ids = d_rids; p.item_node = d_node_use;
@@ -248,28 +245,22 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
       p.non_leaf_offset = h->non_leaf_offset; p.max_code = h->max_code;
       p.codes = d_codes; p.seqs = d_seqs; p.rmask = d_mask; p.bad = d_bad;
       hipLaunchKernelGGL(dm_jtm_expand_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream, p);
-      if ((rc = din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, d_out)) != DM_OK) break;
+      if ((rc = din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, d_out)) != DM_OK) return rc;
     }
     hipLaunchKernelGGL(dm_jtm_sum_kernel, dim3((unsigned)((ni * nchild + 255) / 256)), dim3(256), 0, h->stream, d_off, R0, ni, gap, d_out, d_w_use);
     e = resident ? hipSuccess : hipMemcpyAsync(weights + i0 * nchild, d_w, (size_t)ni * nchild * 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);       // row_item (host staging) is reused by the next chunk
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, std::string("dm_jtm_child_weights: ") + hipGetErrorString(e)); break; }
+    if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("dm_jtm_child_weights: ") + hipGetErrorString(e));
     i0 = i1;
   }
-  if (rc == DM_OK) {
-    int bad = 0;
-    if (hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, DM_ERR_HIP, "dm_jtm_child_weights: readback failed");
-    else if (bad) {
-      // the per-row code cache was built with the offending positions cleared: drop it, so that a retry reports the same error instead of scoring them as pads
-      dm_free_ptr(h->d_jtm_rseq); dm_free_ptr(h->d_jtm_rmask); h->d_jtm_rseq = nullptr; h->d_jtm_rmask = nullptr; h->jtm_rseq_ids_epoch = 0;
-      rc = fail(h, DM_ERR_INDEX, "dm_jtm_child_weights: history code outside the embedding table");
-    }
+  int bad = 0;
+  if (hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DM_ERR_HIP, "dm_jtm_child_weights: readback failed");
+  if (bad) {
+    // the per-row code cache was built with the offending positions cleared: drop it, so that a retry reports the same error instead of scoring them as pads
+    dm_release(h->d_jtm_rseq, h->d_jtm_rmask); h->jtm_rseq_ids_epoch = 0;
+    return fail(h, DM_ERR_INDEX, "dm_jtm_child_weights: history code outside the embedding table");
   }
-  if (!cached) { dm_free_ptr(d_off); dm_free_ptr(d_ritem); dm_free_ptr(d_rids); }
-  if (!resident) { dm_free_ptr(d_node); dm_free_ptr(d_w); }
-  dm_free_ptr(d_codes); dm_free_ptr(d_seqs);
-  dm_free_ptr(d_mask); dm_free_ptr(d_out); dm_free_ptr(d_bad);
-  return rc;
+  return DM_OK;
 }
 
 int dm_jtm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *row_item_ids, const int32_t *item_node,
@@ -282,8 +273,7 @@ int dm_jtm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
 }
 
 static void jtm_drop_cache(dm_ctx *h) {
-  dm_free_ptr(h->d_jtm_off); dm_free_ptr(h->d_jtm_ritem); dm_free_ptr(h->d_jtm_rids); dm_free_ptr(h->d_jtm_rseq); dm_free_ptr(h->d_jtm_rmask);
-  h->d_jtm_off = nullptr; h->d_jtm_ritem = nullptr; h->d_jtm_rids = nullptr; h->d_jtm_rseq = nullptr; h->d_jtm_rmask = nullptr;
+  dm_release(h->d_jtm_off, h->d_jtm_ritem, h->d_jtm_rids, h->d_jtm_rseq, h->d_jtm_rmask);
   h->jtm_off.clear(); h->jtm_L = 0; h->jtm_i_lo = h->jtm_i_hi = h->jtm_R_base = 0;
 }
 
@@ -653,19 +643,19 @@ static int jtm_rebalance_all_staged(dm_ctx *h, const W *weights, const int32_t *
                                     int level, int max_assign, int32_t *out_node, const char *who) {
   HIPCHK(h, hipSetDevice(h->device));
   const int C = 1 << (level - old_level);
+  DevTemps t(h);
   char *A = nullptr;
-  const size_t bw = ((size_t)n * C * sizeof(W) + 255) & ~(size_t)255, bi = ((size_t)n * 4 + 255) & ~(size_t)255;
-  ALLOC(h, A, bw + 3 * bi);
+  const size_t bw = DevArena::up((size_t)n * C * sizeof(W)), bi = DevArena::up((size_t)n * 4);
+  int rc = t.alloc(A, bw + 3 * bi);
+  if (rc != DM_OK) return rc;
   W *d_w = (W *)A; int32_t *d_old = (int32_t *)(A + bw), *d_node = (int32_t *)(A + bw + bi), *d_out = (int32_t *)(A + bw + 2 * bi);
-  int rc = DM_OK;
   if (hipMemcpyAsync(d_w, weights, (size_t)n * C * sizeof(W), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(d_old, old_node, (size_t)n * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(d_node, item_node, (size_t)n * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-    rc = fail(h, DM_ERR_HIP, std::string(who) + ": upload failed");
-  if (rc == DM_OK) rc = jtm_rebalance_all_dev<W>(h, d_w, d_old, d_node, n, old_level, level, max_assign, d_out);
-  if (rc == DM_OK && hipMemcpy(out_node, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string(who) + ": download failed");
-  dm_free_ptr(A);
-  return rc;
+    return fail(h, DM_ERR_HIP, std::string(who) + ": upload failed");
+  if ((rc = jtm_rebalance_all_dev<W>(h, d_w, d_old, d_node, n, old_level, level, max_assign, d_out)) != DM_OK) return rc;
+  if (hipMemcpy(out_node, d_out, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return fail(h, DM_ERR_HIP, std::string(who) + ": download failed");
+  return DM_OK;
 }
 int dm_jtm_rebalance_all(dm_handle_t h, const float *weights, const int32_t *old_node, const int32_t *item_node, int64_t n,
                          int old_level, int level, int max_assign, int32_t *out_node) {
@@ -691,11 +681,12 @@ int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *o
   if (n_items == 0) return DM_OK;
   HIPCHK(h, hipSetDevice(h->device));
   const int C = 1 << (level - old_level);
+  DevTemps t(h);
   char *A = nullptr;
-  const size_t bw = ((size_t)n_items * C * 4 + 255) & ~(size_t)255, bi = ((size_t)n_items * 4 + 255) & ~(size_t)255;
-  ALLOC(h, A, bw + 3 * bi);
+  const size_t bw = DevArena::up((size_t)n_items * C * 4), bi = DevArena::up((size_t)n_items * 4);
+  int rc = t.alloc(A, bw + 3 * bi);
+  if (rc != DM_OK) return rc;
   float *d_w = (float *)A; int32_t *d_old = (int32_t *)(A + bw), *d_node = (int32_t *)(A + bw + bi), *d_out = (int32_t *)(A + bw + 2 * bi);
-  int rc = DM_OK;
   if (hipMemcpyAsync(d_old, old_node, (size_t)n_items * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(d_node, item_node, (size_t)n_items * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess)
     rc = fail(h, DM_ERR_HIP, "dm_jtm_step_cached: upload failed");
@@ -717,7 +708,6 @@ int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *o
       else rc = jtm_rebalance_all_t<float>(h, w.data(), old_node, item_node, n_items, old_level, level, max_assign, out_node, "dm_jtm_step_cached");
     }
   }
-  dm_free_ptr(A);
   return rc;
 }
 
@@ -779,9 +769,9 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
   unsigned *d_mask = nullptr;
   void *d_out = nullptr;
   size_t cap_pairs = 0;
+  DevTemps t(h);
   int rc = DM_OK;
-  int64_t i0 = 0;
-  while (i0 < n_items && rc == DM_OK) {
+  for (int64_t i0 = 0; i0 < n_items;) {
     int64_t i1 = i0, pairs = 0;
     while (i1 < n_items) {
       const int64_t add = (row_off[i1 + 1] - row_off[i1]) * nchain;
@@ -809,29 +799,28 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
           }
       }
     }
-    if (rc != DM_OK) break;
+    if (rc != DM_OK) return rc;
     if (pairs > 0) {
       if ((size_t)pairs > cap_pairs) {
-        dm_free_ptr(d_codes); dm_free_ptr(d_seqs); dm_free_ptr(d_mask); dm_free_ptr(d_out);
-        d_codes = d_seqs = nullptr; d_mask = nullptr; d_out = nullptr;
+        t.drop(d_codes); t.drop(d_seqs); t.drop(d_mask); t.drop(d_out);
         cap_pairs = (size_t)pairs;
-        if ((rc = dm_alloc(h, (void **)&d_codes, cap_pairs * 4)) != DM_OK) break;
-        if ((rc = dm_alloc(h, (void **)&d_seqs, cap_pairs * L * 4)) != DM_OK) break;
-        if ((rc = dm_alloc(h, (void **)&d_mask, cap_pairs * 4)) != DM_OK) break;
-        if ((rc = dm_alloc(h, &d_out, cap_pairs * esz)) != DM_OK) break;
+        if ((rc = t.alloc(d_codes, cap_pairs * 4)) != DM_OK) return rc;
+        if ((rc = t.alloc(d_seqs, cap_pairs * L * 4)) != DM_OK) return rc;
+        if ((rc = t.alloc(d_mask, cap_pairs * 4)) != DM_OK) return rc;
+        if ((rc = t.alloc(d_out, cap_pairs * esz)) != DM_OK) return rc;
       }
       hipError_t e = hipMemcpyAsync(d_codes, codes.data(), (size_t)pairs * 4, hipMemcpyHostToDevice, h->stream);
       if (e == hipSuccess) e = hipMemcpyAsync(d_seqs, seqs.data(), (size_t)pairs * L * 4, hipMemcpyHostToDevice, h->stream);
       if (e == hipSuccess) e = hipMemcpyAsync(d_mask, rmask.data(), (size_t)pairs * 4, hipMemcpyHostToDevice, h->stream);
-      if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_otm_child_weights: upload failed"); break; }
+      if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_otm_child_weights: upload failed");
       if (f64) rc = din_forward_t<double>(h, d_codes, d_seqs, d_mask, pairs, L, (double *)d_out);
       else rc = L <= DM_MAXL ? din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, (float *)d_out)
                              : din_forward_t<float>(h, d_codes, d_seqs, d_mask, pairs, L, (float *)d_out);
-      if (rc != DM_OK) break;
+      if (rc != DM_OK) return rc;
       if (f64) e = hipMemcpyAsync(logits.data(), d_out, (size_t)pairs * 8, hipMemcpyDeviceToHost, h->stream);
       else { logits32.resize(pairs); e = hipMemcpyAsync(logits32.data(), d_out, (size_t)pairs * 4, hipMemcpyDeviceToHost, h->stream); }
       if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-      if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, std::string("dm_otm_child_weights: ") + hipGetErrorString(e)); break; }
+      if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("dm_otm_child_weights: ") + hipGetErrorString(e));
       if (!f64) for (int64_t k = 0; k < pairs; k++) logits[k] = (double)logits32[k];
     }
     q = 0;
@@ -853,6 +842,5 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
     }
     i0 = i1;
   }
-  dm_free_ptr(d_codes); dm_free_ptr(d_seqs); dm_free_ptr(d_mask); dm_free_ptr(d_out);
-  return rc;
+  return DM_OK;
 }

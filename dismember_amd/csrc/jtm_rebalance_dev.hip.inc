@@ -205,18 +205,18 @@ static int jtm_rebalance_all_dev(dm_ctx *h, const W *d_w, const int32_t *d_old_n
   s.lo = (int32_t)(((int64_t)1 << old_level) - 1); s.P = (int64_t)1 << old_level;
   // one arena: state + double-buffered order / keys / flags + the count arrays of the select / sort passes
   size_t tmp_bytes = dev_sort_scratch_bytes(n);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += up(bytes); return o; };
+  auto take = [&](size_t bytes) { size_t o = off; off += DevArena::up(bytes); return o; };
   const size_t o_cand = take((size_t)n * C), o_cur = take((size_t)n * 2), o_kidx = take((size_t)n * 2), o_sizes = take((size_t)s.P * C * 4),
                o_proc = take((size_t)s.P * s.PW * 4), o_bc = take((size_t)s.P * 2), o_cnt = take(64), o_ord0 = take((size_t)n * 4), o_ord1 = take((size_t)n * 4),
                o_flag = take((size_t)n), o_key = take((size_t)n * 8), o_ckey = take((size_t)n * 8), o_citem = take((size_t)n * 4),
                o_skey = take((size_t)n * 8), o_sitem = take((size_t)n * 4), o_seg = take((size_t)s.P * 8), o_oflag = take((size_t)n),
                o_stay = take((size_t)n), o_ovf = take((size_t)n * 4), o_tmp = take(tmp_bytes);
   char *A = nullptr;
-  ALLOC(h, A, off);
-  int rc = DM_OK;
-  auto fin = [&](int r) { (void)hipStreamSynchronize(h->stream); dm_free_ptr(A); return r; };
+  DevTemps t(h);
+  int rc = t.alloc(A, off);
+  if (rc != DM_OK) return rc;
+  auto fin = [&](int r) { (void)hipStreamSynchronize(h->stream); return r; };
   s.cand = (uint8_t *)(A + o_cand); s.cur = (int16_t *)(A + o_cur); s.kidx = (uint16_t *)(A + o_kidx); s.sizes = (int32_t *)(A + o_sizes);
   s.processed = (uint32_t *)(A + o_proc); s.bc = (int16_t *)(A + o_bc); s.counters = (unsigned long long *)(A + o_cnt);
   int32_t *ord[2] = {(int32_t *)(A + o_ord0), (int32_t *)(A + o_ord1)};

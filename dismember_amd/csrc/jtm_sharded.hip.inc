@@ -121,23 +121,23 @@ static int jtm_optimize_impl(dm_ctx *h, const int32_t *item_code, int64_t n_item
     if (item_code[i] < 0) return fail(h, DM_ERR_INVALID, "dm_jtm_optimize_cached: negative item code");
   HIPCHK(h, hipSetDevice(h->device));
   const int Cmax = 1 << gap;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   char *A = nullptr;
-  const size_t bw = up((size_t)n_items * Cmax * 4), bi = up((size_t)n_items * 4);
+  const size_t bw = DevArena::up((size_t)n_items * Cmax * 4), bi = DevArena::up((size_t)n_items * 4);
   // sharded runs add: owner flags [n], (item, node) pairs of this rank [2n] and of all ranks [2n], select scratch
   size_t tmp_sel = 0;
   if (W > 1) tmp_sel = dev_sort_scratch_bytes(n_items);
-  const size_t extra = W > 1 ? up((size_t)n_items) + 4 * bi + up(tmp_sel) + 256 : 0;
+  const size_t extra = W > 1 ? DevArena::up((size_t)n_items) + 4 * bi + DevArena::up(tmp_sel) + 256 : 0;
   // (a rank-local failure from here to the first gap step is AGREED below before anybody enters a collective: returning at once would
   //  leave the peers waiting in the first step's agreement)
-  int rc = dm_alloc(h, (void **)&A, bw + 4 * bi + extra);
+  DevTemps t(h);
+  int rc = t.alloc(A, bw + 4 * bi + extra);
   float *d_w = (float *)A;
   int32_t *d_code = (int32_t *)(A + bw), *d_old = (int32_t *)(A + bw + bi), *d_proj = (int32_t *)(A + bw + 2 * bi), *d_next = (int32_t *)(A + bw + 3 * bi);
   char *X = A + bw + 4 * bi;
   uint8_t *d_flag = (uint8_t *)X;
-  int32_t *d_pack = (int32_t *)(X + up((size_t)n_items)), *d_all = (int32_t *)(X + up((size_t)n_items) + 2 * bi);
-  void *d_tmp = X + up((size_t)n_items) + 4 * bi;
-  unsigned long long *d_cnt = (unsigned long long *)(X + up((size_t)n_items) + 4 * bi + up(tmp_sel));
+  int32_t *d_pack = (int32_t *)(X + DevArena::up((size_t)n_items)), *d_all = (int32_t *)(X + DevArena::up((size_t)n_items) + 2 * bi);
+  void *d_tmp = X + DevArena::up((size_t)n_items) + 4 * bi;
+  unsigned long long *d_cnt = (unsigned long long *)(X + DevArena::up((size_t)n_items) + 4 * bi + DevArena::up(tmp_sel));
   char *B = nullptr;                 // compact copies of this rank's parents' items (node-sharded steps), grown on demand
   size_t b_cap = 0;
   double t_sc = 0, t_rb = 0, t_ex = 0;
@@ -195,11 +195,11 @@ static int jtm_optimize_impl(dm_ctx *h, const int32_t *item_code, int64_t n_item
         lrc = fail(h, DM_ERR_HIP, "dm_jtm_optimize_cached: item selection failed");
       const int64_t m = lrc == DM_OK ? (int64_t)hm : 0;
       if (lrc == DM_OK && m > 0) {
-        const size_t need = up((size_t)m * C * 4) + 2 * up((size_t)m * 4);
-        if (need > b_cap) { dm_free_ptr(B); B = nullptr; b_cap = 0; if ((lrc = dm_alloc(h, (void **)&B, need + need / 4)) == DM_OK) b_cap = need + need / 4; }
+        const size_t need = DevArena::up((size_t)m * C * 4) + 2 * DevArena::up((size_t)m * 4);
+        if (need > b_cap) { t.drop(B); b_cap = 0; if ((lrc = t.alloc(B, need + need / 4)) == DM_OK) b_cap = need + need / 4; }
         if (lrc == DM_OK) {
           float *c_w = (float *)B;
-          int32_t *c_old = (int32_t *)(B + up((size_t)m * C * 4)), *c_node = (int32_t *)(B + up((size_t)m * C * 4) + up((size_t)m * 4));
+          int32_t *c_old = (int32_t *)(B + DevArena::up((size_t)m * C * 4)), *c_node = (int32_t *)(B + DevArena::up((size_t)m * C * 4) + DevArena::up((size_t)m * 4));
           hipLaunchKernelGGL(jtm_compact_kernel, dim3(2048), dim3(256), 0, h->stream, (const int32_t *)d_pack, m, C, (const float *)d_w, (const int32_t *)d_old,
                              (const int32_t *)d_proj, c_w, c_old, c_node);
           lrc = jtm_rebalance_all_dev(h, c_w, c_old, c_node, m, old_level, level, max_assign, d_pack + m);
@@ -230,7 +230,6 @@ static int jtm_optimize_impl(dm_ctx *h, const int32_t *item_code, int64_t n_item
   }
   if (rc == DM_OK && hipMemcpy(out_proj, d_proj, (size_t)n_items * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(h, DM_ERR_HIP, "dm_jtm_optimize_cached: download failed");
   (void)hipStreamSynchronize(h->stream);
-  dm_free_ptr(A); dm_free_ptr(B);
   h->jtm_score_s = t_sc; h->jtm_rebal_s = t_rb;
   st.scoring_s = t_sc; st.rebalance_s = t_rb; st.exchange_s = t_ex;
   if (step_seconds) { step_seconds[0] = t_sc; step_seconds[1] = t_rb; }

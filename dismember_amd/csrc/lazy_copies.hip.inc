@@ -27,7 +27,7 @@ struct LazyCopies {
 
   void loaded() { split_dirty = true; table_dense_change = true; }
   void released() {
-    for (void **p : {&d_wsplit, (void **)&d_maxabs, &d_emb_split, &d_rows_split, &d_frag64}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    dm_release(d_wsplit, d_maxabs, d_emb_split, d_rows_split, d_frag64);
     emb_split_bytes = 0; table_dense_change = true; sh_e_valid = false; emb_split_need_full = true;
     split_dirty = true; rows_split_dirty = true; frag64_dirty = true; f32_mirror_dirty = false;
   }
@@ -208,7 +208,7 @@ static int ensure_split(dm_ctx *h) {
   // or in the active rows only when nothing else can have moved
   const size_t bytes = (size_t)h->num_index * E * 4;
   if (z.emb_split_bytes != bytes) {
-    dm_free_ptr(z.d_emb_split); z.d_emb_split = nullptr; z.emb_split_bytes = 0;
+    dm_release(z.d_emb_split); z.emb_split_bytes = 0;
     ALLOC(h, z.d_emb_split, bytes);
     z.emb_split_bytes = bytes;
     z.emb_split_need_full = true;

@@ -99,7 +99,7 @@ static int load_weights_host(dm_ctx *h, int dtype, int E, int64_t num_index, con
   free_weights(h);      // before the new vector is allocated: a reload never holds two models on the device
   void *d = nullptr;
   ALLOC(h, d, bytes);
-  if (hipMemcpy(d, w, bytes, hipMemcpyHostToDevice) != hipSuccess) { dm_free_ptr(d); return fail(h, DM_ERR_HIP, "dm_load_weights_din: upload failed"); }
+  if (hipMemcpy(d, w, bytes, hipMemcpyHostToDevice) != hipSuccess) { dm_release(d); return fail(h, DM_ERR_HIP, "dm_load_weights_din: upload failed"); }
   return install_weights(h, dtype, Ep, E, num_index, d);
 }
 

@@ -280,11 +280,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   const int grid = (int)(groups < h->n_cu ? groups : (int64_t)h->n_cu);
   const size_t per_team = ((size_t)kt * (E / 4) * 64 + (size_t)kt * 4 * (E / 16) * 64 + (size_t)fcap / 2 + (size_t)pcap) * 8;
   const size_t need = (size_t)h->n_cu * 12 * per_team;
-  if (h->scratch64_bytes < need) {
-    dm_free_ptr(h->d_scratch64); h->d_scratch64 = nullptr; h->scratch64_bytes = 0;
-    ALLOC(h, h->d_scratch64, need);
-    h->scratch64_bytes = need;
-  }
+  if ((rc = h->scratch64.reserve(h, need)) != DM_OK) return rc;
   const double *base = (const double *)h->d_compact;
   const size_t n = (size_t)E * E;
   const double *l1_b = base + h->num_index * E + 3 * n, *l2_w = l1_b + E;
@@ -303,7 +299,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   p.seq = d_seq; p.U = U; p.L = L; p.beam = beam; p.leaf_level = leaf_level; p.nteams = nteams; p.cap = fcap; p.pcap = pcap;
   p.out_ids = d_ids; p.out_sc64 = d_sc64; p.out_sc32 = d_sc32; p.out_counts = d_counts; p.out_stride = 2 * beam;
   p.tr_codes = d_tc; p.tr_sc64 = d_ts64; p.tr_sc32 = d_ts32; p.tr_counts = d_tn; p.tr_levels = d_tn ? max_levels : 0; p.tr_cap = cap;
-  p.scratch = (double *)h->d_scratch64; p.next_user = h->d_rows + 1; p.scored_rows = (p.static_users && U <= 64) ? h->d_rows + 3 : h->d_rows;
+  p.scratch = (double *)h->scratch64.p; p.next_user = h->d_rows + 1; p.scored_rows = (p.static_users && U <= 64) ? h->d_rows + 3 : h->d_rows;
   rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) { return launch_beam64_E<decltype(e)::value>(h, p, grid, lds); });
   if (rc == DM_OK) *done = true;
   return rc;
@@ -337,18 +333,12 @@ static int otm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, i
   if (Uc > U) Uc = U;
   const size_t b_codes = (size_t)Uc * stride * 4, b_sc = (size_t)Uc * stride * sizeof(T), b_h1 = (size_t)Uc * stride * E * sizeof(T);
   const size_t b_t1 = (size_t)Uc * L * E * sizeof(T);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t need = 2 * up(b_codes) + up(b_sc) + up(b_h1) + 2 * up(b_t1) + 256;
-  int rc = ensure_ws(h, need);
+  DevArena ar(h->ws);
+  const size_t o_c0 = ar.add(b_codes), o_c1 = ar.add(b_codes), o_sc = ar.add(b_sc), o_h1 = ar.add(b_h1), o_t1 = ar.add(b_t1), o_g = ar.add(b_t1), o_zero = ar.add(256);
+  int rc = ar.commit(h);
   if (rc != DM_OK) return rc;
-  char *w = (char *)h->d_ws;
-  int32_t *c0 = (int32_t *)w; w += up(b_codes);
-  int32_t *c1 = (int32_t *)w; w += up(b_codes);
-  T *sc = (T *)w; w += up(b_sc);
-  T *H1 = (T *)w; w += up(b_h1);
-  T *T1 = (T *)w; w += up(b_t1);
-  T *G = (T *)w; w += up(b_t1);
-  T *zero = (T *)w;
+  int32_t *c0 = ar.ptr<int32_t>(o_c0), *c1 = ar.ptr<int32_t>(o_c1);
+  T *sc = ar.ptr<T>(o_sc), *H1 = ar.ptr<T>(o_h1), *T1 = ar.ptr<T>(o_t1), *G = ar.ptr<T>(o_g), *zero = ar.ptr<T>(o_zero);
   HIPCHK(h, hipMemsetAsync(zero, 0, 256, h->stream));
   int pcap = 2;
   while (pcap < stride) pcap <<= 1;
@@ -445,7 +435,7 @@ static int otm64_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int
   frontier_caps(beam, &cap, nullptr);
   const size_t stride = (size_t)2 * beam, ssz = out_sc64 ? 8 : 4, tsz = ts64 ? 8 : 4, b_seq = (size_t)U * L * 4, nt = tn ? (size_t)U * max_levels : 0;
   // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
-  ReqArena ar;
+  ReqArena ar(h);
   const size_t o_seq = ar.add(b_seq), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * ssz), o_cnt = ar.add((size_t)U * 4), o_end = ar.need;
   const size_t o_tc = ar.add(nt * cap * 4), o_ts = ar.add(nt * cap * tsz), o_tn = ar.add(nt * 4);
   if ((rc = ar.commit(h)) != DM_OK) return rc;

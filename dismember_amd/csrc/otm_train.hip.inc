@@ -249,18 +249,17 @@ static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, 
   std::vector<int> n_lv((size_t)levels);
   int nprev = start + 1, n_max = 0;
   for (int it = 0; it < levels; it++) { const int nb = it == 0 ? nprev : std::min(o->beam, nprev); n_lv[(size_t)it] = 2 * nb; nprev = 2 * nb; n_max = std::max(n_max, 2 * nb); }
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t tsz = f64_search ? 8 : 4;
   const OtmTgtArena ar = otm_tgt_arena(U, L, NT, levels);
   size_t off = ar.end;
-  auto take = [&](size_t bytes) { size_t o_ = off; off += up(bytes); return o_; };
+  auto take = [&](size_t bytes) { size_t o_ = off; off += DevArena::up(bytes); return o_; };
   const size_t o_tc = take((size_t)U * levels * cap * 4), o_ts = take((size_t)U * levels * cap * tsz), o_tn = take((size_t)U * levels * 4),
                o_ids = take((size_t)U * 2 * o->beam * 4), o_sc = take((size_t)U * 2 * o->beam * 8), o_cnt = take((size_t)U * 4),
                o_bcodes = take((size_t)U * n_max * 4), o_bseq = take((size_t)U * n_max * L * 4), o_bmask = take((size_t)U * n_max * 4),
                o_blab = take((size_t)U * n_max * 4);
   char *A = nullptr;
-  ALLOC(h, A, off);
-  struct Free { char *p; ~Free() { dm_free_ptr(p); } } free_{A};
+  DevTemps t(h);
+  if ((rc = t.alloc(A, off)) != DM_OK) return rc;
   int32_t *d_seq = (int32_t *)(A + ar.o_seq);
   unsigned *d_umask = (unsigned *)(A + ar.o_umask);
   int64_t *d_toff = (int64_t *)(A + ar.o_toff);
@@ -370,8 +369,8 @@ int dm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, in
   HIPCHK(h, hipSetDevice(h->device));
   const OtmTgtArena ar = otm_tgt_arena(U, L, NT, levels);
   char *A = nullptr;
-  ALLOC(h, A, ar.end);
-  struct Free { char *p; ~Free() { dm_free_ptr(p); } } free_{A};
+  DevTemps t(h);
+  if ((rc = t.alloc(A, ar.end)) != DM_OK) return rc;
   if ((rc = otm_targets_dev(h, A, ar, seq_codes, L, target_off, target_nodes, o, nullptr)) != DM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(out_nodes, A + ar.o_tnode, (size_t)levels * ar.NTc * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(out_labels, A + ar.o_tlab, (size_t)levels * ar.NTc * 8, hipMemcpyDeviceToHost, h->stream));

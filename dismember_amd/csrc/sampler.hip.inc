@@ -204,9 +204,8 @@ int dm_tdm_set_node_probs(dm_handle_t h, const int32_t *codes, const float *prob
     for (size_t k = first; k < lc.size(); k++) { acc += (double)prob_of[lc[k]] / sum; cdf.push_back(acc); }
   }
   st[h->max_level + 1] = (int64_t)lc.size();
-  dm_free_ptr(h->d_lv_codes); dm_free_ptr(h->d_lv_cdf); dm_free_ptr(h->d_lv_start);
+  dm_release(h->d_lv_codes, h->d_lv_cdf, h->d_lv_start);
   model_changed(h);
-  h->d_lv_codes = nullptr; h->d_lv_cdf = nullptr; h->d_lv_start = nullptr;
   ALLOC(h, h->d_lv_codes, lc.size() * 4);
   ALLOC(h, h->d_lv_cdf, cdf.size() * 8);
   ALLOC(h, h->d_lv_start, st.size() * 8);
@@ -259,21 +258,14 @@ static int sample_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int
   for (int l = 0; l < nl; l++) { neg[l] = neg_counts[l]; if (l >= o->start_level && neg[l] > negmax) negmax = neg[l]; }
   for (int l = 0; l < nl; l++) lvl_off[l + 1] = lvl_off[l] + (l >= o->start_level ? 1 + neg[l] : 0);
   // small per-call device state: [neg | lvl_off | tcode[T] | cnt[T] | off[T + 1]]
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t b_neg = up(nl * 4), b_off = up((nl + 1) * 4), b_tc = up((size_t)T * 4 + 4), b_cnt = up((size_t)T * 8 + 8), b_ro = up((size_t)(T + 1) * 8);
-  const size_t need = b_neg + b_off + b_tc + b_cnt + b_ro;
-  if (h->samp_bytes < need) {
-    dm_free_ptr(h->d_samp); h->d_samp = nullptr; h->samp_bytes = 0;
-    ALLOC(h, h->d_samp, need + need / 2);
-    h->samp_bytes = need + need / 2;
-  }
-  char *w = (char *)h->d_samp;
+  DevArena ar(h->samp, 2);
+  const size_t o_neg = ar.add(nl * 4), o_off = ar.add((nl + 1) * 4), o_tc = ar.add((size_t)T * 4 + 4), o_cnt = ar.add((size_t)T * 8 + 8), o_ro = ar.add((size_t)(T + 1) * 8);
+  const int rc_a = ar.commit(h);
+  if (rc_a != DM_OK) return rc_a;
   SampleParams p{};
-  p.neg = (const int32_t *)w; w += b_neg;
-  p.lvl_off = (const int32_t *)w; w += b_off;
-  p.tcode = (int32_t *)w; w += b_tc;
-  int64_t *d_cnt = (int64_t *)w; w += b_cnt;
-  p.row_off = (int64_t *)w;
+  p.neg = ar.ptr<const int32_t>(o_neg); p.lvl_off = ar.ptr<const int32_t>(o_off); p.tcode = ar.ptr<int32_t>(o_tc);
+  int64_t *d_cnt = ar.ptr<int64_t>(o_cnt);
+  p.row_off = ar.ptr<int64_t>(o_ro);
   HIPCHK(h, hipMemcpyAsync((void *)p.neg, neg.data(), nl * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync((void *)p.lvl_off, lvl_off.data(), (nl + 1) * 4, hipMemcpyHostToDevice, h->stream));
   p.seq_ids = d_seq; p.tgt_ids = d_tgt; p.T = T; p.L = L; p.start_level = o->start_level; p.max_level = h->max_level;
@@ -335,27 +327,25 @@ int dm_tdm_make_train_batch(dm_handle_t h, const int32_t *seq_item_ids, const in
   int32_t *d_seq = nullptr, *d_tgt = nullptr, *d_codes = nullptr, *d_seqs = nullptr;
   uint32_t *d_mask = nullptr;
   float *d_lab = nullptr;
-  do {
-    if ((rc = dm_alloc(h, (void **)&d_seq, (size_t)T * L * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_tgt, (size_t)T * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_codes, (size_t)R * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_seqs, (size_t)R * L * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_mask, (size_t)R * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_lab, (size_t)R * 4)) != DM_OK) break;
-    hipError_t e = hipMemcpyAsync(d_seq, seq_item_ids, (size_t)T * L * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tgt, target_item_ids, (size_t)T * 4, hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_tdm_make_train_batch: upload failed"); break; }
-    int64_t n = 0;
-    if ((rc = sample_dev(h, d_seq, d_tgt, T, L, neg_counts, opts, d_codes, d_seqs, d_mask, d_lab, R, &n)) != DM_OK) break;
-    if (n > 0) {
-      e = hipMemcpy(out_codes, d_codes, (size_t)n * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(out_seqs, d_seqs, (size_t)n * L * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(out_rowmask, d_mask, (size_t)n * 4, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(out_labels, d_lab, (size_t)n * 4, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_tdm_make_train_batch: download failed"); break; }
-    }
-    *n_rows = n;
-  } while (0);
-  dm_free_ptr(d_seq); dm_free_ptr(d_tgt); dm_free_ptr(d_codes); dm_free_ptr(d_seqs); dm_free_ptr(d_mask); dm_free_ptr(d_lab);
+  DevTemps t(h);
+  if ((rc = t.alloc(d_seq, (size_t)T * L * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_tgt, (size_t)T * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_codes, (size_t)R * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_seqs, (size_t)R * L * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_mask, (size_t)R * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_lab, (size_t)R * 4)) != DM_OK) return rc;
+  hipError_t e = hipMemcpyAsync(d_seq, seq_item_ids, (size_t)T * L * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tgt, target_item_ids, (size_t)T * 4, hipMemcpyHostToDevice, h->stream);
+  if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_tdm_make_train_batch: upload failed");
+  int64_t n = 0;
+  if ((rc = sample_dev(h, d_seq, d_tgt, T, L, neg_counts, opts, d_codes, d_seqs, d_mask, d_lab, R, &n)) != DM_OK) return rc;
+  if (n > 0) {
+    e = hipMemcpy(out_codes, d_codes, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_seqs, d_seqs, (size_t)n * L * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_rowmask, d_mask, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_labels, d_lab, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_tdm_make_train_batch: download failed");
+  }
+  *n_rows = n;
   return rc;
 }

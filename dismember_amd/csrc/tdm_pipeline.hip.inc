@@ -220,13 +220,11 @@ __global__ __launch_bounds__(256) void tdm_pl_final_kernel(TdmPlFinal p) {
 // the pass's workspace.  The fold below owns the integer logic and never looks inside.
 struct TdmPlScorer {
   virtual ~TdmPlScorer() {}
-  virtual size_t ws_bytes(int64_t Uc, int stride, int L) const = 0;
-  virtual int attach(dm_ctx *h, char *ws, int64_t Uc, int stride, int L) = 0;      // carve the workspace; once per call, before any pass
+  virtual void layout(DevArena &ar, int64_t Uc, int stride, int L) = 0;            // add() the scorer's arrays to the pass's workspace
+  virtual int attach(dm_ctx *h, const DevArena &ar) = 0;                           // after commit(); once per call, before any pass
   virtual int setup(dm_ctx *h, const int32_t *kcode, int64_t Un) = 0;              // kcode [Un][L]: history codes, -1 = a zero row
   virtual int score(dm_ctx *h, const int32_t *cur, const int32_t *ncur, float *sc, int64_t Un) = 0;
 };
-
-static size_t tdm_pl_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // The per-user restructured DIN of DESIGN.md §3 in plain fp32 (histories of 17 .. 32 positions): T1 = K att.W^T, G = T1 W1b^T + b1 per
 // user; per level H1 = Q W1a^T over the children (gather GEMM), then attention + epilogue per row (otm64_attn_kernel<float>)
@@ -235,18 +233,16 @@ struct TdmPlDin : TdmPlScorer {
   const float *base = nullptr, *att_w = nullptr, *l1_w = nullptr, *l1_b = nullptr, *l2_w = nullptr;
   const int32_t *kcode = nullptr;
   float *H1 = nullptr, *T1 = nullptr, *G = nullptr, *zero = nullptr;
+  size_t o_h1 = 0, o_t1 = 0, o_g = 0, o_zero = 0;
   TdmPlDin(const dm_ctx *h, int use_mask_) : use_mask(use_mask_), E(h->embed) {}
-  size_t ws_bytes(int64_t Uc, int stride_, int L_) const override {
-    return tdm_pl_up((size_t)Uc * stride_ * E * 4) + 2 * tdm_pl_up((size_t)Uc * L_ * E * 4) + 256;
-  }
-  int attach(dm_ctx *h, char *w, int64_t Uc, int stride_, int L_) override {
+  void layout(DevArena &ar, int64_t Uc, int stride_, int L_) override {
     L = L_; stride = stride_;
+    o_h1 = ar.add((size_t)Uc * stride * E * 4); o_t1 = ar.add((size_t)Uc * L * E * 4); o_g = ar.add((size_t)Uc * L * E * 4); o_zero = ar.add(256);
+  }
+  int attach(dm_ctx *h, const DevArena &ar) override {
     base = (const float *)h->d_compact;
     att_w = base + h->num_index * E; l1_w = att_w + (int64_t)E * E; l1_b = l1_w + (int64_t)2 * E * E; l2_w = l1_b + E;
-    H1 = (float *)w; w += tdm_pl_up((size_t)Uc * stride * E * 4);
-    T1 = (float *)w; w += tdm_pl_up((size_t)Uc * L * E * 4);
-    G = (float *)w; w += tdm_pl_up((size_t)Uc * L * E * 4);
-    zero = (float *)w;
+    H1 = ar.ptr<float>(o_h1); T1 = ar.ptr<float>(o_t1); G = ar.ptr<float>(o_g); zero = ar.ptr<float>(o_zero);
     HIPCHK(h, hipMemsetAsync(zero, 0, 256, h->stream));
     return DM_OK;
   }
@@ -290,24 +286,18 @@ static int tdm_pl_fold(dm_ctx *h, TdmPlScorer &scorer, const int32_t *d_seq, int
   int64_t Uc = ((int64_t)1 << 30) / ((int64_t)stride * E * 4);
   if (Uc < 1) Uc = 1;
   if (Uc > U) Uc = U;
-  const size_t b_k = tdm_pl_up((size_t)Uc * L * 4), b_codes = tdm_pl_up((size_t)Uc * stride * 4), b_cnt = tdm_pl_up((size_t)Uc * 4);
-  const size_t b_lf = tdm_pl_up((size_t)Uc * lcap * 4);
-  const size_t need = b_k + 3 * b_codes + 3 * b_cnt + 5 * b_lf + scorer.ws_bytes(Uc, stride, L);
-  int rc = ensure_ws(h, need);
+  const size_t b_k = (size_t)Uc * L * 4, b_codes = (size_t)Uc * stride * 4, b_cnt = (size_t)Uc * 4, b_lf = (size_t)Uc * lcap * 4;
+  DevArena ar(h->ws);
+  const size_t o_k = ar.add(b_k), o_c0 = ar.add(b_codes), o_c1 = ar.add(b_codes), o_sc = ar.add(b_codes), o_n0 = ar.add(b_cnt), o_n1 = ar.add(b_cnt),
+               o_lfn = ar.add(b_cnt), o_lfc = ar.add(b_lf), o_lfs = ar.add(b_lf), o_lfp = ar.add(b_lf), o_lfk = ar.add(2 * DevArena::up(b_lf));
+  scorer.layout(ar, Uc, stride, L);
+  int rc = ar.commit(h);
   if (rc != DM_OK) return rc;
-  char *w = (char *)h->d_ws;
-  int32_t *kcode = (int32_t *)w; w += b_k;
-  int32_t *c0 = (int32_t *)w; w += b_codes;
-  int32_t *c1 = (int32_t *)w; w += b_codes;
-  float *sc = (float *)w; w += b_codes;
-  int32_t *n0 = (int32_t *)w; w += b_cnt;
-  int32_t *n1 = (int32_t *)w; w += b_cnt;
-  int32_t *lf_n = (int32_t *)w; w += b_cnt;
-  int32_t *lf_code = (int32_t *)w; w += b_lf;
-  float *lf_score = (float *)w; w += b_lf;
-  int32_t *lf_pos = (int32_t *)w; w += b_lf;
-  unsigned long long *lf_key = (unsigned long long *)w; w += 2 * b_lf;
-  if ((rc = scorer.attach(h, w, Uc, stride, L)) != DM_OK) return rc;
+  int32_t *kcode = ar.ptr<int32_t>(o_k), *c0 = ar.ptr<int32_t>(o_c0), *c1 = ar.ptr<int32_t>(o_c1), *n0 = ar.ptr<int32_t>(o_n0), *n1 = ar.ptr<int32_t>(o_n1);
+  int32_t *lf_n = ar.ptr<int32_t>(o_lfn), *lf_code = ar.ptr<int32_t>(o_lfc), *lf_pos = ar.ptr<int32_t>(o_lfp);
+  float *sc = ar.ptr<float>(o_sc), *lf_score = ar.ptr<float>(o_lfs);
+  unsigned long long *lf_key = ar.ptr<unsigned long long>(o_lfk);
+  if ((rc = scorer.attach(h, ar)) != DM_OK) return rc;
   HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));
   const size_t lds_step = (size_t)stride * 16;
   HIPCHK(h, hipFuncSetAttribute((const void *)tdm_pl_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));

@@ -23,7 +23,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   int rc = ensure_ws(h, off);
   if (rc != DM_OK) return rc;
   if ((rc = ensure_frags64(h)) != DM_OK) return rc;       // att.W / W1b fragments of the fp64 beam kernel's orders + l2.b
-  char *ws = (char *)h->d_ws;
+  char *ws = (char *)h->ws.p;
   TgBufs bufs;
   {
     double *ubase = (double *)(ws + o_ub);
@@ -123,8 +123,9 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
   if (h->dtype != DM_F64 || L > DM_MAXL || !tg_enabled()) {
     // f32 models and long histories: the same batch as plain rows
     int32_t *rseq = nullptr; unsigned *rmask = nullptr;
-    int rc = dm_alloc(h, (void **)&rseq, (size_t)B * L * 4);
-    if (rc == DM_OK) rc = dm_alloc(h, (void **)&rmask, (size_t)B * 4);
+    DevTemps t(h);
+    int rc = t.alloc(rseq, (size_t)B * L * 4);
+    if (rc == DM_OK) rc = t.alloc(rmask, (size_t)B * 4);
     if (rc == DM_OK) {
       hipLaunchKernelGGL(tg_expand_rows_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 8192)), dim3(256), 0, h->stream, d_seq, d_umask, U, n, L, rseq, rmask);
       float lf = 0.f;
@@ -132,7 +133,6 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
       if (loss) *loss = lf;
     }
     if (hipStreamSynchronize(h->stream) != hipSuccess && rc == DM_OK) rc = fail(h, DM_ERR_HIP, "train_fb_grouped_dev: kernel failed");
-    dm_free_ptr(rseq); dm_free_ptr(rmask);
     return rc;
   }
   {
@@ -147,7 +147,7 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
       if (h->d_touch_list && h->touch_cap)
         HIPCHK(h, hipMemcpyAsync(nl, h->d_touch_list, h->touch_cap * 4, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      dm_free_ptr(h->d_touch_list);
+      dm_release(h->d_touch_list);
       h->d_touch_list = nl;
       h->touch_cap = cap;
     }

@@ -20,13 +20,7 @@ int dm_train_init(dm_handle_t h, const dm_adam_opts *o) {
   const int64_t n = compact_len(h);
   const size_t es = elem_size(h);
   const size_t fb = (size_t)h->embed * h->embed * 4;
-  dm_free_ptr(h->d_grad); dm_free_ptr(h->d_adam_s); dm_free_ptr(h->d_adam_r); dm_free_ptr(h->d_attTA); dm_free_ptr(h->d_w1aTA);
-  dm_free_ptr(h->d_w1bTA); dm_free_ptr(h->d_loss); dm_free_ptr(h->d_touch_bits); dm_free_ptr(h->d_touch_list); dm_free_ptr(h->d_touch_cnt);
-  dm_free_ptr(h->d_tr64);
-  dm_free_ptr(h->d_active_bits); dm_free_ptr(h->d_active_list); dm_free_ptr(h->d_active_cnt);
-  h->d_active_bits = nullptr; h->d_active_list = nullptr; h->d_active_cnt = nullptr;
-  h->d_grad = h->d_adam_s = h->d_adam_r = nullptr; h->d_attTA = h->d_w1aTA = h->d_w1bTA = nullptr; h->d_loss = nullptr; h->d_tr64 = nullptr;
-  h->d_touch_bits = nullptr; h->d_touch_list = nullptr; h->d_touch_cnt = nullptr;
+  free_training(h);       // (a failure below leaves a handle that is not training, not one that trains on null buffers)
   ALLOC(h, h->d_grad, (size_t)n * es);
   ALLOC(h, h->d_adam_s, (size_t)n * es);
   ALLOC(h, h->d_adam_r, (size_t)n * es);
@@ -136,7 +130,7 @@ static int train_fb_launch(dm_ctx *h, const int32_t *d_codes, const int32_t *d_s
   p.codes = d_codes; p.seqs = d_seqs; p.rowmask = d_rowmask; p.labels = d_labels; p.B = B; p.L = L; p.inv_B = (T)(1.0 / (double)B);
   p.sm_scale = (T)sm_scale64(h);
   p.grad = (T *)h->d_grad;
-  T *ws = (T *)h->d_ws;
+  T *ws = (T *)h->ws.p;
   p.DZ = ws; p.AT = ws + (size_t)B * E; p.DA = ws + 2 * (size_t)B * E; p.CB = ws + 3 * (size_t)B * E;
   p.logits = ws + 4 * (size_t)B * E;
   p.loss_acc = (T *)h->d_loss;
@@ -176,7 +170,7 @@ static bool fwd64_ready(dm_ctx *h, int L) {
   std::lock_guard<std::recursive_mutex> lk_(h->mu);
   if (h->d_tr64) return true;
   if (dm_alloc(h, &h->d_tr64, 6 * (size_t)h->embed * h->embed * 8) != DM_OK) { h->d_tr64 = nullptr; return false; }
-  if (derive_small(h, DERIVE_OWN) != DM_OK) { dm_free_ptr(h->d_tr64); h->d_tr64 = nullptr; return false; }
+  if (derive_small(h, DERIVE_OWN) != DM_OK) { dm_release(h->d_tr64); return false; }
   return true;
 }
 static int rows_fwd64(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, const unsigned *d_rowmask, int64_t B, int L, double *d_out) {
@@ -220,7 +214,7 @@ static int train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs
       if (h->d_touch_list && h->touch_cap)
         HIPCHK(h, hipMemcpyAsync(nl, h->d_touch_list, h->touch_cap * 4, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(h, hipStreamSynchronize(h->stream));
-      dm_free_ptr(h->d_touch_list);
+      dm_release(h->d_touch_list);
       h->d_touch_list = nl;
       h->touch_cap = cap;
     }
@@ -277,27 +271,25 @@ int dm_train_forward_backward(dm_handle_t h, const int32_t *codes, const int32_t
   int32_t *d_codes = nullptr, *d_seqs = nullptr, *d_pad = nullptr;
   unsigned *d_mask = nullptr;
   float *d_lab = nullptr;
-  do {
-    if ((rc = dm_alloc(h, (void **)&d_codes, B * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_seqs, B * L * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_mask, B * 4)) != DM_OK) break;
-    if ((rc = dm_alloc(h, (void **)&d_lab, B * 4)) != DM_OK) break;
-    hipError_t e = hipMemcpyAsync(d_codes, codes, B * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_seqs, seqs, B * L * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lab, labels, B * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_mask, 0, B * 4, h->stream);
-    if (e != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_train_forward_backward: upload failed"); break; }
-    if (n_pad > 0) {
-      if ((rc = dm_alloc(h, (void **)&d_pad, n_pad * 4)) != DM_OK) break;
-      if (hipMemcpyAsync(d_pad, pad_flat_idx, n_pad * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "upload failed"); break; }
-      hipLaunchKernelGGL(dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, h->stream, d_pad, n_pad, L, d_mask);
-    }
-    float l = 0.f;
-    rc = train_fb_dev(h, d_codes, d_seqs, d_mask, d_lab, B, L, &l);
-    if (rc == DM_OK && loss) *loss = l;
-    if (hipStreamSynchronize(h->stream) != hipSuccess && rc == DM_OK) rc = fail(h, DM_ERR_HIP, "dm_train_forward_backward: kernel failed");
-  } while (0);
-  dm_free_ptr(d_codes); dm_free_ptr(d_seqs); dm_free_ptr(d_mask); dm_free_ptr(d_lab); dm_free_ptr(d_pad);
+  DevTemps t(h);
+  if ((rc = t.alloc(d_codes, B * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_seqs, B * L * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_mask, B * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(d_lab, B * 4)) != DM_OK) return rc;
+  hipError_t e = hipMemcpyAsync(d_codes, codes, B * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_seqs, seqs, B * L * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_lab, labels, B * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_mask, 0, B * 4, h->stream);
+  if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_train_forward_backward: upload failed");
+  if (n_pad > 0) {
+    if ((rc = t.alloc(d_pad, n_pad * 4)) != DM_OK) return rc;
+    if (hipMemcpyAsync(d_pad, pad_flat_idx, n_pad * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
+    hipLaunchKernelGGL(dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, h->stream, d_pad, n_pad, L, d_mask);
+  }
+  float l = 0.f;
+  rc = train_fb_dev(h, d_codes, d_seqs, d_mask, d_lab, B, L, &l);
+  if (rc == DM_OK && loss) *loss = l;
+  if (hipStreamSynchronize(h->stream) != hipSuccess && rc == DM_OK) return fail(h, DM_ERR_HIP, "dm_train_forward_backward: kernel failed");
   return rc;
 }
 
