@@ -436,6 +436,7 @@ static int jtm_rebalance_t(dm_ctx *h, const W *weights, const int32_t *old_node,
                            int threads = 1) {
   if (!weights || !old_node || !out_node || n < 0 || level <= old_level || level - old_level > 8 || max_assign < 0)
     return fail(h, DM_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (level > JTM_MAX_LEVEL) return jtm_level_refused(h, level, who);
   if (n >= ((int64_t)1 << 31)) return fail(h, DM_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 items under one parent");
   typedef JtmInfo<W> Info;
   typedef typename JtmKeyOf<W>::type Key;
@@ -550,6 +551,7 @@ static int jtm_rebalance_all_t(dm_ctx *h, const W *weights, const int32_t *old_n
                                int old_level, int level, int max_assign, int32_t *out_node, const char *who) {
   if (!weights || !old_node || !item_node || !out_node || n < 0 || level <= old_level || level - old_level > 8 || max_assign < 0)
     return fail(h, DM_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (level > JTM_MAX_LEVEL) return jtm_level_refused(h, level, who);
   const int nchild = 1 << (level - old_level);
   // stable grouping by node: the nodes of a level form a contiguous code range -> counting sort
   std::vector<int64_t> order((size_t)n);
@@ -641,6 +643,7 @@ static bool jtm_rebalance_on_device(const dm_ctx *h, int64_t n, int old_level, i
 template <typename W>
 static int jtm_rebalance_all_staged(dm_ctx *h, const W *weights, const int32_t *old_node, const int32_t *item_node, int64_t n, int old_level,
                                     int level, int max_assign, int32_t *out_node, const char *who) {
+  if (level > JTM_MAX_LEVEL) return jtm_level_refused(h, level, who);
   HIPCHK(h, hipSetDevice(h->device));
   const int C = 1 << (level - old_level);
   DevTemps t(h);
@@ -842,5 +845,73 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
     }
     i0 = i1;
   }
+  return DM_OK;
+}
+
+// debug (not part of the public header): the two primitives of dev_sort.hip.inc on host arrays — upload, one call on the handle's stream
+// with scratch of dev_sort_scratch_bytes, download — so that tests can hold them against numpy at sizes and bit ranges no caller reaches
+// (tests/test_gpu_dev_sort.py).  Every device byte is a DevTemps temporary of the call.
+extern "C" int dm_debug_sort_pairs(dm_handle_t h, uint64_t *keys, int32_t *vals, int64_t m, int begin_bit, int end_bit, int *where) {
+  if (!h) return DM_ERR_INVALID;
+  if (!keys || !vals || !where || m < 0 || m >= ((int64_t)1 << 31) || begin_bit < 0 || end_bit < begin_bit || end_bit > 64)
+    return fail(h, DM_ERR_INVALID, "dm_debug_sort_pairs: bad arguments");
+  HIPCHK(h, hipSetDevice(h->device));
+  DevTemps t(h);
+  unsigned long long *k[2] = {nullptr, nullptr};
+  int32_t *v[2] = {nullptr, nullptr};
+  uint32_t *tmp = nullptr;
+  int rc;
+  for (int b = 0; b < 2; b++)
+    if ((rc = t.alloc(k[b], (size_t)m * 8)) != DM_OK || (rc = t.alloc(v[b], (size_t)m * 4)) != DM_OK) return rc;
+  if ((rc = t.alloc(tmp, dev_sort_scratch_bytes(m))) != DM_OK) return rc;
+  auto fin = [&](int r) { (void)hipStreamSynchronize(h->stream); return r; };       // nothing is freed under a running kernel
+  if (m > 0 && (hipMemcpyAsync(k[0], keys, (size_t)m * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+                hipMemcpyAsync(v[0], vals, (size_t)m * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess))
+    return fin(fail(h, DM_ERR_HIP, "dm_debug_sort_pairs: upload failed"));
+  int wh = 0;
+  const hipError_t e = dev_radix_sort_pairs(h->stream, k[0], v[0], k[1], v[1], m, begin_bit, end_bit, tmp, &wh);
+  if (e != hipSuccess) return fin(fail(h, DM_ERR_HIP, std::string("dm_debug_sort_pairs: ") + hipGetErrorString(e)));
+  if (m > 0 && (hipMemcpyAsync(keys, k[wh], (size_t)m * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                hipMemcpyAsync(vals, v[wh], (size_t)m * 4, hipMemcpyDeviceToHost, h->stream) != hipSuccess))
+    return fin(fail(h, DM_ERR_HIP, "dm_debug_sort_pairs: download failed"));
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "dm_debug_sort_pairs: device pass failed");
+  *where = wh;
+  return DM_OK;
+}
+
+// in == NULL: the indices themselves; in2 / out2 (both or neither): a second array that rides along.  out / out2 receive *count elements.
+extern "C" int dm_debug_select_flagged(dm_handle_t h, const int32_t *in, const uint64_t *in2, const uint8_t *flag, int64_t n, int32_t *out,
+                                       uint64_t *out2, uint64_t *count) {
+  if (!h) return DM_ERR_INVALID;
+  if (!flag || !out || !count || (in2 && !out2) || n < 0 || n >= ((int64_t)1 << 31))
+    return fail(h, DM_ERR_INVALID, "dm_debug_select_flagged: bad arguments");
+  HIPCHK(h, hipSetDevice(h->device));
+  DevTemps t(h);
+  int32_t *d_in = nullptr, *d_out = nullptr;
+  unsigned long long *d_in2 = nullptr, *d_out2 = nullptr, *d_count = nullptr;
+  uint8_t *d_flag = nullptr;
+  uint32_t *tmp = nullptr;
+  int rc;
+  if ((rc = t.alloc(d_flag, (size_t)n)) != DM_OK || (rc = t.alloc(d_out, (size_t)n * 4)) != DM_OK || (rc = t.alloc(d_count, 8)) != DM_OK ||
+      (rc = t.alloc(tmp, dev_sort_scratch_bytes(n))) != DM_OK)
+    return rc;
+  if (in && (rc = t.alloc(d_in, (size_t)n * 4)) != DM_OK) return rc;
+  if (in2 && ((rc = t.alloc(d_in2, (size_t)n * 8)) != DM_OK || (rc = t.alloc(d_out2, (size_t)n * 8)) != DM_OK)) return rc;
+  auto fin = [&](int r) { (void)hipStreamSynchronize(h->stream); return r; };
+  if (n > 0 && (hipMemcpyAsync(d_flag, flag, (size_t)n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+                (in && hipMemcpyAsync(d_in, in, (size_t)n * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+                (in2 && hipMemcpyAsync(d_in2, in2, (size_t)n * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess)))
+    return fin(fail(h, DM_ERR_HIP, "dm_debug_select_flagged: upload failed"));
+  const hipError_t e = in2 ? dev_select_flagged<int32_t, unsigned long long>(h->stream, d_in, d_in2, d_flag, d_out, d_out2, d_count, n, tmp)
+                           : dev_select_flagged<int32_t>(h->stream, d_in, (const char *)nullptr, d_flag, d_out, (char *)nullptr, d_count, n, tmp);
+  if (e != hipSuccess) return fin(fail(h, DM_ERR_HIP, std::string("dm_debug_select_flagged: ") + hipGetErrorString(e)));
+  unsigned long long c = 0;
+  if (hipMemcpyAsync(&c, d_count, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+    return fin(fail(h, DM_ERR_HIP, "dm_debug_select_flagged: device pass failed"));
+  if ((int64_t)c > n) return fail(h, DM_ERR_HIP, "dm_debug_select_flagged: internal count mismatch");
+  if (c > 0 && (hipMemcpy(out, d_out, (size_t)c * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                (in2 && hipMemcpy(out2, d_out2, (size_t)c * 8, hipMemcpyDeviceToHost) != hipSuccess)))
+    return fail(h, DM_ERR_HIP, "dm_debug_select_flagged: download failed");
+  *count = c;
   return DM_OK;
 }

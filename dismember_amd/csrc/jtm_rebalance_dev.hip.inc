@@ -19,6 +19,13 @@
 // Rounds end when no parent has an over-full list: at most 2^gap rounds, one 8-byte read-back each.
 #include "dev_sort.hip.inc"
 
+// Node codes are int32_t everywhere (the ABI's out_node included): the last code of level 30 is 2^31 - 2, a level-31 code does not fit.
+// Every re-balance route refuses such a level by name before it allocates anything.
+static const int JTM_MAX_LEVEL = 30;
+static int jtm_level_refused(dm_ctx *h, int level, const char *who) {
+  return fail(h, DM_ERR_INVALID, std::string(who) + ": level " + std::to_string(level) + " is above " + std::to_string(JTM_MAX_LEVEL) + " (its node codes do not fit int32)");
+}
+
 template <typename W>
 struct JtmRbState {
   const W *w;                // [n][C]
@@ -195,6 +202,7 @@ __global__ void jtm_rb_out_kernel(JtmRbState<W> s, int32_t *out) {
 template <typename W>
 static int jtm_rebalance_all_dev(dm_ctx *h, const W *d_w, const int32_t *d_old_node, const int32_t *d_item_node, int64_t n,
                                  int old_level, int level, int max_assign, int32_t *d_out) {
+  if (level > JTM_MAX_LEVEL) return jtm_level_refused(h, level, sizeof(W) == 8 ? "dm_otm_rebalance_all" : "dm_jtm_rebalance_all");
   const int gap = level - old_level, C = 1 << gap;
   const bool two_pass = sizeof(W) == 8;
   if (C > 256 || old_level > 24 || n >= ((int64_t)1 << 31) || n <= 0) return DM_ERR_UNSUPPORTED;

@@ -105,10 +105,11 @@ def test_g9_lowest_distortion_restart_wins(eng, n, E):
 
 
 @pytest.mark.parametrize("E", [16, 128])
-@pytest.mark.parametrize("n", [3, 257, 2500])
+@pytest.mark.parametrize("n", [3, 257, 2500, 9000])
 def test_g10_identical_rows(eng, n, E):
-    """every sort key equal: each split keeps the parent's order (across the radix sort's tiles and in the LDS rank), so the tree is
-    the balanced recursion over the identity order; the mean of copies is the row, the distortion 0, one iteration"""
+    """every sort key equal: each split keeps the parent's order (across the radix sort's tiles — n = 9 000 is three tiles of 4 096 —
+    and in the LDS rank), so the tree is the balanced recursion over the identity order; the mean of copies is the row, the
+    distortion 0, one iteration"""
     row = np.random.default_rng(E).standard_normal(E).astype(np.float32)
     row[0], row[1] = -1.5, 0.0
     x = np.tile(row, (n, 1))
