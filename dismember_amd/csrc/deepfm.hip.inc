@@ -202,9 +202,6 @@ __global__ __launch_bounds__(256) void dfm_forward_kernel(DfmFwd p) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-// kinds of dm_kernel_timing_get_kind
-enum { DFM_KIND_USER = 40, DFM_KIND_LEVEL = 41 };
-
 // device layout of the small blocks behind the table (padded E)
 struct DfmBlocks { const float *l1_w, *l1_b, *l2_w, *l2_b; };
 static DfmBlocks dfm_blocks(const dm_ctx *h) {
@@ -330,7 +327,7 @@ static int dfm_launch_level(dm_ctx *h, const DfmLevel &p) {
   int64_t blocks = (waves + 3) / 4;
   if (blocks > (int64_t)h->n_cu * 4) blocks = (int64_t)h->n_cu * 4;
   if (blocks < 1) blocks = 1;
-  LaunchTimer tm(h, DFM_KIND_LEVEL);
+  LaunchTimer tm(h, EV_DFM_LEVEL);
   if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL((dfm_level_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
@@ -355,7 +352,7 @@ struct TdmPlDeepFM : TdmPlScorer {
     DfmUser p;
     p.emb = h->d_emb32; p.l1_w = b.l1_w; p.l1_b = b.l1_b; p.b2 = h->b2; p.kcode = kcode; p.E = E; p.L = L; p.NC = NCT * 16;
     p.num_index = h->num_index; p.S = S; p.aux = aux;
-    LaunchTimer tm(h, DFM_KIND_USER);
+    LaunchTimer tm(h, EV_DFM_USER);
     if (tm.rc != DM_OK) return tm.rc;
     hipLaunchKernelGGL(dfm_user_kernel, dim3((unsigned)Un), dim3(256), 0, h->stream, p);
     HIPCHK(h, hipGetLastError());

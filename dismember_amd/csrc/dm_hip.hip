@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cfloat>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,6 +59,22 @@ struct dm_otm_stats {
   int levels = 0;
   double targets_s = 0, beam_s = 0, fwdbwd_s = 0, exchange_s = 0, adam_s = 0;
 };
+
+// The handle's counter block on the device (dm_ctx::d_ctr): the kernels get the address of a field, the host never dereferences it.
+struct SearchCounters {
+  unsigned long long rows;             // candidate rows scored by the last search (dm_last_scored_rows)
+  unsigned long long queue_head;       // work-queue head of the persistent beam kernels
+  unsigned long long dr_slow;          // Deep-Retrieval layers that took the exact path (dm_debug_dr_slow_layers)
+  unsigned long long rows_sink;        // where the single-request paths count their rows: never zeroed, never read
+  unsigned long long unused4;
+  unsigned long long dr_wave_count;    // user-layers the one-wave cut handed to the block version, and one byte counter per
+  unsigned long long dr_wave_reasons;  // reason (dm_debug_dr_wave_fallbacks)
+  unsigned long long unused7;
+};
+// drs_select_wave_kernel (dr_sliced.hip.inc) reaches the two fallback counters as slow_count + 3 and slow_count + 4
+static_assert(offsetof(SearchCounters, dr_wave_count) == offsetof(SearchCounters, dr_slow) + 3 * 8 &&
+              offsetof(SearchCounters, dr_wave_reasons) == offsetof(SearchCounters, dr_slow) + 4 * 8 && sizeof(SearchCounters) == 64,
+              "the kernels address the block by slot");
 
 struct dm_ctx {
   int device = 0;
@@ -105,7 +122,6 @@ struct dm_ctx {
   LazyCopies lazy;             // the copies rebuilt on first use after a weight change, and their stale flags (lazy_copies.hip.inc)
   int scorer_mode = DM_SCORER_AUTO;      // dm_set_scorer_mode
   bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
-  bool call_split = false;     // scorer arithmetic of the search being planned (split_for_call)
   double jtm_score_s = 0, jtm_rebal_s = 0;   // dm_jtm_last_step_seconds
   DevGrow scratch64;           // fp64 beam kernel (beam_kernel_f64.hip.inc): per-team K / G fragment scratch
   // training state (dm_train_init)
@@ -128,27 +144,22 @@ struct dm_ctx {
   // measurement
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   size_t ev_used = 0;
-  std::vector<int> ev_kind;    // per pair: 0 = a main kernel, 1 = the second pass over the users the one-wave kernel deferred
-  int ev_next_kind = 0;
-  bool ev_skip = false;        // the single-request path launches without its event pair ...
-  bool time_direct = false;    // ... unless DM_TIME_DIRECT=1 asks for kernel timings of that path too (probes)
+  std::vector<int> ev_kind;    // per pair: what it was recorded as (EvKind, host_request.hip.inc)
+  bool time_direct = false;    // DM_TIME_DIRECT=1: the single-request path, which launches without an event pair, records one too (probes)
   bool direct_ok = true;       // host-mapped single-request path enabled (DM_NO_DIRECT=1 turns it off)
   char last_kernel[64] = "";   // the search kernel of the last beam search (measurement: dm_last_beam_kernel)
-  unsigned long long *d_rows = nullptr;
+  SearchCounters *d_ctr = nullptr;
   unsigned long long *d_phase = nullptr;   // 8 debug counters
-  int64_t last_rows = 0;
   // Deep-Retrieval model (dm_dr_load_model)
   dm_dr_state *dr = nullptr;
   // request arena of the host-buffer entry points (grow only: no hipMalloc / hipFree on the request path)
   DevGrow req;
-  unsigned long long h_rows = 0;
   char *h_stage = nullptr;     // pinned staging block for small host-buffer requests (one upload, one download per call)
   char *d_stage = nullptr;     // the same block as the kernels address it (hipHostGetDevicePointer): single-request path
   size_t stage_bytes = 0;
   // pipelined host-buffer searches (host_pipe_*): a second, non-blocking stream for the result downloads + one event per chunk
   hipStream_t copy_stream = nullptr;
   std::vector<hipEvent_t> chunk_ev;
-  bool rows_keep = false;      // a later chunk of one request: the scored-rows counter keeps counting
   // cached search workspace
   DevGrow ws;
   // device-side negative sampler (sampler.hip.inc): per-level code / cumulative-probability tables, per-call scratch
@@ -388,8 +399,8 @@ int dm_create(int device_id, dm_handle_t *out) {
   { const char *e_ = getenv("DM_NO_DIRECT"); if (e_ && e_[0] == '1') h->direct_ok = false; }
   { const char *e_ = getenv("DM_TIME_DIRECT"); if (e_ && e_[0] == '1') h->time_direct = true; }
   if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return fail(nullptr, DM_ERR_HIP, "hipStreamCreate failed"); }
-  if (dm_alloc(h, (void **)&h->d_rows, 64) != DM_OK) { delete h; return fail(nullptr, DM_ERR_HIP, "hipMalloc failed"); }
-  (void)hipMemset(h->d_rows, 0, 64);
+  if (dm_alloc(h, (void **)&h->d_ctr, sizeof(SearchCounters)) != DM_OK) { delete h; return fail(nullptr, DM_ERR_HIP, "hipMalloc failed"); }
+  (void)hipMemset(h->d_ctr, 0, sizeof(SearchCounters));
   if (dm_alloc(h, (void **)&h->d_phase, 128) == DM_OK) (void)hipMemset(h->d_phase, 0, 128);
   *out = h;
   return DM_OK;
@@ -465,7 +476,7 @@ int dm_destroy(dm_handle_t h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->parent) { clone_forget(h); h->parent->n_clones.fetch_sub(1); h->parent = nullptr; }
   free_tree(h); free_weights(h); dm_dr_free(h->dr);
-  dm_release(h->d_id_to_code, h->d_rows, h->d_phase);
+  dm_release(h->d_id_to_code, h->d_ctr, h->d_phase);
   for (DevGrow *g : {&h->ws, &h->req, &h->sync, &h->samp, &h->defer, &h->scratch64}) g->release();
   if (h->h_stage) (void)hipHostFree(h->h_stage);
   jtm_drop_cache(h);
@@ -780,7 +791,7 @@ static int launch_rows_E(dm_ctx *h, const RowsParams &p) {
 }
 
 // HIP-event pair of kind 30 around a general-rows launch (dm_kernel_timing_get_kind: the roofline of JTM's scorer in bench.py)
-struct RowsTimer : LaunchTimer { explicit RowsTimer(dm_ctx *h_) : LaunchTimer(h_, 30) {} };
+struct RowsTimer : LaunchTimer { explicit RowsTimer(dm_ctx *h_) : LaunchTimer(h_, EV_ROWS) {} };
 
 template <int E, int LC>
 static int launch_rows_split_EL(dm_ctx *h, const RowsSplitParams &p, int64_t blocks) {
@@ -892,7 +903,9 @@ int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, con
 // ------------------------------------------------------------ beam search
 struct SearchPlan {
   int nteams, cap, pcap, grid, ws_cap, lds;
-  bool wkernel;        // the one-wave-per-SIMD kernel with W1a in the AccVGPRs (beam_kernel_w.hip.inc)
+  bool wkernel = false;        // the one-wave-per-SIMD kernel with W1a in the AccVGPRs (beam_kernel_w.hip.inc)
+  bool split = false;          // scorer arithmetic of this search: the split-fp16 copies (split_for_call) or the fp32 inputs
+  int ev_kind = EV_MAIN;       // what its launch is recorded as; only EV_MAIN names the search's kernel (dm_last_beam_kernel)
 };
 
 // AUTO mode inside a training loop (weights_in_motion): a search small next to the split copies' refresh keeps the fp32-input kernel
@@ -937,9 +950,9 @@ static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, 
   const int kt = L > DM_MAXL ? 2 : 1;          // histories of 17 .. 32 positions: the LDS-fed kernel's two-key-tile instance
   const int kq = kt > 1 ? 4 : (L + 3) / 4;
   int nteams = 0;
-  pl->wkernel = false;
-  h->call_split = split_for_call(h, U, max_beam);
-  if (h->call_split && h->beam_w && kt == 1) {
+  *pl = SearchPlan{};
+  pl->split = split_for_call(h, U, max_beam);
+  if (pl->split && h->beam_w && kt == 1) {
     // split-fp16 scorer: one-wave teams, four per workgroup, W1a in registers; falls back when the frontier outgrows LDS
     BeamWLds l = dm_beamw_lds(h->embed, cap, pcap, kq);
     if (l.total <= 160 * 1024) { nteams = DMW_NWAVES; pl->lds = l.total; pl->wkernel = true; }
@@ -947,7 +960,7 @@ static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, 
   // LDS-fed kernel.  A frontier of at most 256 slots fits ONE wave's register sort, so small beams
   // (the reference's serving default is candidateNum 20) run as eight one-wave teams: no team barriers at all on the latency
   // chain sort -> expand -> gather -> score of a level, and eight users per CU in flight instead of four
-  if (!nteams) nteams = beam_teams_that_fit(h->embed, pcap <= 256 ? 8 : 4, cap, pcap, kq, h->call_split, kt, &pl->lds);
+  if (!nteams) nteams = beam_teams_that_fit(h->embed, pcap <= 256 ? 8 : 4, cap, pcap, kq, pl->split, kt, &pl->lds);
   if (!nteams) return fail(h, DM_ERR_UNSUPPORTED, "beam too large for the LDS frontier (about 2*beam*28 bytes + weights must fit 160 KiB)");
   int64_t groups = (U + nteams - 1) / nteams;
   int grid = (int)(groups < h->n_cu ? groups : h->n_cu);
@@ -957,23 +970,22 @@ static int plan_search(dm_ctx *h, int max_beam, int64_t U, int L, int n_levels, 
   return DM_OK;
 }
 
-static int ensure_ws(dm_ctx *h, size_t bytes) {
-  return h->ws.reserve(h, bytes);
+// The second pass of a search on the one-wave-per-SIMD kernel: the LDS-fed split kernel over the users the first pass deferred.  Its own
+// frontier layout, from four teams down; the workspace was sized for the first pass's grid x 4 one-wave teams, and the second pass may
+// use at most as many (block, team) slots.
+static int plan_deferred_pass(dm_ctx *h, const SearchPlan &pl, int L, SearchPlan *pl2) {
+  *pl2 = pl;
+  pl2->wkernel = false;
+  pl2->ev_kind = EV_DEFERRED;
+  pl2->nteams = beam_teams_that_fit(h->embed, 4, pl.cap, pl.pcap, (L + 3) / 4, pl.split, 1, &pl2->lds);
+  if (!pl2->nteams) return fail(h, DM_ERR_UNSUPPORTED, "beam too large for the LDS frontier");
+  if (pl2->grid * pl2->nteams > pl.grid * pl.nteams) pl2->grid = pl.grid * pl.nteams / pl2->nteams;
+  if (pl2->grid < 1) pl2->grid = 1;
+  return DM_OK;
 }
 
-static int next_events(dm_ctx *h, hipEvent_t *a, hipEvent_t *b) {
-  if (h->ev_used >= 4096) h->ev_used = 0;      // a service that never reads the timings keeps a bounded pool (oldest pairs are reused)
-  if (h->ev_used == h->ev_pool.size()) {
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0));
-    HIPCHK(h, hipEventCreate(&e1));
-    h->ev_pool.push_back({e0, e1});
-  }
-  *a = h->ev_pool[h->ev_used].first; *b = h->ev_pool[h->ev_used].second;
-  if (h->ev_kind.size() <= h->ev_used) h->ev_kind.resize(h->ev_used + 1);
-  h->ev_kind[h->ev_used] = h->ev_next_kind;
-  h->ev_used++;
-  return DM_OK;
+static int ensure_ws(dm_ctx *h, size_t bytes) {
+  return h->ws.reserve(h, bytes);
 }
 
 template <int E, int KQ, bool SPLIT, int KT = 1>
@@ -981,11 +993,11 @@ static int launch_beam_EK(dm_ctx *h, const BeamParams &p_in, const SearchPlan &p
   BeamParams p = p_in;
   p.static_users = (p.mode != 2 && !p.user_list && p.U <= (int64_t)pl.grid * pl.nteams) ? 1 : 0;
   HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam_kernel<E, KQ, SPLIT, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
-  if (h->ev_next_kind == 0) {
+  if (pl.ev_kind == EV_MAIN) {
     if (KT == 1) snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_kernel<%d, %d, %s>", E, KQ, SPLIT ? "true" : "false");
     else snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_kernel<%d, %d, %s, %d>", E, KQ, SPLIT ? "true" : "false", KT);
   }
-  LaunchTimer tm(h, LaunchTimer::KEEP, !(h->ev_skip && !h->time_direct));       // single-request path: the launch and nothing else
+  LaunchTimer tm(h, pl.ev_kind, !(p.host_direct && !h->time_direct));       // single-request path: the launch and nothing else
   if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL((dm_beam_kernel<E, KQ, SPLIT, KT>), dim3(pl.grid), dim3(DM_BLOCK), pl.lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
@@ -1039,7 +1051,7 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
   // the brute-force recall oracle (mode 2) always scores with the fp32-input MFMA
   if (h->scorer_mode == DM_SCORER_SPLIT_F16 && h->embed % 32 != 0)
     return fail(h, DM_ERR_UNSUPPORTED, "the split-fp16 scorer needs an embedding size of 32, 64 or 128");
-  if (h->call_split && p.mode != 2) {
+  if (pl.split && p.mode != 2) {
     int rc = ensure_split(h);
     if (rc != DM_OK) return rc;
     p.wsplit = (const dm_h8 *)h->lazy.d_wsplit;
@@ -1055,24 +1067,16 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       const char *const no_split = "the split-fp16 scorer needs an embedding size of 32, 64 or 128";
       int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
       if (rc != DM_OK) return rc;
-      // second pass (an empty list costs one launch): same parameters, the list as the work queue, its own frontier layout
-      SearchPlan pl2 = pl;
-      pl2.wkernel = false;
-      pl2.nteams = beam_teams_that_fit(h->embed, 4, pl.cap, pl.pcap, (p.L + 3) / 4, true, 1, &pl2.lds);
-      if (!pl2.nteams) return fail(h, DM_ERR_UNSUPPORTED, "beam too large for the LDS frontier");
-      // the workspace was sized for grid x 4 one-wave teams; the second pass may use at most as many (block, team) slots
-      if (pl2.grid * pl2.nteams > pl.grid * pl.nteams) pl2.grid = pl.grid * pl.nteams / pl2.nteams;
-      if (pl2.grid < 1) pl2.grid = 1;
+      // second pass (an empty list costs one launch): same parameters, the list as the work queue, its own plan
+      SearchPlan pl2;
+      if ((rc = plan_deferred_pass(h, pl, p.L, &pl2)) != DM_OK) return rc;
       BeamParams p2 = p;
       p2.nteams = pl2.nteams;
       p2.user_count = (const unsigned long long *)h->defer.p;
       p2.user_list = (const int32_t *)((char *)h->defer.p + 16);
       p2.next_user = (unsigned long long *)((char *)h->defer.p + 8);
       p2.defer_count = nullptr; p2.defer_users = nullptr;
-      h->ev_next_kind = 1;
-      rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p2, pl2); });
-      h->ev_next_kind = 0;
-      return rc;
+      return dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p2, pl2); });
     }
     return dispatch_E<32>(h, h->embed, "the split-fp16 scorer needs an embedding size of 32, 64 or 128",
                           [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p, pl); });
@@ -1108,10 +1112,35 @@ static void fill_common(dm_ctx *h, BeamParams &p) {
   p.b2 = h->b2; p.num_index = h->num_index;
   p.exists_bits = h->d_exists; p.leaf_bits = h->d_leaf; p.node_id = h->d_node_id; p.id_to_code = h->d_id_to_code;
   p.n_slots = h->n_slots; p.non_leaf_offset = h->non_leaf_offset; p.max_code = h->max_code; p.max_level = h->max_level;
-  p.scored_rows = h->d_rows;
+  p.scored_rows = &h->d_ctr->rows;
   p.sm_scale = sm_scale32(h);
   p.phase_cycles = h->d_phase;
-  p.next_user = h->d_rows + 1;
+  p.next_user = &h->d_ctr->queue_head;
+}
+
+// the frontier shape and its global-memory workspace (four arrays of grid x nteams x ws_cap words in h->ws), as the plan sized them
+static int fill_frontier(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
+  const size_t per = (size_t)pl.grid * pl.nteams * pl.ws_cap;
+  const int rc = ensure_ws(h, per * 16);
+  if (rc != DM_OK) return rc;
+  p.nteams = pl.nteams; p.cap = pl.cap; p.pcap = pl.pcap;
+  p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p + per; p.ws_khi = (uint32_t *)h->ws.p + 2 * per;
+  p.ws_klo = (uint32_t *)h->ws.p + 3 * per; p.ws_cap = pl.ws_cap;
+  return DM_OK;
+}
+
+// before a search: the work-queue head restarts, and so does the scored-rows counter unless this search is a later chunk of one request
+static hipError_t reset_search_counters(dm_ctx *h, bool keep_rows) {
+  return keep_rows ? hipMemsetAsync(&h->d_ctr->queue_head, 0, sizeof h->d_ctr->queue_head, h->stream)
+                   : hipMemsetAsync(h->d_ctr, 0, offsetof(SearchCounters, dr_slow), h->stream);      // rows + queue_head
+}
+
+// result rows before a search whose kernels write the live slots only: ids -1, scores 0 (score_bytes each), counts 0
+static hipError_t prefill_results(dm_ctx *h, int64_t U, size_t stride, int32_t *d_ids, void *d_scores, size_t score_bytes, int32_t *d_counts) {
+  hipError_t e = hipMemsetAsync(d_ids, 0xFF, (size_t)U * stride * 4, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_scores, 0, (size_t)U * stride * score_bytes, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream);
+  return e;
 }
 
 static int tdm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
@@ -1128,7 +1157,7 @@ static bool level_pipeline(const dm_ctx *h, int max_beam, int L) {
 
 static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, const dm_tdm_search_opts *o, int max_beam,
                           const int64_t *d_coff, const int32_t *d_cids, int32_t *d_ids, float *d_scores, int32_t *d_counts,
-                          int trace_levels, int32_t *d_tc, float *d_ts, int32_t *d_tn, bool *direct = nullptr) {
+                          int trace_levels, int32_t *d_tc, float *d_ts, int32_t *d_tn, bool keep_rows, bool *direct = nullptr) {
   if (!h->tree_loaded || !h->ids_loaded || !h->w_loaded) return fail(h, DM_ERR_STATE, "tdm beam search: tree, id maps and weights must be loaded first");
   if (U < 0 || L <= 0 || L > DM_PIPE_MAXL || !o || o->beam <= 0 || o->topk <= 0) return fail(h, DM_ERR_INVALID, "tdm beam search: bad arguments (L must be 1..32)");
   if (U == 0) return DM_OK;          // an empty batch is not an error
@@ -1139,9 +1168,7 @@ static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, con
   if (dfm && L != h->dfm_L) return fail(h, DM_ERR_INVALID, "tdm beam search: L = " + std::to_string(L) + " but the DeepFM model was built for seq_len " + std::to_string(h->dfm_L));
   if (level_pipeline(h, max_beam, L)) {
     if (direct) { *direct = false; return DM_OK; }          // (the caller takes the staged path and comes back)
-    HIPCHK(h, hipMemsetAsync(d_ids, 0xFF, (size_t)U * o->topk * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)U * o->topk * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream));
+    HIPCHK(h, prefill_results(h, U, o->topk, d_ids, d_scores, 4, d_counts));
     int cap_;
     frontier_caps(max_beam, &cap_, nullptr);
     return (dfm ? dfm_pipeline_dev : tdm_pipeline_dev)(h, d_seq, U, L, o, max_beam, d_coff, d_cids, d_ids, d_scores, d_counts, trace_levels, cap_, d_tc, d_ts, d_tn);
@@ -1153,37 +1180,25 @@ static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, con
   SearchPlan pl;
   int rc = plan_search(h, max_beam, U, L, n_levels, true, &pl);
   if (rc != DM_OK) return rc;
-  const size_t per = (size_t)pl.grid * pl.nteams * pl.ws_cap;
-  rc = ensure_ws(h, per * 16);
-  if (rc != DM_OK) return rc;
   BeamParams p;
   fill_common(h, p);
+  if ((rc = fill_frontier(h, p, pl)) != DM_OK) return rc;
   p.seq = d_seq; p.U = U; p.L = L; p.use_mask = o->use_mask; p.beam = o->beam; p.topk = o->topk;
   p.widen = (o->widen_consumed && d_coff) ? 1 : 0;
-  p.consumed_off = d_coff; p.consumed_ids = d_cids; p.mode = 0; p.nteams = pl.nteams; p.cap = pl.cap; p.pcap = pl.pcap; p.leaf_fast = h->leaves_at_max_only ? 1 : 0;
+  p.consumed_off = d_coff; p.consumed_ids = d_cids; p.mode = 0; p.leaf_fast = h->leaves_at_max_only ? 1 : 0;
   p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_stride = o->topk;
-  p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p + per; p.ws_khi = (uint32_t *)h->ws.p + 2 * per;
-  p.ws_klo = (uint32_t *)h->ws.p + 3 * per; p.ws_cap = pl.ws_cap;
   p.trace_codes = d_tc; p.trace_scores = d_ts; p.trace_counts = d_tn; p.trace_levels = trace_levels;
   if (direct) {
     // single-request path (tdm_search_host): request and results live in host-mapped pinned memory, one team per user without the
     // work queue, the kernel fills every output slot and publishes the counts last — ONE launch, no memsets, no copies, no events
     *direct = *direct && !pl.wkernel && U <= (int64_t)pl.grid * pl.nteams && !d_coff && !d_tn;
     if (!*direct) return DM_OK;             // nothing launched: the caller takes the staged path
-    {
-      p.host_direct = 1;
-      p.scored_rows = h->d_rows + 3;          // not zeroed on this path: keep dm_last_scored_rows' counter out of it
-      h->ev_skip = true;
-      const int rc_ = launch_beam(h, p, pl);
-      h->ev_skip = false;
-      return rc_;
-    }
+    p.host_direct = 1;
+    p.scored_rows = &h->d_ctr->rows_sink;     // nothing is zeroed on this path: keep dm_last_scored_rows' counter out of it
+    return launch_beam(h, p, pl);
   }
-  if (h->rows_keep) HIPCHK(h, hipMemsetAsync(h->d_rows + 1, 0, 8, h->stream));      // (the work-queue head only)
-  else HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_ids, 0xFF, (size_t)U * o->topk * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)U * o->topk * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream));
+  HIPCHK(h, reset_search_counters(h, keep_rows));
+  HIPCHK(h, prefill_results(h, U, o->topk, d_ids, d_scores, 4, d_counts));
   return launch_beam(h, p, pl);
 }
 
@@ -1237,7 +1252,7 @@ int dm_tdm_beam_search_dev(dm_handle_t h, const int32_t *d_seq_item_ids, int64_t
     mb = host_max_beam(opts, coff.data(), U);
   }
   return tdm_search_dev(h, d_seq_item_ids, U, L, opts, mb, d_consumed_off, d_consumed_ids, d_out_item_ids, d_out_scores,
-                        d_out_counts, 0, nullptr, nullptr, nullptr);
+                        d_out_counts, 0, nullptr, nullptr, nullptr, false);
 }
 
 static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, const dm_tdm_search_opts *opts,
@@ -1275,7 +1290,7 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
     for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
     bool direct = true;
     rc = tdm_search_dev(h, (const int32_t *)h->d_stage, U, L, opts, mb, nullptr, nullptr, (int32_t *)(h->d_stage + o_ids),
-                        (float *)(h->d_stage + o_sc), (int32_t *)(h->d_stage + o_cnt), 0, nullptr, nullptr, nullptr, &direct);
+                        (float *)(h->d_stage + o_sc), (int32_t *)(h->d_stage + o_cnt), 0, nullptr, nullptr, nullptr, false, &direct);
     if (rc != DM_OK) return rc;
     if (direct) {
       if ((rc = wait_host_direct(h, m_cnt, U, "tdm beam search")) == DM_OK) copy_from_stage(h, outs, 3, U);
@@ -1288,8 +1303,8 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
   const int n_chunks = (staged || coff || tn || level_pipeline(h, mb, L)) ? 1 : host_pipe_plan(topk * 8, U, off);
   if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
     int launched;
-    rc = launch_chunks(h, n_chunks, off, [&](int, int64_t u0, int64_t uk) {
-      return tdm_search_dev(h, d_seq + u0 * L, uk, L, opts, mb, nullptr, nullptr, d_ids + u0 * topk, d_scores + u0 * topk, d_counts + u0, 0, nullptr, nullptr, nullptr);
+    rc = launch_chunks(h, n_chunks, off, [&](int k, int64_t u0, int64_t uk) {
+      return tdm_search_dev(h, d_seq + u0 * L, uk, L, opts, mb, nullptr, nullptr, d_ids + u0 * topk, d_scores + u0 * topk, d_counts + u0, 0, nullptr, nullptr, nullptr, k > 0);
     }, &launched);
     const hipError_t e = download_chunks(h, outs, 3, off, launched);
     if (rc == DM_OK && e != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string("tdm beam search (pipelined download): ") + hipGetErrorString(e));
@@ -1301,7 +1316,7 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
   }
   // the search and its download; d_tc / d_ts / d_tn: device trace buffers or null
   auto finish = [&](int32_t *d_tc, float *d_ts, int32_t *d_tn) -> int {
-    int rc_f = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tc, d_ts, d_tn);
+    int rc_f = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tc, d_ts, d_tn, false);
     if (rc_f != DM_OK) return rc_f;
     hipError_t e = staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1353,22 +1368,16 @@ static int otm64_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int
 // OTM search on device buffers: d_ids / d_scores [U][2*beam], d_counts [U]; optional level traces (device)
 static int otm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, int beam, int leaf_level, int32_t *d_ids,
                           float *d_scores, int32_t *d_counts, int max_levels, int32_t *d_tc, float *d_ts, int32_t *d_tn,
-                          const SearchPlan &pl) {
+                          const SearchPlan &pl, bool keep_rows) {
   const int stride = 2 * beam;
-  int rc = ensure_ws(h, (size_t)pl.grid * pl.nteams * pl.ws_cap * 16);
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipMemsetAsync(d_ids, 0xFF, (size_t)U * stride * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_scores, 0, (size_t)U * stride * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream));
-  if (h->rows_keep) HIPCHK(h, hipMemsetAsync(h->d_rows + 1, 0, 8, h->stream));
-  else HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));
   BeamParams p;
   fill_common(h, p);
-  const size_t per = (size_t)pl.grid * pl.nteams * pl.ws_cap;
+  const int rc = fill_frontier(h, p, pl);
+  if (rc != DM_OK) return rc;
+  HIPCHK(h, prefill_results(h, U, stride, d_ids, d_scores, 4, d_counts));
+  HIPCHK(h, reset_search_counters(h, keep_rows));
   p.seq = d_seq; p.U = U; p.L = L; p.use_mask = 1; p.beam = beam; p.topk = stride; p.mode = 1; p.otm_leaf_level = leaf_level;
-  p.nteams = pl.nteams; p.cap = pl.cap; p.pcap = pl.pcap; p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_stride = stride;
-  p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p + per; p.ws_khi = (uint32_t *)h->ws.p + 2 * per;
-  p.ws_klo = (uint32_t *)h->ws.p + 3 * per; p.ws_cap = pl.ws_cap;
+  p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_stride = stride;
   p.trace_codes = d_tc; p.trace_scores = d_ts; p.trace_counts = d_tn; p.trace_levels = d_tn ? max_levels : 0;
   return launch_beam(h, p, pl);
 }
@@ -1401,7 +1410,7 @@ int dm_otm_beam_search_dev(dm_handle_t h, const int32_t *d_seq_codes, int64_t U,
   level_start_int(beam, &start, &level);
   SearchPlan pl;
   if ((rc = plan_search(h, beam, U, L, leaf_level - level, false, &pl)) != DM_OK) return rc;
-  return otm_search_dev(h, d_seq_codes, U, L, beam, leaf_level, d_out_node_ids, d_out_scores, d_out_counts, 0, nullptr, nullptr, nullptr, pl);
+  return otm_search_dev(h, d_seq_codes, U, L, beam, leaf_level, d_out_node_ids, d_out_scores, d_out_counts, 0, nullptr, nullptr, nullptr, pl, false);
 }
 
 static int otm_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L, int beam, int leaf_level,
@@ -1435,22 +1444,20 @@ static int otm_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L
   const int n_chunks = tn ? 1 : host_pipe_plan(stride * 8, U, off);
   if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
     int launched;
-    rc = launch_chunks(h, n_chunks, off, [&](int, int64_t u0, int64_t uk) {
+    rc = launch_chunks(h, n_chunks, off, [&](int k, int64_t u0, int64_t uk) {
       SearchPlan plk;
       const int rc_ = plan_search(h, beam, uk, L, leaf_level - level, false, &plk);
-      return rc_ != DM_OK ? rc_ : otm_search_dev(h, d_seq + u0 * L, uk, L, beam, leaf_level, d_ids + u0 * stride, d_scores + u0 * stride, d_counts + u0, 0, nullptr, nullptr, nullptr, plk);
+      return rc_ != DM_OK ? rc_ : otm_search_dev(h, d_seq + u0 * L, uk, L, beam, leaf_level, d_ids + u0 * stride, d_scores + u0 * stride, d_counts + u0, 0, nullptr, nullptr, nullptr, plk, k > 0);
     }, &launched);
     const hipError_t e = download_chunks(h, outs, 3, off, launched);
     if (rc == DM_OK && e != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string("dm_otm_beam_search (pipelined download): ") + hipGetErrorString(e));
     if (rc != DM_OK) return rc;
   } else {
     if (tn) HIPCHK(h, hipMemsetAsync(d_tn, 0, nt * 4, h->stream));
-    if ((rc = otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts, max_levels, d_tc, d_ts, d_tn, pl)) != DM_OK) return rc;
+    if ((rc = otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts, max_levels, d_tc, d_ts, d_tn, pl, false)) != DM_OK) return rc;
     HIPCHK(h, download_all(h, outs, tn ? 6 : 3, U, h->stream));
   }
-  HIPCHK(h, hipMemcpyAsync(&h->h_rows, h->d_rows, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->last_rows = (int64_t)h->h_rows;
   return DM_OK;
 }
 
@@ -1517,7 +1524,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
   if ((rc = t.alloc(d_seq, (size_t)U * L * 4)) != DM_OK) return rc;
   if ((rc = t.alloc(d_keys, keys.size() * 8)) != DM_OK) return rc;
   hipError_t e = hipMemcpyAsync(d_seq, seq_item_ids, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(h->d_rows, 0, 16, h->stream);
+  if (e == hipSuccess) e = reset_search_counters(h, false);
   if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_tdm_bruteforce_topk: upload failed");
   BeamParams p;
   fill_common(h, p);
@@ -1527,8 +1534,8 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
   p.bf_per_slice = per; p.bf_out_keys = d_keys;
   p.ws_code = (int32_t *)h->ws.p; p.ws_score = (float *)h->ws.p; p.ws_khi = (uint32_t *)h->ws.p; p.ws_klo = (uint32_t *)h->ws.p;
   p.ws_cap = 0;
-  SearchPlan pl;
-  pl.nteams = nteams; pl.cap = cap; pl.pcap = pcap; pl.lds = lds; pl.ws_cap = 0; pl.wkernel = false;
+  SearchPlan pl;          // mode 2 always scores with the fp32-input MFMA: split stays false
+  pl.nteams = nteams; pl.cap = cap; pl.pcap = pcap; pl.lds = lds; pl.ws_cap = 0;
   int64_t groups = (n_work + nteams - 1) / nteams;
   pl.grid = (int)(groups < h->n_cu ? groups : h->n_cu);
   if ((rc = launch_beam(h, p, pl)) != DM_OK) return rc;
@@ -1650,25 +1657,24 @@ extern "C" int dm_debug_phase_cycles(dm_handle_t h, unsigned long long *out8) {
 extern "C" int dm_debug_dr_slow_layers(dm_handle_t h, unsigned long long *out, int reset) {
   if (!h || !out) return DM_ERR_INVALID;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(out, h->d_rows + 2, 8, hipMemcpyDeviceToHost));
-  if (reset) HIPCHK(h, hipMemset(h->d_rows + 2, 0, 8));
+  HIPCHK(h, hipMemcpy(out, &h->d_ctr->dr_slow, 8, hipMemcpyDeviceToHost));
+  if (reset) HIPCHK(h, hipMemset(&h->d_ctr->dr_slow, 0, 8));
   return DM_OK;
 }
 // debug: user-layers the one-wave cut of the sliced Deep-Retrieval search handed to the block version
 extern "C" int dm_debug_dr_wave_fallbacks(dm_handle_t h, unsigned long long *out, int reset) {
   if (!h || !out) return DM_ERR_INVALID;
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(out, h->d_rows + 5, 16, hipMemcpyDeviceToHost));      // out[0] = count, out[1] = per-reason byte counters
-  if (reset) HIPCHK(h, hipMemset(h->d_rows + 5, 0, 16));
+  HIPCHK(h, hipMemcpy(out, &h->d_ctr->dr_wave_count, 16, hipMemcpyDeviceToHost));      // out[0] = count, out[1] = per-reason byte counters
+  if (reset) HIPCHK(h, hipMemset(&h->d_ctr->dr_wave_count, 0, 16));
   return DM_OK;
 }
 int dm_last_scored_rows(dm_handle_t h, int64_t *rows) {
   if (!h || !rows) return DM_ERR_INVALID;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   unsigned long long r = 0;
-  HIPCHK(h, hipMemcpy(&r, h->d_rows, 8, hipMemcpyDeviceToHost));
-  h->last_rows = (int64_t)r;
-  *rows = h->last_rows;
+  HIPCHK(h, hipMemcpy(&r, &h->d_ctr->rows, 8, hipMemcpyDeviceToHost));
+  *rows = (int64_t)r;
   return DM_OK;
 }
 

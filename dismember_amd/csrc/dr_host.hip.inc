@@ -45,7 +45,7 @@ template <typename T>
 static int dr_launch_gemm(dm_ctx *h, const DrGemmParams<T> &p, bool timed = true) {
   if (p.M <= 0 || p.N <= 0) return DM_OK;
   dim3 grid((unsigned)((p.N + DR_TN - 1) / DR_TN), (unsigned)((p.M + DR_TM - 1) / DR_TM));
-  LaunchTimer tm(h, LaunchTimer::KEEP, timed);
+  LaunchTimer tm(h, EV_MAIN, timed);
   if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL(dr_gemm_kernel<T>, grid, dim3(256), 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
@@ -54,7 +54,7 @@ static int dr_launch_gemm(dm_ctx *h, const DrGemmParams<T> &p, bool timed = true
 // A search is several launches (history GEMM, layer 0, statistics and cut per layer).  An event pair around EACH of them (what
 // dm_kernel_timing_get_kind reports by kind) drains the GPU between two kernels: measured 0.39 -> 0.32 ms per 1 024 users, 0.63 -> 0.55 per
 // 4 096, 2.12 -> 2.07 per 16 384 without them — back-to-back kernels overlap their tails.  So by default ONE pair brackets the whole
-// search (kind 0: its device time), and the per-launch pairs are recorded only under DM_DR_TIME_LAUNCHES=1 (read per call: bench.py and
+// search (EV_MAIN: its device time), and the per-launch pairs are recorded only under DM_DR_TIME_LAUNCHES=1 (read per call: bench.py and
 // tools/dr_bench.py time the search without, then run a breakdown pass with).
 static inline bool dr_time_launches() { const char *e = getenv("DM_DR_TIME_LAUNCHES"); return e && e[0] == '1'; }
 
@@ -264,12 +264,8 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
   for (int64_t u0 = 0; u0 < U; u0 += chunk) {
     const int64_t n = U - u0 < chunk ? U - u0 : chunk;
     const bool detail = dr_time_launches();
-    hipEvent_t w0 = nullptr, w1 = nullptr;
-    if (!detail) {
-      h->ev_next_kind = 0;
-      if ((rc = next_events(h, &w0, &w1)) != DM_OK) return rc;
-      HIPCHK(h, hipEventRecord(w0, h->stream));
-    }
+    LaunchTimer whole(h, EV_MAIN, !detail);          // the one pair around the whole search; stopped where either route ends
+    if (whole.rc != DM_OK) return whole.rc;
     DrGemmParams<T> g{};
     g.A = (const T *)s->d_layer_emb; g.lda = 0; g.gidx = d_seq + u0 * L; g.Lg = L; g.E = E;
     g.B = (const T *)s->d_wseq; g.ldb = (int64_t)L * E; g.bias = (const T *)s->d_sbias; g.zero = (const T *)s->d_zero;
@@ -282,30 +278,26 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
       q.a_scale = ldexpf(1.0f, s->sh_a); q.c_unscale = ldexpf(1.0f, -(s->sh_a + s->sh_b));
       q.embp = (const _Float16 *)s->d_emb_stages; q.Bt = (const _Float16 *)s->d_wseq_stages; q.zeroh = (const _Float16 *)s->d_zero;
       const bool x = s->d_emb_stages && L <= DR_X_MAXL && (s->x_min_rows > 0 ? n >= s->x_min_rows : dr_gemm_x_pays(n, q.N, h->n_cu));
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (detail) {
-        if ((rc = next_events(h, &e0, &e1)) != DM_OK) return rc;
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-      }
+      LaunchTimer tm(h, EV_MAIN, detail);
+      if (tm.rc != DM_OK) return tm.rc;
       if (x) hipLaunchKernelGGL(dr_gemm_split_x_kernel, dim3(dr_gemm_x_grid(q.M, q.N)), dim3(512), 0, h->stream, q);
       else {
         dim3 grid((unsigned)((q.N + DR_TN - 1) / DR_TN), (unsigned)((q.M + DR_TM - 1) / DR_TM));
         hipLaunchKernelGGL(dr_gemm_split_kernel, grid, dim3(256), 0, h->stream, q);
       }
       HIPCHK(h, hipGetLastError());
-      if (detail) HIPCHK(h, hipEventRecord(e1, h->stream));
+      if ((rc = tm.stop()) != DM_OK) return rc;
     } else if ((rc = dr_launch_gemm<T>(h, g, detail)) != DM_OK) return rc;
     DrBeamParams<T> p{};
     p.S = (const T *)s->S.p;
     for (int i = 0; i < DR_MAXD * (DR_MAXD - 1) / 2; i++) p.tabs[i] = (const T *)s->d_tabs[i];
     p.K = K; p.D = D; p.beam = beam; p.n2 = n2; p.U = n;
     p.fast = dr_beam_fast_ok(K, n2) && !s->exact_only ? 1 : 0; p.nl = dr_beam_nl(K, n2);
-    p.slow_count = (unsigned long long *)h->d_rows + 2;
+    p.slow_count = &h->d_ctr->dr_slow;
     p.phase = h->d_phase;
     p.out_paths = d_paths + u0 * beam * D; p.out_probs = d_probs + u0 * beam; p.out_counts = d_counts + u0;
     const int64_t max_grid = (int64_t)h->n_cu * 8;
     const unsigned grid = (unsigned)(n < max_grid ? n : max_grid);
-    hipEvent_t e0, e1;
     if (s->sliced && p.fast && K <= DRS_W * DRS_NS && n2 <= 64 && D <= DR_MAXD && n >= s->sliced_min) {      // (small batches: one launch beats five)
       // column-sliced search (dr_sliced.hip.inc): layer 0, then per layer a statistics launch over (user, path, slice) and a cut
       // launch over users; state and partial statistics in one grow-only block
@@ -323,9 +315,9 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
       q.out_paths = p.out_paths; q.out_probs = p.out_probs; q.out_counts = p.out_counts; q.slow_count = p.slow_count;
       HIPCHK(h, hipFuncSetAttribute((const void *)drs_layer0_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       q.nodes_n = nodes[0]; q.pprob_n = pprob[0]; q.np_n = npv[0]; q.last = D == 1 ? 1 : 0;
-      // every launch gets its own event pair; dm_kernel_timing_get_kind: 11 = layer 0, 10 + 2d = statistics of layer d, 11 + 2d = its cut,
-      // 21 + 2d = the block version's pass over the users the one-wave cut flagged
-      // (10 = the history GEMM of a sliced search)
+      // under DM_DR_TIME_LAUNCHES every launch gets its own event pair; dm_kernel_timing_get_kind: EV_DR_CUT = layer 0, EV_DR_STATS + 2 d =
+      // statistics of layer d, EV_DR_CUT + 2 d = its cut, EV_DR_BLOCK + 2 d = the block version's pass over the users the one-wave version
+      // flagged (the history GEMM is EV_MAIN, like the single kernel of the other route)
       auto timed = [&](int kind, auto launch) -> int {
         LaunchTimer tm(h, kind, detail);
         if (tm.rc != DM_OK) return tm.rc;
@@ -339,10 +331,10 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
         q.only_todo = 0;
         if (wave0) {
           HIPCHK(h, hipMemsetAsync(q.todo, 0, (size_t)n * 4, h->stream));
-          if ((rc = timed(11, [&]() { hipLaunchKernelGGL(drs_layer0_wave_kernel<T>, dim3((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)h->n_cu * 8)), dim3(256), 0, h->stream, q); })) != DM_OK) return rc;
+          if ((rc = timed(EV_DR_CUT, [&]() { hipLaunchKernelGGL(drs_layer0_wave_kernel<T>, dim3((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)h->n_cu * 8)), dim3(256), 0, h->stream, q); })) != DM_OK) return rc;
           q.only_todo = 1;                                      // the users the one-wave version flagged
         }
-        if ((rc = timed(wave0 ? 21 : 11, [&]() { hipLaunchKernelGGL(drs_layer0_kernel<T>, dim3(grid), dim3(DR_NT), lds, h->stream, p, q); })) != DM_OK) return rc;
+        if ((rc = timed(wave0 ? EV_DR_BLOCK : EV_DR_CUT, [&]() { hipLaunchKernelGGL(drs_layer0_kernel<T>, dim3(grid), dim3(DR_NT), lds, h->stream, p, q); })) != DM_OK) return rc;
         q.only_todo = 0;
       }
       const size_t lds_sel = drs_select_lds((int)sizeof(T), D, n2, p.nl);
@@ -361,13 +353,13 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
         do {                                                                                                                                       \
           HIPCHK(h, hipFuncSetAttribute((const void *)(drs_select_kernel<T, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sel));      \
           HIPCHK(h, hipFuncSetAttribute((const void *)(drs_select_wave_kernel<T, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_selw)); \
-          if ((rc = timed(10 + 2 * d, [&]() { hipLaunchKernelGGL((drs_stats_kernel<T, NT>), dim3(g_stats), dim3(256), 0, h->stream, q, d); })) != DM_OK) return rc; \
+          if ((rc = timed(EV_DR_STATS + 2 * d, [&]() { hipLaunchKernelGGL((drs_stats_kernel<T, NT>), dim3(g_stats), dim3(256), 0, h->stream, q, d); })) != DM_OK) return rc; \
           q.only_todo = 0;                                                                                                                         \
           if (wave_cut) {                                                                                                                          \
-            if ((rc = timed(11 + 2 * d, [&]() { hipLaunchKernelGGL((drs_select_wave_kernel<T, NT>), dim3(g_selw), dim3(256), lds_selw, h->stream, q, d); })) != DM_OK) return rc; \
+            if ((rc = timed(EV_DR_CUT + 2 * d, [&]() { hipLaunchKernelGGL((drs_select_wave_kernel<T, NT>), dim3(g_selw), dim3(256), lds_selw, h->stream, q, d); })) != DM_OK) return rc; \
             q.only_todo = 1;                                                                                                                       \
           }                                                                                                                                        \
-          if ((rc = timed(wave_cut ? 21 + 2 * d : 11 + 2 * d, [&]() { hipLaunchKernelGGL((drs_select_kernel<T, NT>), dim3(grid), dim3(DR_NT), lds_sel, h->stream, q, d); })) != DM_OK) return rc; \
+          if ((rc = timed((wave_cut ? EV_DR_BLOCK : EV_DR_CUT) + 2 * d, [&]() { hipLaunchKernelGGL((drs_select_kernel<T, NT>), dim3(grid), dim3(DR_NT), lds_sel, h->stream, q, d); })) != DM_OK) return rc; \
         } while (0)
         switch (d) {
           case 1: DRS_LAYER(1); break;
@@ -377,17 +369,15 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
 #undef DRS_LAYER
         cur ^= 1;
       }
-      if (!detail) HIPCHK(h, hipEventRecord(w1, h->stream));
+      if ((rc = whole.stop()) != DM_OK) return rc;
       continue;
     }
-    if (detail) {
-      if ((rc = next_events(h, &e0, &e1)) != DM_OK) return rc;
-      HIPCHK(h, hipEventRecord(e0, h->stream));
-    }
+    LaunchTimer tm(h, EV_MAIN, detail);
+    if (tm.rc != DM_OK) return tm.rc;
     if (D <= 3) hipLaunchKernelGGL((dr_beam_kernel<T, 3>), dim3(grid), dim3(DR_NT), lds, h->stream, p);
     else hipLaunchKernelGGL((dr_beam_kernel<T, DR_MAXD>), dim3(grid), dim3(DR_NT), lds, h->stream, p);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(detail ? e1 : w1, h->stream));
+    if ((rc = tm.stop()) != DM_OK || (rc = whole.stop()) != DM_OK) return rc;
   }
   return DM_OK;
 }

@@ -671,7 +671,7 @@ __global__ __launch_bounds__(256, DRS_SELW_WPS) void drs_select_wave_kernel(DrsP
       }
     }
     if (fallback) {
-      if (lane == 0) { p.todo[u] = 1; if (p.slow_count) { atomicAdd(p.slow_count + 3, 1ull); atomicAdd(p.slow_count + 4, 1ull << (8 * why)); } }      // (d_rows + 5, + 6: dm_debug_dr_wave_fallbacks)
+      if (lane == 0) { p.todo[u] = 1; if (p.slow_count) { atomicAdd(p.slow_count + 3, 1ull); atomicAdd(p.slow_count + 4, 1ull << (8 * why)); } }      // (SearchCounters::dr_wave_count, dr_wave_reasons: dm_debug_dr_wave_fallbacks)
       continue;
     }
     // rank sort of the nc candidates by (probability key, lower index first); the first ksel are the new paths (CandidateSearcher.scala:49-57)

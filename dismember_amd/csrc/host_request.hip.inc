@@ -2,8 +2,6 @@
 // dm_hip.hip, otm64_search_host in otm64.hip.inc) and the event pair around one launch.  A front end states its own policy — which
 // requests are staged, served in place or cut into chunks — and calls these.
 
-static int next_events(dm_ctx *h, hipEvent_t *a, hipEvent_t *b);
-
 // ---- frontier sizing of a beam search: cap = slots of a level's candidate list (2 * beam in whole 16-row tiles, at least two tiles),
 // pcap = the sort's power of two above it
 static void frontier_caps(int max_beam, int *cap, int *pcap) {
@@ -15,17 +13,42 @@ static void frontier_caps(int max_beam, int *cap, int *pcap) {
   if (pcap) *pcap = p;
 }
 
-// ---- HIP-event pair around one launch on the handle's stream (dm_kernel_timing_get[_kind]).  kind: what the pair is recorded as
-// (KEEP = the handle's current ev_next_kind); on = false: no pair at all, rc stays DM_OK and stop() does nothing.
+// ---- what an event pair is recorded as (dm_kernel_timing_get_kind).  The numbers are read by tools and tests: they do not change.
+// Deep-Retrieval's sliced search numbers its launches per layer d: EV_DR_STATS + 2 d = the statistics of layer d >= 1, EV_DR_CUT + 2 d =
+// its cut (d = 0: the layer-0 launch), EV_DR_BLOCK + 2 d = the block version's second pass over the users the one-wave cut flagged.
+// 40 and 41 mean two things: the grouped fp64 training step of a DIN model and the serving launches of a DeepFM model (a handle holds one).
+enum EvKind {
+  EV_MAIN = 0,            // a search's main kernel, a whole Deep-Retrieval search, and every launch nobody asks for by kind
+  EV_DEFERRED = 1,        // the second pass over the users the one-wave-per-SIMD beam kernel deferred
+  EV_DR_STATS = 10, EV_DR_CUT = 11, EV_DR_BLOCK = 21,
+  EV_ROWS = 30,           // general rows (rows_kernel.hip.inc)
+  EV_DFM_USER = 40, EV_DFM_LEVEL = 41,
+  EV_TG_SETUP = 40, EV_TG_ROWS = 41, EV_TG_WGRAD_A = 42, EV_TG_USER_BWD = 43, EV_TG_WGRAD_B = 44,
+};
+
+// the next pair of the handle's pool, recorded as `kind`
+static int next_events(dm_ctx *h, int kind, hipEvent_t *a, hipEvent_t *b) {
+  if (h->ev_used >= 4096) h->ev_used = 0;      // a service that never reads the timings keeps a bounded pool (oldest pairs are reused)
+  if (h->ev_used == h->ev_pool.size()) {
+    hipEvent_t e0, e1;
+    HIPCHK(h, hipEventCreate(&e0));
+    HIPCHK(h, hipEventCreate(&e1));
+    h->ev_pool.push_back({e0, e1});
+  }
+  *a = h->ev_pool[h->ev_used].first; *b = h->ev_pool[h->ev_used].second;
+  if (h->ev_kind.size() <= h->ev_used) h->ev_kind.resize(h->ev_used + 1);
+  h->ev_kind[h->ev_used] = kind;
+  h->ev_used++;
+  return DM_OK;
+}
+
+// ---- HIP-event pair around one launch (or one bracket of launches) on the handle's stream.  on = false: no pair at all, rc stays
+// DM_OK and stop() does nothing.
 struct LaunchTimer {
-  static constexpr int KEEP = -1;
   dm_ctx *h; hipEvent_t e0 = nullptr, e1 = nullptr; int rc = DM_OK; bool on;
-  explicit LaunchTimer(dm_ctx *h_, int kind = KEEP, bool on_ = true) : h(h_), on(on_) {
+  explicit LaunchTimer(dm_ctx *h_, int kind = EV_MAIN, bool on_ = true) : h(h_), on(on_) {
     if (!on) return;
-    const int k = h->ev_next_kind;
-    if (kind != KEEP) h->ev_next_kind = kind;
-    rc = next_events(h, &e0, &e1);
-    h->ev_next_kind = k;
+    rc = next_events(h, kind, &e0, &e1);
     if (rc == DM_OK && hipEventRecord(e0, h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "hipEventRecord failed");
   }
   int stop() { return (on && rc == DM_OK && hipEventRecord(e1, h->stream) != hipSuccess) ? fail(h, DM_ERR_HIP, "hipEventRecord failed") : rc; }
@@ -74,8 +97,8 @@ static int wait_host_direct(dm_ctx *h, volatile int32_t *m_cnt, int64_t U, const
 }
 
 // ---- pipelined download of a request cut into chunks of users (host_pipe_plan in dm_hip.hip says why and how).
-// fn(k, u0, uk) enqueues the search of chunk k = users [u0, u0 + uk).  Chunks after the first keep the scored-rows counter counting
-// (rows_keep); the first failure stops the launches.  *launched = the chunks whose event was recorded.
+// fn(k, u0, uk) enqueues the search of chunk k = users [u0, u0 + uk); a chunk k > 0 keeps the scored-rows counter counting
+// (keep_rows of the searches).  The first failure stops the launches.  *launched = the chunks whose event was recorded.
 template <typename Fn>
 static int launch_chunks(dm_ctx *h, int n_chunks, const int64_t *off, Fn fn, int *launched) {
   *launched = 0;
@@ -89,9 +112,7 @@ static int launch_chunks(dm_ctx *h, int n_chunks, const int64_t *off, Fn fn, int
   for (int k = 0; k < n_chunks && rc == DM_OK; k++) {
     const int64_t u0 = off[k], uk = off[k + 1] - u0;
     if (uk <= 0) break;
-    h->rows_keep = k > 0;
     rc = fn(k, u0, uk);
-    h->rows_keep = false;
     if (rc == DM_OK && hipEventRecord(h->chunk_ev[(size_t)k], h->stream) != hipSuccess) rc = fail(h, DM_ERR_HIP, "host-buffer search: event record failed");
     if (rc == DM_OK) ++*launched;
   }

@@ -225,7 +225,7 @@ static int launch_beam64_EK(dm_ctx *h, const Beam64Params &p, int grid, int lds)
   HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam64_kernel<E, KQ, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   if (KT == 1) snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam64_kernel<%d, %d>", E, KQ);
   else snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam64_kernel<%d, %d, %d>", E, KQ, KT);
-  LaunchTimer tm(h, LaunchTimer::KEEP, !(p.host_direct && !h->time_direct));       // single-request path: the launch and nothing else
+  LaunchTimer tm(h, EV_MAIN, !(p.host_direct && !h->time_direct));       // single-request path: the launch and nothing else
   if (tm.rc != DM_OK) return tm.rc;
   hipLaunchKernelGGL((dm_beam64_kernel<E, KQ, KT>), dim3(grid), dim3(DM64_BLOCK), lds, h->stream, p);
   HIPCHK(h, hipGetLastError());
@@ -293,13 +293,14 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   { const char *e_ = getenv("DM_OTM64_LDS_SORT"); p.force_lds_sort = (e_ && e_[0] == '1') ? 1 : 0; }
   p.sm_scale = sm_scale64(h);
   p.phase_cycles = h->d_phase;
-  if (!p.static_users || U > 64) HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));       // queue head + scored-row counter
+  if (!p.static_users || U > 64) HIPCHK(h, reset_search_counters(h, false));
   const double *f = (const double *)h->lazy.d_frag64;
   p.emb = base; p.num_index = h->num_index; p.w1aA = (const f64x2 *)f; p.attA = f + n; p.w1bB = f + 2 * n; p.b1 = l1_b; p.w2 = l2_w; p.b2 = b2;
   p.seq = d_seq; p.U = U; p.L = L; p.beam = beam; p.leaf_level = leaf_level; p.nteams = nteams; p.cap = fcap; p.pcap = pcap;
   p.out_ids = d_ids; p.out_sc64 = d_sc64; p.out_sc32 = d_sc32; p.out_counts = d_counts; p.out_stride = 2 * beam;
   p.tr_codes = d_tc; p.tr_sc64 = d_ts64; p.tr_sc32 = d_ts32; p.tr_counts = d_tn; p.tr_levels = d_tn ? max_levels : 0; p.tr_cap = cap;
-  p.scratch = (double *)h->scratch64.p; p.next_user = h->d_rows + 1; p.scored_rows = (p.static_users && U <= 64) ? h->d_rows + 3 : h->d_rows;
+  p.scratch = (double *)h->scratch64.p; p.next_user = &h->d_ctr->queue_head;
+  p.scored_rows = (p.static_users && U <= 64) ? &h->d_ctr->rows_sink : &h->d_ctr->rows;
   rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) { return launch_beam64_E<decltype(e)::value>(h, p, grid, lds); });
   if (rc == DM_OK) *done = true;
   return rc;
@@ -313,10 +314,7 @@ static int otm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, i
                             double *d_ts64, float *d_ts32, int32_t *d_tn) {
   snprintf(h->last_kernel, sizeof(h->last_kernel), sizeof(T) == 8 ? "otm64 pipeline" : "otm level pipeline (f32, L > 16)");
   // the pipeline's emit kernel writes the live slots only (the fused kernel fills whole rows itself)
-  HIPCHK(h, hipMemsetAsync(d_ids, 0xFF, (size_t)U * 2 * beam * 4, h->stream));
-  if (d_sc64) HIPCHK(h, hipMemsetAsync(d_sc64, 0, (size_t)U * 2 * beam * 8, h->stream));
-  if (d_sc32) HIPCHK(h, hipMemsetAsync(d_sc32, 0, (size_t)U * 2 * beam * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(d_counts, 0, (size_t)U * 4, h->stream));
+  HIPCHK(h, prefill_results(h, U, (size_t)2 * beam, d_ids, d_sc64 ? (void *)d_sc64 : (void *)d_sc32, d_sc64 ? 8 : 4, d_counts));
   const int E = h->embed;
   const T *base = (const T *)h->d_compact;
   const T *att_w = base + h->num_index * E, *l1_w = att_w + (int64_t)E * E, *l1_b = l1_w + (int64_t)2 * E * E;
@@ -401,7 +399,7 @@ static int otm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, i
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));      // the workspace is reused by the next pass
   }
-  { const unsigned long long r_ = (unsigned long long)rows_scored; HIPCHK(h, hipMemcpy(h->d_rows, &r_, 8, hipMemcpyHostToDevice)); }   // dm_last_scored_rows
+  { const unsigned long long r_ = (unsigned long long)rows_scored; HIPCHK(h, hipMemcpy(&h->d_ctr->rows, &r_, 8, hipMemcpyHostToDevice)); }   // dm_last_scored_rows
   return DM_OK;
 }
 

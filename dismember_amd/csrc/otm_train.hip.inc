@@ -278,7 +278,7 @@ static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, 
   if (pipe_search) rc = otm64_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, f64_search ? (double *)(A + o_sc) : nullptr,
                                          f64_search ? nullptr : (float *)(A + o_sc), d_cnt, levels, cap, d_tc,
                                          f64_search ? (double *)(A + o_ts) : nullptr, f64_search ? nullptr : (float *)(A + o_ts), d_tnn);
-  else rc = otm_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, (float *)(A + o_sc), d_cnt, levels, d_tc, (float *)(A + o_ts), d_tnn, pl);
+  else rc = otm_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, (float *)(A + o_sc), d_cnt, levels, d_tc, (float *)(A + o_ts), d_tnn, pl, false);
   if (rc != DM_OK) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const auto t2 = clk::now();

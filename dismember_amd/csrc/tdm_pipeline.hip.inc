@@ -298,7 +298,7 @@ static int tdm_pl_fold(dm_ctx *h, TdmPlScorer &scorer, const int32_t *d_seq, int
   float *sc = ar.ptr<float>(o_sc), *lf_score = ar.ptr<float>(o_lfs);
   unsigned long long *lf_key = ar.ptr<unsigned long long>(o_lfk);
   if ((rc = scorer.attach(h, ar)) != DM_OK) return rc;
-  HIPCHK(h, hipMemsetAsync(h->d_rows, 0, 16, h->stream));
+  HIPCHK(h, reset_search_counters(h, false));
   const size_t lds_step = (size_t)stride * 16;
   HIPCHK(h, hipFuncSetAttribute((const void *)tdm_pl_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
   TdmPlTree t{h->d_exists, h->d_leaf, h->d_node_id, h->d_id_to_code, h->n_slots, h->num_index, h->non_leaf_offset, h->max_code};
@@ -311,7 +311,7 @@ static int tdm_pl_fold(dm_ctx *h, TdmPlScorer &scorer, const int32_t *d_seq, int
     sp.t = t; sp.lf_code = lf_code; sp.lf_score = lf_score; sp.lf_pos = lf_pos; sp.lf_n = lf_n;
     sp.consumed_off = d_coff ? d_coff + u0 : nullptr; sp.stride = stride; sp.lcap = lcap; sp.beam = o->beam; sp.topk = o->topk;
     sp.widen = (o->widen_consumed && d_coff) ? 1 : 0; sp.n_iter = n_iter; sp.start = start; sp.U = Un;
-    sp.scored_rows = (unsigned long long *)h->d_rows;
+    sp.scored_rows = &h->d_ctr->rows;
     int32_t *cur = c0, *nxt = c1, *ncur = n0, *nnxt = n1;
     sp.init = 1; sp.next = cur; sp.next_cnt = ncur; sp.sc = sc;
     hipLaunchKernelGGL(tdm_pl_step_kernel, dim3((unsigned)Un), dim3(256), lds_step, h->stream, sp);

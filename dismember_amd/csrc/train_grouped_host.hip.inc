@@ -36,8 +36,8 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   const double *f64f = (const double *)h->lazy.d_frag64;          // w1aA, attA, w1bB
   const double *tr = (const double *)h->d_tr64;              // attA, w1aA, w1bA, attTA, w1aTA, w1bTA (training fragment order)
   double *grad = (double *)h->d_grad;
-  // every launch gets an event pair (dm_kernel_timing_get_kind: 40 = per-user setup, 41 = the row kernel, 42 = dW1a + per-user sums,
-  // 43 = per-user backward, 44 = dW1b / datt.W): bench.py prices the row kernel against the fp64 matrix peak from these
+  // every launch gets an event pair (dm_kernel_timing_get_kind: EV_TG_SETUP = per-user setup, EV_TG_ROWS = the row kernel, EV_TG_WGRAD_A = dW1a +
+  // per-user sums, EV_TG_USER_BWD = per-user backward, EV_TG_WGRAD_B = dW1b / datt.W): bench.py prices the row kernel against the fp64 matrix peak from these
   auto timed = [&](int kind, auto launch) -> int {
     LaunchTimer tm(h, kind);
     if (tm.rc != DM_OK) return tm.rc;
@@ -48,7 +48,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   // ---- per-user setup
   TgSetupParams sp{};
   sp.emb = base; sp.num_index = h->num_index; sp.attA = f64f + n2; sp.w1bB = f64f + 2 * n2; sp.b1 = b1; sp.seq = d_seq; sp.U = U; sp.L = L; sp.b = bufs;
-  if ((rc = timed(40, [&] { hipLaunchKernelGGL((tg_setup_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, sp); })) != DM_OK) return rc;
+  if ((rc = timed(EV_TG_SETUP, [&] { hipLaunchKernelGGL((tg_setup_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, sp); })) != DM_OK) return rc;
   // ---- rows: forward + backward
   TgRowsParams rp{};
   rp.emb = base; rp.num_index = h->num_index; rp.l1_w = l1_w; rp.w2 = w2; rp.b2 = h->lazy.b2_64;
@@ -73,7 +73,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     if (blocks > h->n_cu) blocks = h->n_cu;
     auto go = [&](auto kern) -> int {
       HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      return timed(41, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(TG_BLOCK), lds, h->stream, rp); });
+      return timed(EV_TG_ROWS, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(TG_BLOCK), lds, h->stream, rp); });
     };
     switch ((L + 3) / 4) {
       case 1: rc = go(tg_rows_kernel<E, 1>); break;
@@ -95,13 +95,13 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     const int64_t want = std::max<int64_t>(1, (int64_t)h->n_cu * 8 / NBq);     // two waves per SIMD, a few chunks per slot
     wp.users_per_chunk = (int)std::max<int64_t>(1, (U + 4 * want - 1) / (4 * want));
     const unsigned chunks = (unsigned)((U + wp.users_per_chunk - 1) / wp.users_per_chunk);
-    if ((rc = timed(42, [&] { hipLaunchKernelGGL((tg_wgrad_kernel<E>), dim3(1, chunks), dim3(64 * NBq), 0, h->stream, wp); })) != DM_OK) return rc;
+    if ((rc = timed(EV_TG_WGRAD_A, [&] { hipLaunchKernelGGL((tg_wgrad_kernel<E>), dim3(1, chunks), dim3(64 * NBq), 0, h->stream, wp); })) != DM_OK) return rc;
   }
   // ---- per-user backward, then dW1b / datt.W over the U x 16 per-user rows
   TgUserBwdParams up{};
   up.attTA = (const f64x4 *)(tr + 3 * n2); up.w1bTA = (const f64x4 *)(tr + 5 * n2); up.seq = d_seq; up.U = U; up.L = L; up.num_index = h->num_index;
   up.b = bufs; up.grad = grad;
-  if ((rc = timed(43, [&] { hipLaunchKernelGGL((tg_user_bwd_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, up); })) != DM_OK) return rc;
+  if ((rc = timed(EV_TG_USER_BWD, [&] { hipLaunchKernelGGL((tg_user_bwd_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, up); })) != DM_OK) return rc;
   WGradParamsT<double> wg{};
   wg.emb = base; wg.codes = nullptr; wg.DZ = bufs.dGrows; wg.AT = bufs.T1rows; wg.DA = bufs.dTrows; wg.CB = bufs.Krows;
   wg.B = U * 16; wg.num_index = h->num_index; wg.grad = grad; wg.mat_base = 1;
@@ -109,7 +109,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     const int64_t want = std::max<int64_t>(1, (int64_t)h->n_cu * 16 / (2 * NBq));
     wg.chunk = std::max<int64_t>(128, (((wg.B + want - 1) / want) + 7) / 8 * 8);
     const int chunks = (int)((wg.B + wg.chunk - 1) / wg.chunk);
-    if ((rc = timed(44, [&] { hipLaunchKernelGGL((dm_wgrad_kernel<double, E>), dim3(2 * NBq, chunks), dim3(64), 0, h->stream, wg); })) != DM_OK) return rc;
+    if ((rc = timed(EV_TG_WGRAD_B, [&] { hipLaunchKernelGGL((dm_wgrad_kernel<double, E>), dim3(2 * NBq, chunks), dim3(64), 0, h->stream, wg); })) != DM_OK) return rc;
   }
   HIPCHK(h, hipGetLastError());
   return DM_OK;

@@ -731,7 +731,11 @@ class Engine:
         return n.value, ms.value
 
     def timing_get_kind(self, kind):
-        """launches and summed milliseconds of one kind of launch (0 = search kernels, 1 = deferred-user second pass)"""
+        """launches and summed milliseconds of one kind of launch, as the library's EvKind names them (csrc/host_request.hip.inc):
+        0 = a search's main kernel, a whole Deep-Retrieval search and every launch without a kind of its own; 1 = the second pass over
+        the users the one-wave beam kernel deferred; under DM_DR_TIME_LAUNCHES=1 the sliced Deep-Retrieval search's launches, per
+        layer d: 11 = layer 0, 10 + 2d = statistics, 11 + 2d = cut, 21 + 2d = the block version's second pass; 30 = general rows
+        (din_forward); 40 / 41 = DeepFM user / level launches, and 40 .. 44 the launches of the grouped fp64 training step"""
         n, ms = C.c_int(0), C.c_double(0)
         self._chk(N.lib().dm_kernel_timing_get_kind(self._h, int(kind), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -61,7 +61,7 @@ def main():
     os.environ.pop("DM_DR_TIME_LAUNCHES", None)
     nl, ms = eng.timing_get()
     out["beam_search"].update({"kernel_ms_per_step": ms / a.steps, "launches_per_step": nl / a.steps, "ms_per_step_with_per_launch_events": dtb / a.steps * 1e3})
-    per = {}
+    per = {}      # by EvKind (csrc/host_request.hip.inc): 0 = EV_MAIN, 11 = EV_DR_CUT, 10 / 11 / 21 + 2 d = statistics / cut / block pass of layer d
     for kind, name in ((0, "gemm / single kernel"), (11, "layer0"), (12, "stats_d1"), (13, "select_d1"), (14, "stats_d2"), (15, "select_d2"), (23, "select_d1_todo_pass"), (25, "select_d2_todo_pass")):
         n_, ms_ = eng.timing_get_kind(kind)
         if n_:
