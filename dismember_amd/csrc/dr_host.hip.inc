@@ -1,11 +1,23 @@
 // Host side of the Deep-Retrieval entry points (dm_dr_*), SURVEY.md row A13.  Kernels: dr_kernel.hip.inc.
 
+struct dm_dr_train;
+struct dm_dr_state;
+static void dr_train_release(dm_dr_state *s);
 struct dm_dr_state {
   bool loaded = false, has_rerank = false, paths_loaded = false;
   bool exact_only = false;            // DM_DR_EXACT_ONLY=1 at load time: always take the radix-select path (debugging)
   int dtype = DM_F32, E = 0, L = 0, K = 0, D = 0;
   int64_t num_item = 0;
-  void *d_layer_emb = nullptr;       // [(num_item + K(D-1)) x E]
+  // the layer model as ONE vector [layer_emb ; W_0 ; b_0 ; ... ; W_{D-1} ; b_{D-1}] (what dm_dr_adam_step moves); d_layer_emb, d_w and
+  // d_b point into it.  Everything below d_zero is derived from it (dr_derive) and goes stale when it moves
+  void *d_par = nullptr;
+  int64_t n_par = 0;
+  void *d_w[DR_MAXD] = {}, *d_b[DR_MAXD] = {};   // W_d [K x (L+d)E] with its node columns, b_d [K]
+  bool derived_stale = false;        // dm_dr_adam_step moved the weights: dr_check_search derives again before the next search
+  bool wseq_stale = false;           // ... and the training step refreshes d_wseq alone (its dX product reads it)
+  bool x_refused = false;            // the 256 x 256 GEMM's second table copy did not fit at load
+  struct dm_dr_train *tr = nullptr;  // dm_dr_train_init (dr_train.hip.inc)
+  void *d_layer_emb = nullptr;       // [(num_item + K(D-1)) x E]: the first section of d_par
   void *d_wseq = nullptr;            // [D*K x L*E]: history columns of every layer's Linear
   void *d_sbias = nullptr;           // [D*K]
   void *d_zero = nullptr;            // 64 zero bytes x 4: the row a padding id gathers
@@ -33,7 +45,9 @@ struct dm_dr_state {
 
 static void dm_dr_free(dm_dr_state *s) {
   if (!s) return;
-  dm_release(s->d_layer_emb, s->d_wseq, s->d_sbias, s->d_zero, s->d_wseq_split, s->d_wseq_stages, s->d_emb_stages);
+  dr_train_release(s);
+  s->d_layer_emb = nullptr;
+  dm_release(s->d_par, s->d_wseq, s->d_sbias, s->d_zero, s->d_wseq_split, s->d_wseq_stages, s->d_emb_stages);
   for (auto *v : {&s->d_tabs, &s->d_rowmax, &s->d_etabs})
     for (auto &t : *v) dm_release(t);
   dm_release(s->d_rr_emb, s->d_rr_w, s->d_rr_b, s->d_sm_w, s->d_sm_b, s->d_codes, s->d_item_off, s->d_items);
@@ -65,59 +79,62 @@ static int dr_copy_in(dm_ctx *h, void **dst, const void *src, size_t bytes, bool
   return DM_OK;
 }
 
+// the history columns of every layer, [D*K x L*E], out of the W_d (the training step refreshes these alone: its dX product reads them)
 template <typename T>
-static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
-  dm_dr_state *s = new dm_dr_state();
-  dm_dr_free(h->dr); h->dr = s;
-  const int E = m->embed, L = m->seq_len, K = m->num_node, D = m->num_layer;
-  const bool dev = m->on_device != 0;
-  s->dtype = m->dtype; s->E = E; s->L = L; s->K = K; s->D = D; s->num_item = m->num_item;
-  s->exact_only = getenv("DM_DR_EXACT_ONLY") != nullptr;
-  { const char *e_ = getenv("DM_DR_SLICED"); if (e_ && e_[0] == '0') s->sliced = false; }
-  { const char *e_ = getenv("DM_DR_SLICED_MIN_USERS"); if (e_ && atoll(e_) > 0) s->sliced_min = atoll(e_); }
+static int dr_refresh_wseq(dm_ctx *h, dm_dr_state *s) {
+  const int E = s->E, L = s->L, K = s->K, D = s->D;
   const size_t esz = sizeof(T);
-  const int64_t n_emb = (m->num_item + (int64_t)K * (D - 1)) * E;    // LayerModel.scala:24
-  int rc;
-  if ((rc = dr_copy_in(h, &s->d_layer_emb, m->layer_emb, n_emb * esz, dev)) != DM_OK) return rc;
-  ALLOC(h, s->d_wseq, (size_t)D * K * L * E * esz);
-  ALLOC(h, s->d_sbias, (size_t)D * K * esz);
-  const size_t zero_bytes = (size_t)4 * E * esz > 4096 ? (size_t)4 * E * esz : 4096;   // the 256 x 256 split GEMM steps through a zero block as long as a
-  ALLOC(h, s->d_zero, zero_bytes);                                                     // row's records (4 E bytes); the other GEMMs read one row of E values
-  HIPCHK(h, hipMemsetAsync(s->d_zero, 0, zero_bytes, h->stream));
-  DevTemps tmp(h);
-  std::vector<void *> tmpw(D, nullptr);
   for (int d = 0; d < D; d++) {
     const size_t cols = (size_t)(L + d) * E;
-    if ((rc = tmp.alloc(tmpw[d], (size_t)K * cols * esz)) != DM_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(tmpw[d], m->layer_w[d], (size_t)K * cols * esz, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpy2DAsync((char *)s->d_wseq + (size_t)d * K * L * E * esz, (size_t)L * E * esz, tmpw[d], cols * esz,
+    HIPCHK(h, hipMemcpy2DAsync((char *)s->d_wseq + (size_t)d * K * L * E * esz, (size_t)L * E * esz, s->d_w[d], cols * esz,
                                (size_t)L * E * esz, K, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync((char *)s->d_sbias + (size_t)d * K * esz, m->layer_b[d], K * esz,
-                             dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+  }
+  s->wseq_stale = false;
+  return DM_OK;
+}
+#define DR_ALLOC_ONCE(h, ptr, bytes) do { if (!(ptr)) ALLOC(h, ptr, bytes); } while (0)      // dr_derive runs more than once per model
+
+// Everything the search reads that is computed FROM the weights: the history columns d_wseq, the biases d_sbias, the node tables with their
+// row maxima and exp tables, the split scales, planes and stage records.  Called after the copy-in of dm_dr_load_model and again (by
+// dr_check_search) after the weights moved on the device (dm_dr_adam_step): every buffer is allocated on the first call and refilled on
+// the later ones, with the same kernels on the same inputs — a model that was trained here and one loaded from the downloaded weights
+// search bit for bit alike.
+template <typename T>
+static int dr_derive(dm_ctx *h, dm_dr_state *s) {
+  const int E = s->E, L = s->L, K = s->K, D = s->D;
+  const size_t esz = sizeof(T);
+  const int64_t n_emb = (s->num_item + (int64_t)K * (D - 1)) * E;
+  int rc;
+  DR_ALLOC_ONCE(h, s->d_wseq, (size_t)D * K * L * E * esz);
+  DR_ALLOC_ONCE(h, s->d_sbias, (size_t)D * K * esz);
+  if ((rc = dr_refresh_wseq<T>(h, s)) != DM_OK) return rc;
+  for (int d = 0; d < D; d++) {
+    const size_t cols = (size_t)(L + d) * E;
+    HIPCHK(h, hipMemcpyAsync((char *)s->d_sbias + (size_t)d * K * esz, s->d_b[d], K * esz, hipMemcpyDeviceToDevice, h->stream));
     for (int t = 0; t < d; t++) {           // T_{d,t}[node][k] = W_d[k, (L+t)E:(L+t+1)E] . emb(num_item + t*K + node)
       void *&tab = s->d_tabs[d * (d - 1) / 2 + t];
-      ALLOC(h, tab, ((size_t)K * K + 1024) * esz);          // +1024: the beam kernel reads whole 64-wide chunks past a row's end
+      DR_ALLOC_ONCE(h, tab, ((size_t)K * K + 1024) * esz);          // +1024: the beam kernel reads whole 64-wide chunks past a row's end
       HIPCHK(h, hipMemsetAsync((char *)tab + (size_t)K * K * esz, 0, 1024 * esz, h->stream));
       DrGemmParams<T> g{};
-      g.A = (const T *)s->d_layer_emb + (m->num_item + (int64_t)t * K) * E; g.lda = E;
+      g.A = (const T *)s->d_layer_emb + (s->num_item + (int64_t)t * K) * E; g.lda = E;
       g.gidx = nullptr; g.Lg = 0; g.E = E;
-      g.B = (const T *)tmpw[d] + (size_t)(L + t) * E; g.ldb = (int64_t)cols;
+      g.B = (const T *)s->d_w[d] + (size_t)(L + t) * E; g.ldb = (int64_t)cols;
       g.bias = nullptr; g.zero = (const T *)s->d_zero;
       g.C = (T *)tab; g.ldc = K;
       g.M = K; g.N = K; g.Kd = E;
       if ((rc = dr_launch_gemm<T>(h, g)) != DM_OK) return rc;
       void *&rm = s->d_rowmax[d * (d - 1) / 2 + t];
-      ALLOC(h, rm, (size_t)K * esz);
+      DR_ALLOC_ONCE(h, rm, (size_t)K * esz);
       hipLaunchKernelGGL(drs_rowmax_kernel<T>, dim3(256), dim3(256), 0, h->stream, (const T *)tab, K, (T *)rm);
       void *&et = s->d_etabs[d * (d - 1) / 2 + t];
-      ALLOC(h, et, ((size_t)K * K + 1024) * esz);
+      DR_ALLOC_ONCE(h, et, ((size_t)K * K + 1024) * esz);
       HIPCHK(h, hipMemsetAsync((char *)et + (size_t)K * K * esz, 0, 1024 * esz, h->stream));
       hipLaunchKernelGGL(drs_exptab_kernel<T>, dim3(1024), dim3(256), 0, h->stream, (const T *)tab, (const T *)rm, K, (T *)et);
       HIPCHK(h, hipGetLastError());
     }
   }
   if (sizeof(T) == 4 && E % 64 == 0) {       // (the split GEMM stages 64-column tiles: a tile never straddles an embedding row)
-    // split-fp16 history GEMM (dm_set_scorer_mode): scales from the largest magnitudes, W planes built once
+    // split-fp16 history GEMM (dm_set_scorer_mode): scales from the largest magnitudes, W planes built once per set of weights
     if (!h->lazy.d_maxabs) ALLOC(h, h->lazy.d_maxabs, 8);
     HIPCHK(h, hipMemsetAsync(h->lazy.d_maxabs, 0, 8, h->stream));
     hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, nullptr, n_emb, 0, h->lazy.d_maxabs);
@@ -127,18 +144,10 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
     HIPCHK(h, hipMemcpyAsync(mb, h->lazy.d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s->sh_a = split_shift(mb[0]); s->sh_b = split_shift(mb[1]);
-    ALLOC(h, s->d_wseq_split, (size_t)2 * D * K * L * E * 2);
+    DR_ALLOC_ONCE(h, s->d_wseq_split, (size_t)2 * D * K * L * E * 2);
     hipLaunchKernelGGL(dr_split_planes_kernel, dim3(1024), dim3(256), 0, h->stream, (const float *)s->d_wseq, (int64_t)D * K * L * E,
                        ldexpf(1.0f, s->sh_b), (_Float16 *)s->d_wseq_split);
     HIPCHK(h, hipGetLastError());
-  }
-  if (m->rerank_emb) {
-    if ((rc = dr_copy_in(h, &s->d_rr_emb, m->rerank_emb, (size_t)m->num_item * E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_rr_w, m->rerank_w, (size_t)E * L * E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_rr_b, m->rerank_b, (size_t)E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_sm_w, m->softmax_w, (size_t)m->num_item * E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_sm_b, m->softmax_b, (size_t)m->num_item * esz, dev)) != DM_OK) return rc;
-    s->has_rerank = true;
   }
   if (sizeof(T) == 4 && s->d_wseq_split && L <= DR_X_MAXL) {
     // operands of the 256 x 256 history GEMM: a second copy of the embedding rows (4 E bytes per row, as the fp32 table) and of the
@@ -146,11 +155,13 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
     // there the model keeps the 128 x 128 kernel for every batch size
     { const char *e_ = getenv("DM_DR_GEMM_X_MIN_ROWS"); if (e_ && atoll(e_) > 0) s->x_min_rows = atoll(e_); }
     const char *x_ = getenv("DM_DR_GEMM_X");                   // "0": keep the 128 x 128 kernel (and save the second table copy)
-    if (!(x_ && x_[0] == '0')) {
+    if (!(x_ && x_[0] == '0') && !s->x_refused) {
       const std::string err0 = h->err;           // (an optimisation that does not fit leaves no trace, not even a last-error string)
-      if (dm_alloc(h, &s->d_emb_stages, (size_t)n_emb * 4) != DM_OK || dm_alloc(h, &s->d_wseq_stages, (size_t)D * K * L * E * 4) != DM_OK) {
+      if ((!s->d_emb_stages && dm_alloc(h, &s->d_emb_stages, (size_t)n_emb * 4) != DM_OK) ||
+          (!s->d_wseq_stages && dm_alloc(h, &s->d_wseq_stages, (size_t)D * K * L * E * 4) != DM_OK)) {
         (void)hipGetLastError();
         dm_release(s->d_emb_stages, s->d_wseq_stages);
+        s->x_refused = true;                     // (a later derive of the same model does not try again)
         h->err = err0;
       } else {
         hipLaunchKernelGGL(dr_split_rows_kernel, dim3(8192), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, n_emb / E, E,
@@ -162,6 +173,56 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
     }
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  s->derived_stale = false;
+  return DM_OK;
+}
+
+// number of elements of the trainable vector [layer_emb ; W_0 ; b_0 ; ... ; W_{D-1} ; b_{D-1}] (LayerModel.scala:22-39)
+static int64_t dr_param_count(int64_t num_item, int K, int D, int L, int E) {
+  int64_t n = (num_item + (int64_t)K * (D - 1)) * E;
+  for (int d = 0; d < D; d++) n += (int64_t)K * (L + d) * E + K;
+  return n;
+}
+
+template <typename T>
+static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
+  dm_dr_state *s = new dm_dr_state();
+  dm_dr_free(h->dr); h->dr = s;          // (drops the training state of the model that was there)
+  const int E = m->embed, L = m->seq_len, K = m->num_node, D = m->num_layer;
+  const bool dev = m->on_device != 0;
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  s->dtype = m->dtype; s->E = E; s->L = L; s->K = K; s->D = D; s->num_item = m->num_item;
+  s->exact_only = getenv("DM_DR_EXACT_ONLY") != nullptr;
+  { const char *e_ = getenv("DM_DR_SLICED"); if (e_ && e_[0] == '0') s->sliced = false; }
+  { const char *e_ = getenv("DM_DR_SLICED_MIN_USERS"); if (e_ && atoll(e_) > 0) s->sliced_min = atoll(e_); }
+  const size_t esz = sizeof(T);
+  const int64_t n_emb = (m->num_item + (int64_t)K * (D - 1)) * E;    // LayerModel.scala:24
+  // ---- copy-in: ONE vector holds the layer model, in the order Adam sees it; the table the search gathers from is its first section
+  s->n_par = dr_param_count(m->num_item, K, D, L, E);
+  ALLOC(h, s->d_par, (size_t)s->n_par * esz);
+  s->d_layer_emb = s->d_par;
+  HIPCHK(h, hipMemcpyAsync(s->d_par, m->layer_emb, (size_t)n_emb * esz, kind, h->stream));
+  int64_t off = n_emb;
+  for (int d = 0; d < D; d++) {
+    const int64_t nw = (int64_t)K * (L + d) * E;
+    s->d_w[d] = (char *)s->d_par + (size_t)off * esz; s->d_b[d] = (char *)s->d_par + (size_t)(off + nw) * esz;
+    HIPCHK(h, hipMemcpyAsync(s->d_w[d], m->layer_w[d], (size_t)nw * esz, kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_b[d], m->layer_b[d], (size_t)K * esz, kind, h->stream));
+    off += nw + K;
+  }
+  const size_t zero_bytes = (size_t)4 * E * esz > 4096 ? (size_t)4 * E * esz : 4096;   // the 256 x 256 split GEMM steps through a zero block as long as a
+  ALLOC(h, s->d_zero, zero_bytes);                                                     // row's records (4 E bytes); the other GEMMs read one row of E values
+  HIPCHK(h, hipMemsetAsync(s->d_zero, 0, zero_bytes, h->stream));
+  int rc;
+  if (m->rerank_emb) {
+    if ((rc = dr_copy_in(h, &s->d_rr_emb, m->rerank_emb, (size_t)m->num_item * E * esz, dev)) != DM_OK) return rc;
+    if ((rc = dr_copy_in(h, &s->d_rr_w, m->rerank_w, (size_t)E * L * E * esz, dev)) != DM_OK) return rc;
+    if ((rc = dr_copy_in(h, &s->d_rr_b, m->rerank_b, (size_t)E * esz, dev)) != DM_OK) return rc;
+    if ((rc = dr_copy_in(h, &s->d_sm_w, m->softmax_w, (size_t)m->num_item * E * esz, dev)) != DM_OK) return rc;
+    if ((rc = dr_copy_in(h, &s->d_sm_b, m->softmax_b, (size_t)m->num_item * esz, dev)) != DM_OK) return rc;
+    s->has_rerank = true;
+  }
+  if ((rc = dr_derive<T>(h, s)) != DM_OK) return rc;
   h->ev_used = 0;
   s->loaded = true;
   return DM_OK;
@@ -388,6 +449,10 @@ static int dr_check_search(dm_ctx *h, const char *who, int64_t U, int beam, bool
   if (need_rerank && !s->has_rerank) return fail(h, DM_ERR_STATE, std::string(who) + ": model was loaded without rerank arrays");
   if (need_rerank && !s->paths_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": path -> items table not loaded");
   if (U < 0 || beam < 1 || beam > 2048) return fail(h, DM_ERR_INVALID, std::string(who) + ": beam must be in [1, 2048]");
+  if (s->derived_stale) {               // the weights moved since the tables were built (dm_dr_adam_step): once per search, not per step
+    HIPCHK(h, hipSetDevice(h->device));
+    return s->dtype == DM_F32 ? dr_derive<float>(h, s) : dr_derive<double>(h, s);
+  }
   return DM_OK;
 }
 

@@ -24,6 +24,9 @@ enum EvKind {
   EV_ROWS = 30,           // general rows (rows_kernel.hip.inc)
   EV_DFM_USER = 40, EV_DFM_LEVEL = 41,
   EV_TG_SETUP = 40, EV_TG_ROWS = 41, EV_TG_WGRAD_A = 42, EV_TG_USER_BWD = 43, EV_TG_WGRAD_B = 44,
+  // the Deep-Retrieval training step under DM_DR_TIME_LAUNCHES=1 (dr_train.hip.inc): forward GEMMs, softmax + cross-entropy, dX products,
+  // dW / db products with their slab sums, embedding gradient (pairs, sort, segment sums), Adam
+  EV_DRT_FWD = 50, EV_DRT_SOFTMAX = 51, EV_DRT_DX = 52, EV_DRT_DW = 53, EV_DRT_EMB = 54, EV_DRT_ADAM = 55,
 };
 
 // the next pair of the handle's pool, recorded as `kind`

@@ -682,6 +682,48 @@ class Engine:
     def dr_recommend_dev(self, d_seq, U, beam, topk, d_ids, d_scores, d_counts):
         self._chk(N.lib().dm_dr_recommend_dev(self._h, d_seq, U, int(beam), int(topk), d_ids, d_scores, d_counts))
 
+    # ---- Deep-Retrieval E-step: the layer model's training step
+    def dr_train_init(self, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
+        o = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)
+        self._chk(N.lib().dm_dr_train_init(self._h, C.byref(o)))
+
+    def dr_train_free(self):
+        self._chk(N.lib().dm_dr_train_free(self._h))
+
+    def dr_train_forward_backward(self, seq_ids, paths):
+        """seq_ids [B, L] internal ids (-1 = padding), paths [B, D] nodes: one row per (sample, path of its target item).
+        Replaces the gradient with this batch's; -> per-layer losses [D] (float64)."""
+        d = self.dr_dims
+        seq = _i32(seq_ids).reshape(-1, d["L"])
+        pa = _i32(paths).reshape(-1, d["D"])
+        assert len(seq) == len(pa)
+        loss = np.empty(d["D"], np.float64)
+        self._chk(N.lib().dm_dr_train_forward_backward(self._h, _p(seq, N.i32p), _p(pa, N.i32p), len(seq),
+                                                       loss.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss
+
+    def dr_train_forward_backward_dev(self, d_seq, d_paths, B):
+        """the same on device arrays (not range-checked) -> per-layer losses [D]"""
+        loss = np.empty(self.dr_dims["D"], np.float64)
+        self._chk(N.lib().dm_dr_train_forward_backward_dev(self._h, d_seq, d_paths, int(B), loss.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss
+
+    def dr_adam_step(self, grad_scale=1.0):
+        self._chk(N.lib().dm_dr_adam_step(self._h, float(grad_scale)))
+
+    def dr_train_param_count(self):
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_dr_train_param_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def dr_train_download(self, what="weights"):
+        """The trainable vector [layer_emb ; W_0 ; b_0 ; ... ; W_{D-1} ; b_{D-1}] ("weights"), its gradient ("grad") or an Adam
+        moment ("s", "r"), in the model's dtype."""
+        n = self.dr_train_param_count()
+        out = np.empty(n, self.dr_dims["dtype"])
+        self._chk(N.lib().dm_dr_train_download(self._h, {"weights": 0, "grad": 1, "s": 2, "r": 3}[what], out.ctypes.data_as(C.c_void_p), n))
+        return out
+
     # ---- device-resident path (bench)
     def dev_alloc(self, nbytes):
         p = C.c_void_p()
@@ -735,7 +777,9 @@ class Engine:
         0 = a search's main kernel, a whole Deep-Retrieval search and every launch without a kind of its own; 1 = the second pass over
         the users the one-wave beam kernel deferred; under DM_DR_TIME_LAUNCHES=1 the sliced Deep-Retrieval search's launches, per
         layer d: 11 = layer 0, 10 + 2d = statistics, 11 + 2d = cut, 21 + 2d = the block version's second pass; 30 = general rows
-        (din_forward); 40 / 41 = DeepFM user / level launches, and 40 .. 44 the launches of the grouped fp64 training step"""
+        (din_forward); 40 / 41 = DeepFM user / level launches, and 40 .. 44 the launches of the grouped fp64 training step; under
+        DM_DR_TIME_LAUNCHES=1 the Deep-Retrieval training step: 50 = forward GEMMs, 51 = softmax + cross-entropy, 52 = dX products,
+        53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam"""
         n, ms = C.c_int(0), C.c_double(0)
         self._chk(N.lib().dm_kernel_timing_get_kind(self._h, int(kind), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -502,6 +502,35 @@ int dm_dr_beam_search_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, in
 int dm_dr_recommend_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, int beam, int topk, int32_t *d_out_ids,
                         double *d_out_scores, int32_t *d_out_counts);
 
+/* ---- Deep-Retrieval E-step: one training step of the LAYER model on the device ----
+ * D/model/LayerModel.scala:22-49, D/dataset/MiniBatch.scala:18-50, D/loss/CrossEntropyLayer.scala, D/optim/LocalOptimizer.scala:58-116.
+ * A batch is B rows, one per (training sample, one of the target item's J paths) — the host expands the J paths per item, as
+ * transformLayerData does: seq_ids [B x seq_len] internal ids (-1 = padding: a zero row that receives no gradient), paths [B x D] nodes
+ * in [0, K).  Per layer d: Z_d = X_d W_d^T + b_d over X_d[r] = [emb[seq] ; emb[num_item + t K + path[r][t]], t < d], loss_d = the mean
+ * over the B rows of -log softmax(Z_d[r])[path[r][d]] (targets 0-based, sizeAverage), and the gradient of sum_d loss_d.
+ * The gradient is the mean over the WHOLE batch: the reference splits a batch over its threads and averages the per-thread means
+ * (LocalOptimizer.scala:135-194), the same value whenever the thread count divides B.
+ * The trainable vector is [layer_emb ; W_0 ; b_0 ; ... ; W_{D-1} ; b_{D-1}], in the model's type (DM_F64 is the reference's); the rerank
+ * arrays are neither read nor written.  There is one copy of the embedding table: the search reads the vector's first section.
+ * Every sum has a fixed order: the same state and the same batch give the same bytes in gradient and weights, run to run.
+ * All of these are refused on a clone (DM_ERR_STATE); dm_dr_load_model on a training handle drops the training state. */
+int dm_dr_train_init(dm_handle_t h, const dm_adam_opts *opts);      /* needs dm_dr_load_model (DM_ERR_STATE); zero gradient and moments */
+int dm_dr_train_free(dm_handle_t h);                                /* the model keeps serving */
+/* replaces the gradient with this batch's (zeroGradParameters + forward + backward); out_loss [D] (host) or NULL.  Range-checks ids and
+ * nodes (DM_ERR_INDEX); B <= 0 or a null array is DM_ERR_INVALID; DM_ERR_STATE before dm_dr_train_init; more than 4 194 240 rows, or
+ * B (L + D - 1) >= 2^31, is DM_ERR_UNSUPPORTED. */
+int dm_dr_train_forward_backward(dm_handle_t h, const int32_t *seq_ids, const int32_t *paths, int64_t B, double *out_loss);
+/* the same on device arrays, NOT range-checked; out_loss is still a host pointer (the call synchronizes) */
+int dm_dr_train_forward_backward_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_paths, int64_t B, double *out_loss);
+/* Adam.optimize (scalann/.../optim/Adam.scala:19-73) over the vector with dm_adam_step's kernels and rules (lr_decay, bias correction,
+ * gradient scaled by grad_scale and zeroed): the embedding rows a gradient has ever reached plus the dense blocks, or the whole vector
+ * when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 — the same bytes either way.  Marks the search's derived
+ * copies (history columns, node tables, split planes) stale: the next search rebuilds them, not every step. */
+int dm_dr_adam_step(dm_handle_t h, float grad_scale);
+int dm_dr_train_param_count(dm_handle_t h, int64_t *n);
+/* what: 0 weights (needs no training state), 1 gradient, 2 first moment, 3 second moment; n must be the parameter count (DM_ERR_INVALID) */
+int dm_dr_train_download(dm_handle_t h, int what, void *out, int64_t n);
+
 /* ---- synthetic-data helpers (bench / tests only; nothing in the reference corresponds) ---- */
 /* fill d_ptr[0..n) (float, device) with N(mean, std): counter-based splitmix64 + Box-Muller, reproducible per (seed, index) */
 int dm_fill_normal(dm_handle_t h, float *d_ptr, int64_t n, float mean, float std, uint64_t seed);
