@@ -135,6 +135,14 @@ SIGNATURES = {
     "dm_dr_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
     "dm_dr_train_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dm_dr_train_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "dm_dr_rerank_train_init": (C.c_int, [C.c_void_p, C.POINTER(AdamOpts), C.POINTER(AdamOpts), C.c_int, C.c_uint64, C.c_int]),
+    "dm_dr_rerank_train_free": (C.c_int, [C.c_void_p]),
+    "dm_dr_rerank_forward_backward": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int64, C.POINTER(C.c_double)]),
+    "dm_dr_rerank_forward_backward_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]),
+    "dm_dr_rerank_sample": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int64, i32p]),
+    "dm_dr_rerank_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
+    "dm_dr_rerank_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "dm_dr_rerank_full_loss": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.POINTER(C.c_double)]),
     "dm_memcpy_d2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "dm_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "dm_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,8 +1,10 @@
 // Host side of the Deep-Retrieval entry points (dm_dr_*), SURVEY.md row A13.  Kernels: dr_kernel.hip.inc.
 
 struct dm_dr_train;
+struct dm_dr_rr_train;
 struct dm_dr_state;
 static void dr_train_release(dm_dr_state *s);
+static void dr_rr_train_release(dm_dr_state *s);
 struct dm_dr_state {
   bool loaded = false, has_rerank = false, paths_loaded = false;
   bool exact_only = false;            // DM_DR_EXACT_ONLY=1 at load time: always take the radix-select path (debugging)
@@ -32,7 +34,12 @@ struct dm_dr_state {
   bool sliced = true;                 // DM_DR_SLICED=0 at load time keeps the one-workgroup-per-user kernel
   int64_t sliced_min = 512;           // batches below this take the single launch (DM_DR_SLICED_MIN_USERS: tests run the sliced path on tiny batches)
   DevGrow state;                                     // layer state + partial statistics of the sliced search
+  // the rerank model as TWO vectors, one per optimizer (dm_dr_rerank_adam_step, dr_rerank_train.hip.inc): the graph's
+  // [rerank_emb ; rerank_w ; rerank_b] and the criterion's [softmax_w ; softmax_b].  The five pointers below point into them; the
+  // rerank path keeps no derived copies, so serving reads the trained bytes as they are
+  void *d_rr_par = nullptr, *d_sm_par = nullptr;
   void *d_rr_emb = nullptr, *d_rr_w = nullptr, *d_rr_b = nullptr, *d_sm_w = nullptr, *d_sm_b = nullptr;
+  struct dm_dr_rr_train *rt = nullptr;  // dm_dr_rerank_train_init
   // path -> items
   int64_t P = 0;
   int max_bucket = 0;
@@ -46,11 +53,13 @@ struct dm_dr_state {
 static void dm_dr_free(dm_dr_state *s) {
   if (!s) return;
   dr_train_release(s);
+  dr_rr_train_release(s);
   s->d_layer_emb = nullptr;
   dm_release(s->d_par, s->d_wseq, s->d_sbias, s->d_zero, s->d_wseq_split, s->d_wseq_stages, s->d_emb_stages);
   for (auto *v : {&s->d_tabs, &s->d_rowmax, &s->d_etabs})
     for (auto &t : *v) dm_release(t);
-  dm_release(s->d_rr_emb, s->d_rr_w, s->d_rr_b, s->d_sm_w, s->d_sm_b, s->d_codes, s->d_item_off, s->d_items);
+  s->d_rr_emb = s->d_rr_w = s->d_rr_b = s->d_sm_w = s->d_sm_b = nullptr;
+  dm_release(s->d_rr_par, s->d_sm_par, s->d_codes, s->d_item_off, s->d_items);
   for (DevGrow *g : {&s->state, &s->S, &s->UV, &s->io, &s->cand}) g->release();
   delete s;
 }
@@ -71,13 +80,6 @@ static int dr_launch_gemm(dm_ctx *h, const DrGemmParams<T> &p, bool timed = true
 // search (EV_MAIN: its device time), and the per-launch pairs are recorded only under DM_DR_TIME_LAUNCHES=1 (read per call: bench.py and
 // tools/dr_bench.py time the search without, then run a breakdown pass with).
 static inline bool dr_time_launches() { const char *e = getenv("DM_DR_TIME_LAUNCHES"); return e && e[0] == '1'; }
-
-static int dr_copy_in(dm_ctx *h, void **dst, const void *src, size_t bytes, bool on_device) {
-  int rc = dm_alloc(h, dst, bytes);
-  if (rc != DM_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(*dst, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-  return DM_OK;
-}
 
 // the history columns of every layer, [D*K x L*E], out of the W_d (the training step refreshes these alone: its dX product reads them)
 template <typename T>
@@ -215,11 +217,16 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
   HIPCHK(h, hipMemsetAsync(s->d_zero, 0, zero_bytes, h->stream));
   int rc;
   if (m->rerank_emb) {
-    if ((rc = dr_copy_in(h, &s->d_rr_emb, m->rerank_emb, (size_t)m->num_item * E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_rr_w, m->rerank_w, (size_t)E * L * E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_rr_b, m->rerank_b, (size_t)E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_sm_w, m->softmax_w, (size_t)m->num_item * E * esz, dev)) != DM_OK) return rc;
-    if ((rc = dr_copy_in(h, &s->d_sm_b, m->softmax_b, (size_t)m->num_item * esz, dev)) != DM_OK) return rc;
+    const size_t n_emb_rr = (size_t)m->num_item * E, n_w = (size_t)E * L * E;
+    ALLOC(h, s->d_rr_par, (n_emb_rr + n_w + E) * esz);
+    ALLOC(h, s->d_sm_par, (n_emb_rr + (size_t)m->num_item) * esz);
+    s->d_rr_emb = s->d_rr_par; s->d_rr_w = (char *)s->d_rr_par + n_emb_rr * esz; s->d_rr_b = (char *)s->d_rr_w + n_w * esz;
+    s->d_sm_w = s->d_sm_par; s->d_sm_b = (char *)s->d_sm_par + n_emb_rr * esz;
+    HIPCHK(h, hipMemcpyAsync(s->d_rr_emb, m->rerank_emb, n_emb_rr * esz, kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_rr_w, m->rerank_w, n_w * esz, kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_rr_b, m->rerank_b, (size_t)E * esz, kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_sm_w, m->softmax_w, n_emb_rr * esz, kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(s->d_sm_b, m->softmax_b, (size_t)m->num_item * esz, kind, h->stream));
     s->has_rerank = true;
   }
   if ((rc = dr_derive<T>(h, s)) != DM_OK) return rc;

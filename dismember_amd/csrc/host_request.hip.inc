@@ -27,6 +27,9 @@ enum EvKind {
   // the Deep-Retrieval training step under DM_DR_TIME_LAUNCHES=1 (dr_train.hip.inc): forward GEMMs, softmax + cross-entropy, dX products,
   // dW / db products with their slab sums, embedding gradient (pairs, sort, segment sums), Adam
   EV_DRT_FWD = 50, EV_DRT_SOFTMAX = 51, EV_DRT_DX = 52, EV_DRT_DW = 53, EV_DRT_EMB = 54, EV_DRT_ADAM = 55,
+  // the rerank model's training step (dr_rerank_train.hip.inc): user-vector GEMM, classes of the rows (sampler), sampled softmax, the
+  // softmax tables' gradient (pairs, sort, segment sums), dX, dW / db with their slab sums, embedding gradient, both Adam updates
+  EV_DRR_FWD = 60, EV_DRR_SAMPLE = 61, EV_DRR_SOFTMAX = 62, EV_DRR_SMGRAD = 63, EV_DRR_DX = 64, EV_DRR_DW = 65, EV_DRR_EMB = 66, EV_DRR_ADAM = 67,
 };
 
 // the next pair of the handle's pool, recorded as `kind`

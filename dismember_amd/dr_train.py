@@ -1,6 +1,8 @@
-"""Deep-Retrieval E-step over the device training step: `LocalOptimizer.optimize`'s layer-model half
-(deep-retrieval/src/main/scala/com/mass/dr/optim/LocalOptimizer.scala:58-116) — expand every sample by the J paths of its target
-item (dataset/MiniBatch.scala:18-50, transformLayerData), one forward/backward, one Adam step.  The rerank model is not trained here.
+"""Deep-Retrieval E-step over the device training steps: `LocalOptimizer.optimize`
+(deep-retrieval/src/main/scala/com/mass/dr/optim/LocalOptimizer.scala:58-133).  The layer model: expand every sample by the J paths of
+its target item (dataset/MiniBatch.scala:18-50, transformLayerData), one forward/backward, one Adam step.  With `rerank=True` the rerank
+model follows on the same batch, as the reference trains both on every mini-batch: sampled softmax over the target and `num_sampled`
+negatives, its own two Adam updates (scalann nn/SampledSoftmaxLoss.scala).
 
 One E-step / M-step round on an engine that holds a Deep-Retrieval model (`Engine.dr_load_model`):
 
@@ -16,6 +18,14 @@ One E-step / M-step round on an engine that holds a Deep-Retrieval model (`Engin
     trainer.set_item_paths(np.array([new_paths[i] for i in range(num_item)]))
 
 The first search after a step rebuilds the search's derived copies of the weights; steps in between do not.
+
+Both halves, served end to end:
+
+    trainer = DRTrainer(engine, item_paths, lr=1e-3, rerank=True, num_sampled=20, seed=1)
+    for seqs, targets in batches:
+        layer_loss, rerank_loss = trainer.step(seqs, targets)
+    print(trainer.evaluate_rerank(eval_seqs, eval_targets))      # Evaluator.evaluateReRankModel: the full softmax
+    engine.dr_recommend(user_seqs, beam, topk)                   # reads the trained rerank arrays in place
 """
 import numpy as np
 
@@ -50,15 +60,51 @@ def expand_batch(seqs, targets, item_paths):
     return np.repeat(seqs, J, axis=0), np.ascontiguousarray(item_paths[tg].reshape(len(tg) * J, -1), np.int32)
 
 
-class DRTrainer:
-    """Trains the layer model of the Deep-Retrieval model `engine` holds.  item_paths [num_item, J, D] int: the current item -> paths
-    mapping (MappingOp.itemPathMapping).  `losses` collects the per-layer loss [D] of every step."""
+def init_rerank_weights(num_item, L, E, rng, dtype=np.float64):
+    """The five rerank arrays as the reference's modules initialise them: Embedding and Linear weights and softmaxWeights N(0, 0.05)
+    (scalann nn/Embedding.scala:20, nn/Linear.scala:12, RerankModel.scala:15), the Linear bias and softmaxBiases zero (Linear.scala:13,
+    RerankModel.scala:16).  rng: a numpy Generator."""
+    n = lambda *shape: (rng.standard_normal(shape) * 0.05).astype(dtype)
+    return dict(rerank_emb=n(num_item, E), rerank_w=n(E, L * E), rerank_b=np.zeros(E, dtype),
+                softmax_w=n(num_item, E), softmax_b=np.zeros(num_item, dtype))
 
-    def __init__(self, engine, item_paths, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
+
+def split_rerank(graph, softmax, E, L, num_item):
+    """the two trainable vectors [rerank_emb ; rerank_w ; rerank_b] and [softmax_w ; softmax_b] -> the five arrays of dr_load_model"""
+    a, b = num_item * E, num_item * E + E * L * E
+    return dict(rerank_emb=graph[:a].reshape(num_item, E), rerank_w=graph[a:b].reshape(E, L * E), rerank_b=graph[b:],
+                softmax_w=softmax[:a].reshape(num_item, E), softmax_b=softmax[a:])
+
+
+def pack_rerank(weights, dtype=np.float64):
+    f = lambda k: np.asarray(weights[k], dtype).ravel()
+    return np.concatenate([f("rerank_emb"), f("rerank_w"), f("rerank_b")]), np.concatenate([f("softmax_w"), f("softmax_b")])
+
+
+class DRTrainer:
+    """Trains the Deep-Retrieval model `engine` holds.  item_paths [num_item, J, D] int: the current item -> paths mapping
+    (MappingOp.itemPathMapping).  `losses` collects the per-layer loss [D] of every step.
+
+    rerank=True also trains the rerank model (the engine's model must hold the five rerank arrays): num_sampled negatives per row drawn
+    on the device from `seed`; accumulate=True is the reference's never-cleared softmax-table gradient, False clears it per
+    batch; rerank_epochs: the reference's reRankStoppingEpoch — the rerank step runs while `epoch` (1-based, advanced by next_epoch())
+    is <= rerank_epochs (None: always).  `rerank_losses` collects its loss per step (NaN once stopped).  The rerank optimizer takes the
+    layer optimizer's options (one learning rate in the reference's conf); its softmax tables take the criterion's own (eps 1e-7, no decay)."""
+
+    def __init__(self, engine, item_paths, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8, rerank=False, num_sampled=None, seed=0,
+                 accumulate=True, rerank_epochs=None):
         self.engine = engine
         self.set_item_paths(item_paths)
         self.losses = []
+        self.rerank = bool(rerank)
+        self.rerank_losses = []
+        self.rerank_epochs = rerank_epochs
+        self.epoch = 1
         engine.dr_train_init(lr=lr, lr_decay=lr_decay, beta1=beta1, beta2=beta2, eps=eps)
+        if self.rerank:
+            if num_sampled is None:
+                raise ValueError("rerank=True needs num_sampled")
+            engine.dr_rerank_train_init(num_sampled, seed=seed, accumulate=accumulate, lr=lr, lr_decay=lr_decay, beta1=beta1, beta2=beta2, eps=eps)
 
     def set_item_paths(self, item_paths):
         p = np.ascontiguousarray(item_paths, np.int32)
@@ -68,12 +114,32 @@ class DRTrainer:
         self.item_paths = p
 
     def step(self, seqs, targets):
-        """one batch: expand by the targets' paths, forward/backward, Adam -> per-layer losses [D]"""
+        """one batch: expand by the targets' paths, forward/backward, Adam -> per-layer losses [D]; with rerank=True the rerank step
+        follows on the unexpanded batch -> (per-layer losses [D], sampled-softmax loss)"""
         seq, paths = expand_batch(seqs, targets, self.item_paths)
         loss = self.engine.dr_train_forward_backward(seq, paths)
         self.engine.dr_adam_step(1.0)
         self.losses.append(loss)
-        return loss
+        if not self.rerank:
+            return loss
+        rr = float("nan")
+        if self.rerank_epochs is None or self.epoch <= self.rerank_epochs:
+            rr = self.engine.dr_rerank_forward_backward(seqs, targets)
+            self.engine.dr_rerank_adam_step(1.0)
+        self.rerank_losses.append(rr)
+        return loss, rr
+
+    def next_epoch(self):
+        self.epoch += 1
+
+    def evaluate_rerank(self, seqs, targets):
+        """Evaluator.evaluateReRankModel: the full-softmax loss of the rerank model on (seqs, targets)"""
+        return self.engine.dr_rerank_full_loss(seqs, targets)
+
+    def rerank_weights(self):
+        """the five rerank arrays as dr_load_model takes them"""
+        d = self.engine.dr_dims
+        return split_rerank(self.engine.dr_rerank_download("graph"), self.engine.dr_rerank_download("softmax"), d["E"], d["L"], d["num_item"])
 
     def weights(self):
         d = self.engine.dr_dims
@@ -81,3 +147,5 @@ class DRTrainer:
 
     def close(self):
         self.engine.dr_train_free()
+        if self.rerank:
+            self.engine.dr_rerank_train_free()

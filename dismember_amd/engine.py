@@ -724,6 +724,71 @@ class Engine:
         self._chk(N.lib().dm_dr_train_download(self._h, {"weights": 0, "grad": 1, "s": 2, "r": 3}[what], out.ctypes.data_as(C.c_void_p), n))
         return out
 
+    # ---- Deep-Retrieval E-step: the rerank model's training step
+    def dr_rerank_train_init(self, num_sampled, seed=0, accumulate=True, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8, softmax=None):
+        """graph optimizer from the keywords; softmax: None (the reference's criterion optimizer: lr, 0.9, 0.999, eps 1e-7, no decay) or a
+        dict(lr, lr_decay, beta1, beta2, eps)"""
+        g = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)
+        sm = None if softmax is None else C.byref(N.AdamOpts(softmax["lr"], softmax.get("lr_decay", 0.0), softmax.get("beta1", 0.9),
+                                                            softmax.get("beta2", 0.999), softmax.get("eps", 1e-7)))
+        self._chk(N.lib().dm_dr_rerank_train_init(self._h, C.byref(g), sm, int(num_sampled), int(seed), 1 if accumulate else 0))
+        self._dr_num_sampled = int(num_sampled)
+
+    def dr_rerank_train_free(self):
+        self._chk(N.lib().dm_dr_rerank_train_free(self._h))
+
+    def dr_rerank_forward_backward(self, seq_ids, targets, negatives=None):
+        """seq_ids [B, L] internal ids (-1 = padding), targets [B], negatives [B, num_sampled] or None (the device draws them).
+        Replaces the graph's gradient, adds to (accumulate) or replaces the softmax tables'; -> the sampled-softmax loss (float)."""
+        seq = _i32(seq_ids).reshape(-1, self.dr_dims["L"])
+        tg = _i32(targets).reshape(-1)
+        assert len(seq) == len(tg)
+        neg = None
+        if negatives is not None:
+            neg = _i32(negatives).reshape(len(tg), self._dr_num_sampled)
+        loss = C.c_double(0.0)
+        self._chk(N.lib().dm_dr_rerank_forward_backward(self._h, _p(seq, N.i32p), _p(tg, N.i32p), None if neg is None else _p(neg, N.i32p),
+                                                        len(seq), C.byref(loss)))
+        return float(loss.value)
+
+    def dr_rerank_forward_backward_dev(self, d_seq, d_targets, d_negatives, B):
+        """the same on device arrays (not range-checked); d_negatives may be None"""
+        loss = C.c_double(0.0)
+        self._chk(N.lib().dm_dr_rerank_forward_backward_dev(self._h, d_seq, d_targets, d_negatives, int(B), C.byref(loss)))
+        return float(loss.value)
+
+    def dr_rerank_sample(self, targets, step):
+        """the negatives the device draws for `targets` at forward/backward call number `step` (0-based) -> [B, num_sampled]"""
+        tg = _i32(targets).reshape(-1)
+        out = np.empty((len(tg), self._dr_num_sampled), np.int32)
+        self._chk(N.lib().dm_dr_rerank_sample(self._h, _p(tg, N.i32p), len(tg), int(step), _p(out, N.i32p)))
+        return out
+
+    def dr_rerank_adam_step(self, grad_scale=1.0):
+        self._chk(N.lib().dm_dr_rerank_adam_step(self._h, float(grad_scale)))
+
+    def dr_rerank_sizes(self):
+        """lengths of the two trainable vectors: {"graph": [rerank_emb ; rerank_w ; rerank_b], "softmax": [softmax_w ; softmax_b]}"""
+        d = self.dr_dims
+        return {"graph": d["num_item"] * d["E"] + d["E"] * d["L"] * d["E"] + d["E"], "softmax": d["num_item"] * d["E"] + d["num_item"]}
+
+    def dr_rerank_download(self, vec="graph", what="weights"):
+        """one of the two trainable vectors ("graph", "softmax"): its weights, gradient ("grad") or an Adam moment ("s", "r")"""
+        n = self.dr_rerank_sizes()[vec]
+        out = np.empty(n, self.dr_dims["dtype"])
+        self._chk(N.lib().dm_dr_rerank_download(self._h, {"graph": 0, "softmax": 1}[vec], {"weights": 0, "grad": 1, "s": 2, "r": 3}[what],
+                                                out.ctypes.data_as(C.c_void_p), n))
+        return out
+
+    def dr_rerank_full_loss(self, seq_ids, targets):
+        """Evaluator.evaluateReRankModel: -mean log softmax over ALL items at the target"""
+        seq = _i32(seq_ids).reshape(-1, self.dr_dims["L"])
+        tg = _i32(targets).reshape(-1)
+        assert len(seq) == len(tg)
+        out = C.c_double(0.0)
+        self._chk(N.lib().dm_dr_rerank_full_loss(self._h, _p(seq, N.i32p), _p(tg, N.i32p), len(seq), C.byref(out)))
+        return float(out.value)
+
     # ---- device-resident path (bench)
     def dev_alloc(self, nbytes):
         p = C.c_void_p()

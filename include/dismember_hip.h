@@ -511,7 +511,7 @@ int dm_dr_recommend_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, int 
  * The gradient is the mean over the WHOLE batch: the reference splits a batch over its threads and averages the per-thread means
  * (LocalOptimizer.scala:135-194), the same value whenever the thread count divides B.
  * The trainable vector is [layer_emb ; W_0 ; b_0 ; ... ; W_{D-1} ; b_{D-1}], in the model's type (DM_F64 is the reference's); the rerank
- * arrays are neither read nor written.  There is one copy of the embedding table: the search reads the vector's first section.
+ * arrays are neither read nor written (their step: dm_dr_rerank_*, below).  There is one copy of the embedding table: the search reads the vector's first section.
  * Every sum has a fixed order: the same state and the same batch give the same bytes in gradient and weights, run to run.
  * All of these are refused on a clone (DM_ERR_STATE); dm_dr_load_model on a training handle drops the training state. */
 int dm_dr_train_init(dm_handle_t h, const dm_adam_opts *opts);      /* needs dm_dr_load_model (DM_ERR_STATE); zero gradient and moments */
@@ -530,6 +530,48 @@ int dm_dr_adam_step(dm_handle_t h, float grad_scale);
 int dm_dr_train_param_count(dm_handle_t h, int64_t *n);
 /* what: 0 weights (needs no training state), 1 gradient, 2 first moment, 3 second moment; n must be the parameter count (DM_ERR_INVALID) */
 int dm_dr_train_download(dm_handle_t h, int what, void *out, int64_t n);
+
+/* ---- Deep-Retrieval E-step: one training step of the RERANK model on the device ----
+ * D/model/RerankModel.scala, scalann nn/SampledSoftmaxLoss.scala + nn/mixin/ParameterOptimizer.scala, D/dataset/MiniBatch.scala:52-61,
+ * D/optim/LocalOptimizer.scala:118-133, D/evaluation/Evaluator.scala:83-93.  The second half of LocalOptimizer.optimize; independent of the
+ * layer model's training state (dm_dr_train_*), and possible on the same handle at the same time.
+ * A batch is B samples: seq_ids [B x seq_len] internal ids (-1 = padding: a zero row that receives no gradient), targets [B] in
+ * [0, num_item).  With S = num_sampled: U = X rerank_w^T + rerank_b over X[r] = [rerank_emb[seq[r][j]]]; the classes of row r are its
+ * target (slot 0) and S negatives; z[r][s] = softmax_w[class] . U[r] + softmax_b[class]; loss = the mean over the rows of
+ * -log softmax(z[r])[0]; and the gradient of that loss with respect to all five arrays.
+ * Two trainable vectors in the model's type, each with its own Adam: vec 0 = [rerank_emb ; rerank_w ; rerank_b] (the graph's optimizer,
+ * gradient replaced by every batch) and vec 1 = [softmax_w ; softmax_b] (the criterion's own optimizer).  The reference never clears the
+ * criterion's gradient (ParameterOptimizer.scala:65-88 only adds): accumulate != 0 keeps that running sum over all batches since init and
+ * is what parity with the reference means; accumulate == 0 replaces it per batch, as every other gradient here.
+ * dm_dr_recommend reads the two vectors in place: what a step wrote is what the next recommend serves, no copy, nothing to refresh.
+ * Every sum has a fixed order and there are no floating-point atomics: the same state, batch, seed and step give the same bytes.
+ * All of these are refused on a clone, on a model loaded without the five rerank arrays and (except init) before init (DM_ERR_STATE);
+ * dm_dr_load_model drops the state. */
+/* softmax == NULL: the reference's criterion optimizer (lr = graph->lr, beta 0.9 / 0.999, eps 1e-7, no decay).  num_sampled < 1 or
+ * >= num_item is DM_ERR_INVALID (the reference requires numSampled < numClasses), num_sampled + 1 > 256 DM_ERR_UNSUPPORTED.  Zero
+ * gradients and moments, both time steps at 0; released again when any allocation fails. */
+int dm_dr_rerank_train_init(dm_handle_t h, const dm_adam_opts *graph, const dm_adam_opts *softmax, int num_sampled, uint64_t seed, int accumulate);
+int dm_dr_rerank_train_free(dm_handle_t h);                         /* the model keeps serving */
+/* forward + backward of one batch; out_loss: one double (host) or NULL.  negatives [B x num_sampled] or NULL.  NULL: the device draws
+ * them (distinct, != target, uniform, ascending; `step` = the number of forward_backward calls on this state so far, what
+ * dm_dr_rerank_sample reproduces) — offered for 2 num_sampled <= num_item, DM_ERR_UNSUPPORTED above ("pass the negatives").  Given
+ * negatives are range-checked like sequence ids and targets (DM_ERR_INDEX) but may repeat within a row and may equal the target.  More
+ * than 4 194 240 rows, or B max(seq_len, num_sampled + 1) >= 2^31, is DM_ERR_UNSUPPORTED; B <= 0 or a null array DM_ERR_INVALID. */
+int dm_dr_rerank_forward_backward(dm_handle_t h, const int32_t *seq_ids, const int32_t *targets, const int32_t *negatives, int64_t B, double *out_loss);
+/* the same on device arrays, NOT range-checked; out_loss is still a host pointer (the call synchronizes) */
+int dm_dr_rerank_forward_backward_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_targets, const int32_t *d_negatives, int64_t B, double *out_loss);
+/* the draw alone: out [B x num_sampled] (host) for (seed of init, step, row).  Advances nothing. */
+int dm_dr_rerank_sample(dm_handle_t h, const int32_t *targets, int64_t B, int64_t step, int32_t *out);
+/* both Adam updates, each with its own time step; dm_dr_adam_step's rules per vector (active rows, or the whole vector when eps == 0,
+ * when a quarter of the rows is active or under DM_ADAM_DENSE=1).  The accumulating criterion's gradient is left as it is. */
+int dm_dr_rerank_adam_step(dm_handle_t h, float grad_scale);
+/* vec: 0 [rerank_emb ; rerank_w ; rerank_b], 1 [softmax_w ; softmax_b]; what: 0 weights (needs no training state), 1 gradient, 2 first
+ * moment, 3 second moment; n must be the vector's length (DM_ERR_INVALID) */
+int dm_dr_rerank_download(dm_handle_t h, int vec, int what, void *out, int64_t n);
+/* Evaluator.evaluateReRankModel's fullEvaluate: -mean log softmax(U softmax_w^T + softmax_b)[target] over ALL num_item classes, in row
+ * chunks under 256 MB of logits (DM_DR_FULL_LOSS_ROWS in the environment forces a chunk size), chunk sums added in chunk order.
+ * Needs no training state. */
+int dm_dr_rerank_full_loss(dm_handle_t h, const int32_t *seq_ids, const int32_t *targets, int64_t B, double *out);
 
 /* ---- synthetic-data helpers (bench / tests only; nothing in the reference corresponds) ---- */
 /* fill d_ptr[0..n) (float, device) with N(mean, std): counter-based splitmix64 + Box-Muller, reproducible per (seed, index) */

@@ -59,6 +59,7 @@ VOID_HOST = {
     "dm_din_forward": {"logits": [("F32", "float"), ("F64", "double")]},
     "dm_load_weights_deepfm": {"compact": [("F32", "float")]},                     # DM_F32 only
     "dm_train_download": {"out": [("F32", "float"), ("F64", "double")]},               # the loaded dtype
+    "dm_dr_rerank_download": {"out": [("F32", "float"), ("F64", "double")]},         # the loaded dtype
     "dm_comm_unique_id": {"id128": [("", "uint8_t")]},
     "dm_comm_create_rccl": {"id128": [("", "uint8_t")]},
     "dm_comm_all_gather_v": {"send": [("", "uint8_t")], "recv": [("", "uint8_t")]},
@@ -117,6 +118,11 @@ EXTENTS = {
                                 "out_seqs": "cap * L", "out_rowmask": "cap", "out_labels": "cap", "n_rows": "1"},
     "dm_tdm_sample_train_batch_dev": {"neg_counts": "n_counts", "n_rows": "1"},
     "dm_dr_load_path_items": {"item_off": "n_paths + 1"},
+    "dm_dr_rerank_forward_backward": {"targets": "B", "out_loss": "1"},
+    "dm_dr_rerank_forward_backward_dev": {"out_loss": "1"},
+    "dm_dr_rerank_sample": {"targets": "B"},
+    "dm_dr_rerank_download": {"out": "n"},
+    "dm_dr_rerank_full_loss": {"targets": "B", "out": "1"},
     "dm_allreduce_grads": {"hs": "n"},
     "dm_cluster_tree": {"emb": "n * E", "codes_out": "n", "stats": "8"},
     "dm_cluster_tree_model": {"item_ids": "n", "codes_out": "n", "stats": "8"},
