@@ -503,7 +503,7 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
     ncclResult_t e = ncclGroupStart();
     for (int i = 0; i < nh && e == ncclSuccess; i++) {
       dm_ctx *h = hs[i];
-      char *dense = (char *)h->d_grad + (size_t)(h->num_index * E) * es;
+      char *dense = (char *)h->train.grad + (size_t)(h->num_index * E) * es;
       e = ncclAllReduce(dense, dense, (size_t)nd, nty, ncclSum, h->comm->nccl, h->stream);
       if (e == ncclSuccess && maxc) e = ncclAllGather(lay[i].mine, lay[i].all, blk, ncclChar, h->comm->nccl, h->stream);
     }
@@ -517,7 +517,7 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
     const uint64_t mine = cnt[c0->rank];
     std::vector<char> sendbuf((size_t)nd * es + mine * 4 + mine * E * es), recv;
     std::vector<uint64_t> sz;
-    HIPCHK(h, hipMemcpyAsync(sendbuf.data(), (char *)h->d_grad + (size_t)(h->num_index * E) * es, (size_t)nd * es, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(sendbuf.data(), (char *)h->train.grad + (size_t)(h->num_index * E) * es, (size_t)nd * es, hipMemcpyDeviceToHost, h->stream));
     if (mine) {
       HIPCHK(h, hipMemcpyAsync(sendbuf.data() + nd * es, lay[0].my_rows, mine * 4, hipMemcpyDeviceToHost, h->stream));
       HIPCHK(h, hipMemcpyAsync(sendbuf.data() + nd * es + mine * 4, lay[0].my_grads, mine * E * es, hipMemcpyDeviceToHost, h->stream));
@@ -537,7 +537,7 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
       off += sz[r]; ro += cnt[r]; go += cnt[r] * E;
     }
     S.bytes_sent = sendbuf.size(); S.bytes_recv = off;
-    char *dense = (char *)h->d_grad + (size_t)(h->num_index * E) * es;
+    char *dense = (char *)h->train.grad + (size_t)(h->num_index * E) * es;
     if (f64) hipLaunchKernelGGL(dm_sum_blocks_kernel<double>, dim3(64), dim3(256), 0, h->stream, (double *)dense, (const double *)lay[0].dense_all, nd, W);
     else hipLaunchKernelGGL(dm_sum_blocks_kernel<float>, dim3(64), dim3(256), 0, h->stream, (float *)dense, (const float *)lay[0].dense_all, nd, W);
     HIPCHK(h, hipGetLastError());
@@ -550,8 +550,8 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
     HIPCHK(h, hipSetDevice(h->device));
     const uint64_t mine = cnt[h->comm->rank];
     if (mine) {
-      if (f64) hipLaunchKernelGGL(dm_zero_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (double *)h->d_grad, h->d_touch_list, (int64_t)mine, (int)E);
-      else hipLaunchKernelGGL(dm_zero_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (float *)h->d_grad, h->d_touch_list, (int64_t)mine, (int)E);
+      if (f64) hipLaunchKernelGGL(dm_zero_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (double *)h->train.grad, h->d_touch_list, (int64_t)mine, (int)E);
+      else hipLaunchKernelGGL(dm_zero_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (float *)h->train.grad, h->d_touch_list, (int64_t)mine, (int)E);
       HIPCHK(h, hipGetLastError());
     }
     size_t ro = 0, go = 0;

@@ -39,6 +39,8 @@
 #include "dev_mem.hip.inc"
 #define DM_LAZY_COPIES_PART 1      // struct LazyCopies
 #include "lazy_copies.hip.inc"
+#define DM_ADAM_VEC_PART 1         // struct TrainVec
+#include "adam_vec.hip.inc"
 // ------------------------------------------------------------------ context
 struct dm_dr_state;
 static void dm_dr_free(dm_dr_state *s);
@@ -126,9 +128,8 @@ struct dm_ctx {
   DevGrow scratch64;           // fp64 beam kernel (beam_kernel_f64.hip.inc): per-team K / G fragment scratch
   // training state (dm_train_init)
   bool train_ready = false;
-  dm_adam_opts adam{};
-  int adam_t = 0;
-  void *d_grad = nullptr, *d_adam_s = nullptr, *d_adam_r = nullptr, *d_loss = nullptr;   // in the loaded dtype
+  TrainVec train;                // gradient, Adam moments, active rows, options and time step of the compact vector (adam_vec.hip.inc)
+  void *d_loss = nullptr;        // in the loaded dtype
   void *d_tr64 = nullptr;        // f64 model: A fragments of att.W, W1a, W1b and of their transposes for the training kernels
   void *d_tail32 = nullptr;      // f64 model: f32 copy of the small matrices (source of the f32 mirror's fragments)
   double last_loss = 0.0;
@@ -136,9 +137,6 @@ struct dm_ctx {
   unsigned *d_touch_bits = nullptr;
   int32_t *d_touch_list = nullptr;
   unsigned long long *d_touch_cnt = nullptr;
-  unsigned *d_active_bits = nullptr;   // rows a gradient has ever reached since dm_train_init (the rows the Adam step has to visit)
-  int32_t *d_active_list = nullptr;
-  unsigned long long *d_active_cnt = nullptr;
   int adam_last_sparse = 0; unsigned long long adam_last_rows = 0;
   size_t touch_cap = 0, touch_ub = 0;   // list capacity; host-side upper bound of its length since the last Adam step
   // measurement
@@ -423,8 +421,8 @@ static void free_tree(dm_ctx *h) {
 }
 // the training state of dm_train_init: its buffers, and the flags that say they exist
 static void free_training(dm_ctx *h) {
-  dm_release(h->d_grad, h->d_adam_s, h->d_adam_r, h->d_loss, h->d_tr64, h->d_attTA, h->d_w1aTA, h->d_w1bTA);
-  dm_release(h->d_touch_bits, h->d_touch_list, h->d_touch_cnt, h->d_active_bits, h->d_active_list, h->d_active_cnt);
+  h->train.release();
+  dm_release(h->d_loss, h->d_tr64, h->d_attTA, h->d_w1aTA, h->d_w1bTA, h->d_touch_bits, h->d_touch_list, h->d_touch_cnt);
   h->train_ready = false; h->touch_cap = 0; h->touch_ub = 0;
 }
 static void free_weights(dm_ctx *h) {
@@ -1569,6 +1567,8 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 
 #include "jtm_rebalance_dev.hip.inc"
 #include "jtm_host.hip.inc"
+#define DM_ADAM_VEC_PART 2         // TrainVec's methods, adam_step
+#include "adam_vec.hip.inc"
 #include "train_host.hip.inc"
 #include "sampler.hip.inc"
 #include "dr_host.hip.inc"

@@ -26,26 +26,18 @@
 // drt_seg_rows_kernel (demb).  Every sum has a fixed order, no floating-point atomics: the same state, batch, seed and step give the same bytes.
 
 struct dm_dr_rr_train {
-  dm_adam_opts adam_g{}, adam_s{};
-  int t_g = 0, t_s = 0;                                       // the two Adam time steps
+  TrainVec g, c;                                              // the graph's vector over d_rr_par, the criterion's over d_sm_par: each its own Adam
   int S = 0, accumulate = 1;
   unsigned long long seed = 0;
   int64_t fb_count = 0;                                       // forward/backward calls so far: the sampler's `step` of the next one
-  int64_t n_g = 0, n_s = 0;
-  void *g_grad = nullptr, *g_s = nullptr, *g_r = nullptr;     // [n_g]: gradient and moments of [rerank_emb ; rerank_w ; rerank_b]
-  void *s_grad = nullptr, *s_s = nullptr, *s_r = nullptr;     // [n_s]: of [softmax_w ; softmax_b]
-  unsigned *g_bits = nullptr, *s_bits = nullptr;              // rows a gradient has ever reached (what the Adam steps visit)
-  int32_t *g_list = nullptr, *s_list = nullptr;
-  unsigned long long *g_cnt = nullptr, *s_cnt = nullptr;
-  DevGrow ws, io, prev_g, prev_s;                             // prev_*: sorted destination rows of the last batch (zeroed by the next)
-  int64_t prev_g_m = 0, prev_s_m = 0;
+  DevGrow ws, io;
 };
 
 static void dr_rr_train_release(dm_dr_state *s) {
   dm_dr_rr_train *t = s->rt;
   if (!t) return;
-  dm_release(t->g_grad, t->g_s, t->g_r, t->s_grad, t->s_s, t->s_r, t->g_bits, t->s_bits, t->g_list, t->s_list, t->g_cnt, t->s_cnt);
-  for (DevGrow *g : {&t->ws, &t->io, &t->prev_g, &t->prev_s}) g->release();
+  t->g.release(); t->c.release();
+  for (DevGrow *g : {&t->ws, &t->io}) g->release();
   delete t;
   s->rt = nullptr;
 }
@@ -278,14 +270,7 @@ __global__ __launch_bounds__(256) void drr_seg_smx_kernel(const unsigned long lo
       if (lane == 63) gb[key] = (T)0;
       continue;
     }
-    int64_t qe = i + 1;                                     // end of the segment, 64 positions per look
-    while (qe < m) {
-      const bool differs = qe + lane >= m || keys[qe + lane] != key;
-      const unsigned long long mask = __ballot(differs);
-      if (mask) { qe += __builtin_ctzll(mask); break; }
-      qe += 64;
-    }
-    if (qe > m) qe = m;
+    const int64_t qe = drt_segment_end(keys, i, m, key, lane);
     for (int e = lane; e < E; e += 64) {
       T acc = 0;
       int64_t q = i;
@@ -303,33 +288,6 @@ __global__ __launch_bounds__(256) void drr_seg_smx_kernel(const unsigned long lo
       for (int64_t q = i; q < qe; q++) b += G[vals[q]];
       gb[key] = MODE == 2 ? gb[key] + b : b;
     }
-  }
-}
-
-// dm_adam_elem / dm_adam_elem_f64 over a vector or over listed rows; KEEP puts the gradient back (the accumulating criterion:
-// ParameterOptimizer never clears it).  KEEP = false is what dm_adam_kernel / dm_adam_rows_kernel compute.
-__device__ __forceinline__ void drr_adam_elem(float *w, float *g, float *s, float *r, int64_t i, float gs, float b1, float c1, float b2, float c2, float eps, float ns) {
-  dm_adam_elem(w, g, s, r, i, gs, b1, c1, b2, c2, eps, ns);
-}
-__device__ __forceinline__ void drr_adam_elem(double *w, double *g, double *s, double *r, int64_t i, double gs, double b1, double c1, double b2, double c2, double eps, double ns) {
-  dm_adam_elem_f64(w, g, s, r, i, gs, b1, c1, b2, c2, eps, ns);
-}
-template <typename T, bool KEEP>
-__global__ void drr_adam_kernel(T *w, T *g, T *s, T *r, int64_t n, T gs, T b1, T c1, T b2, T c2, T eps, T ns) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const T gi = g[i];
-    drr_adam_elem(w, g, s, r, i, gs, b1, c1, b2, c2, eps, ns);
-    if (KEEP) g[i] = gi;
-  }
-}
-template <typename T, bool KEEP>
-__global__ void drr_adam_rows_kernel(T *w, T *g, T *s, T *r, const int32_t *rows, int64_t n_rows, int E, T gs, T b1, T c1, T b2, T c2, T eps, T ns) {
-  const int64_t n = n_rows * E;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = (int64_t)rows[t / E] * E + (t % E);
-    const T gi = g[i];
-    drr_adam_elem(w, g, s, r, i, gs, b1, c1, b2, c2, eps, ns);
-    if (KEEP) g[i] = gi;
   }
 }
 
@@ -358,25 +316,14 @@ int dm_dr_rerank_train_init(dm_handle_t h, const dm_adam_opts *graph, const dm_a
   s->rt = t;
   const size_t es = s->dtype == DM_F64 ? 8 : 4;
   const int64_t NI = s->num_item, E = s->E;
-  t->n_g = NI * E + E * (int64_t)s->L * E + E;
-  t->n_s = NI * E + NI;
-  const size_t words = (size_t)((NI + 31) / 32 + 1) * 4;
-  auto bad = [&](int r) { dr_rr_train_release(s); return r; };
-  for (void **p : {&t->g_grad, &t->g_s, &t->g_r})
-    if ((rc = dm_alloc(h, p, (size_t)t->n_g * es)) != DM_OK) return bad(rc);
-  for (void **p : {&t->s_grad, &t->s_s, &t->s_r})
-    if ((rc = dm_alloc(h, p, (size_t)t->n_s * es)) != DM_OK) return bad(rc);
-  if ((rc = dm_alloc(h, (void **)&t->g_bits, words)) != DM_OK || (rc = dm_alloc(h, (void **)&t->s_bits, words)) != DM_OK ||
-      (rc = dm_alloc(h, (void **)&t->g_list, (size_t)NI * 4)) != DM_OK || (rc = dm_alloc(h, (void **)&t->s_list, (size_t)NI * 4)) != DM_OK ||
-      (rc = dm_alloc(h, (void **)&t->g_cnt, 8)) != DM_OK || (rc = dm_alloc(h, (void **)&t->s_cnt, 8)) != DM_OK) return bad(rc);
-  for (void *p : {t->g_grad, t->g_s, t->g_r}) HIPCHK(h, hipMemsetAsync(p, 0, (size_t)t->n_g * es, h->stream));
-  for (void *p : {t->s_grad, t->s_s, t->s_r}) HIPCHK(h, hipMemsetAsync(p, 0, (size_t)t->n_s * es, h->stream));
-  for (unsigned *p : {t->g_bits, t->s_bits}) HIPCHK(h, hipMemsetAsync(p, 0, words, h->stream));
-  for (unsigned long long *p : {t->g_cnt, t->s_cnt}) HIPCHK(h, hipMemsetAsync(p, 0, 8, h->stream));
+  dm_adam_opts crit{};
+  if (softmax) crit = *softmax;
+  else { crit.lr = graph->lr; crit.lr_decay = 0; crit.beta1 = 0.9; crit.beta2 = 0.999; crit.eps = 1e-7; }      // SampledSoftmaxLoss.scala
+  if ((rc = t->g.init(h, NI, (int)E, NI * E + E * (int64_t)s->L * E + E, es, *graph)) != DM_OK || (rc = t->c.init(h, NI, (int)E, NI * E + NI, es, crit)) != DM_OK) {
+    dr_rr_train_release(s);      // (a handle that is not training, not one that trains on null buffers)
+    return rc;
+  }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  t->adam_g = *graph;
-  if (softmax) t->adam_s = *softmax;
-  else { t->adam_s.lr = graph->lr; t->adam_s.lr_decay = 0; t->adam_s.beta1 = 0.9; t->adam_s.beta2 = 0.999; t->adam_s.eps = 1e-7; }      // SampledSoftmaxLoss.scala
   t->S = num_sampled; t->seed = seed; t->accumulate = accumulate ? 1 : 0;
   return DM_OK;
 }
@@ -391,13 +338,11 @@ int dm_dr_rerank_train_free(dm_handle_t h) {
   return DM_OK;
 }
 
-static unsigned drr_blocks(dm_ctx *h, int64_t n, int per) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, (int64_t)h->n_cu * 16)); }
-
 static int drr_launch_sampler(dm_ctx *h, const int32_t *d_tgt, int64_t B, long long step, int32_t *out, int64_t ld) {
   dm_dr_state *s = h->dr;
   DrrSampleParams sp{};
   sp.targets = d_tgt; sp.B = B; sp.S = s->rt->S; sp.num_item = s->num_item; sp.seed = s->rt->seed; sp.step = step; sp.out = out; sp.ld = ld;
-  hipLaunchKernelGGL(drr_sample_kernel, dim3(drr_blocks(h, B, 4)), dim3(256), 0, h->stream, sp);
+  hipLaunchKernelGGL(drr_sample_kernel, dim3(drt_blocks(h, B, 4)), dim3(256), 0, h->stream, sp);
   HIPCHK(h, hipGetLastError());
   return DM_OK;
 }
@@ -443,30 +388,29 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
   if ((rc = ar.commit(h)) != DM_OK) return rc;
   T *U = ar.ptr<T>(o_u), *dU = ar.ptr<T>(o_du), *G = ar.ptr<T>(o_g), *dX = ar.ptr<T>(o_dx), *part = ar.ptr<T>(o_part);
   int32_t *items = ar.ptr<int32_t>(o_items);
-  unsigned long long *k0 = ar.ptr<unsigned long long>(o_k0), *k1 = ar.ptr<unsigned long long>(o_k1);
-  int32_t *v0 = ar.ptr<int32_t>(o_v0), *v1 = ar.ptr<int32_t>(o_v1);
-  T *gg = (T *)t->g_grad, *sg = (T *)t->s_grad;
-  int bits = 1;
-  while (((int64_t)1 << bits) <= NI) bits++;                // NI itself (padding) sorts last
+  const DrtSortBufs sb{ar.ptr<unsigned long long>(o_k0), ar.ptr<unsigned long long>(o_k1), ar.ptr<int32_t>(o_v0), ar.ptr<int32_t>(o_v1), ar.ptr<uint32_t>(o_tmp)};
+  const unsigned long long *ks;
+  const int32_t *vs;
+  T *gg = (T *)t->g.grad, *sg = (T *)t->c.grad;
   // ---- zeroGradParameters of the graph: the rows the last batch reached (the dense blocks are overwritten below); the criterion's
   // gradient is cleared only when it does not accumulate
-  if (t->prev_g_m > 0) {
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, true>), dim3(drr_blocks(h, t->prev_g_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->prev_g.p, nullptr,
-                       t->prev_g_m, NI, nullptr, E, gg);
+  if (t->g.prev_m > 0) {
+    hipLaunchKernelGGL((drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->g.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->g.prev.p, nullptr,
+                       t->g.prev_m, NI, nullptr, E, gg);
     HIPCHK(h, hipGetLastError());
-    t->prev_g_m = 0;
+    t->g.forget();
   }
-  if (t->prev_s_m > 0) {
-    hipLaunchKernelGGL((drr_seg_smx_kernel<T, 0>), dim3(drr_blocks(h, t->prev_s_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->prev_s.p, nullptr,
-                       t->prev_s_m, NI, nullptr, nullptr, S1, E, sg, sg + NI * E);
+  if (t->c.prev_m > 0) {
+    hipLaunchKernelGGL((drr_seg_smx_kernel<T, 0>), dim3(drt_blocks(h, t->c.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->c.prev.p, nullptr,
+                       t->c.prev_m, NI, nullptr, nullptr, S1, E, sg, sg + NI * E);
     HIPCHK(h, hipGetLastError());
-    t->prev_s_m = 0;
+    t->c.forget();
   }
   // ---- the S + 1 classes of every row
   {
     LaunchTimer tm(h, EV_DRR_SAMPLE, detail);
     if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drr_items_kernel, dim3(drr_blocks(h, m2, 256)), dim3(256), 0, h->stream, d_tgt, d_neg, B, S, items);
+    hipLaunchKernelGGL(drr_items_kernel, dim3(drt_blocks(h, m2, 256)), dim3(256), 0, h->stream, d_tgt, d_neg, B, S, items);
     HIPCHK(h, hipGetLastError());
     if (!d_neg && (rc = drr_launch_sampler(h, d_tgt, B, (long long)t->fb_count, items + 1, S1)) != DM_OK) return rc;
     if ((rc = tm.stop()) != DM_OK) return rc;
@@ -495,25 +439,14 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
   {
     LaunchTimer tm(h, EV_DRR_SMGRAD, detail);
     if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_pairs_kernel, dim3(drr_blocks(h, m2, 256)), dim3(256), 0, h->stream, (const int32_t *)items, m2, NI, k0, v0);
-    HIPCHK(h, hipGetLastError());
-    int where = 0;
-    HIPCHK(h, dev_radix_sort_pairs(h->stream, k0, v0, k1, v1, m2, 0, bits, ar.ptr<uint32_t>(o_tmp), &where));
-    const unsigned long long *ks = where ? k1 : k0;
-    const int32_t *vs = where ? v1 : v0;
+    if ((rc = drt_sort_slots(h, items, m2, NI, sb, ks, vs)) != DM_OK) return rc;
     if (t->accumulate)
-      hipLaunchKernelGGL((drr_seg_smx_kernel<T, 2>), dim3(drr_blocks(h, m2, 4)), dim3(256), 0, h->stream, ks, vs, m2, NI, (const T *)G, (const T *)U, S1, E, sg, sg + NI * E);
+      hipLaunchKernelGGL((drr_seg_smx_kernel<T, 2>), dim3(drt_blocks(h, m2, 4)), dim3(256), 0, h->stream, ks, vs, m2, NI, (const T *)G, (const T *)U, S1, E, sg, sg + NI * E);
     else
-      hipLaunchKernelGGL((drr_seg_smx_kernel<T, 1>), dim3(drr_blocks(h, m2, 4)), dim3(256), 0, h->stream, ks, vs, m2, NI, (const T *)G, (const T *)U, S1, E, sg, sg + NI * E);
+      hipLaunchKernelGGL((drr_seg_smx_kernel<T, 1>), dim3(drt_blocks(h, m2, 4)), dim3(256), 0, h->stream, ks, vs, m2, NI, (const T *)G, (const T *)U, S1, E, sg, sg + NI * E);
     HIPCHK(h, hipGetLastError());
-    if (!t->accumulate) {
-      if ((rc = t->prev_s.reserve(h, (size_t)m2 * 8, (size_t)m2)) != DM_OK) return rc;
-      HIPCHK(h, hipMemcpyAsync(t->prev_s.p, ks, (size_t)m2 * 8, hipMemcpyDeviceToDevice, h->stream));
-      t->prev_s_m = m2;
-    }
-    hipLaunchKernelGGL(dm_mark_active_kernel, dim3(drr_blocks(h, m2, 256)), dim3(256), 0, h->stream, (const int32_t *)items, m2, (const int32_t *)nullptr, (int64_t)0,
-                       t->s_bits, t->s_list, t->s_cnt, NI);
-    HIPCHK(h, hipGetLastError());
+    if (!t->accumulate && (rc = t->c.remember(h, ks, m2)) != DM_OK) return rc;
+    if ((rc = t->c.mark_active(h, drt_blocks(h, m2, 256), items, m2)) != DM_OK) return rc;
     if ((rc = tm.stop()) != DM_OK) return rc;
   }
   // ---- the graph: dX = dU rerank_w, then dW / db over slabs of the batch
@@ -530,7 +463,7 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
     if ((rc = drt_launch_gemm<T>(h, q, EV_DRR_DW, detail)) != DM_OK) return rc;
     LaunchTimer tm(h, EV_DRR_DW, detail);
     if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drr_blocks(h, (int64_t)E * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, E, cols,
+    hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)E * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, E, cols,
                        gg + NI * E, gg + NI * E + (int64_t)E * cols);
     HIPCHK(h, hipGetLastError());
     if ((rc = tm.stop()) != DM_OK) return rc;
@@ -539,20 +472,10 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
   {
     LaunchTimer tm(h, EV_DRR_EMB, detail);
     if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_pairs_kernel, dim3(drr_blocks(h, m1, 256)), dim3(256), 0, h->stream, d_seq, m1, NI, k0, v0);
+    if ((rc = drt_sort_slots(h, d_seq, m1, NI, sb, ks, vs)) != DM_OK) return rc;
+    hipLaunchKernelGGL((drt_seg_rows_kernel<T, false>), dim3(drt_blocks(h, m1, 4)), dim3(256), 0, h->stream, ks, vs, m1, NI, (const T *)dX, E, gg);
     HIPCHK(h, hipGetLastError());
-    int where = 0;
-    HIPCHK(h, dev_radix_sort_pairs(h->stream, k0, v0, k1, v1, m1, 0, bits, ar.ptr<uint32_t>(o_tmp), &where));
-    const unsigned long long *ks = where ? k1 : k0;
-    const int32_t *vs = where ? v1 : v0;
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, false>), dim3(drr_blocks(h, m1, 4)), dim3(256), 0, h->stream, ks, vs, m1, NI, (const T *)dX, E, gg);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = t->prev_g.reserve(h, (size_t)m1 * 8, (size_t)m1)) != DM_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(t->prev_g.p, ks, (size_t)m1 * 8, hipMemcpyDeviceToDevice, h->stream));
-    t->prev_g_m = m1;
-    hipLaunchKernelGGL(dm_mark_active_kernel, dim3(drr_blocks(h, m1, 256)), dim3(256), 0, h->stream, d_seq, m1, (const int32_t *)nullptr, (int64_t)0, t->g_bits,
-                       t->g_list, t->g_cnt, NI);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = t->g.remember(h, ks, m1)) != DM_OK || (rc = t->g.mark_active(h, drt_blocks(h, m1, 256), d_seq, m1)) != DM_OK) return rc;
     if ((rc = tm.stop()) != DM_OK) return rc;
   }
   if (out_loss) HIPCHK(h, hipMemcpyAsync(out_loss, ar.ptr<double>(o_loss), 8, hipMemcpyDeviceToHost, h->stream));
@@ -623,64 +546,28 @@ int dm_dr_rerank_sample(dm_handle_t h, const int32_t *targets, int64_t B, int64_
   return DM_OK;
 }
 
-// one vector's Adam step: `rows` table rows of E values first (visited through `list` on the rows path), then `tail` values —
-// dense for the graph ([rerank_w ; rerank_b]), one per table row for the criterion (softmax_b: tail_by_row, the same list with E = 1)
-template <typename T, bool KEEP>
-static void drr_adam_vec(dm_ctx *h, T *w, T *g, T *s_, T *r_, int64_t rows, int E, int64_t tail, bool tail_by_row, const int32_t *list, int64_t act, bool sparse,
-                         const dm_adam_opts &o, double step, float grad_scale) {
-  const T gs = (T)grad_scale, b1 = (T)o.beta1, c1 = (T)(1 - o.beta1), b2 = (T)o.beta2, c2 = (T)(1 - o.beta2), eps = (T)o.eps, ns = (T)(-step);
-  const int64_t table = rows * E;
-  if (!sparse) {
-    hipLaunchKernelGGL((drr_adam_kernel<T, KEEP>), dim3(8192), dim3(256), 0, h->stream, w, g, s_, r_, table + tail, gs, b1, c1, b2, c2, eps, ns);
-    return;
-  }
-  if (act) hipLaunchKernelGGL((drr_adam_rows_kernel<T, KEEP>), dim3(4096), dim3(256), 0, h->stream, w, g, s_, r_, list, act, E, gs, b1, c1, b2, c2, eps, ns);
-  if (tail_by_row) {
-    if (act) hipLaunchKernelGGL((drr_adam_rows_kernel<T, KEEP>), dim3(256), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, list, act, 1, gs, b1, c1, b2,
-                                c2, eps, ns);
-  } else
-    hipLaunchKernelGGL((drr_adam_kernel<T, KEEP>), dim3(1024), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, tail, gs, b1, c1, b2, c2, eps, ns);
-}
-
-template <typename T>
-static int drr_adam_step_t(dm_ctx *h, float grad_scale) {
-  dm_dr_state *s = h->dr;
-  dm_dr_rr_train *t = s->rt;
-  unsigned long long act[2] = {0, 0};
-  HIPCHK(h, hipMemcpyAsync(&act[0], t->g_cnt, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&act[1], t->s_cnt, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int64_t NI = s->num_item, E = s->E;
-  const char *fd_ = getenv("DM_ADAM_DENSE");
-  const bool dense = fd_ && fd_[0] == '1';
-  auto step_of = [](const dm_adam_opts &o, int &tt) {
-    const double clr = o.lr / (1 + tt * o.lr_decay);
-    tt += 1;
-    return clr * sqrt(1 - pow(o.beta2, tt)) / (1 - pow(o.beta1, tt));
-  };
-  const double step_g = step_of(t->adam_g, t->t_g), step_s = step_of(t->adam_s, t->t_s);
-  LaunchTimer tm(h, EV_DRR_ADAM, dr_time_launches());
-  if (tm.rc != DM_OK) return tm.rc;
-  drr_adam_vec<T, false>(h, (T *)s->d_rr_par, (T *)t->g_grad, (T *)t->g_s, (T *)t->g_r, NI, (int)E, t->n_g - NI * E, false, t->g_list, (int64_t)act[0],
-                         !dense && t->adam_g.eps > 0 && (int64_t)act[0] * 4 < NI, t->adam_g, step_g, grad_scale);
-  const bool sparse_s = !dense && t->adam_s.eps > 0 && (int64_t)act[1] * 4 < NI;
-  if (t->accumulate)
-    drr_adam_vec<T, true>(h, (T *)s->d_sm_par, (T *)t->s_grad, (T *)t->s_s, (T *)t->s_r, NI, (int)E, NI, true, t->s_list, (int64_t)act[1], sparse_s, t->adam_s, step_s, grad_scale);
-  else
-    drr_adam_vec<T, false>(h, (T *)s->d_sm_par, (T *)t->s_grad, (T *)t->s_s, (T *)t->s_r, NI, (int)E, NI, true, t->s_list, (int64_t)act[1], sparse_s, t->adam_s, step_s, grad_scale);
-  HIPCHK(h, hipGetLastError());
-  t->prev_g_m = 0; t->prev_s_m = 0;      // the steps zeroed every gradient they visited (the accumulating criterion keeps no list)
-  return tm.stop();
-}
-
-// Both Adam updates, each with its own time step.  The rows-path / dense-path rule of dm_dr_adam_step holds per vector.
+// Both Adam updates, each with its own time step and its own rows-path / dense-path decision (TrainVec::plan_step).  The graph's tail
+// [rerank_w ; rerank_b] is dense; the criterion's is softmax_b, one value per table row, and its gradient is put back when it accumulates.
 int dm_dr_rerank_adam_step(dm_handle_t h, float grad_scale) {
   if (!h) return DM_ERR_INVALID;
   DM_OWNER_ONLY(h, "dm_dr_rerank_adam_step");
   int rc = drr_check(h, "dm_dr_rerank_adam_step", true);
   if (rc != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  return h->dr->dtype == DM_F32 ? drr_adam_step_t<float>(h, grad_scale) : drr_adam_step_t<double>(h, grad_scale);
+  dm_dr_state *s = h->dr;
+  dm_dr_rr_train *t = s->rt;
+  unsigned long long act[2] = {0, 0};
+  HIPCHK(h, hipMemcpyAsync(&act[0], t->g.active_cnt, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&act[1], t->c.active_cnt, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const AdamPlan plan_g = t->g.plan_step(act[0]), plan_c = t->c.plan_step(act[1]);
+  const bool f64 = s->dtype == DM_F64;
+  LaunchTimer tm(h, EV_DRR_ADAM, dr_time_launches());
+  if (tm.rc != DM_OK) return tm.rc;
+  if ((rc = adam_step(h, t->g, plan_g, s->d_rr_par, f64, false, grad_scale, false, 1024)) != DM_OK) return rc;
+  if ((rc = adam_step(h, t->c, plan_c, s->d_sm_par, f64, t->accumulate != 0, grad_scale, true, 256)) != DM_OK) return rc;
+  t->g.forget(); t->c.forget();      // the steps zeroed every gradient they visited (the accumulating criterion keeps no list)
+  return tm.stop();
 }
 
 int dm_dr_rerank_download(dm_handle_t h, int vec, int what, void *out, int64_t n) {
@@ -693,9 +580,7 @@ int dm_dr_rerank_download(dm_handle_t h, int vec, int what, void *out, int64_t n
   const int64_t want = vec == 0 ? NI * E + E * (int64_t)s->L * E + E : NI * E + NI;
   if (!out || vec < 0 || vec > 1 || what < 0 || what > 3 || n != want)
     return fail(h, DM_ERR_INVALID, "dm_dr_rerank_download: vec must be 0 or 1, what 0..3 and n the vector's length");
-  const dm_dr_rr_train *t = s->rt;
-  const void *src = vec == 0 ? (what == 0 ? s->d_rr_par : what == 1 ? t->g_grad : what == 2 ? t->g_s : t->g_r)
-                             : (what == 0 ? s->d_sm_par : what == 1 ? t->s_grad : what == 2 ? t->s_s : t->s_r);
+  const void *src = what == 0 ? (vec == 0 ? s->d_rr_par : s->d_sm_par) : (vec == 0 ? s->rt->g : s->rt->c).buffer(what);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, src, (size_t)n * (s->dtype == DM_F64 ? 8 : 4), hipMemcpyDeviceToHost));

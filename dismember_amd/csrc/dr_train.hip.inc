@@ -25,21 +25,15 @@
 // Every sum has a fixed order: the same state and batch give the same bytes (the M-step is a discontinuous function of the model).
 
 struct dm_dr_train {
-  dm_adam_opts adam{};
-  int adam_t = 0;
-  void *d_grad = nullptr, *d_s = nullptr, *d_r = nullptr;      // [n_par] in the model's type
-  unsigned *d_active_bits = nullptr;                           // embedding rows a gradient has ever reached (what the Adam step visits)
-  int32_t *d_active_list = nullptr;
-  unsigned long long *d_active_cnt = nullptr;
-  DevGrow ws, io, prev;                                        // prev: the sorted destination rows of the last forward/backward (zeroed by the next)
-  int64_t prev_m = 0;
+  TrainVec vec;              // over d_par: [layer_emb ; W_0 ; b_0 ; ...], rows = the embedding table's
+  DevGrow ws, io;
 };
 
 static void dr_train_release(dm_dr_state *s) {
   dm_dr_train *t = s->tr;
   if (!t) return;
-  dm_release(t->d_grad, t->d_s, t->d_r, t->d_active_bits, t->d_active_list, t->d_active_cnt);
-  for (DevGrow *g : {&t->ws, &t->io, &t->prev}) g->release();
+  t->vec.release();
+  for (DevGrow *g : {&t->ws, &t->io}) g->release();
   delete t;
   s->tr = nullptr;
 }
@@ -238,6 +232,17 @@ __global__ void drt_pairs_kernel(const int32_t *idx, int64_t m, int64_t NR, unsi
     vals[i] = (int32_t)i;
   }
 }
+// the end of the segment of equal keys that starts at position i (all 64 lanes call it), 64 positions per look
+__device__ __forceinline__ int64_t drt_segment_end(const unsigned long long *keys, int64_t i, int64_t m, unsigned long long key, int lane) {
+  int64_t qe = i + 1;
+  while (qe < m) {
+    const bool differs = qe + lane >= m || keys[qe + lane] != key;
+    const unsigned long long mask = __ballot(differs);
+    if (mask) { qe += __builtin_ctzll(mask); break; }
+    qe += 64;
+  }
+  return qe > m ? m : qe;
+}
 // one wave per sorted position; the wave at a destination's FIRST position owns the row.  zero: clear it; otherwise add the E-wide
 // slices dX[slot] of its slots in sorted order (the sort is stable: ascending slot = batch order)
 template <typename T, bool ZERO>
@@ -249,14 +254,7 @@ __global__ __launch_bounds__(256) void drt_seg_rows_kernel(const unsigned long l
     if (key >= (unsigned long long)NR || (i > 0 && keys[i - 1] == key)) continue;
     T *dst = grad + (int64_t)key * E;
     if (ZERO) { for (int e = lane; e < E; e += 64) dst[e] = (T)0; continue; }
-    int64_t qe = i + 1;                                     // end of the segment, 64 positions per look
-    while (qe < m) {
-      const bool differs = qe + lane >= m || keys[qe + lane] != key;
-      const unsigned long long mask = __ballot(differs);
-      if (mask) { qe += __builtin_ctzll(mask); break; }
-      qe += 64;
-    }
-    if (qe > m) qe = m;
+    const int64_t qe = drt_segment_end(keys, i, m, key, lane);
     for (int e = lane; e < E; e += 64) {
       T acc = 0;
       int64_t q = i;
@@ -290,19 +288,11 @@ int dm_dr_train_init(dm_handle_t h, const dm_adam_opts *o) {
   dr_train_release(s);
   dm_dr_train *t = new dm_dr_train();
   s->tr = t;
-  const size_t es = s->dtype == DM_F64 ? 8 : 4, nb = (size_t)s->n_par * es;
-  const int64_t NR = s->num_item + (int64_t)s->K * (s->D - 1);
-  const size_t words = (size_t)((NR + 31) / 32 + 1) * 4;
-  auto bad = [&](int r) { dr_train_release(s); return r; };       // (a handle that is not training, not one that trains on null buffers)
-  for (void **p : {&t->d_grad, &t->d_s, &t->d_r})
-    if ((rc = dm_alloc(h, p, nb)) != DM_OK) return bad(rc);
-  if ((rc = dm_alloc(h, (void **)&t->d_active_bits, words)) != DM_OK || (rc = dm_alloc(h, (void **)&t->d_active_list, (size_t)NR * 4)) != DM_OK ||
-      (rc = dm_alloc(h, (void **)&t->d_active_cnt, 8)) != DM_OK) return bad(rc);
-  for (void *p : {t->d_grad, t->d_s, t->d_r}) HIPCHK(h, hipMemsetAsync(p, 0, nb, h->stream));
-  HIPCHK(h, hipMemsetAsync(t->d_active_bits, 0, words, h->stream));
-  HIPCHK(h, hipMemsetAsync(t->d_active_cnt, 0, 8, h->stream));
+  if ((rc = t->vec.init(h, s->num_item + (int64_t)s->K * (s->D - 1), s->E, s->n_par, s->dtype == DM_F64 ? 8 : 4, *o)) != DM_OK) {
+    dr_train_release(s);
+    return rc;
+  }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  t->adam = *o; t->adam_t = 0; t->prev_m = 0;
   return DM_OK;
 }
 
@@ -313,6 +303,25 @@ int dm_dr_train_free(dm_handle_t h) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   dr_train_release(h->dr);
+  return DM_OK;
+}
+
+// grid of a grid-stride kernel: one workgroup per `per` elements, at most 16 per compute unit
+static unsigned drt_blocks(dm_ctx *h, int64_t n, int per) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, (int64_t)h->n_cu * 16)); }
+
+// "Scatter a batch's per-slot values into table rows in a fixed order", first half: slot i of ids[0..m) -> (destination row | NR for
+// padding, i), sorted by destination (stable: ascending slot = batch order inside a destination).  ks / vs: where the sorted pairs are.
+// The caller's segment kernel (one wave per destination) adds the slots' values; then TrainVec::remember and mark_active.
+struct DrtSortBufs { unsigned long long *k0, *k1; int32_t *v0, *v1; uint32_t *tmp; };
+static int drt_sort_slots(dm_ctx *h, const int32_t *ids, int64_t m, int64_t NR, const DrtSortBufs &b, const unsigned long long *&ks, const int32_t *&vs) {
+  hipLaunchKernelGGL(drt_pairs_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, ids, m, NR, b.k0, b.v0);
+  HIPCHK(h, hipGetLastError());
+  int bits = 1;
+  while (((int64_t)1 << bits) <= NR) bits++;                // NR itself (padding) sorts last
+  int where = 0;
+  HIPCHK(h, dev_radix_sort_pairs(h->stream, b.k0, b.v0, b.k1, b.v1, m, 0, bits, b.tmp, &where));
+  ks = where ? b.k1 : b.k0;
+  vs = where ? b.v1 : b.v0;
   return DM_OK;
 }
 
@@ -352,21 +361,20 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
   const size_t o_lp = ar.add((size_t)D * nb * 8), o_loss = ar.add((size_t)D * 8);
   if ((rc = ar.commit(h)) != DM_OK) return rc;
   T *Z = ar.ptr<T>(o_z), *dX = ar.ptr<T>(o_dx), *part = ar.ptr<T>(o_part);
-  T *grad = (T *)t->d_grad;
+  T *grad = (T *)t->vec.grad;
   if (s->wseq_stale && (rc = dr_refresh_wseq<T>(h, s)) != DM_OK) return rc;
-  auto blocks = [&](int64_t n, int per) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, (int64_t)h->n_cu * 16)); };
   // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
-  if (t->prev_m > 0) {
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, true>), dim3(blocks(t->prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->prev.p, nullptr, t->prev_m, NR,
-                       nullptr, E, grad);
+  if (t->vec.prev_m > 0) {
+    hipLaunchKernelGGL((drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->vec.prev.p, nullptr,
+                       t->vec.prev_m, NR, nullptr, E, grad);
     HIPCHK(h, hipGetLastError());
-    t->prev_m = 0;
+    t->vec.forget();
   }
   // ---- inputs
   DrtIdxParams ip{};
   ip.seq = d_seq; ip.paths = d_paths; ip.B = B; ip.L = L; ip.D = D; ip.K = K; ip.num_item = s->num_item;
   for (int d = 0; d < D; d++) ip.idx[d] = ar.ptr<int32_t>(o_idx[d]);
-  hipLaunchKernelGGL(drt_build_idx_kernel, dim3(blocks(m, 256)), dim3(256), 0, h->stream, ip);
+  hipLaunchKernelGGL(drt_build_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, ip);
   HIPCHK(h, hipGetLastError());
   // ---- forward
   for (int d = 0; d < D; d++) {
@@ -420,7 +428,7 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
       if ((rc = drt_launch_gemm<T>(h, g, EV_DRT_DW, detail)) != DM_OK) return rc;
       LaunchTimer tm(h, EV_DRT_DW, detail);
       if (tm.rc != DM_OK) return tm.rc;
-      hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(blocks((int64_t)K * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, K, cols,
+      hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)K * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, K, cols,
                          grad + off, grad + off + (int64_t)K * cols);
       HIPCHK(h, hipGetLastError());
       if ((rc = tm.stop()) != DM_OK) return rc;
@@ -431,25 +439,14 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
   {
     LaunchTimer tm(h, EV_DRT_EMB, detail);
     if (tm.rc != DM_OK) return tm.rc;
-    unsigned long long *k0 = ar.ptr<unsigned long long>(o_k0), *k1 = ar.ptr<unsigned long long>(o_k1);
-    int32_t *v0 = ar.ptr<int32_t>(o_v0), *v1 = ar.ptr<int32_t>(o_v1);
+    const DrtSortBufs sb{ar.ptr<unsigned long long>(o_k0), ar.ptr<unsigned long long>(o_k1), ar.ptr<int32_t>(o_v0), ar.ptr<int32_t>(o_v1), ar.ptr<uint32_t>(o_tmp)};
     const int32_t *full = ip.idx[D - 1];                    // [B x (L+D-1)]: every input position of the batch
-    hipLaunchKernelGGL(drt_pairs_kernel, dim3(blocks(m, 256)), dim3(256), 0, h->stream, full, m, NR, k0, v0);
+    const unsigned long long *ks;
+    const int32_t *vs;
+    if ((rc = drt_sort_slots(h, full, m, NR, sb, ks, vs)) != DM_OK) return rc;
+    hipLaunchKernelGGL((drt_seg_rows_kernel<T, false>), dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NR, (const T *)dX, E, grad);
     HIPCHK(h, hipGetLastError());
-    int bits = 1;
-    while (((int64_t)1 << bits) <= NR) bits++;              // NR itself (padding) sorts last
-    int where = 0;
-    HIPCHK(h, dev_radix_sort_pairs(h->stream, k0, v0, k1, v1, m, 0, bits, ar.ptr<uint32_t>(o_tmp), &where));
-    const unsigned long long *ks = where ? k1 : k0;
-    const int32_t *vs = where ? v1 : v0;
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, false>), dim3(blocks(m, 4)), dim3(256), 0, h->stream, ks, vs, m, NR, (const T *)dX, E, grad);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = t->prev.reserve(h, (size_t)m * 8, (size_t)m)) != DM_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(t->prev.p, ks, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));
-    t->prev_m = m;
-    hipLaunchKernelGGL(dm_mark_active_kernel, dim3(blocks(m, 256)), dim3(256), 0, h->stream, full, m, (const int32_t *)nullptr, (int64_t)0, t->d_active_bits,
-                       t->d_active_list, t->d_active_cnt, NR);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = t->vec.remember(h, ks, m)) != DM_OK || (rc = t->vec.mark_active(h, drt_blocks(h, m, 256), full, m)) != DM_OK) return rc;
     if ((rc = tm.stop()) != DM_OK) return rc;
   }
   if (out_loss) HIPCHK(h, hipMemcpyAsync(out_loss, ar.ptr<double>(o_loss), (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
@@ -496,43 +493,15 @@ int dm_dr_adam_step(dm_handle_t h, float grad_scale) {
   HIPCHK(h, hipSetDevice(h->device));
   dm_dr_state *s = h->dr;
   dm_dr_train *t = s->tr;
-  const dm_adam_opts &o = t->adam;
-  const double clr = o.lr / (1 + t->adam_t * o.lr_decay);
-  t->adam_t += 1;
-  const double bc1 = 1 - pow(o.beta1, t->adam_t), bc2 = 1 - pow(o.beta2, t->adam_t);
-  const double step = clr * sqrt(bc2) / bc1;
   unsigned long long act = 0;
-  HIPCHK(h, hipMemcpyAsync(&act, t->d_active_cnt, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&act, t->vec.active_cnt, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int64_t E = s->E, NR = s->num_item + (int64_t)s->K * (s->D - 1), table = NR * E, n = s->n_par;
-  const char *fd_ = getenv("DM_ADAM_DENSE");
-  const bool sparse = !(fd_ && fd_[0] == '1') && o.eps > 0 && (int64_t)act * 4 < NR;
+  const AdamPlan plan = t->vec.plan_step(act);
   s->derived_stale = true; s->wseq_stale = true;      // before the first launch: a step that fails half-way has still moved weights
   LaunchTimer tm(h, EV_DRT_ADAM, dr_time_launches());
   if (tm.rc != DM_OK) return tm.rc;
-  if (s->dtype == DM_F64) {
-    double *w = (double *)s->d_par, *g = (double *)t->d_grad, *s_ = (double *)t->d_s, *r_ = (double *)t->d_r;
-    if (sparse) {
-      if (act) hipLaunchKernelGGL(dm_adam_rows_kernel_f64, dim3(4096), dim3(256), 0, h->stream, w, g, s_, r_, t->d_active_list, (int64_t)act, (int)E,
-                                  (double)grad_scale, o.beta1, 1 - o.beta1, o.beta2, 1 - o.beta2, o.eps, -step);
-      hipLaunchKernelGGL(dm_adam_kernel_f64, dim3(1024), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, n - table,
-                         (double)grad_scale, o.beta1, 1 - o.beta1, o.beta2, 1 - o.beta2, o.eps, -step);
-    } else
-      hipLaunchKernelGGL(dm_adam_kernel_f64, dim3(8192), dim3(256), 0, h->stream, w, g, s_, r_, n, (double)grad_scale, o.beta1, 1 - o.beta1,
-                         o.beta2, 1 - o.beta2, o.eps, -step);
-  } else {
-    float *w = (float *)s->d_par, *g = (float *)t->d_grad, *s_ = (float *)t->d_s, *r_ = (float *)t->d_r;
-    if (sparse) {
-      if (act) hipLaunchKernelGGL(dm_adam_rows_kernel, dim3(4096), dim3(256), 0, h->stream, w, g, s_, r_, t->d_active_list, (int64_t)act, (int)E,
-                                  grad_scale, (float)o.beta1, (float)(1 - o.beta1), (float)o.beta2, (float)(1 - o.beta2), (float)o.eps, (float)(-step));
-      hipLaunchKernelGGL(dm_adam_kernel, dim3(1024), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, n - table, grad_scale,
-                         (float)o.beta1, (float)(1 - o.beta1), (float)o.beta2, (float)(1 - o.beta2), (float)o.eps, (float)(-step));
-    } else
-      hipLaunchKernelGGL(dm_adam_kernel, dim3(8192), dim3(256), 0, h->stream, w, g, s_, r_, n, grad_scale, (float)o.beta1, (float)(1 - o.beta1),
-                         (float)o.beta2, (float)(1 - o.beta2), (float)o.eps, (float)(-step));
-  }
-  HIPCHK(h, hipGetLastError());
-  t->prev_m = 0;                  // the step zeroed every gradient it visited, and it visited every row a batch has reached
+  if ((rc = adam_step(h, t->vec, plan, s->d_par, s->dtype == DM_F64, false, grad_scale, false, 1024)) != DM_OK) return rc;
+  t->vec.forget();                // the step zeroed every gradient it visited, and it visited every row a batch has reached
   return tm.stop();
 }
 
@@ -553,7 +522,7 @@ int dm_dr_train_download(dm_handle_t h, int what, void *out, int64_t n) {
   if (rc != DM_OK) return rc;
   dm_dr_state *s = h->dr;
   if (!out || what < 0 || what > 3 || n != s->n_par) return fail(h, DM_ERR_INVALID, "dm_dr_train_download: what must be 0..3 and n the parameter count");
-  const void *src = what == 0 ? s->d_par : what == 1 ? s->tr->d_grad : what == 2 ? s->tr->d_s : s->tr->d_r;
+  const void *src = what == 0 ? s->d_par : s->tr->vec.buffer(what);
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(out, src, (size_t)n * (s->dtype == DM_F64 ? 8 : 4), hipMemcpyDeviceToHost));

@@ -167,13 +167,13 @@ static int ensure_split_scales(dm_ctx *h) {
   if (!z.d_wsplit) ALLOC(h, z.d_wsplit, (size_t)E * E * 4);
   if (!z.d_maxabs) ALLOC(h, z.d_maxabs, 8);
   // a training loop whose Adam steps visit the active rows only: the last full scan's scale stays, only those rows are re-split
-  bool patch = h->train_ready && split_patchable(h) && h->d_active_list;
+  bool patch = h->train_ready && split_patchable(h) && h->train.active_list;
   unsigned mb[2];
   for (;;) {
     HIPCHK(h, hipMemsetAsync(z.d_maxabs, 0, 8, h->stream));
     if (patch) {
       if (z.active_rows_host)
-        hipLaunchKernelGGL(dm_maxabs_kernel<true>, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->d_active_list, (int64_t)z.active_rows_host * E, E, z.d_maxabs);
+        hipLaunchKernelGGL(dm_maxabs_kernel<true>, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->train.active_list, (int64_t)z.active_rows_host * E, E, z.d_maxabs);
     } else
       hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, h->stream, h->d_emb32, nullptr, h->num_index * (int64_t)E, E, z.d_maxabs);
     hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(16), dim3(256), 0, h->stream, (const float *)h->d_wfrag, nullptr, (int64_t)E * E, E, z.d_maxabs + 1);
@@ -218,7 +218,7 @@ static int ensure_split(dm_ctx *h) {
                        (_Float16 *)z.d_emb_split);
     z.emb_split_need_full = false;
   } else if (z.active_rows_host) {
-    hipLaunchKernelGGL(dm_build_emb_split_kernel<true>, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->d_active_list, (int64_t)z.active_rows_host,
+    hipLaunchKernelGGL(dm_build_emb_split_kernel<true>, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->train.active_list, (int64_t)z.active_rows_host,
                        E, ldexpf(1.0f, z.sh_e), (_Float16 *)z.d_emb_split);
   }
   HIPCHK(h, hipGetLastError());

@@ -35,7 +35,7 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   const double *att_w = base + h->num_index * E, *l1_w = att_w + n2, *b1 = l1_w + 2 * n2, *w2 = b1 + E;
   const double *f64f = (const double *)h->lazy.d_frag64;          // w1aA, attA, w1bB
   const double *tr = (const double *)h->d_tr64;              // attA, w1aA, w1bA, attTA, w1aTA, w1bTA (training fragment order)
-  double *grad = (double *)h->d_grad;
+  double *grad = (double *)h->train.grad;
   // every launch gets an event pair (dm_kernel_timing_get_kind: EV_TG_SETUP = per-user setup, EV_TG_ROWS = the row kernel, EV_TG_WGRAD_A = dW1a +
   // per-user sums, EV_TG_USER_BWD = per-user backward, EV_TG_WGRAD_B = dW1b / datt.W): bench.py prices the row kernel against the fp64 matrix peak from these
   auto timed = [&](int kind, auto launch) -> int {
@@ -161,9 +161,8 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
                      h->d_touch_list, h->d_touch_cnt, (unsigned long long)h->touch_cap, h->num_index);
   hipLaunchKernelGGL(dm_mark_touched_kernel, dim3(64), dim3(256), 0, h->stream, d_seq, (const int32_t *)nullptr, U * L, 0, h->d_touch_bits,
                      h->d_touch_list, h->d_touch_cnt, (unsigned long long)h->touch_cap, h->num_index);
-  hipLaunchKernelGGL(dm_mark_active_kernel, dim3(256), dim3(256), 0, h->stream, d_codes, B, d_seq, U * L, h->d_active_bits, h->d_active_list,
-                     h->d_active_cnt, h->num_index);
   HIPCHK(h, hipGetLastError());
+  if ((rc = h->train.mark_active(h, 256, d_codes, B, d_seq, U * L)) != DM_OK) return rc;
   if (loss) {
     double acc[2];
     HIPCHK(h, hipMemcpyAsync(acc, h->d_loss, 16, hipMemcpyDeviceToHost, h->stream));

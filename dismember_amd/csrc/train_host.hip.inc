@@ -21,25 +21,16 @@ int dm_train_init(dm_handle_t h, const dm_adam_opts *o) {
   const size_t es = elem_size(h);
   const size_t fb = (size_t)h->embed * h->embed * 4;
   free_training(h);       // (a failure below leaves a handle that is not training, not one that trains on null buffers)
-  ALLOC(h, h->d_grad, (size_t)n * es);
-  ALLOC(h, h->d_adam_s, (size_t)n * es);
-  ALLOC(h, h->d_adam_r, (size_t)n * es);
+  int rc = h->train.init(h, h->num_index, h->embed, n, es, *o);
+  if (rc != DM_OK) return rc;
   if (h->dtype == DM_F64) ALLOC(h, h->d_tr64, 6 * (size_t)h->embed * h->embed * 8);
   else { ALLOC(h, h->d_attTA, fb); ALLOC(h, h->d_w1aTA, fb); ALLOC(h, h->d_w1bTA, fb); }
   ALLOC(h, h->d_loss, 16);
   ALLOC(h, h->d_touch_bits, (size_t)((h->num_index + 31) / 32 + 1) * 4);
   ALLOC(h, h->d_touch_cnt, 8);
-  ALLOC(h, h->d_active_bits, (size_t)((h->num_index + 31) / 32 + 1) * 4);
-  ALLOC(h, h->d_active_list, (size_t)(h->num_index > 0 ? h->num_index : 1) * 4);
-  ALLOC(h, h->d_active_cnt, 8);
-  HIPCHK(h, hipMemsetAsync(h->d_active_bits, 0, (size_t)((h->num_index + 31) / 32 + 1) * 4, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->d_active_cnt, 0, 8, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->d_grad, 0, (size_t)n * es, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->d_adam_s, 0, (size_t)n * es, h->stream));
-  HIPCHK(h, hipMemsetAsync(h->d_adam_r, 0, (size_t)n * es, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_touch_bits, 0, (size_t)((h->num_index + 31) / 32 + 1) * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_touch_cnt, 0, 8, h->stream));
-  h->adam = *o; h->adam_t = 0; h->touch_cap = 0; h->touch_ub = 0; h->train_ready = true; h->last_loss = 0.0;
+  h->touch_cap = 0; h->touch_ub = 0; h->train_ready = true; h->last_loss = 0.0;
   model_changed(h);      // (clones re-mirror: the lazily rebuilt copies are stale)
   h->lazy.training_started();
   return derive_small(h, DERIVE_OWN);      // d_tr64 / the transposed fragments were just allocated
@@ -58,19 +49,6 @@ __global__ void dm_mark_touched_kernel(const int32_t *codes, const int32_t *seqs
       const unsigned long long pos = atomicAdd(cnt, 1ull);
       if (pos < cap) list[pos] = idx;      // the host sizes the list so that this always holds (touch_ub)
     }
-  }
-}
-
-// rows that have ever received a gradient (dm_adam_step visits these and the small matrices only: dm_adam_rows_kernel)
-__global__ void dm_mark_active_kernel(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, unsigned *bits, int32_t *list,
-                                      unsigned long long *cnt, int64_t num_index) {
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < na + nb; t += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t idx = t < na ? a[t] : b[t - na];
-    if (idx < 0 || idx >= num_index) continue;
-    const unsigned bit = 1u << (idx & 31);
-    if (bits[idx >> 5] & bit) continue;
-    const unsigned old = atomicOr(bits + (idx >> 5), bit);
-    if (!(old & bit)) list[atomicAdd(cnt, 1ull)] = idx;        // at most num_index entries: the list has that capacity
   }
 }
 
@@ -129,14 +107,14 @@ static int train_fb_launch(dm_ctx *h, const int32_t *d_codes, const int32_t *d_s
   }
   p.codes = d_codes; p.seqs = d_seqs; p.rowmask = d_rowmask; p.labels = d_labels; p.B = B; p.L = L; p.inv_B = (T)(1.0 / (double)B);
   p.sm_scale = (T)sm_scale64(h);
-  p.grad = (T *)h->d_grad;
+  p.grad = (T *)h->train.grad;
   T *ws = (T *)h->ws.p;
   p.DZ = ws; p.AT = ws + (size_t)B * E; p.DA = ws + 2 * (size_t)B * E; p.CB = ws + 3 * (size_t)B * E;
   p.logits = ws + 4 * (size_t)B * E;
   p.loss_acc = (T *)h->d_loss;
   WGradParamsT<T> wg;
   wg.emb = base; wg.codes = d_codes; wg.DZ = p.DZ; wg.AT = p.AT; wg.DA = p.DA; wg.CB = p.CB; wg.B = B;
-  wg.num_index = h->num_index; wg.grad = (T *)h->d_grad;
+  wg.num_index = h->num_index; wg.grad = (T *)h->train.grad;
   wg.chunk = 256;
   return dispatch_E(h, E, "unsupported embed size", [&](auto e) { return launch_train_E<T, decltype(e)::value>(h, p, wg); });
 }
@@ -225,9 +203,8 @@ static int train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs
   if (rc != DM_OK) return rc;
   hipLaunchKernelGGL(dm_mark_touched_kernel, dim3(256), dim3(256), 0, h->stream, d_codes, d_seqs, B, L, h->d_touch_bits,
                      h->d_touch_list, h->d_touch_cnt, (unsigned long long)h->touch_cap, h->num_index);
-  hipLaunchKernelGGL(dm_mark_active_kernel, dim3(256), dim3(256), 0, h->stream, d_codes, B, d_seqs, B * L, h->d_active_bits, h->d_active_list,
-                     h->d_active_cnt, h->num_index);
   HIPCHK(h, hipGetLastError());
+  if ((rc = h->train.mark_active(h, 256, d_codes, B, d_seqs, B * L)) != DM_OK) return rc;
   if (loss) {
     if (h->dtype == DM_F64) {
       double acc[2];
@@ -303,47 +280,14 @@ int dm_adam_step(dm_handle_t h, float grad_scale) {
   int rc = train_check(h, "dm_adam_step");
   if (rc != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const dm_adam_opts &o = h->adam;
-  const double clr = o.lr / (1 + h->adam_t * o.lr_decay);
-  h->adam_t += 1;
-  const double bc1 = 1 - pow(o.beta1, h->adam_t), bc2 = 1 - pow(o.beta2, h->adam_t);
-  const double step = clr * sqrt(bc2) / bc1;
-  const int64_t n = compact_len(h);
   unsigned long long cnt = 0, act = 0;
   HIPCHK(h, hipMemcpyAsync(&cnt, h->d_touch_cnt, 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(&act, h->d_active_cnt, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(&act, h->train.active_cnt, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  // Rows no gradient has ever reached keep g = s = r = 0 and the dense update leaves their weights bit-identical (see
-  // dm_adam_rows_kernel): visit the active rows and the small matrices only, unless most of the table is active anyway.
-  // DM_ADAM_DENSE=1 forces the dense stream (tests compare the two).
-  const int64_t E = h->embed, table = h->num_index * E;
-  const char *fd_ = getenv("DM_ADAM_DENSE");
-  const bool force_dense = fd_ && fd_[0] == '1';
-  const bool sparse = !force_dense && o.eps > 0 && (int64_t)act * 4 < h->num_index;
-  h->adam_last_sparse = sparse ? 1 : 0; h->adam_last_rows = sparse ? act : (unsigned long long)h->num_index;
-  h->lazy.adam_stepped(sparse, act, h->dtype == DM_F64);      // before the first launch: a step that fails half-way has still moved weights
-  if (h->dtype == DM_F64) {
-    double *w = (double *)h->d_compact, *g = (double *)h->d_grad, *s_ = (double *)h->d_adam_s, *r_ = (double *)h->d_adam_r;
-    if (sparse) {
-      if (act) hipLaunchKernelGGL(dm_adam_rows_kernel_f64, dim3(4096), dim3(256), 0, h->stream, w, g, s_, r_, h->d_active_list, (int64_t)act, (int)E,
-                                  (double)grad_scale, o.beta1, 1 - o.beta1, o.beta2, 1 - o.beta2, o.eps, -step);
-      hipLaunchKernelGGL(dm_adam_kernel_f64, dim3(64), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, n - table,
-                         (double)grad_scale, o.beta1, 1 - o.beta1, o.beta2, 1 - o.beta2, o.eps, -step);
-    } else
-      hipLaunchKernelGGL(dm_adam_kernel_f64, dim3(8192), dim3(256), 0, h->stream, w, g, s_, r_, n, (double)grad_scale, o.beta1, 1 - o.beta1,
-                         o.beta2, 1 - o.beta2, o.eps, -step);
-  } else {
-    float *w = (float *)h->d_compact, *g = (float *)h->d_grad, *s_ = (float *)h->d_adam_s, *r_ = (float *)h->d_adam_r;
-    if (sparse) {
-      if (act) hipLaunchKernelGGL(dm_adam_rows_kernel, dim3(4096), dim3(256), 0, h->stream, w, g, s_, r_, h->d_active_list, (int64_t)act, (int)E,
-                                  grad_scale, (float)o.beta1, (float)(1 - o.beta1), (float)o.beta2, (float)(1 - o.beta2), (float)o.eps, (float)(-step));
-      hipLaunchKernelGGL(dm_adam_kernel, dim3(64), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, n - table, grad_scale,
-                         (float)o.beta1, (float)(1 - o.beta1), (float)o.beta2, (float)(1 - o.beta2), (float)o.eps, (float)(-step));
-    } else
-      hipLaunchKernelGGL(dm_adam_kernel, dim3(8192), dim3(256), 0, h->stream, w, g, s_, r_, n, grad_scale, (float)o.beta1, (float)(1 - o.beta1),
-                         (float)o.beta2, (float)(1 - o.beta2), (float)o.eps, (float)(-step));
-  }
-  HIPCHK(h, hipGetLastError());
+  const AdamPlan plan = h->train.plan_step(act);
+  h->adam_last_sparse = plan.rows_path ? 1 : 0; h->adam_last_rows = plan.rows_path ? act : (unsigned long long)h->num_index;
+  h->lazy.adam_stepped(plan.rows_path, act, h->dtype == DM_F64);      // before the first launch: a step that fails half-way has still moved weights
+  if ((rc = adam_step(h, h->train, plan, h->d_compact, h->dtype == DM_F64, false, grad_scale, false, 64)) != DM_OK) return rc;
   // forget which rows were touched in this step
   if (cnt > 0 && h->d_touch_list) {
     hipLaunchKernelGGL(dm_clear_touched_kernel, dim3(256), dim3(256), 0, h->stream, h->d_touch_list, (int64_t)cnt, h->d_touch_bits);
@@ -370,7 +314,7 @@ int dm_train_download(dm_handle_t h, int what, void *out, int64_t n) {
   DM_DIN_ONLY(h, "dm_train_download");
   const bool padded = h->embed_log != h->embed;
   if (!out || n != compact_len_for(h->num_index, h->embed_log)) return fail(h, DM_ERR_INVALID, "dm_train_download: n must be the compact vector length");
-  const void *src = what == 0 ? h->d_compact : what == 1 ? h->d_grad : what == 2 ? h->d_adam_s : h->d_adam_r;
+  const void *src = what == 0 ? h->d_compact : h->train.buffer(what);
   if (!src) return fail(h, DM_ERR_STATE, "dm_train_download: call dm_train_init first");
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -390,7 +334,7 @@ int dm_train_dense_block(dm_handle_t h, void **d_ptr, int64_t *n) {
   if (rc != DM_OK) return rc;
   if (h->embed_log != h->embed) return fail(h, DM_ERR_UNSUPPORTED, "dm_train_dense_block: the model's embed size is zero-padded on the device; use dm_train_sync_gradients");
   const int64_t E = h->embed;
-  *d_ptr = (char *)h->d_grad + (size_t)(h->num_index * E) * elem_size(h);
+  *d_ptr = (char *)h->train.grad + (size_t)(h->num_index * E) * elem_size(h);
   *n = 3 * E * E + 2 * E + 1;
   return DM_OK;
 }
@@ -413,19 +357,19 @@ __global__ void dm_add_rows_kernel(T *grad, const int32_t *rows, const T *g, int
 }
 static int launch_gather_rows(dm_ctx *h, int64_t cnt, int32_t *d_rows, void *d_grads) {
   if (h->dtype == DM_F64)
-    hipLaunchKernelGGL(dm_gather_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (const double *)h->d_grad, h->d_touch_list, cnt, h->embed, d_rows, (double *)d_grads);
+    hipLaunchKernelGGL(dm_gather_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (const double *)h->train.grad, h->d_touch_list, cnt, h->embed, d_rows, (double *)d_grads);
   else
-    hipLaunchKernelGGL(dm_gather_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (const float *)h->d_grad, h->d_touch_list, cnt, h->embed, d_rows, (float *)d_grads);
+    hipLaunchKernelGGL(dm_gather_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (const float *)h->train.grad, h->d_touch_list, cnt, h->embed, d_rows, (float *)d_grads);
   HIPCHK(h, hipGetLastError());
   return DM_OK;
 }
 static int launch_add_rows(dm_ctx *h, const int32_t *d_rows, const void *d_grads, int64_t n) {
-  hipLaunchKernelGGL(dm_mark_active_kernel, dim3(256), dim3(256), 0, h->stream, d_rows, n, (const int32_t *)nullptr, (int64_t)0, h->d_active_bits,
-                     h->d_active_list, h->d_active_cnt, h->num_index);
+  const int rc = h->train.mark_active(h, 256, d_rows, n);
+  if (rc != DM_OK) return rc;
   if (h->dtype == DM_F64)
-    hipLaunchKernelGGL(dm_add_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (double *)h->d_grad, d_rows, (const double *)d_grads, n, h->embed, h->num_index);
+    hipLaunchKernelGGL(dm_add_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (double *)h->train.grad, d_rows, (const double *)d_grads, n, h->embed, h->num_index);
   else
-    hipLaunchKernelGGL(dm_add_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (float *)h->d_grad, d_rows, (const float *)d_grads, n, h->embed, h->num_index);
+    hipLaunchKernelGGL(dm_add_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (float *)h->train.grad, d_rows, (const float *)d_grads, n, h->embed, h->num_index);
   HIPCHK(h, hipGetLastError());
   return DM_OK;
 }

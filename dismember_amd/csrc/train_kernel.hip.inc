@@ -555,27 +555,10 @@ __device__ __forceinline__ void dm_adam_elem(float *w, float *g, float *s, float
   w[i] = w[i] + t3;
   s[i] = si; r[i] = ri; g[i] = 0.0f;
 }
-__global__ void dm_adam_kernel(float *w, float *g, float *s, float *r, int64_t n, float gscale, float b1, float c1,
-                               float b2, float c2, float eps, float neg_step) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dm_adam_elem(w, g, s, r, i, gscale, b1, c1, b2, c2, eps, neg_step);
-}
-// The same update over the ACTIVE embedding rows only (rows[0..n_rows): every row a gradient has ever reached since dm_train_init).
-// For any other row g = s = r = 0, so the dense step computes s = 0 b1 + c1 0 = 0, r = 0, de = 0 / (sqrt(0) + eps) = 0 (eps > 0),
-// t3 = neg_step 0 = -0 and w + (-0) = w bit for bit: leaving those rows alone IS the reference's dense Adam (Adam.scala:19-73),
-// without streaming the 8 x 4 bytes per parameter of a table that cannot change.
-__global__ void dm_adam_rows_kernel(float *w, float *g, float *s, float *r, const int32_t *rows, int64_t n_rows, int E, float gscale,
-                                    float b1, float c1, float b2, float c2, float eps, float neg_step) {
-  const int64_t n = n_rows * E;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
-    dm_adam_elem(w, g, s, r, (int64_t)rows[t / E] * E + (t % E), gscale, b1, c1, b2, c2, eps, neg_step);
-}
-
 // The same step for a DIN[Double]: Adam.optimize is generic in the tensor's element type, so every operation below is the IEEE
 // double operation the JVM performs (plain operators, no FMA contraction; sqrt and divide are correctly rounded in fp64).
-__device__ __forceinline__ void dm_adam_elem_f64(double *w, double *g, double *s, double *r, int64_t i, double gscale, double b1, double c1,
-                                                 double b2, double c2, double eps, double neg_step) {
+__device__ __forceinline__ void dm_adam_elem(double *w, double *g, double *s, double *r, int64_t i, double gscale, double b1, double c1,
+                                             double b2, double c2, double eps, double neg_step) {
 #pragma clang fp contract(off)
   const double gi = gscale == 1.0 ? g[i] : g[i] * gscale;
   double si = s[i] * b1;
@@ -592,17 +575,29 @@ __device__ __forceinline__ void dm_adam_elem_f64(double *w, double *g, double *s
   w[i] = w[i] + t3;
   s[i] = si; r[i] = ri; g[i] = 0.0;
 }
-__global__ void dm_adam_kernel_f64(double *w, double *g, double *s, double *r, int64_t n, double gscale, double b1, double c1,
-                                   double b2, double c2, double eps, double neg_step) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) dm_adam_elem_f64(w, g, s, r, i, gscale, b1, c1, b2, c2, eps, neg_step);
+// The update over a whole vector.  KEEP puts the gradient back after the element update (an accumulating owner: dr_rerank_train.hip.inc).
+template <typename T, bool KEEP>
+__global__ void dm_adam_kernel(T *w, T *g, T *s, T *r, int64_t n, T gscale, T b1, T c1, T b2, T c2, T eps, T neg_step) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const T gi = g[i];
+    dm_adam_elem(w, g, s, r, i, gscale, b1, c1, b2, c2, eps, neg_step);
+    if (KEEP) g[i] = gi;
+  }
 }
-__global__ void dm_adam_rows_kernel_f64(double *w, double *g, double *s, double *r, const int32_t *rows, int64_t n_rows, int E, double gscale,
-                                        double b1, double c1, double b2, double c2, double eps, double neg_step) {
+// The same update over the ACTIVE embedding rows only (rows[0..n_rows): every row a gradient has ever reached since its TrainVec::init).
+// For any other row g = s = r = 0, so the dense step computes s = 0 b1 + c1 0 = 0, r = 0, de = 0 / (sqrt(0) + eps) = 0 (eps > 0),
+// t3 = neg_step 0 = -0 and w + (-0) = w bit for bit: leaving those rows alone IS the reference's dense Adam (Adam.scala:19-73),
+// without streaming the 8 x 4 bytes per parameter of a table that cannot change.
+template <typename T, bool KEEP>
+__global__ void dm_adam_rows_kernel(T *w, T *g, T *s, T *r, const int32_t *rows, int64_t n_rows, int E, T gscale, T b1, T c1, T b2, T c2, T eps,
+                                    T neg_step) {
   const int64_t n = n_rows * E;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
-    dm_adam_elem_f64(w, g, s, r, (int64_t)rows[t / E] * E + (t % E), gscale, b1, c1, b2, c2, eps, neg_step);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = (int64_t)rows[t / E] * E + (t % E);
+    const T gi = g[i];
+    dm_adam_elem(w, g, s, r, i, gscale, b1, c1, b2, c2, eps, neg_step);
+    if (KEEP) g[i] = gi;
+  }
 }
 
 // Rebuild every fragment-ordered copy of the three small matrices from the (updated) compact vector.  The fp32 beam kernels'

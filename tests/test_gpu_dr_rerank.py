@@ -189,6 +189,50 @@ def test_adam_wiring(dt):
 
 
 @pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_reinit_resets_the_optimizer_state(dt):
+    """dm_dr_rerank_train_init on a handle that has trained: both vectors' gradient (the criterion's accumulates), moments, time steps,
+    active rows and remembered rows start over, and so does the sampler's call count.  Two steps, init again, one step on the FIRST
+    batch with negatives drawn on the device: every buffer equals, byte for byte, a fresh engine's that was loaded with the weights
+    at re-init; and a fresh engine's under DM_ADAM_DENSE=1 — a list that kept its bits but lost its count would leave the first
+    batch's rows out of the rows path."""
+    c = R.make_case("tiny-" + dt)                                            # E = 16, L = 1, B = 1
+    E, L, NI = c["dims"]
+    T, S = R.NP[dt], 1
+    kw = dict(lr=1e-2, lr_decay=0.5, seed=5)
+    rng = np.random.default_rng(14)
+    first = (c["seq"], c["targets"])
+    other = R.make_batch(rng, L, 3, S, "pad")
+
+    def one_step(eng, dense=False):
+        loss = eng.dr_rerank_forward_backward(*first)                        # the sampler's step 0 on a new training state
+        g = [eng.dr_rerank_download(v, "grad").tobytes() for v in ("graph", "softmax")]
+        if dense:
+            os.environ["DM_ADAM_DENSE"] = "1"
+        try:
+            eng.dr_rerank_adam_step(1.0)
+        finally:
+            os.environ.pop("DM_ADAM_DENSE", None)
+        return [loss] + g + state_bytes(eng)
+
+    eng = engine_for(c["weights"], c["dims"], c["layer"], T, S=S, **kw)
+    for batch in (first + (c["negatives"][:, :S],), other):
+        eng.dr_rerank_forward_backward(*batch)
+        eng.dr_rerank_adam_step(1.0)
+    eng.dr_rerank_forward_backward(*other)                                   # gradients and remembered rows the new run must not see
+    w_at = dict(c["weights"])
+    w_at.update(split_rerank(eng.dr_rerank_download("graph"), eng.dr_rerank_download("softmax"), E, L, NI))
+    eng.dr_rerank_train_init(S, **kw)
+    assert all((eng.dr_rerank_download(v, w) == 0).all() for v in ("graph", "softmax") for w in ("grad", "s", "r"))
+    got = one_step(eng)
+    eng.close()
+    for dense in (False, True):
+        fresh = engine_for(w_at, c["dims"], c["layer"], T, S=S, **kw)
+        want = one_step(fresh, dense)
+        fresh.close()
+        assert got == want, "dense twin" if dense else "fresh engine"
+
+
+@pytest.mark.parametrize("dt", ["f32", "f64"])
 @pytest.mark.parametrize("accumulate", [True, False])
 def test_the_softmax_tables_have_their_own_optimizer(dt, accumulate):
     """graph options lr_decay = 0.5, eps 1e-8; the criterion's default: the same lr, NO decay, eps 1e-7.  Two steps: the softmax tables

@@ -127,6 +127,49 @@ def test_adam_wiring(dt):
         assert a.tobytes() == b.tobytes()
 
 
+@pytest.mark.parametrize("dt", ["f32", "f64"])
+def test_reinit_resets_the_optimizer_state(dt):
+    """dm_dr_train_init on a handle that has trained: gradient, both moments, the time step, the active rows and the remembered rows of
+    the last batch all start over.  Two steps, init again, one step on the FIRST batch (rows the old run had listed): every buffer
+    equals, byte for byte, a fresh engine's that was loaded with the weights at re-init; and a fresh engine's under DM_ADAM_DENSE=1 —
+    a list that kept its bits but lost its count would leave those rows out of the rows path."""
+    K, D, L, E, NI, B = 7, 3, 4, 16, R.NUM_ITEM, 8
+    dims, T = (E, L, K, D, NI), R.NP[dt]
+    rng = np.random.default_rng(13)
+    wd = synth.make_dr_model(NI, K, D, L, E, rng)
+    batches = [R.make_batch(rng, K, D, L, B, "pad") for _ in range(2)]
+    adam = dict(lr=1e-2, lr_decay=0.5)
+    assert 4 * R.touched_rows(dict(dims=dims, seq=batches[0][0], paths=batches[0][1])).sum() < NI + K * (D - 1)      # the rows path
+
+    def one_step(eng, dense=False):
+        eng.dr_train_forward_backward(*batches[0])
+        g = eng.dr_train_download("grad").tobytes()
+        if dense:
+            os.environ["DM_ADAM_DENSE"] = "1"
+        try:
+            eng.dr_adam_step(1.0)
+        finally:
+            os.environ.pop("DM_ADAM_DENSE", None)
+        return [g] + [eng.dr_train_download(w).tobytes() for w in ("weights", "grad", "s", "r")]
+
+    eng = engine_for(wd, dims, T, **adam)
+    for seq, paths in batches:
+        eng.dr_train_forward_backward(seq, paths)
+        eng.dr_adam_step(1.0)
+    eng.dr_train_forward_backward(*batches[1])                               # a gradient and remembered rows the new run must not see
+    w_at = eng.dr_train_download("weights")
+    eng.dr_train_init(**adam)
+    assert eng.dr_train_download("weights").tobytes() == w_at.tobytes()
+    assert all((eng.dr_train_download(w) == 0).all() for w in ("grad", "s", "r"))
+    got = one_step(eng)
+    eng.close()
+    for dense in (False, True):
+        fresh = engine_for(split_params(w_at, *dims), dims, T, **adam)
+        want = one_step(fresh, dense)
+        fresh.close()
+        assert got == want, "dense twin" if dense else "fresh engine"
+
+
 # ------------------------------------------------------------------------------------------------------------------------ G4
 @pytest.fixture(params=["one_kernel", "sliced"])
 def search_path(request):

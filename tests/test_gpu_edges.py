@@ -580,6 +580,51 @@ def test_adam_step_over_active_rows_equals_dense_stream(dtype):
     assert np.signbit(res["active"][0][6 * E: 7 * E]).all() and not np.signbit(res["active"][0][8 * E: 9 * E]).any()      # untouched signed zeros
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_train_init_again_resets_the_optimizer_state(dtype):
+    """dm_train_init on a handle that has trained: gradient, both moments, the time step and the active rows start over.  Two steps,
+    init again, one step on the FIRST step's rows (rows the old run had listed): weights, gradient and moments equal, byte for byte,
+    a fresh engine's that was loaded with the weights at re-init, and the step takes the active-rows path over those rows alone."""
+    from dismember_amd import Engine
+    from dismember_amd import _native as N
+    E, NI, n_rows = 16, 4095, 300
+    rng = np.random.default_rng(15)
+    w = random_din_weights(rng, E, NI, dtype=dtype)
+    steps = [(rng.choice(NI, n_rows, replace=False).astype(np.int32), rng.normal(0, 1e-2, (n_rows, E)).astype(dtype)) for _ in range(2)]
+    adam = dict(lr=1e-2, lr_decay=0.5)
+
+    def add_rows(eng, rows, g):          # one gradient row per touched row, added once each: bitwise reproducible
+        d_r = eng.dev_alloc(rows.nbytes); d_g = eng.dev_alloc(g.nbytes)
+        eng.h2d(d_r, rows); eng.h2d(d_g, g)
+        eng._chk(N.lib().dm_train_add_rows(eng._h, d_r, d_g, rows.size))
+        eng.dev_free(d_r); eng.dev_free(d_g)
+
+    def one_step(eng):
+        add_rows(eng, *steps[0])
+        g = eng.train_download("grad").tobytes()
+        eng.adam_step()
+        assert eng.adam_last_step_rows() == (n_rows, True)
+        return [g] + [eng.train_download(x).tobytes() for x in ("weights", "grad", "s", "r")]
+
+    eng = Engine(0); eng.load_weights_din(w, E, NI)
+    eng.train_init(**adam)
+    for rows, g in steps:
+        add_rows(eng, rows, g)
+        eng.adam_step()
+    add_rows(eng, *steps[1])                                                 # a gradient the new run must not see
+    w_at = eng.train_download("weights")
+    eng.train_init(**adam)
+    assert eng.train_download("weights").tobytes() == w_at.tobytes()
+    assert all((eng.train_download(x) == 0).all() for x in ("grad", "s", "r"))
+    got = one_step(eng)
+    eng.close()
+    fresh = Engine(0); fresh.load_weights_din(w_at, E, NI)
+    fresh.train_init(**adam)
+    want = one_step(fresh)
+    fresh.close()
+    assert got == want
+
+
 def test_jtm_cached_entry_points_reject_bad_calls():
     """dm_jtm_step_cached / dm_jtm_optimize_cached without a cached catalogue, with a catalogue of another size, with impossible
     levels: an error code and a message, never a launch."""
