@@ -74,6 +74,18 @@ SIGNATURES = {
     "dm_load_weights_deepfm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "dm_get_scorer_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dm_deepfm_forward": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, f32p]),
+    "dm_deepfm_train_init": (C.c_int, [C.c_void_p, C.POINTER(AdamOpts)]),
+    "dm_deepfm_train_free": (C.c_int, [C.c_void_p]),
+    "dm_deepfm_train_forward_backward": (C.c_int, [C.c_void_p, i32p, i32p, f32p, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
+    "dm_deepfm_train_forward_backward_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                                       C.POINTER(C.c_double)]),
+    "dm_deepfm_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
+    "dm_deepfm_train_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "dm_deepfm_train_download": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_int64]),
+    "dm_deepfm_make_train_batch": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, i32p, C.c_int, C.POINTER(SampleOpts),
+                                             i32p, i32p, f32p, C.c_int64, i64p]),
+    "dm_deepfm_sample_train_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, i32p, C.c_int,
+                                                   C.POINTER(SampleOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, i64p]),
     "dm_din_forward": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "dm_tdm_beam_search": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, C.POINTER(SearchOpts), i64p, i32p, i32p,
                                      f32p, i32p]),

@@ -121,6 +121,7 @@ struct dm_ctx {
   int dfm_L = 0;               // DeepFM: the history length l1.W is sized by
   float *d_dfm_frag = nullptr; // DeepFM: [0 ; W1a ; 0] as MFMA B fragments, and l2.W over the same padded columns
   float *d_dfm_w2p = nullptr;
+  struct dm_dfm_train *dfm_tr = nullptr;   // DeepFM training state (dm_deepfm_train_init, dfm_train.hip.inc): the owner's, never mirrored by a clone
   LazyCopies lazy;             // the copies rebuilt on first use after a weight change, and their stale flags (lazy_copies.hip.inc)
   int scorer_mode = DM_SCORER_AUTO;      // dm_set_scorer_mode
   bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
@@ -425,8 +426,10 @@ static void free_training(dm_ctx *h) {
   dm_release(h->d_loss, h->d_tr64, h->d_attTA, h->d_w1aTA, h->d_w1bTA, h->d_touch_bits, h->d_touch_list, h->d_touch_cnt);
   h->train_ready = false; h->touch_cap = 0; h->touch_ub = 0;
 }
+static void dfm_train_release(dm_ctx *h);
 static void free_weights(dm_ctx *h) {
   model_changed(h);
+  dfm_train_release(h);
   if (h->emb32_owned) dm_release(h->d_emb32);
   h->d_emb32 = nullptr; h->emb32_owned = false;
   dm_release(h->d_compact, h->d_wfrag, h->d_afrag, h->d_bfrag, h->d_attA, h->d_w1aA, h->d_w1bA, h->d_b1, h->d_w2, h->d_att_wT_t, h->d_l1T_t);
@@ -1577,6 +1580,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "otm64.hip.inc"
 #include "tdm_pipeline.hip.inc"
 #include "deepfm.hip.inc"
+#include "dfm_train.hip.inc"
 #include "comm.hip.inc"
 #include "jtm_sharded.hip.inc"
 #include "train_grouped_host.hip.inc"

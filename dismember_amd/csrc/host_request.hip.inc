@@ -29,6 +29,9 @@ enum EvKind {
   EV_DRT_FWD = 50, EV_DRT_SOFTMAX = 51, EV_DRT_DX = 52, EV_DRT_DW = 53, EV_DRT_EMB = 54, EV_DRT_ADAM = 55,
   // the rerank model's training step (dr_rerank_train.hip.inc): user-vector GEMM, classes of the rows (sampler), sampled softmax, the
   // softmax tables' gradient (pairs, sort, segment sums), dX, dW / db with their slab sums, embedding gradient, both Adam updates
+  // the DeepFM training step under DM_DFM_TIME_LAUNCHES=1 (dfm_train.hip.inc): the fused rows kernel (forward, loss, dH, dX), the l1.W / l1.b
+  // product with its slab sum, embedding gradient (pairs, sort, segment sums), Adam
+  EV_DFT_ROWS = 70, EV_DFT_DW = 71, EV_DFT_EMB = 72, EV_DFT_ADAM = 73,
   EV_DRR_FWD = 60, EV_DRR_SAMPLE = 61, EV_DRR_SOFTMAX = 62, EV_DRR_SMGRAD = 63, EV_DRR_DX = 64, EV_DRR_DW = 65, EV_DRR_EMB = 66, EV_DRR_ADAM = 67,
 };
 

@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void dm_sample_kernel(SampleParams p) {
       const int64_t q = q0 + r;
       if (q >= p.cap) break;
       if (lane < p.L) p.seqs[q * p.L + lane] = hc;
-      if (lane == 0) p.rowmask[q] = hm;
+      if (lane == 0 && p.rowmask) p.rowmask[q] = hm;
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -215,9 +215,10 @@ int dm_tdm_set_node_probs(dm_handle_t h, const int32_t *codes, const float *prob
   return DM_OK;
 }
 
-static int sample_check(dm_ctx *h, int64_t T, int L, const int32_t *neg_counts, int n_counts, const dm_sample_opts *o, int64_t *per_target) {
+// kind: the scorer whose training step the rows feed (DM_KIND_DIN: the two entry points below; DM_KIND_DEEPFM: their twins in dfm_train.hip.inc)
+static int sample_check(dm_ctx *h, int kind, int64_t T, int L, const int32_t *neg_counts, int n_counts, const dm_sample_opts *o, int64_t *per_target) {
   if (!h->tree_loaded || !h->ids_loaded) return fail(h, DM_ERR_STATE, "negative sampling: tree and id maps must be loaded first");
-  DM_DIN_ONLY(h, "negative sampling");      // (the rows it makes feed the DIN training step)
+  if (kind == DM_KIND_DIN) DM_DIN_ONLY(h, "negative sampling");      // (the rows it makes feed the DIN training step)
   if (!neg_counts || !o || T < 0 || L <= 0 || L > 32 || o->start_level < 1)
     return fail(h, DM_ERR_INVALID, "negative sampling: bad arguments (start_sample_level must be >= 1, seq_len <= 32)");
   // the sampled rows go straight to dm_train_forward_backward_dev, which does not range-check them: an id map or a tree that
@@ -300,7 +301,7 @@ int dm_tdm_sample_train_batch_dev(dm_handle_t h, const int32_t *d_seq_item_ids, 
                                   int32_t *d_seqs, uint32_t *d_rowmask, float *d_labels, int64_t cap, int64_t *n_rows) {
   if (!h || !n_rows) return DM_ERR_INVALID;
   int64_t per = 0;
-  int rc = sample_check(h, T, L, neg_counts, n_counts, opts, &per);
+  int rc = sample_check(h, DM_KIND_DIN, T, L, neg_counts, n_counts, opts, &per);
   if (rc != DM_OK) return rc;
   *n_rows = T * per;
   if (!d_codes) return DM_OK;                        // size query: an upper bound (targets outside the tree yield no rows)
@@ -315,7 +316,7 @@ int dm_tdm_make_train_batch(dm_handle_t h, const int32_t *seq_item_ids, const in
                             int32_t *out_seqs, uint32_t *out_rowmask, float *out_labels, int64_t cap, int64_t *n_rows) {
   if (!h || !n_rows) return DM_ERR_INVALID;
   int64_t per = 0;
-  int rc = sample_check(h, T, L, neg_counts, n_counts, opts, &per);
+  int rc = sample_check(h, DM_KIND_DIN, T, L, neg_counts, n_counts, opts, &per);
   if (rc != DM_OK) return rc;
   *n_rows = T * per;
   if (!out_codes) return DM_OK;                       // size query

@@ -724,6 +724,106 @@ class Engine:
         self._chk(N.lib().dm_dr_train_download(self._h, {"weights": 0, "grad": 1, "s": 2, "r": 3}[what], out.ctypes.data_as(C.c_void_p), n))
         return out
 
+    # ---- DeepFM: the training step
+    def deepfm_train_init(self, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
+        o = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)
+        self._chk(N.lib().dm_deepfm_train_init(self._h, C.byref(o)))
+
+    def deepfm_train_free(self):
+        self._chk(N.lib().dm_deepfm_train_free(self._h))
+
+    def deepfm_train_forward_backward(self, codes, seqs, labels):
+        """codes [B], seqs [B, L] node codes (-1 = a zero row), labels [B].  Replaces the gradient with this batch's; -> the mean
+        BCE-with-logits loss (float64)."""
+        codes = _i32(codes).ravel()
+        B = codes.size
+        seqs = _i32(seqs).reshape(B, -1) if B else _i32(seqs).reshape(0, 1)
+        lab = np.ascontiguousarray(labels, np.float32).ravel()
+        assert lab.size == B
+        loss = C.c_double(0)
+        self._chk(N.lib().dm_deepfm_train_forward_backward(self._h, _p(codes, N.i32p), _p(seqs, N.i32p), _p(lab, N.f32p), B,
+                                                           seqs.shape[1], C.byref(loss)))
+        return loss.value
+
+    def deepfm_train_forward_backward_dev(self, d_codes, d_seqs, d_labels, B, L):
+        """the same on device arrays (not range-checked) -> the mean loss"""
+        loss = C.c_double(0)
+        self._chk(N.lib().dm_deepfm_train_forward_backward_dev(self._h, d_codes, d_seqs, d_labels, int(B), int(L), C.byref(loss)))
+        return loss.value
+
+    def deepfm_make_train_batch(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, with_prob=False, tolerance=20):
+        """make_train_batch for a DeepFM model (no mask): (codes [R], seqs [R, L], labels [R])."""
+        seq = _i32(seq_item_ids)
+        tgt = _i32(target_item_ids).ravel()
+        T, L = seq.shape
+        neg = _i32(neg_counts)
+        o = N.SampleOpts(int(start_level), int(bool(with_prob)), int(tolerance), 0, int(seed))
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_deepfm_make_train_batch(self._h, _p(seq, N.i32p), _p(tgt, N.i32p), T, L, _p(neg, N.i32p), neg.size,
+                                                     C.byref(o), None, None, None, 0, C.byref(n)))
+        R = n.value
+        codes = np.empty(max(R, 1), np.int32); seqs = np.empty((max(R, 1), L), np.int32); lab = np.empty(max(R, 1), np.float32)
+        self._chk(N.lib().dm_deepfm_make_train_batch(self._h, _p(seq, N.i32p), _p(tgt, N.i32p), T, L, _p(neg, N.i32p), neg.size,
+                                                     C.byref(o), _p(codes, N.i32p), _p(seqs, N.i32p), _p(lab, N.f32p), R, C.byref(n)))
+        R = n.value
+        return codes[:R], seqs[:R], lab[:R]
+
+    def deepfm_train_step_sampled(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, with_prob=False, tolerance=20,
+                                  return_rows=False):
+        """train_step_sampled for a DeepFM model: dm_deepfm_sample_train_batch_dev expands the targets on the device straight into
+        the buffers of dm_deepfm_train_forward_backward_dev.  Returns the mean BCE loss of the expanded rows (with return_rows: and
+        the rows (codes, seqs, labels), downloaded)."""
+        seq = _i32(seq_item_ids)
+        tgt = _i32(target_item_ids).ravel()
+        T, L = seq.shape
+        neg = _i32(neg_counts)
+        o = N.SampleOpts(int(start_level), int(bool(with_prob)), int(tolerance), 0, int(seed))
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_deepfm_sample_train_batch_dev(self._h, None, None, T, L, _p(neg, N.i32p), neg.size, C.byref(o), None, None,
+                                                           None, 0, C.byref(n)))
+        R = max(n.value, 1)
+        al = lambda v: (v + 255) & ~255
+        need = al(T * L * 4) + al(T * 4) + al(R * 4) + al(R * L * 4) + al(R * 4)        # the five sub-buffers as carved below
+        if getattr(self, "_samp_bytes", 0) < need:
+            if getattr(self, "_samp_buf", None):
+                self.dev_free(self._samp_buf)
+            self._samp_buf, self._samp_bytes = self.dev_alloc(need + need // 2), need + need // 2
+        base = self._samp_buf.value
+        d_seq = C.c_void_p(base); base += al(T * L * 4)
+        d_tgt = C.c_void_p(base); base += al(T * 4)
+        d_codes = C.c_void_p(base); base += al(R * 4)
+        d_seqs = C.c_void_p(base); base += al(R * L * 4)
+        d_lab = C.c_void_p(base)
+        self.h2d(d_seq, seq); self.h2d(d_tgt, tgt)
+        self._chk(N.lib().dm_deepfm_sample_train_batch_dev(self._h, d_seq, d_tgt, T, L, _p(neg, N.i32p), neg.size, C.byref(o), d_codes,
+                                                           d_seqs, d_lab, R, C.byref(n)))
+        R = n.value
+        loss = C.c_double(0)
+        if R:
+            self._chk(N.lib().dm_deepfm_train_forward_backward_dev(self._h, d_codes, d_seqs, d_lab, R, L, C.byref(loss)))
+        if not return_rows:
+            return loss.value
+        codes = np.empty(R, np.int32); seqs = np.empty((R, L), np.int32); lab = np.empty(R, np.float32)
+        if R:
+            self.d2h(codes, d_codes); self.d2h(seqs, d_seqs); self.d2h(lab, d_lab)
+        return loss.value, (codes, seqs, lab)
+
+    def deepfm_adam_step(self, grad_scale=1.0):
+        self._chk(N.lib().dm_deepfm_adam_step(self._h, float(grad_scale)))
+
+    def deepfm_train_param_count(self):
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_deepfm_train_param_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def deepfm_train_download(self, what="weights"):
+        """The trained vector [emb ; l1.W ; l1.b ; l2.W ; l2.b] ("weights"), its gradient ("grad") or an Adam moment ("s", "r"), in
+        the model's own (unpadded) layout, float32."""
+        n = self.deepfm_train_param_count()
+        out = np.empty(n, np.float32)
+        self._chk(N.lib().dm_deepfm_train_download(self._h, {"weights": 0, "grad": 1, "s": 2, "r": 3}[what], _p(out, N.f32p), n))
+        return out
+
     # ---- Deep-Retrieval E-step: the rerank model's training step (DESIGN.md §11)
     def dr_rerank_train_init(self, num_sampled, seed=0, accumulate=True, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8, softmax=None):
         """graph optimizer from the keywords; softmax: None (the reference's criterion optimizer: lr, 0.9, 0.999, eps 1e-7, no decay) or a

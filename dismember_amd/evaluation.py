@@ -2,7 +2,7 @@
 (tdm/src/main/scala/com/mass/tdm/evaluation/Evaluator.scala:14-74), `Metrics.computeMetrics` (Metrics.scala:5-25) and
 `EvalResult` (EvalResult.scala:3-37) over the device entry points: one batched `dm_tdm_beam_search` (consumed-item
 filtering + the beam-widening rule of Recommender.scala:28-33) per eval batch instead of one recommend call per
-user, and one `dm_din_forward` for the loss rows.  Only the O(topk) set intersections and the BCE reduction of the
+user, and one `dm_din_forward` (`dm_deepfm_forward` on a DeepFM engine, whose graph has no mask) for the loss rows.  Only the O(topk) set intersections and the BCE reduction of the
 logits run on the host."""
 import numpy as np
 
@@ -71,13 +71,21 @@ def evaluate(engine, sequences, labels, users, user_consumed, neg_counts, topk, 
     step = max(1, batch_size // per)
     total = EvalResult()
     batches = []
+    deepfm = engine.scorer == "deepfm"
+    if deepfm:
+        use_mask = False
     for off in range(0, N, step):
         n = min(step, N - off)
         tgt = np.array([labels[i][0] for i in range(off, off + n)], np.int32)
-        codes, rseq, rmask, rlab = engine.make_train_batch(seqs[off:off + n], tgt, neg, start_level=start_level,
-                                                           seed=seed + off, use_mask=use_mask)
-        pad = engine.rowmask_to_flat(rmask, L)
-        out = engine.din_forward(codes, rseq, pad, L=L)
+        if deepfm:
+            codes, rseq, rlab = engine.deepfm_make_train_batch(seqs[off:off + n], tgt, neg, start_level=start_level, seed=seed + off)
+            pad = np.zeros(0, np.int32)
+            out = engine.deepfm_forward(codes, rseq) if codes.size else np.zeros(0, np.float32)
+        else:
+            codes, rseq, rmask, rlab = engine.make_train_batch(seqs[off:off + n], tgt, neg, start_level=start_level,
+                                                               seed=seed + off, use_mask=use_mask)
+            pad = engine.rowmask_to_flat(rmask, L)
+            out = engine.din_forward(codes, rseq, pad, L=L)
         res = EvalResult(loss=bce_with_logits(out, rlab) * n, count=n)
         ids, _, cnt = engine.tdm_beam_search(seqs[off:off + n], candidate_num, topk, use_mask=use_mask,
                                              consumed=[user_consumed[int(users[i])] for i in range(off, off + n)],

@@ -7,9 +7,10 @@
 
 Each function is the body of the reference's `CommandApp` of the same name (examples/src/main/scala/com/mass/retrieval/):
 the conf file is read by dismember_amd.conf (same keys, same defaults, same "failed to find <key>" stop), the steps are the
-reference's, and every hot step is a library call — tree index + DIN weights in HBM, level-wise negative sampling, forward /
-backward / Adam, the batched evaluator, `JTM.optimize` in one call.  What is NOT carried over: Java serialisation (the model file
-is `dm_save_model`'s flat checkpoint), HDFS paths, the DeepFM graph and spectral clustering in `TDMClusterTree`.
+reference's, and every hot step is a library call — tree index + scorer weights in HBM, level-wise negative sampling, forward /
+backward / Adam, the batched evaluator, `JTM.optimize` in one call.  `deep_model` selects DIN or, for TDM, DeepFM (trained through
+`dm_deepfm_train_*`; OTM's `DeepFM[Double]` is not built).  What is NOT carried over: Java serialisation (the model file is
+`dm_save_model`'s flat checkpoint), HDFS paths and spectral clustering in `TDMClusterTree`.
 
   tdm_initialize_tree   tdm/TDMInitializeTree.scala:14-48  -> TreeInit.generate (tdm/.../tree/TreeInit.scala:33-66)
   tdm_cluster_tree      tdm/TDMClusterTree.scala           -> RecursiveCluster.run on the device (dismember_amd/cluster.py; also
@@ -82,14 +83,26 @@ def _din_init(E, num_index, seed, dtype=np.float32):
     return w
 
 
+def _deepfm_init(E, L, num_index, seed):
+    """DeepFM.buildModel's initial parameters in Graph.parameters order [emb ; l1.W ; l1.b ; l2.W ; l2.b], by _din_init's rule:
+    N(0, 0.05) tables and weights, zero biases (tdm/.../model/DeepFM.scala:11-45)."""
+    rng = np.random.default_rng(seed)
+    T = L + 1
+    w = (rng.standard_normal(num_index * E + T * T * E + 2 * T + 1) * 0.05).astype(np.float32)
+    b1 = num_index * E + T * T * E
+    w[b1:b1 + T] = 0
+    w[-1] = 0
+    return w
+
+
 def tdm_train_deep_model(conf_path, quiet=True, engine=None, seed=2024, max_iterations=None, time_recommend=True):
     """-> dict(losses, eval (list of (iteration, EvalResult means)), recommendation, params)."""
     from .engine import Engine
     from .facade import TDM
     from .trainer import TDMTrainer
     p = C.task_params("TDMTrainDeepModel", conf_path)
-    if p["deep_model"] != "din":
-        raise ValueError("DeepModel name should either be DeepFM or DIN (DeepFM is out of scope of this build)")
+    if p["deep_model"] not in ("din", "deepfm"):
+        raise ValueError("DeepModel name should either be DeepFM or DIN")
     if not quiet:
         print("\n".join("%s: %s" % kv for kv in sorted(p.items())))
     L, E = p["seq_len"], p["embed_size"]
@@ -97,7 +110,10 @@ def tdm_train_deep_model(conf_path, quiet=True, engine=None, seed=2024, max_iter
     eng.load_tree_file(p["tree_protobuf_path"])                       # TDMOp.initTree
     depth = eng.max_level
     ni = (1 << (depth + 1)) - 1
-    eng.load_weights_din(_din_init(E, ni, seed), E, ni)
+    if p["deep_model"] == "deepfm":
+        eng.load_weights_deepfm(_deepfm_init(E, L, ni, seed), E, L, ni)
+    else:
+        eng.load_weights_din(_din_init(E, ni, seed), E, ni)
     with open(p["train_path"]) as f:
         tseq, ttgt = tree_io.read_train_data(f)
     with open(p["eval_path"]) as f:
@@ -140,7 +156,7 @@ def tdm_train_deep_model(conf_path, quiet=True, engine=None, seed=2024, max_iter
             epoch += 1
             order = rng.permutation(len(ttgt)); pos, count, t_epoch = 0, 0, 0.0
     _mkdir_for(p["model_path"], p["embed_path"])
-    tdm = TDM(eng, p["deep_model"])
+    tdm = TDM(eng, "DeepFM" if p["deep_model"] == "deepfm" else p["deep_model"])
     tdm.save_model(p["model_path"], p["embed_path"])
     out = dict(losses=losses, eval=evals, params=p, engine=eng)
     query = [0, 0, 2126, 204, 3257, 3439, 996, 1681, 3438, 1882][-L:] if L <= 10 else [0] * (L - 10) + [0, 0, 2126, 204, 3257, 3439, 996, 1681, 3438, 1882]

@@ -1,4 +1,4 @@
-"""Data-parallel training of the DIN scorer: mirror of the reference's LocalOptimizer
+"""Training of the node scorer (DIN data-parallel; DeepFM on one device): mirror of the reference's LocalOptimizer
 (tdm/src/main/scala/com/mass/tdm/optim/LocalOptimizer.scala:58-187) with one worker per GPU.
 
 Reference: N worker threads, each with a model clone sharing the weights and a private gradient buffer;
@@ -16,7 +16,9 @@ class TDMTrainer:
     """One worker of LocalOptimizer.optimize: sample negatives, forward/backward, exchange, Adam.
 
     comm: dismember_amd.comm.Comm (or None for a single worker).  sampler: "device" draws the negatives on the GPU
-    (dm_tdm_sample_train_batch_dev; rows never visit the host), "host" uses dm_tdm_make_train_batch."""
+    (dm_tdm_sample_train_batch_dev; rows never visit the host), "host" uses dm_tdm_make_train_batch.
+    An engine that holds a DeepFM model is driven through its own entry points (Engine.deepfm_*), without a mask — the graph has none,
+    tdm/.../model/TDM.scala:26-29 — and without a communicator: gradient exchange for DeepFM is not built."""
 
     def __init__(self, engine, neg_counts, start_level=1, use_mask=True, lr=1e-3, comm=None, seed=0, sampler="device",
                  with_prob=False, tolerance=20):
@@ -24,6 +26,13 @@ class TDMTrainer:
         self.comm, self.seed, self.it, self.sampler, self.with_prob = comm, seed, 0, sampler, bool(with_prob)
         self.tolerance = int(tolerance)                   # model.sample_tolerance (NegativeSampler.scala:116-145)
         self.sync_s, self.sync_calls = 0.0, 0             # wall time spent in the gradient exchange (bench.py reports it)
+        self.deepfm = engine.scorer == "deepfm"
+        if self.deepfm:
+            if comm is not None:
+                raise ValueError("TDMTrainer: gradient exchange for a DeepFM model is not built (comm must be None)")
+            self.use_mask = False
+            engine.deepfm_train_init(lr=lr)
+            return
         engine.train_init(lr=lr)
         if comm is not None:
             engine.attach_comm(comm)
@@ -33,6 +42,17 @@ class TDMTrainer:
         rank = self.comm.rank if self.comm is not None else 0
         world = self.comm.world if self.comm is not None else 1
         seed = self.seed + 1000003 * self.it + rank
+        if self.deepfm:
+            if self.sampler == "device":
+                loss = self.e.deepfm_train_step_sampled(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
+                                                        with_prob=self.with_prob, tolerance=self.tolerance)
+            else:
+                codes, seqs, y = self.e.deepfm_make_train_batch(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
+                                                                with_prob=self.with_prob, tolerance=self.tolerance)
+                loss = self.e.deepfm_train_forward_backward(codes, seqs, y) if codes.size else 0.0
+            self.e.deepfm_adam_step(1.0)
+            self.it += 1
+            return loss
         if self.sampler == "device":
             loss = self.e.train_step_sampled(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
                                              use_mask=self.use_mask, with_prob=self.with_prob, tolerance=self.tolerance)

@@ -96,7 +96,7 @@ int dm_level_start(int candidate_num, int *start_code, int *level);
 int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, const void *compact,
                         int64_t n_elems);
 
-/* The reference's second node scorer, DeepFM (T/model/DeepFM.scala:11-45; `deep_model DeepFM` in the TDM conf files), serving half:
+/* The reference's second node scorer, DeepFM (T/model/DeepFM.scala:11-45; `deep_model DeepFM` in the TDM conf files); training: dm_deepfm_train_*, below:
  * compact vector in Graph.parameters order (S/nn/graphnn/Graph.scala:37-48; EmbeddingShare DeepFM.scala:18, Linear :35, Linear :39 —
  * FM holds no parameters), T = L + 1:
  *   [emb num_index x E ; l1.W T x (T E) ; l1.b T ; l2.W 1 x T ; l2.b 1]          n_elems = num_index E + T T E + 2 T + 1
@@ -108,7 +108,8 @@ int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, cons
  * pipeline for every L, use_mask must be 0 — the graph has no mask, T/model/TDM.scala:26-29 — and L must be the model's: DM_ERR_INVALID
  * otherwise); dm_get_leaf_embeddings, dm_cluster_tree_model, dm_save_model / dm_load_model work as for DIN; every entry point that
  * evaluates DIN (dm_din_forward, dm_otm_*, dm_tdm_bruteforce_topk, dm_jtm_*, dm_train_*, dm_adam_step, dm_tdm_make_train_batch,
- * dm_tdm_sample_train_batch_dev, dm_set_scorer_mode) returns DM_ERR_UNSUPPORTED and leaves the handle usable. */
+ * dm_tdm_sample_train_batch_dev, dm_set_scorer_mode) returns DM_ERR_UNSUPPORTED and leaves the handle usable (training and its
+ * sampler have DeepFM entry points of their own, below). */
 enum { DM_KIND_DIN = 0, DM_KIND_DEEPFM = 1 };
 int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_index, const void *compact, int64_t n_elems);
 int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len);
@@ -501,6 +502,42 @@ int dm_dr_beam_search_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, in
                           double *d_out_probs, int32_t *d_out_counts);
 int dm_dr_recommend_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, int beam, int topk, int32_t *d_out_ids,
                         double *d_out_scores, int32_t *d_out_counts);
+
+/* ---- DeepFM: one training step on the device ----
+ * LocalOptimizer.trainBatch with the DeepFM graph (T/optim/LocalOptimizer.scala:139-162, useMask = false; T/model/DeepFM.scala:11-45;
+ * S/nn/FM.scala:24-71, S/nn/Linear.scala, S/nn/BCECriterionWithLogits.scala:27-64 averaged over the batch; S/optim/Adam.scala:19-73).
+ * A batch is B rows (codes[r], seqs[r][0..L), labels[r]): node codes, -1 = a zero row that receives no gradient; L is the model's seq_len.
+ * The trained vector is the model's own [emb ; l1.W ; l1.b ; l2.W ; l2.b]; fp32; no floating-point atomics, every sum in a fixed order:
+ * the same state and batch give the same bytes.  Entry points of their own because the DIN ones (dm_train_*, dm_adam_step,
+ * dm_tdm_make_train_batch, dm_tdm_sample_train_batch_dev) keep answering DM_ERR_UNSUPPORTED while a DeepFM model is loaded.
+ * All of them: owner only (DM_ERR_STATE on a dm_clone clone), DM_ERR_STATE without a model or on a DIN model; the handle stays usable after
+ * every refusal.  Any later dm_load_weights_* / dm_load_model drops the training state. */
+int dm_deepfm_train_init(dm_handle_t h, const dm_adam_opts *opts);      /* zero gradient and moments; bad options: DM_ERR_INVALID */
+int dm_deepfm_train_free(dm_handle_t h);                                /* the model keeps serving */
+/* replaces the gradient with this batch's (zeroGradParameters + forward + backward, LocalOptimizer.scala:139-162); *out_loss (host, or NULL)
+ * = the mean BCE-with-logits loss.  Host arrays, range-checked like LookupTable.scala:29-53 (an id outside [-1, num_index): DM_ERR_INDEX).
+ * L != the model's seq_len, B <= 0 or a null array: DM_ERR_INVALID; before dm_deepfm_train_init: DM_ERR_STATE; B (L + 1) >= 2^31 or more
+ * than 4 194 240 rows: DM_ERR_UNSUPPORTED. */
+int dm_deepfm_train_forward_backward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, const float *labels, int64_t B, int L, double *out_loss);
+/* the same on device arrays, NOT range-checked (an id outside [0, num_index) is read as -1); out_loss is still a host pointer */
+int dm_deepfm_train_forward_backward_dev(dm_handle_t h, const int32_t *d_codes, const int32_t *d_seqs, const float *d_labels, int64_t B, int L, double *out_loss);
+/* Adam.optimize (S/optim/Adam.scala:19-73) over the vector with dm_dr_adam_step's rules: the embedding rows a gradient has ever reached plus
+ * the dense blocks, or the whole vector when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 - the same bytes
+ * either way.  Rebuilds every copy the searches read and tells the clones: serving continues with the new weights. */
+int dm_deepfm_adam_step(dm_handle_t h, float grad_scale);
+int dm_deepfm_train_param_count(dm_handle_t h, int64_t *n);             /* of the model's own (unpadded) layout */
+/* what: 0 weights (needs no training state), 1 gradient, 2 first moment, 3 second moment, in the model's own layout; n must be the
+ * parameter count (DM_ERR_INVALID) */
+int dm_deepfm_train_download(dm_handle_t h, int what, float *out, int64_t n);
+/* dm_tdm_make_train_batch / dm_tdm_sample_train_batch_dev for a DeepFM model (NegativeSampler.scala:76-158 + MiniBatch.convert,
+ * T/dataset/MiniBatch.scala:49-88 without transformWithMask): the same rows from the same seed, no row mask.  opts->use_mask must be 0 and
+ * L the model's seq_len (DM_ERR_INVALID). */
+int dm_deepfm_make_train_batch(dm_handle_t h, const int32_t *seq_item_ids, const int32_t *target_item_ids, int64_t T, int L,
+                               const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *out_codes,
+                               int32_t *out_seqs, float *out_labels, int64_t cap, int64_t *n_rows);
+int dm_deepfm_sample_train_batch_dev(dm_handle_t h, const int32_t *d_seq_item_ids, const int32_t *d_target_item_ids, int64_t T, int L,
+                                     const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *d_codes,
+                                     int32_t *d_seqs, float *d_labels, int64_t cap, int64_t *n_rows);
 
 /* ---- Deep-Retrieval E-step: one training step of the LAYER model on the device ----
  * D/model/LayerModel.scala:22-49, D/dataset/MiniBatch.scala:18-50, D/loss/CrossEntropyLayer.scala, D/optim/LocalOptimizer.scala:58-116.
