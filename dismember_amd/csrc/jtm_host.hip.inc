@@ -138,6 +138,16 @@ __global__ void dm_jtm_sum_kernel(const int64_t *row_off, int64_t R0, int64_t n_
   weights[t] = w;
 }
 
+// DM_JTM_MAX_PAIRS=<positive integer>: scored rows per chunk of the child-weight loops, read per call like DM_JTM_REBALANCE (tests: chunk
+// boundaries at catalogue sizes a test can afford); unset or invalid: the caller's default
+static int64_t jtm_max_pairs(int64_t dflt) {
+  const char *e = getenv("DM_JTM_MAX_PAIRS");
+  if (!e || !*e) return dflt;
+  char *end = nullptr;
+  const long long v = strtoll(e, &end, 10);
+  return (*end == 0 && v > 0) ? (int64_t)v : dflt;
+}
+
 // row_off / row_item_ids: host arrays of the items [0, n_items) — or, with cached = true, the handle's device copies made by
 // dm_jtm_cache_rows (then the items are [i_lo, i_lo + n_items) of the cached catalogue and nothing but item_node goes up)
 static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32_t *row_item_ids, bool cached, int64_t i_lo,
@@ -157,7 +167,7 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
   const int gap = level - old_level;
   const int nchild = 1 << gap;
   const int nchain = (2 << gap) - 2;            // distinct nodes below the item's node, levels old+1..level
-  const int64_t max_pairs = (int64_t)16 << 20;  // scored rows per chunk (640 MB of history codes at L = 10)
+  const int64_t max_pairs = jtm_max_pairs((int64_t)16 << 20);  // scored rows per chunk (640 MB of history codes at L = 10)
   std::vector<int32_t> row_item;
   int64_t *d_off = nullptr;
   int32_t *d_ritem = nullptr, *d_rids = nullptr, *d_node = nullptr, *d_codes = nullptr, *d_seqs = nullptr;
@@ -763,7 +773,8 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
   const int gap = level - old_level, nchild = 1 << gap, nchain = (2 << gap) - 2;
   const bool f64 = h->dtype == DM_F64;
   const size_t esz = f64 ? 8 : 4;
-  const int64_t max_pairs = (int64_t)4 << 20;
+  const int64_t max_pairs = jtm_max_pairs((int64_t)4 << 20);
+  const int64_t all_pairs = n_items > 0 ? (row_off[n_items] - row_off[0]) * nchain : 0;      // every chunk takes the kernel of the whole call
   std::vector<int32_t> codes, seqs;
   std::vector<unsigned> rmask;
   std::vector<double> logits;
@@ -816,7 +827,7 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
       if (e == hipSuccess) e = hipMemcpyAsync(d_seqs, seqs.data(), (size_t)pairs * L * 4, hipMemcpyHostToDevice, h->stream);
       if (e == hipSuccess) e = hipMemcpyAsync(d_mask, rmask.data(), (size_t)pairs * 4, hipMemcpyHostToDevice, h->stream);
       if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_otm_child_weights: upload failed");
-      if (f64) rc = din_forward_t<double>(h, d_codes, d_seqs, d_mask, pairs, L, (double *)d_out);
+      if (f64) rc = din_forward_t<double>(h, d_codes, d_seqs, d_mask, pairs, L, (double *)d_out, all_pairs);
       else rc = L <= DM_MAXL ? din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, (float *)d_out)
                              : din_forward_t<float>(h, d_codes, d_seqs, d_mask, pairs, L, (float *)d_out);
       if (rc != DM_OK) return rc;
