@@ -74,6 +74,12 @@ SIGNATURES = {
     "dm_load_weights_deepfm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64]),
     "dm_get_scorer_kind": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "dm_deepfm_forward": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, f32p]),
+    "dm_deepfm_pairs_forward": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, C.c_int, f32p]),
+    "dm_deepfm_jtm_child_weights": (C.c_int, [C.c_void_p, i64p, i32p, i32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, f32p]),
+    "dm_deepfm_jtm_child_weights_cached": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
+    "dm_deepfm_jtm_step_cached": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p]),
+    "dm_deepfm_jtm_optimize_cached": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, C.POINTER(C.c_double)]),
     "dm_deepfm_train_init": (C.c_int, [C.c_void_p, C.POINTER(AdamOpts)]),
     "dm_deepfm_train_free": (C.c_int, [C.c_void_p]),
     "dm_deepfm_train_forward_backward": (C.c_int, [C.c_void_p, i32p, i32p, f32p, C.c_int64, C.c_int, C.POINTER(C.c_double)]),

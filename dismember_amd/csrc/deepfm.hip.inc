@@ -43,6 +43,21 @@ __global__ void dfm_derive_kernel(const float *l1_w, const float *l2_w, int E, i
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NCT * 16; i += gridDim.x * blockDim.x) w2p[i] = (i >= 1 && i <= T) ? l2_w[i - 1] : 0.0f;
 }
 
+// ---- W1s (the L history blocks of every l1.W row) as MFMA B fragments, for the per-history set-up of dfm_jtm.hip.inc:
+// fragS[ct][j][jc][lane = (g, r)][t] = W1s[col 16 ct + r - 1][history position j][feature 16 jc + 4 g + t] for col = 1 .. T, 0 for column 0
+// (c goes there) and beyond T: the column numbering of aux.  NCT L E 64 bytes.
+__global__ void dfm_jtm_derive_kernel(const float *l1_w, int E, int L, int NCT, float *fragS) {
+  const int NJ = E / 16, T = L + 1;
+  const int64_t n = (int64_t)NCT * L * NJ * 256;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int t = (int)(i & 3), lane = (int)(i >> 2) & 63;
+    const int64_t blk = i >> 8;
+    const int jc = (int)(blk % NJ), j = (int)((blk / NJ) % L), ct = (int)(blk / ((int64_t)NJ * L));
+    const int col = 16 * ct + (lane & 15), e = 16 * jc + 4 * (lane >> 4) + t;
+    fragS[i] = (col >= 1 && col <= T) ? l1_w[((int64_t)(col - 1) * T + 1 + j) * E + e] : 0.0f;
+  }
+}
+
 // ---- per user: s [U][E], aux [U][NC]: aux[0] = c, aux[n] = a[n - 1] for n = 1 .. T, 0 beyond.  One workgroup of 256 per user.
 struct DfmUser {
   const float *emb, *l1_w, *l1_b;      // l1_w [T][T E]
@@ -251,8 +266,10 @@ int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_i
   const int NCT = dfm_col_tiles(L);
   ALLOC(h, h->d_dfm_frag, (size_t)NCT * Ep * 64);
   ALLOC(h, h->d_dfm_w2p, (size_t)NCT * 16 * 4);
+  ALLOC(h, h->d_dfm_fragS, (size_t)NCT * L * Ep * 64);
   const DfmBlocks b = dfm_blocks(h);
   hipLaunchKernelGGL(dfm_derive_kernel, dim3(32), dim3(256), 0, h->stream, b.l1_w, b.l2_w, Ep, L + 1, NCT, h->d_dfm_frag, h->d_dfm_w2p);
+  hipLaunchKernelGGL(dfm_jtm_derive_kernel, dim3(256), dim3(256), 0, h->stream, b.l1_w, Ep, L, NCT, h->d_dfm_fragS);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(&h->b2, b.l2_b, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -307,6 +307,7 @@ static int dfm_rederive(dm_ctx *h) {
   const DfmBlocks b = dfm_blocks(h);
   const int E = h->embed, T = h->dfm_L + 1;
   hipLaunchKernelGGL(dfm_derive_kernel, dim3(32), dim3(256), 0, h->stream, b.l1_w, b.l2_w, E, T, dfm_col_tiles(h->dfm_L), h->d_dfm_frag, h->d_dfm_w2p);
+  hipLaunchKernelGGL(dfm_jtm_derive_kernel, dim3(256), dim3(256), 0, h->stream, b.l1_w, E, h->dfm_L, dfm_col_tiles(h->dfm_L), h->d_dfm_fragS);
   if (h->dfm_tr)
     hipLaunchKernelGGL(dfm_train_derive_kernel, dim3(256), dim3(256), 0, h->stream, b.l1_w, E, T, dfm_train_col_tiles(h->dfm_L), h->dfm_tr->fragF, h->dfm_tr->fragB);
   HIPCHK(h, hipGetLastError());

@@ -121,11 +121,13 @@ struct dm_ctx {
   int dfm_L = 0;               // DeepFM: the history length l1.W is sized by
   float *d_dfm_frag = nullptr; // DeepFM: [0 ; W1a ; 0] as MFMA B fragments, and l2.W over the same padded columns
   float *d_dfm_w2p = nullptr;
+  float *d_dfm_fragS = nullptr; // DeepFM: W1s as MFMA B fragments (dfm_jtm_derive_kernel), for the per-history set-up of the pair scorer
   struct dm_dfm_train *dfm_tr = nullptr;   // DeepFM training state (dm_deepfm_train_init, dfm_train.hip.inc): the owner's, never mirrored by a clone
   LazyCopies lazy;             // the copies rebuilt on first use after a weight change, and their stale flags (lazy_copies.hip.inc)
   int scorer_mode = DM_SCORER_AUTO;      // dm_set_scorer_mode
   bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
   double jtm_score_s = 0, jtm_rebal_s = 0;   // dm_jtm_last_step_seconds
+  DevGrow dfm_jtm_ws;          // DeepFM pair scorer (dfm_jtm.hip.inc): s and aux of one slice of histories
   DevGrow scratch64;           // fp64 beam kernel (beam_kernel_f64.hip.inc): per-team K / G fragment scratch
   // training state (dm_train_init)
   bool train_ready = false;
@@ -434,7 +436,7 @@ static void free_weights(dm_ctx *h) {
   h->d_emb32 = nullptr; h->emb32_owned = false;
   dm_release(h->d_compact, h->d_wfrag, h->d_afrag, h->d_bfrag, h->d_attA, h->d_w1aA, h->d_w1bA, h->d_b1, h->d_w2, h->d_att_wT_t, h->d_l1T_t);
   h->lazy.released();
-  dm_release(h->d_dfm_frag, h->d_dfm_w2p, h->d_tail32);
+  dm_release(h->d_dfm_frag, h->d_dfm_w2p, h->d_dfm_fragS, h->d_tail32);
   h->scorer_kind = DM_KIND_DIN; h->dfm_L = 0;
   free_training(h);
   h->w_loaded = false;
@@ -446,7 +448,7 @@ static void free_weights(dm_ctx *h) {
   X(tree_loaded) X(ids_loaded) X(leaves_at_max_only) X(max_level) X(n_slots) X(n_leaf_nodes) X(d_exists) X(d_leaf) X(d_node_id)          \
   X(d_id_to_code) X(d_leaf_codes) X(non_leaf_offset) X(max_code) X(w_loaded) X(dtype) X(embed) X(embed_log) X(num_index) X(d_compact)    \
   X(d_emb32) X(d_wfrag) X(d_afrag) X(d_bfrag) X(d_attA) X(d_w1aA) X(d_w1bA) X(d_b1) X(d_w2) X(b2) X(d_att_wT_t) X(d_l1T_t) X(d_tail32)   \
-  X(lazy) X(d_lv_codes) X(d_lv_cdf) X(d_lv_start) X(scorer_kind) X(dfm_L) X(d_dfm_frag) X(d_dfm_w2p)
+  X(lazy) X(d_lv_codes) X(d_lv_cdf) X(d_lv_start) X(scorer_kind) X(dfm_L) X(d_dfm_frag) X(d_dfm_w2p) X(d_dfm_fragS)
 
 static void clone_mirror(dm_ctx *c, dm_ctx *p) {
 #define X(f) c->f = p->f;
@@ -478,7 +480,7 @@ int dm_destroy(dm_handle_t h) {
   if (h->parent) { clone_forget(h); h->parent->n_clones.fetch_sub(1); h->parent = nullptr; }
   free_tree(h); free_weights(h); dm_dr_free(h->dr);
   dm_release(h->d_id_to_code, h->d_ctr, h->d_phase);
-  for (DevGrow *g : {&h->ws, &h->req, &h->sync, &h->samp, &h->defer, &h->scratch64}) g->release();
+  for (DevGrow *g : {&h->ws, &h->req, &h->sync, &h->samp, &h->defer, &h->scratch64, &h->dfm_jtm_ws}) g->release();
   if (h->h_stage) (void)hipHostFree(h->h_stage);
   jtm_drop_cache(h);
   for (auto &pr : h->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -1584,6 +1586,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "deepfm.hip.inc"
 #include "dfm_train.hip.inc"
 #include "comm.hip.inc"
+#include "dfm_jtm.hip.inc"
 #include "jtm_sharded.hip.inc"
 #include "train_grouped_host.hip.inc"
 #include "otm_train.hip.inc"

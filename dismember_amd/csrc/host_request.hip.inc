@@ -16,13 +16,15 @@ static void frontier_caps(int max_beam, int *cap, int *pcap) {
 // ---- what an event pair is recorded as (dm_kernel_timing_get_kind).  The numbers are read by tools and tests: they do not change.
 // Deep-Retrieval's sliced search numbers its launches per layer d: EV_DR_STATS + 2 d = the statistics of layer d >= 1, EV_DR_CUT + 2 d =
 // its cut (d = 0: the layer-0 launch), EV_DR_BLOCK + 2 d = the block version's second pass over the users the one-wave cut flagged.
-// 40 and 41 mean two things: the grouped fp64 training step of a DIN model and the serving launches of a DeepFM model (a handle holds one).
+// 40 .. 43 mean two things: the grouped fp64 training step of a DIN model and the serving / tree-learning launches of a DeepFM model (a
+// handle holds one).
 enum EvKind {
   EV_MAIN = 0,            // a search's main kernel, a whole Deep-Retrieval search, and every launch nobody asks for by kind
   EV_DEFERRED = 1,        // the second pass over the users the one-wave-per-SIMD beam kernel deferred
   EV_DR_STATS = 10, EV_DR_CUT = 11, EV_DR_BLOCK = 21,
   EV_ROWS = 30,           // general rows (rows_kernel.hip.inc)
   EV_DFM_USER = 40, EV_DFM_LEVEL = 41,
+  EV_DFM_JTM_ROWS = 42, EV_DFM_JTM_PAIRS = 43,      // the pair scorer of JTM tree learning (dfm_jtm.hip.inc): per-history set-up, per-pair score
   EV_TG_SETUP = 40, EV_TG_ROWS = 41, EV_TG_WGRAD_A = 42, EV_TG_USER_BWD = 43, EV_TG_WGRAD_B = 44,
   // the Deep-Retrieval training step under DM_DR_TIME_LAUNCHES=1 (dr_train.hip.inc): forward GEMMs, softmax + cross-entropy, dX products,
   // dW / db products with their slab sums, embedding gradient (pairs, sort, segment sums), Adam

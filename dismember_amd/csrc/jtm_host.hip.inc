@@ -148,9 +148,15 @@ static int64_t jtm_max_pairs(int64_t dflt) {
   return (*end == 0 && v > 0) ? (int64_t)v : dflt;
 }
 
+// The scorer of the pairs is a parameter (DM_KIND_DIN: din_rows_dev, history masks included; DM_KIND_DEEPFM: dfm_pairs_dev of
+// dfm_jtm.hip.inc, which has no mask input); the expansion, the chunk loop and the sums are shared.
+static int dfm_pairs_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, int64_t P, int L, float *d_out, int seq_div);
+static int dfm_jtm_enter(dm_ctx *h, const char *who, int use_mask, int L);
+static inline int jtm_max_L(int scorer) { return scorer == DM_KIND_DEEPFM ? 32 : DM_MAXL; }      // (32: DFM_MAXL)
+
 // row_off / row_item_ids: host arrays of the items [0, n_items) — or, with cached = true, the handle's device copies made by
 // dm_jtm_cache_rows (then the items are [i_lo, i_lo + n_items) of the cached catalogue and nothing but item_node goes up)
-static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32_t *row_item_ids, bool cached, int64_t i_lo,
+static int jtm_child_weights_impl(dm_ctx *h, int scorer, const int64_t *row_off, const int32_t *row_item_ids, bool cached, int64_t i_lo,
                                   const int32_t *item_node, int64_t n_items, int L, int old_level, int level, int hierarchical,
                                   int min_level, int use_mask, float *weights, const int32_t *d_item_node_all = nullptr,
                                   float *d_weights_all = nullptr) {
@@ -160,7 +166,7 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
   if (resident) { item_node = (const int32_t *)1; weights = (float *)1; }    // host arrays unused
   if (!h->ids_loaded || !h->w_loaded) return fail(h, DM_ERR_STATE, "dm_jtm_child_weights: id maps and weights must be loaded first");
   if (h->dtype != DM_F32) return fail(h, DM_ERR_UNSUPPORTED, "dm_jtm_child_weights: f32 weights only");
-  if (!row_off || !item_node || !weights || n_items < 0 || L <= 0 || L > DM_MAXL || level <= old_level || level - old_level > 8)
+  if (!row_off || !item_node || !weights || n_items < 0 || L <= 0 || L > jtm_max_L(scorer) || level <= old_level || level - old_level > 8)
     return fail(h, DM_ERR_INVALID, "dm_jtm_child_weights: bad arguments");
   if ((((int64_t)1) << (level + 1)) - 1 > h->num_index) return fail(h, DM_ERR_INDEX, "dm_jtm_child_weights: level exceeds the embedding table");
   HIPCHK(h, hipSetDevice(h->device));
@@ -245,7 +251,9 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
     if (pairs > 0 && per_row) {
       hipLaunchKernelGGL(dm_jtm_codes_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream, (const int64_t *)d_off, (const int32_t *)d_ritem,
                          (int32_t)(i_lo + i0), d_node_use, R0, nrows, gap, d_codes);
-      if ((rc = din_rows_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, use_mask ? h->d_jtm_rmask + (R0 - Rb) : nullptr, pairs, L, d_out, nchain)) != DM_OK) return rc;
+      rc = scorer == DM_KIND_DEEPFM ? dfm_pairs_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, pairs, L, d_out, nchain)
+                                    : din_rows_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, use_mask ? h->d_jtm_rmask + (R0 - Rb) : nullptr, pairs, L, d_out, nchain);
+      if (rc != DM_OK) return rc;
     } else if (pairs > 0) {
       JtmExpandParams p;
       p.row_off = d_off; p.row_item = d_ritem; p.item_base = cached ? (int32_t)(i_lo + i0) : 0; p.row_ids = d_rids; p.item_node = d_node_use;
@@ -255,7 +263,9 @@ static int jtm_child_weights_impl(dm_ctx *h, const int64_t *row_off, const int32
       p.non_leaf_offset = h->non_leaf_offset; p.max_code = h->max_code;
       p.codes = d_codes; p.seqs = d_seqs; p.rmask = d_mask; p.bad = d_bad;
       hipLaunchKernelGGL(dm_jtm_expand_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream, p);
-      if ((rc = din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, d_out)) != DM_OK) return rc;
+      // (hierarchical: the histories differ per chain depth, so the DeepFM set-up runs once per pair here)
+      rc = scorer == DM_KIND_DEEPFM ? dfm_pairs_dev(h, d_codes, d_seqs, pairs, L, d_out, 1) : din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, d_out);
+      if (rc != DM_OK) return rc;
     }
     hipLaunchKernelGGL(dm_jtm_sum_kernel, dim3((unsigned)((ni * nchild + 255) / 256)), dim3(256), 0, h->stream, d_off, R0, ni, gap, d_out, d_w_use);
     e = resident ? hipSuccess : hipMemcpyAsync(weights + i0 * nchild, d_w, (size_t)ni * nchild * 4, hipMemcpyDeviceToHost, h->stream);
@@ -279,7 +289,19 @@ int dm_jtm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   DM_DIN_ONLY(h, "dm_jtm_child_weights");
-  return jtm_child_weights_impl(h, row_off, row_item_ids, false, 0, item_node, n_items, L, old_level, level, hierarchical, min_level, use_mask, weights);
+  return jtm_child_weights_impl(h, DM_KIND_DIN, row_off, row_item_ids, false, 0, item_node, n_items, L, old_level, level, hierarchical, min_level, use_mask, weights);
+}
+
+// The DeepFM twins of the scoring entry points (dm_deepfm_jtm_*): the same signatures, the pairs scored by dfm_pairs_dev.  use_mask must
+// be 0 (the graph has no mask input), L the model's, one rank.
+int dm_deepfm_jtm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *row_item_ids, const int32_t *item_node,
+                                int64_t n_items, int L, int old_level, int level, int hierarchical, int min_level, int use_mask,
+                                float *weights) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  const int rc = dfm_jtm_enter(h, "dm_deepfm_jtm_child_weights", use_mask, L);
+  if (rc != DM_OK) return rc;
+  return jtm_child_weights_impl(h, DM_KIND_DEEPFM, row_off, row_item_ids, false, 0, item_node, n_items, L, old_level, level, hierarchical, min_level, 0, weights);
 }
 
 static void jtm_drop_cache(dm_ctx *h) {
@@ -310,7 +332,7 @@ int dm_jtm_cache_rows_range(dm_handle_t h, const int64_t *row_off, const int32_t
   HIPCHK(h, hipSetDevice(h->device));
   jtm_drop_cache(h);
   if (n_items == 0) return DM_OK;
-  if (!row_off || !row_item_ids || n_items < 0 || L <= 0 || L > DM_MAXL || n_items >= ((int64_t)1 << 31) || i_lo < 0 || i_hi < i_lo || i_hi > n_items)
+  if (!row_off || !row_item_ids || n_items < 0 || L <= 0 || L > jtm_max_L(h->scorer_kind) || n_items >= ((int64_t)1 << 31) || i_lo < 0 || i_hi < i_lo || i_hi > n_items)
     return fail(h, DM_ERR_INVALID, "dm_jtm_cache_rows: bad arguments");
   for (int64_t i = 0; i < n_items; i++)
     if (row_off[i + 1] < row_off[i]) return fail(h, DM_ERR_INVALID, "dm_jtm_cache_rows: row_off must be non-decreasing");
@@ -335,15 +357,27 @@ int dm_jtm_cache_rows(dm_handle_t h, const int64_t *row_off, const int32_t *row_
 }
 
 // dm_jtm_child_weights for the items [i_lo, i_lo + n_items) of the cached catalogue: item_node / weights are indexed from i_lo
+static int jtm_child_weights_cached_impl(dm_ctx *h, int scorer, const int32_t *item_node, int64_t i_lo, int64_t n_items, int old_level, int level,
+                                         int hierarchical, int min_level, int use_mask, float *weights) {
+  if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_child_weights_cached: call dm_jtm_cache_rows first");
+  if (i_lo < 0 || n_items < 0 || i_lo + n_items > (int64_t)h->jtm_off.size() - 1) return fail(h, DM_ERR_INVALID, "dm_jtm_child_weights_cached: item range outside the cached catalogue");
+  return jtm_child_weights_impl(h, scorer, h->jtm_off.data() + i_lo, nullptr, true, i_lo, item_node, n_items, h->jtm_L, old_level, level, hierarchical,
+                                min_level, use_mask, weights);
+}
 int dm_jtm_child_weights_cached(dm_handle_t h, const int32_t *item_node, int64_t i_lo, int64_t n_items, int old_level, int level,
                                 int hierarchical, int min_level, int use_mask, float *weights) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
   DM_DIN_ONLY(h, "dm_jtm_child_weights_cached");
-  if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_child_weights_cached: call dm_jtm_cache_rows first");
-  if (i_lo < 0 || n_items < 0 || i_lo + n_items > (int64_t)h->jtm_off.size() - 1) return fail(h, DM_ERR_INVALID, "dm_jtm_child_weights_cached: item range outside the cached catalogue");
-  return jtm_child_weights_impl(h, h->jtm_off.data() + i_lo, nullptr, true, i_lo, item_node, n_items, h->jtm_L, old_level, level, hierarchical,
-                                min_level, use_mask, weights);
+  return jtm_child_weights_cached_impl(h, DM_KIND_DIN, item_node, i_lo, n_items, old_level, level, hierarchical, min_level, use_mask, weights);
+}
+int dm_deepfm_jtm_child_weights_cached(dm_handle_t h, const int32_t *item_node, int64_t i_lo, int64_t n_items, int old_level, int level,
+                                       int hierarchical, int min_level, int use_mask, float *weights) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  const int rc = dfm_jtm_enter(h, "dm_deepfm_jtm_child_weights_cached", use_mask, h->jtm_off.empty() ? -1 : h->jtm_L);
+  if (rc != DM_OK) return rc;
+  return jtm_child_weights_cached_impl(h, DM_KIND_DEEPFM, item_node, i_lo, n_items, old_level, level, hierarchical, min_level, 0, weights);
 }
 
 static int java_double_compare_h(double x, double y) {
@@ -683,11 +717,8 @@ int dm_jtm_rebalance_all(dm_handle_t h, const float *weights, const int32_t *old
 // One gap step of JTM.optimize over the WHOLE cached catalogue (JTM.scala:36-72) without a host round trip in between: child
 // weights of every item (dm_jtm_child_weights_cached) -> greedy re-balance of every parent node (dm_jtm_rebalance_all) with the
 // [n x 2^gap] weight matrix kept in HBM.  item_node / old_node in, out_node out (host, [n_items] each).
-int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *old_node, int64_t n_items, int old_level, int level,
-                       int hierarchical, int min_level, int use_mask, int max_assign, int32_t *out_node) {
-  if (!h) return DM_ERR_INVALID;
-  DM_CLONE_ENTER(h);
-  DM_DIN_ONLY(h, "dm_jtm_step_cached");
+static int jtm_step_cached_impl(dm_ctx *h, int scorer, const int32_t *item_node, const int32_t *old_node, int64_t n_items, int old_level, int level,
+                                int hierarchical, int min_level, int use_mask, int max_assign, int32_t *out_node) {
   if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_step_cached: call dm_jtm_cache_rows first");
   if (!item_node || !old_node || !out_node || n_items != (int64_t)h->jtm_off.size() - 1 || level <= old_level || level - old_level > 8 || max_assign < 0)
     return fail(h, DM_ERR_INVALID, "dm_jtm_step_cached: bad arguments (n_items must be the cached catalogue)");
@@ -704,7 +735,7 @@ int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *o
       hipMemcpyAsync(d_node, item_node, (size_t)n_items * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess)
     rc = fail(h, DM_ERR_HIP, "dm_jtm_step_cached: upload failed");
   const auto t0 = std::chrono::steady_clock::now();
-  if (rc == DM_OK) rc = jtm_child_weights_impl(h, h->jtm_off.data(), nullptr, true, 0, nullptr, n_items, h->jtm_L, old_level, level, hierarchical,
+  if (rc == DM_OK) rc = jtm_child_weights_impl(h, scorer, h->jtm_off.data(), nullptr, true, 0, nullptr, n_items, h->jtm_L, old_level, level, hierarchical,
                                                min_level, use_mask, nullptr, d_node, d_w);
   const auto t1 = std::chrono::steady_clock::now();       // the scoring pass ends with a stream synchronise
   struct Tm { dm_ctx *h; std::chrono::steady_clock::time_point t0, t1; ~Tm() {
@@ -722,6 +753,21 @@ int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *o
     }
   }
   return rc;
+}
+int dm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *old_node, int64_t n_items, int old_level, int level,
+                       int hierarchical, int min_level, int use_mask, int max_assign, int32_t *out_node) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  DM_DIN_ONLY(h, "dm_jtm_step_cached");
+  return jtm_step_cached_impl(h, DM_KIND_DIN, item_node, old_node, n_items, old_level, level, hierarchical, min_level, use_mask, max_assign, out_node);
+}
+int dm_deepfm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *old_node, int64_t n_items, int old_level, int level,
+                              int hierarchical, int min_level, int use_mask, int max_assign, int32_t *out_node) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  const int rc = dfm_jtm_enter(h, "dm_deepfm_jtm_step_cached", use_mask, h->jtm_off.empty() ? -1 : h->jtm_L);
+  if (rc != DM_OK) return rc;
+  return jtm_step_cached_impl(h, DM_KIND_DEEPFM, item_node, old_node, n_items, old_level, level, hierarchical, min_level, 0, max_assign, out_node);
 }
 
 // JTMTree.getAncestorAtLevel (jtm/.../tree/JTMTree.scala:36-43) of every item's current leaf code

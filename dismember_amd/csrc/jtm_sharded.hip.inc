@@ -105,9 +105,8 @@ static int jtm_rebalance_step(dm_ctx *h, const float *d_w, const int32_t *d_old,
   return rc;
 }
 
-static int jtm_optimize_impl(dm_ctx *h, const int32_t *item_code, int64_t n_items, int max_level, int gap, int hierarchical, int min_level,
+static int jtm_optimize_impl(dm_ctx *h, int scorer, const int32_t *item_code, int64_t n_items, int max_level, int gap, int hierarchical, int min_level,
                              int use_mask, int32_t *out_proj, double *step_seconds) {
-  DM_DIN_ONLY(h, "dm_jtm_optimize_cached");
   if (h->jtm_off.empty()) return fail(h, DM_ERR_STATE, "dm_jtm_optimize_cached: call dm_jtm_cache_rows first");
   if (!item_code || !out_proj || n_items != (int64_t)h->jtm_off.size() - 1 || max_level < 1 || max_level > 30 || gap < 1 || gap > 8)
     return fail(h, DM_ERR_INVALID, "dm_jtm_optimize_cached: bad arguments (n_items must be the cached catalogue)");
@@ -158,7 +157,7 @@ static int jtm_optimize_impl(dm_ctx *h, const int32_t *item_code, int64_t n_item
     if (W > 1) jtm_shard_range(n_items, rank, W, &lo, &hi);
     const auto t0 = clk::now();
     if (hi > lo)
-      rc = jtm_child_weights_impl(h, h->jtm_off.data() + lo, nullptr, true, lo, nullptr, hi - lo, h->jtm_L, old_level, level, hierarchical, min_level,
+      rc = jtm_child_weights_impl(h, scorer, h->jtm_off.data() + lo, nullptr, true, lo, nullptr, hi - lo, h->jtm_L, old_level, level, hierarchical, min_level,
                                   use_mask, nullptr, d_proj + lo, d_w + lo * C);
     const auto t1 = clk::now();
     t_sc += secs(t0, t1);
@@ -240,8 +239,20 @@ int dm_jtm_optimize_cached(dm_handle_t h, const int32_t *item_code, int64_t n_it
                            int use_mask, int32_t *out_proj, double *step_seconds) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
-  try { return jtm_optimize_impl(h, item_code, n_items, max_level, gap, hierarchical, min_level, use_mask, out_proj, step_seconds); }
+  DM_DIN_ONLY(h, "dm_jtm_optimize_cached");
+  try { return jtm_optimize_impl(h, DM_KIND_DIN, item_code, n_items, max_level, gap, hierarchical, min_level, use_mask, out_proj, step_seconds); }
   catch (const std::exception &e) { return fail(h, DM_ERR_INVALID, std::string("dm_jtm_optimize_cached: ") + e.what()); }
+}
+
+// The DeepFM twin: one rank (dfm_jtm_enter refuses an attached communicator of more), so none of the collectives above is entered
+int dm_deepfm_jtm_optimize_cached(dm_handle_t h, const int32_t *item_code, int64_t n_items, int max_level, int gap, int hierarchical, int min_level,
+                                  int use_mask, int32_t *out_proj, double *step_seconds) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  const int rc = dfm_jtm_enter(h, "dm_deepfm_jtm_optimize_cached", use_mask, h->jtm_off.empty() ? -1 : h->jtm_L);
+  if (rc != DM_OK) return rc;
+  try { return jtm_optimize_impl(h, DM_KIND_DEEPFM, item_code, n_items, max_level, gap, hierarchical, min_level, 0, out_proj, step_seconds); }
+  catch (const std::exception &e) { return fail(h, DM_ERR_INVALID, std::string("dm_deepfm_jtm_optimize_cached: ") + e.what()); }
 }
 
 // The same for ONE process driving every rank of a dm_comm_create_all clique (the reference's shape: one JVM, N workers): hs[i] carries

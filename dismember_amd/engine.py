@@ -278,6 +278,21 @@ class Engine:
         self._chk(N.lib().dm_deepfm_forward(self._h, _p(codes, N.i32p), _p(seqs, N.i32p), B, int(L), _p(out, N.f32p)))
         return out
 
+    def deepfm_pairs_forward(self, codes, seqs, seq_div=1):
+        """dm_deepfm_pairs_forward: logits [P] float32 of P (node code, history) pairs; pair i is scored against history i // seq_div
+        of seqs [ceil(P / seq_div), L] (codes, -1 = a zero row).  The scorer of JTM tree learning with a DeepFM model."""
+        codes = _i32(codes).ravel()
+        seqs = _i32(seqs)
+        P, seq_div = codes.size, int(seq_div)
+        H = -(-P // max(seq_div, 1))
+        L = seqs.shape[-1] if seqs.ndim == 2 else seqs.size // max(H, 1)
+        if seq_div >= 1 and seqs.size != H * L:
+            raise ValueError("deepfm_pairs_forward: %d pairs at seq_div %d need %d histories, got %d values of L = %d" % (P, seq_div, H, seqs.size, L))
+        seqs = seqs.ravel()
+        out = np.empty(P, dtype=np.float32)
+        self._chk(N.lib().dm_deepfm_pairs_forward(self._h, _p(codes, N.i32p), _p(seqs, N.i32p), P, int(L), seq_div, _p(out, N.f32p)))
+        return out
+
     # ---- beam search
     @staticmethod
     def _csr(consumed, U):
@@ -942,7 +957,8 @@ class Engine:
         0 = a search's main kernel, a whole Deep-Retrieval search and every launch without a kind of its own; 1 = the second pass over
         the users the one-wave beam kernel deferred; under DM_DR_TIME_LAUNCHES=1 the sliced Deep-Retrieval search's launches, per
         layer d: 11 = layer 0, 10 + 2d = statistics, 11 + 2d = cut, 21 + 2d = the block version's second pass; 30 = general rows
-        (din_forward); 40 / 41 = DeepFM user / level launches, and 40 .. 44 the launches of the grouped fp64 training step; under
+        (din_forward); 40 / 41 = DeepFM user / level launches, 42 / 43 = the DeepFM pair scorer's per-history set-up / per-pair launches
+        (JTM tree learning), and 40 .. 44 the launches of the grouped fp64 training step; under
         DM_DR_TIME_LAUNCHES=1 the Deep-Retrieval training step: 50 = forward GEMMs, 51 = softmax + cross-entropy, 52 = dX products,
         53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam"""
         n, ms = C.c_int(0), C.c_double(0)

@@ -8,6 +8,10 @@ reference's workers (JTM.scala:33-68): item-sharded scoring, the weight slices a
 the re-balance sharded by parent node once a level has as many parents as ranks — bit-identical to one rank.
 Items are iterated in ascending id (the reference iterates a Scala HashMap — only relevant for ties, see
 DESIGN.md).
+
+The engine's scorer decides which entry points run: a DIN model the dm_jtm_* ones, a DeepFM model their dm_deepfm_jtm_* twins
+(DESIGN.md section 13).  The DeepFM graph has no mask input, so use_mask is off there whatever the caller passes (as TDMTrainer does),
+and DeepFM tree learning runs on one rank: a `comm` of more is a ValueError.
 """
 import ctypes as C
 
@@ -29,6 +33,7 @@ class JTM:
         self.max_level, self.gap, self.L = int(max_level), int(gap), int(seq_len)
         self.hierarchical, self.min_level, self.use_mask = bool(hierarchical), int(min_level), bool(use_mask)
         self.comm = comm              # comm.Comm: items sharded over ranks, weight blocks all-gathered (sharding.py)
+        self._pick_scorer()
         off = np.zeros(self.items.size + 1, np.int64)
         rows = []
         for k, it in enumerate(self.items.tolist()):
@@ -51,10 +56,23 @@ class JTM:
         o.max_level, o.gap, o.L = int(max_level), int(gap), int(seq_len)
         o.hierarchical, o.min_level, o.use_mask = bool(hierarchical), int(min_level), bool(use_mask)
         o.comm = comm
+        o._pick_scorer()
         o.row_off = np.ascontiguousarray(row_off, np.int64)
         o.row_ids = _i32(row_ids)
         assert o.row_off.size == o.items.size + 1 and o.row_ids.size >= int(o.row_off[-1]) * o.L
         return o
+
+    def _pick_scorer(self):
+        """the entry points of the engine's scorer, looked up when the object is made (load the model first)"""
+        self.deepfm = self.engine.scorer == "deepfm"
+        if self.deepfm:
+            if self.comm is not None and int(getattr(self.comm, "world", 1)) > 1:
+                raise ValueError("JTM with a DeepFM model runs on one rank (nothing of DeepFM is multi-GPU); got a communicator of %d" % self.comm.world)
+            self.use_mask = False
+        pre = "dm_deepfm_jtm_" if self.deepfm else "dm_jtm_"
+        lib = N.lib()
+        self._child_weights, self._child_weights_cached = getattr(lib, pre + "child_weights"), getattr(lib, pre + "child_weights_cached")
+        self._step_cached, self._optimize_cached = getattr(lib, pre + "step_cached"), getattr(lib, pre + "optimize_cached")
 
     def weights_range(self, item_node, old_level, level, lo, hi):
         """TreeLearning.aggregateWeights for the items [lo, hi) of the ascending-id item list (their rows only)."""
@@ -66,16 +84,16 @@ class JTM:
             return w[:0]
         if getattr(self, "_cached", False):          # rows already on the device (optimize): only the node list goes up
             sub = np.ascontiguousarray(node[lo:hi])
-            self.engine._chk(N.lib().dm_jtm_child_weights_cached(self.engine._h, _p(sub, N.i32p), lo, n, old_level, level,
-                                                                 int(self.hierarchical), self.min_level, int(self.use_mask), _p(w, N.f32p)))
+            self.engine._chk(self._child_weights_cached(self.engine._h, _p(sub, N.i32p), lo, n, old_level, level,
+                                                        int(self.hierarchical), self.min_level, int(self.use_mask), _p(w, N.f32p)))
             return w[:n]
         off = np.ascontiguousarray(self.row_off[lo:hi + 1] - self.row_off[lo])
         r0, r1 = int(self.row_off[lo]), int(self.row_off[hi])
         rows = np.ascontiguousarray(self.row_ids[r0 * self.L:max(r1, r0 + 1) * self.L])
         sub = np.ascontiguousarray(node[lo:hi])
-        self.engine._chk(N.lib().dm_jtm_child_weights(self.engine._h, _p(off, N.i64p), _p(rows, N.i32p), _p(sub, N.i32p), n,
-                                                      self.L, old_level, level, int(self.hierarchical), self.min_level,
-                                                      int(self.use_mask), _p(w, N.f32p)))
+        self.engine._chk(self._child_weights(self.engine._h, _p(off, N.i64p), _p(rows, N.i32p), _p(sub, N.i32p), n,
+                                             self.L, old_level, level, int(self.hierarchical), self.min_level,
+                                             int(self.use_mask), _p(w, N.f32p)))
         return w[:n]
 
     def child_weights(self, item_node, old_level, level):
@@ -127,8 +145,8 @@ class JTM:
                 t1 = time.perf_counter()
                 out = np.empty(self.items.size, np.int32)
                 secs = (C.c_double * 2)()
-                self.engine._chk(N.lib().dm_jtm_optimize_cached(self.engine._h, _p(self.item_code, N.i32p), self.items.size, self.max_level, self.gap,
-                                                                int(self.hierarchical), self.min_level, int(self.use_mask), _p(out, N.i32p), secs))
+                self.engine._chk(self._optimize_cached(self.engine._h, _p(self.item_code, N.i32p), self.items.size, self.max_level, self.gap,
+                                                       int(self.hierarchical), self.min_level, int(self.use_mask), _p(out, N.i32p), secs))
                 if timing is not None:
                     timing.update(scoring_s=secs[0], rebalance_s=secs[1], host_glue_s=0.0, rows_upload_s=t_up, rows_uploaded=self._cached_rows, fused_step_s=time.perf_counter() - t1,
                                   sharding=self.optimize_stats())
@@ -166,8 +184,8 @@ class JTM:
                 # single rank, rows cached: scoring and re-balance of the step in one call, weights never leave the device
                 new = np.empty_like(proj)
                 t1 = time.perf_counter()
-                self.engine._chk(N.lib().dm_jtm_step_cached(self.engine._h, _p(proj, N.i32p), _p(old_node, N.i32p), proj.size, old_level, level,
-                                                            int(self.hierarchical), self.min_level, int(self.use_mask), int(max_assign), _p(new, N.i32p)))
+                self.engine._chk(self._step_cached(self.engine._h, _p(proj, N.i32p), _p(old_node, N.i32p), proj.size, old_level, level,
+                                                   int(self.hierarchical), self.min_level, int(self.use_mask), int(max_assign), _p(new, N.i32p)))
                 t_host += t1 - t0; t_step += time.perf_counter() - t1
                 a_, b_ = C.c_double(0), C.c_double(0)
                 self.engine._chk(N.lib().dm_jtm_last_step_seconds(self.engine._h, C.byref(a_), C.byref(b_)))

@@ -198,7 +198,8 @@ def jtm_tree_learning(conf_path, quiet=True, engine=None):
             rows.setdefault(int(arr[-1]), []).extend(int(float(x)) for x in arr[1:-1])
     rows = {k: np.asarray(v, np.int32) for k, v in rows.items()}
     jtm = JTM(eng, t["leaf_ids"], t["leaf_codes"], t["max_level"], rows, gap=p["gap"], seq_len=p["seq_len"],
-              hierarchical=p["hierarchical_preference"], min_level=p["min_level"], use_mask=p["use_mask"])
+              hierarchical=p["hierarchical_preference"], min_level=p["min_level"],
+              use_mask=p["use_mask"] and eng.scorer != "deepfm")                   # (the DeepFM graph has no mask input, TDM.scala:26-29)
     t0 = time.perf_counter()
     proj = jtm.optimize()
     dt = time.perf_counter() - t0

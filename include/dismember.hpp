@@ -350,6 +350,8 @@ struct Metrics {
 // workers (JTM.scala:33-68) are GPUs here: attach a communicator to the engine (Engine::attachComm: one process per GPU, every process
 // constructs the same JTM and calls optimize() — collective), or hand optimizeAll() the engines of one process driving several GPUs
 // (dm_comm_create_all clique); both give the single-GPU projection bit for bit.
+// The engine's scorer decides the entry point: a DeepFM model (Engine::scorerKind) runs dm_deepfm_jtm_optimize_cached, without a mask —
+// the graph has none — and on one GPU (optimizeAll with more than one engine throws).
 class JTM {
  public:
   // leafItemIds / leafCodes: the CURRENT tree's item -> leaf code map; itemRows[item] = flattened [rows x seqLen] histories
@@ -387,8 +389,11 @@ class JTM {
     e_.check(dm_jtm_cache_rows(e_.handle(), rowOff_.data(), rowIds_.data(), (int64_t)n, L_));
     struct Drop { Engine &e; int L; ~Drop() { dm_jtm_cache_rows(e.handle(), nullptr, nullptr, 0, L); } } drop{e_, L_};
     // the loop over the gap steps is one call: projection and weights stay in HBM between the steps; dropped items keep their old node (:72)
-    e_.check(dm_jtm_optimize_cached(e_.handle(), itemCode_.data(), (int64_t)n, maxLevel_, gap_, hier_ ? 1 : 0, minLevel_, useMask_ ? 1 : 0,
-                                    proj.data(), nullptr));
+    if (e_.scorerKind() == DM_KIND_DEEPFM)
+      e_.check(dm_deepfm_jtm_optimize_cached(e_.handle(), itemCode_.data(), (int64_t)n, maxLevel_, gap_, hier_ ? 1 : 0, minLevel_, 0, proj.data(), nullptr));
+    else
+      e_.check(dm_jtm_optimize_cached(e_.handle(), itemCode_.data(), (int64_t)n, maxLevel_, gap_, hier_ ? 1 : 0, minLevel_, useMask_ ? 1 : 0,
+                                      proj.data(), nullptr));
     std::map<int32_t, int32_t> res;
     for (size_t i = 0; i < n; i++) res[items_[i]] = proj[i];
     return res;
@@ -397,6 +402,10 @@ class JTM {
   // every engine gets the rows of ITS item range, the ranks run on host threads inside the call and must end with the same projection
   std::map<int32_t, int32_t> optimizeAll(const std::vector<Engine *> &engines) {
     const size_t n = items_.size();
+    if (e_.scorerKind() == DM_KIND_DEEPFM) {
+      if (engines.size() != 1 || engines[0] != &e_) throw Error(DM_ERR_UNSUPPORTED, "JTM: tree learning with a DeepFM model runs on one GPU");
+      return optimize();
+    }
     std::vector<int32_t> proj(n, 0);
     std::vector<dm_handle_t> hs;
     for (size_t r = 0; r < engines.size(); r++) {             // every rank: the bookkeeping of all items, the ROWS of the range it scores

@@ -104,12 +104,14 @@ int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, cons
  * (l1.W is sized by it) and is kept on the handle; a wrong n_elems, L or E is DM_ERR_INVALID.  The handle records which scorer is
  * loaded (dm_get_scorer_kind: *seq_len is DeepFM's L, 0 for DIN); loading DIN weights afterwards switches it back.  dm_clone clones
  * serve the same model through the shared storage.
- * With a DeepFM model loaded: dm_deepfm_forward and dm_tdm_beam_search / _trace / _dev serve it (the searches through the per-level
+ * With a DeepFM model loaded: dm_deepfm_forward, dm_deepfm_pairs_forward and dm_tdm_beam_search / _trace / _dev serve it, and
+ * dm_deepfm_jtm_* learn the tree with it (the searches through the per-level
  * pipeline for every L, use_mask must be 0 — the graph has no mask, T/model/TDM.scala:26-29 — and L must be the model's: DM_ERR_INVALID
  * otherwise); dm_get_leaf_embeddings, dm_cluster_tree_model, dm_save_model / dm_load_model work as for DIN; every entry point that
  * evaluates DIN (dm_din_forward, dm_otm_*, dm_tdm_bruteforce_topk, dm_jtm_*, dm_train_*, dm_adam_step, dm_tdm_make_train_batch,
  * dm_tdm_sample_train_batch_dev, dm_set_scorer_mode) returns DM_ERR_UNSUPPORTED and leaves the handle usable (training and its
- * sampler have DeepFM entry points of their own, below). */
+ * sampler have DeepFM entry points of their own, below, and so has JTM's scoring: dm_deepfm_jtm_*; OTM tree learning with DeepFM
+ * stays refused — the reference's is a DeepFM[Double]). */
 enum { DM_KIND_DIN = 0, DM_KIND_DEEPFM = 1 };
 int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_index, const void *compact, int64_t n_elems);
 int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len);
@@ -117,6 +119,11 @@ int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len);
  * 93-94 with SeqModelInputs, TDM.predict): codes [B], seqs [B*L] node codes, -1 = a zero row; an index outside [0, num_index) is
  * DM_ERR_INDEX as in dm_din_forward; L must equal the model's seq_len; logits [B] float.  DM_ERR_STATE on a DIN model. */
 int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, int64_t B, int L, float *logits);
+/* The same logits for P (node, history) pairs whose histories are shared: pair i is scored against history i / seq_div of
+ * seqs [ceil(P / seq_div)][L] (seq_div >= 1; 1: one history per pair).  This is the scorer of dm_deepfm_jtm_* on host arrays — a
+ * per-history set-up kernel, then a per-pair kernel: a pair's logit depends on its (code, history) only, not on
+ * P, seq_div or its neighbours, and two runs give the same bytes.  Errors as dm_deepfm_forward. */
+int dm_deepfm_pairs_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, int64_t P, int L, int seq_div, float *logits);
 
 /* Checkpoint (replaces TDM.saveModel / loadModel, T/utils/Serialization.scala:60-101 — a Java ObjectOutputStream of the module graph
  * there; tdm/src/test/scala/TdmModelTrainSpec.scala:85-96 pins save -> load -> identical recommendations): one flat little-endian
@@ -260,6 +267,22 @@ int dm_jtm_optimize_cached(dm_handle_t h, const int32_t *item_code, int64_t n_it
  * (DM_ERR_STATE if they differ) and out_proj receives the common one.  n == 1 is dm_jtm_optimize_cached. */
 int dm_jtm_optimize_all(dm_handle_t *hs, int n, const int32_t *item_code, int64_t n_items, int max_level, int gap, int hierarchical,
                         int min_level, int use_mask, int32_t *out_proj, double *step_seconds);
+/* JTM tree learning with a DeepFM model (TreeLearning.aggregateWeights runs dlModel.forward on whatever graph the model file holds,
+ * TreeLearning.scala:152-174): the twins of dm_jtm_child_weights, dm_jtm_child_weights_cached, dm_jtm_step_cached and
+ * dm_jtm_optimize_cached, with the same arguments and results; the pairs are scored as dm_deepfm_pairs_forward scores them.
+ * dm_jtm_cache_rows[_range], dm_jtm_rebalance*, dm_jtm_optimize_stats and dm_jtm_last_step_seconds hold no scorer and serve both.
+ * DM_ERR_STATE on a DIN model; DM_ERR_INVALID for use_mask != 0 (the DeepFM graph has no mask input) and for an L (the call's, or the
+ * cached catalogue's) that is not the model's; DM_ERR_INDEX for a history code outside the table; DM_ERR_UNSUPPORTED while a
+ * communicator of more than one rank is attached (nothing of DeepFM runs multi-GPU).  The handle stays usable after every refusal. */
+int dm_deepfm_jtm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *row_item_ids, const int32_t *item_node,
+                                int64_t n_items, int L, int old_level, int level, int hierarchical, int min_level, int use_mask,
+                                float *weights);
+int dm_deepfm_jtm_child_weights_cached(dm_handle_t h, const int32_t *item_node, int64_t i_lo, int64_t n_items, int old_level, int level,
+                                       int hierarchical, int min_level, int use_mask, float *weights);
+int dm_deepfm_jtm_step_cached(dm_handle_t h, const int32_t *item_node, const int32_t *old_node, int64_t n_items, int old_level, int level,
+                              int hierarchical, int min_level, int use_mask, int max_assign, int32_t *out_node);
+int dm_deepfm_jtm_optimize_cached(dm_handle_t h, const int32_t *item_code, int64_t n_items, int max_level, int gap, int hierarchical,
+                                  int min_level, int use_mask, int32_t *out_proj, double *step_seconds);
 /* measurement — what the last dm_jtm_optimize_cached on this handle did: out10[0..9] = ranks, transport (DM_COMM_*; 2^64-1 = no
  * communicator), items this rank scored summed over the gap steps, items it re-balanced in node-sharded steps, steps with a replicated
  * re-balance, node-sharded steps, weight bytes all-gathered, projection bytes all-gathered, 0, 0; secs3 = scoring, re-balance,
@@ -680,7 +703,9 @@ int dm_kernel_timing_get(dm_handle_t h, int *launches, double *total_ms);
  * DM_DR_TIME_LAUNCHES=1 in the environment (read per call) every launch gets its own pair — kind 0 the history
  * GEMM, 11 layer 0, 10 + 2d / 11 + 2d the statistics / cut of layer d — at 2 - 14 % of the search's wall time.
  * Kind 30: the general-rows scorer (dm_din_forward, JTM child weights: dm_din_rows_split*_kernel), one pair per launch.
- * Kinds 40 / 41: a DeepFM search's user set-up (dfm_user_kernel, one per pass of users) / its level kernel (dfm_level_kernel, one per level). */
+ * Kinds 40 / 41: a DeepFM search's user set-up (dfm_user_kernel, one per pass of users) / its level kernel (dfm_level_kernel, one per level).
+ * Kinds 42 / 43: the DeepFM pair scorer's per-history set-up (dfm_jtm_rows_kernel) / its per-pair kernel (dfm_jtm_pairs_kernel), one
+ * pair each per slice of histories of a chunk. */
 int dm_kernel_timing_get_kind(dm_handle_t h, int kind, int *launches, double *total_ms);
 /* name (with template arguments) of the kernel that ran the last TDM / OTM beam search, as a profiler lists it
  * (owned by the handle, valid until the next search) */

@@ -4,6 +4,8 @@
 // The reference's `numThreads` workers (JTM.scala:33-68: items of a node split while a level has fewer nodes than workers, contiguous
 // node ranges afterwards) are GPUs here: pass the engines of this JVM's GPUs as `workers` and the run is sharded over them inside the
 // library (RCCL all-gathers over xGMI), with the single-GPU projection bit for bit.
+// The engine's scorer decides the entry point (dm_get_scorer_kind): a DeepFM model runs dm_deepfm_jtm_optimize_cached, without a mask
+// (the graph has none) and on one GPU.
 package com.mass.hip
 
 class JTM(engine: HipEngine, itemIds: Array[Int], itemCodes: Array[Int], maxLevel: Int,
@@ -11,6 +13,8 @@ class JTM(engine: HipEngine, itemIds: Array[Int], itemCodes: Array[Int], maxLeve
           useMask: Boolean, workers: Array[HipEngine] = Array.empty) {
 
   private val engines: Array[HipEngine] = if (workers.isEmpty) Array(engine) else workers
+  private val deepFM = TDM.isDeepFM(engine)
+  require(!deepFM || engines.length == 1, "JTM with a DeepFM model runs on one GPU")
   private val comms = new Array[Long](engines.length)
   if (engines.length > 1) {
     Native.commCreateAll(engines.length, engines.map(_.device), comms)                         // ncclCommInitAll: rank i on engines(i)
@@ -28,8 +32,11 @@ class JTM(engine: HipEngine, itemIds: Array[Int], itemCodes: Array[Int], maxLeve
       Native.jtmCacheRowsRange(e.handle, rowOff, rowItemIds, n.toLong, seqLen, lo(0), hi(0))
     }
     try {
-      Native.jtmOptimizeAll(engines.map(_.handle), engines.length, itemCodes, n.toLong, maxLevel, gap, if (hierarchical) 1 else 0, minLevel,
-        if (useMask) 1 else 0, node, null)
+      if (deepFM)
+        Native.deepfmJtmOptimizeCached(engine.handle, itemCodes, n.toLong, maxLevel, gap, if (hierarchical) 1 else 0, minLevel, 0, node, null)
+      else
+        Native.jtmOptimizeAll(engines.map(_.handle), engines.length, itemCodes, n.toLong, maxLevel, gap, if (hierarchical) 1 else 0, minLevel,
+          if (useMask) 1 else 0, node, null)
     } finally engines.foreach(e => Native.jtmCacheRows(e.handle, null, null, 0L, seqLen))
     itemIds.zip(node).toMap
   }

@@ -89,6 +89,11 @@ EXTENTS = {
     "dm_tdm_id_to_code": {"item_ids": "n", "codes": "n", "mask_pos": "n", "n_mask": "1"},
     "dm_din_forward": {"codes": "B", "seqs": "B * L", "pad_flat_idx": "n_pad", "logits": "B"},
     "dm_deepfm_forward": {"codes": "B", "seqs": "B * L", "logits": "B"},
+    "dm_deepfm_pairs_forward": {"codes": "P", "seqs": "(seq_div > 0 ? (P + seq_div - 1) / seq_div : P) * L", "logits": "P"},
+    "dm_deepfm_jtm_child_weights": {"row_off": "n_items + 1", "item_node": "n_items", "weights": "n_items * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))"},
+    "dm_deepfm_jtm_child_weights_cached": {"item_node": "n_items", "weights": "n_items * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))"},
+    "dm_deepfm_jtm_step_cached": {"item_node": "n_items", "old_node": "n_items", "out_node": "n_items"},
+    "dm_deepfm_jtm_optimize_cached": {"item_code": "n_items", "out_proj": "n_items"},
     "dm_tdm_beam_search": dict(_SEARCH_OUT, seq_item_ids="U * L", consumed_off="U + 1"),
     "dm_tdm_beam_search_trace": dict(_SEARCH_OUT, seq_item_ids="U * L", trace_counts="U * max_levels"),
     "dm_otm_beam_search": _OTM_OUT, "dm_otm_beam_search_f64": _OTM_OUT,
