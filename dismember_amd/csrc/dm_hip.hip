@@ -1581,6 +1581,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "dr_host.hip.inc"
 #include "dr_train.hip.inc"
 #include "dr_rerank_train.hip.inc"
+#include "dr_mstep.hip.inc"
 #include "otm64.hip.inc"
 #include "tdm_pipeline.hip.inc"
 #include "deepfm.hip.inc"

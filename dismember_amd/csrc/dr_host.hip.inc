@@ -48,6 +48,7 @@ struct dm_dr_state {
   int32_t *d_items = nullptr;
   // scratch (grow only)
   DevGrow S, UV, io, cand;                          // io: seq ids + paths + probs + counts + outputs of one chunk
+  DevGrow ms, ms_io;                                // the M-step's path scores (dr_mstep.hip.inc): every array of a call; the host entry's uploads
 };
 
 static void dm_dr_free(dm_dr_state *s) {
@@ -60,7 +61,7 @@ static void dm_dr_free(dm_dr_state *s) {
     for (auto &t : *v) dm_release(t);
   s->d_rr_emb = s->d_rr_w = s->d_rr_b = s->d_sm_w = s->d_sm_b = nullptr;
   dm_release(s->d_rr_par, s->d_sm_par, s->d_codes, s->d_item_off, s->d_items);
-  for (DevGrow *g : {&s->state, &s->S, &s->UV, &s->io, &s->cand}) g->release();
+  for (DevGrow *g : {&s->state, &s->S, &s->UV, &s->io, &s->cand, &s->ms, &s->ms_io}) g->release();
   delete s;
 }
 

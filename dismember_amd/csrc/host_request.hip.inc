@@ -35,6 +35,11 @@ enum EvKind {
   // product with its slab sum, embedding gradient (pairs, sort, segment sums), Adam
   EV_DFT_ROWS = 70, EV_DFT_DW = 71, EV_DFT_EMB = 72, EV_DFT_ADAM = 73,
   EV_DRR_FWD = 60, EV_DRR_SAMPLE = 61, EV_DRR_SOFTMAX = 62, EV_DRR_SMGRAD = 63, EV_DRR_DX = 64, EV_DRR_DW = 65, EV_DRR_EMB = 66, EV_DRR_ADAM = 67,
+  // the Deep-Retrieval M-step's path scores under DM_DR_TIME_LAUNCHES=1 (dr_mstep.hip.inc): pairs of a chunk, the (item, path) sort, segment
+  // heads (flags + compaction), segment sums, the sort by score, the sort by item (with its key kernel), the cut at C (flags + compaction),
+  // codes / scores / offsets, occurrences.  The searches of the chunks are EV_MAIN, as everywhere
+  EV_DRM_PAIRS = 80, EV_DRM_SORT = 81, EV_DRM_HEADS = 82, EV_DRM_SEGSUM = 83, EV_DRM_SCORE_SORT = 84, EV_DRM_ITEM_SORT = 85, EV_DRM_CUT = 86, EV_DRM_EMIT = 87,
+  EV_DRM_OCC = 88,
 };
 
 // the next pair of the handle's pool, recorded as `kind`

@@ -2,7 +2,8 @@
 (deep-retrieval/src/main/scala/com/mass/dr/optim/CoordinateDescent.scala:29-83) over the device beam search.
 
 The expensive part — one beam search with `beam = numCandidatePath` per training sample (:143-147, :181-186) — is ONE
-batched `dm_dr_beam_search` call per chunk; per-item aggregation is a sort + segmented sum over 64-bit path codes.  The greedy,
+batched `dm_dr_beam_search` call per chunk; per-item aggregation is a sort + segmented sum over 64-bit path codes, on the host
+(`batch_path_scores`) or without the candidates leaving the device (`batch_path_scores_dev`, `optimize(path_scores="device")`).  The greedy,
 penalised path choice is inherently sequential over items (a shared path-size table), as in the reference, and stays on the host.
 Orders the reference takes from hash maps are fixed here: ties between equal path scores resolve to the smaller path code
 (ascending node tuple), items are visited in ascending id."""
@@ -53,7 +54,10 @@ def batch_path_scores(engine, sequences, targets, num_candidate_path):
     new = np.ones(len(c), bool)
     new[1:] = (tg[1:] != tg[:-1]) | (c[1:] != c[:-1])
     starts = np.flatnonzero(new)
-    sums = np.add.reduceat(p, starts) if len(starts) else p[:0]     # pairwise inside numpy? no: reduceat is sequential
+    # NOT the reference's left-to-right order: reduceat gives first + sum(rest) per segment, and numpy's add loop sums the rest with eight
+    # accumulators once it has eight or more terms.  Two terms always agree with the reference; from three on the last bit can differ.
+    # batch_path_scores_dev folds left to right, as the reference does
+    sums = np.add.reduceat(p, starts) if len(starts) else p[:0]
     gi, gc = tg[starts], c[starts]
     out = {}
     bounds = np.flatnonzero(np.r_[True, gi[1:] != gi[:-1], True])
@@ -62,6 +66,19 @@ def batch_path_scores(engine, sequences, targets, num_candidate_path):
         k = np.argsort(-s, kind="stable")[:num_candidate_path]     # ties: ascending path code
         out[int(gi[a])] = (cc[k], s[k])
     return out
+
+
+def batch_path_scores_dev(engine, sequences, targets, num_candidate_path, with_occurrence=False):
+    """batch_path_scores on the device (Engine.dr_mstep_path_scores): search, aggregation and the cut at C without the
+    candidates leaving the device; every score is summed in sample order.  -> the dict batch_path_scores returns (and, with
+    with_occurrence, {item: number of samples})."""
+    off, codes, scores, occ = engine.dr_mstep_path_scores(sequences, targets, num_candidate_path)
+    items = np.flatnonzero(off[1:] > off[:-1])
+    out = {int(v): (codes[off[v]:off[v + 1]], scores[off[v]:off[v + 1]]) for v in items}
+    if not with_occurrence:
+        return out
+    hit = np.flatnonzero(occ)
+    return out, dict(zip(hit.tolist(), occ[hit].tolist()))
 
 
 def streaming_path_scores(engine, sequences, targets, num_candidate_path, decay_factor=0.999, batch_size=8192):
@@ -127,9 +144,18 @@ def assign_paths(item_path_scores, item_occurrence, all_items, num_iteration, nu
 
 
 def optimize(engine, sequences, targets, all_items, num_candidate_path, num_path_per_item, num_iteration=3, train_mode="batch",
-             decay_factor=0.999, batch_size=8192, seed=0, penalty_factor=3e-6, penalty_poly_order=4):
-    """CoordinateDescent.optimize(model, trainMode) -> item -> paths (internal ids)."""
+             decay_factor=0.999, batch_size=8192, seed=0, penalty_factor=3e-6, penalty_poly_order=4, path_scores="host"):
+    """CoordinateDescent.optimize(model, trainMode) -> item -> paths (internal ids).  path_scores="device" (batch mode only) aggregates the
+    candidates on the device (batch_path_scores_dev) and takes the item occurrences from the same call."""
     K, D = engine.dr_dims["K"], engine.dr_dims["D"]
+    if path_scores not in ("host", "device"):
+        raise ValueError(path_scores)
+    if path_scores == "device":
+        if train_mode != "batch":
+            raise ValueError("path_scores=\"device\" serves train_mode=\"batch\" only")
+        sc, occ = batch_path_scores_dev(engine, sequences, targets, num_candidate_path, with_occurrence=True)
+        return assign_paths(sc, occ, sorted(int(i) for i in all_items), num_iteration, num_path_per_item, K, D, seed,
+                            penalty_factor, penalty_poly_order)
     if train_mode == "batch":
         sc = batch_path_scores(engine, sequences, targets, num_candidate_path)
     elif train_mode == "streaming":

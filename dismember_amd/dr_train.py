@@ -14,7 +14,8 @@ One E-step / M-step round on an engine that holds a Deep-Retrieval model (`Engin
         trainer.step(seqs, targets)
     print(trainer.losses[-1])                                    # per-layer cross-entropy of the last batch
     new_paths = dr_mstep.optimize(engine, all_seqs, all_targets, range(num_item),      # M-step: re-assign the paths from a
-                                  num_candidate_path=20, num_path_per_item=J)          # beam search over the TRAINED weights
+                                  num_candidate_path=20, num_path_per_item=J,          # beam search over the TRAINED weights;
+                                  path_scores="device")                                # the candidates never leave the device
     trainer.set_item_paths(np.array([new_paths[i] for i in range(num_item)]))
 
 The first search after a step rebuilds the search's derived copies of the weights; steps in between do not.

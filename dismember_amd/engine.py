@@ -697,6 +697,44 @@ class Engine:
     def dr_recommend_dev(self, d_seq, U, beam, topk, d_ids, d_scores, d_counts):
         self._chk(N.lib().dm_dr_recommend_dev(self._h, d_seq, U, int(beam), int(topk), d_ids, d_scores, d_counts))
 
+    # ---- Deep-Retrieval M-step: per-item path scores
+    def dr_mstep_path_scores(self, seqs, targets, num_candidate_path, trace=False, cap=None):
+        """dm_dr_mstep_path_scores: seqs [N, L] internal ids (-1 = padding), targets [N] -> (item_off [num_item + 1], codes [total] int64,
+        scores [total] float64, occurrence [num_item]); item v's candidates are codes / scores [item_off[v], item_off[v + 1]), at most
+        num_candidate_path, descending by score, ties in ascending path code.  trace=True appends the beams the call aggregated:
+        (paths [N, C, D], probs [N, C], counts [N]).  cap: capacity of codes / scores (default: min(N, num_item) * C, always enough)."""
+        d = self.dr_dims
+        seq = _i32(seqs).reshape(-1, d["L"])
+        tg = _i32(targets).reshape(-1)
+        assert len(seq) == len(tg)
+        n, c = len(seq), int(num_candidate_path)
+        if cap is None:
+            cap = min(n, d["num_item"]) * max(c, 0)
+        f64p = C.POINTER(C.c_double)
+        off = np.empty(d["num_item"] + 1, np.int64)
+        occ = np.empty(d["num_item"], np.int64)
+        codes = np.empty(max(cap, 1), np.int64)
+        scores = np.empty(max(cap, 1), np.float64)
+        total = np.zeros(1, np.int64)
+        tr = None
+        if trace:
+            tr = (np.empty((n, max(c, 0), d["D"]), np.int32), np.empty((n, max(c, 0)), np.float64), np.empty(n, np.int32))
+        self._chk(N.lib().dm_dr_mstep_path_scores(self._h, _p(seq, N.i32p), _p(tg, N.i32p), n, c, int(cap), _p(off, N.i64p), _p(codes, N.i64p),
+                                                  _p(scores, f64p), _p(occ, N.i64p), _p(total, N.i64p),
+                                                  _p(tr[0], N.i32p) if trace else None, _p(tr[1], f64p) if trace else None,
+                                                  _p(tr[2], N.i32p) if trace else None))
+        t = int(total[0])
+        out = (off, codes[:t].copy(), scores[:t].copy(), occ)
+        return out + tr if trace else out
+
+    def dr_mstep_path_scores_dev(self, d_seq, d_targets, n, num_candidate_path, cap, d_item_off, d_codes, d_scores, d_occurrence=None,
+                                 d_trace=(None, None, None)):
+        """the same on device arrays (ids not range-checked) -> total"""
+        total = np.zeros(1, np.int64)
+        self._chk(N.lib().dm_dr_mstep_path_scores_dev(self._h, d_seq, d_targets, int(n), int(num_candidate_path), int(cap), d_item_off, d_codes,
+                                                      d_scores, d_occurrence, _p(total, N.i64p), d_trace[0], d_trace[1], d_trace[2]))
+        return int(total[0])
+
     # ---- Deep-Retrieval E-step: the layer model's training step (DESIGN.md §10)
     def dr_train_init(self, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
         o = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)
@@ -960,7 +998,9 @@ class Engine:
         (din_forward); 40 / 41 = DeepFM user / level launches, 42 / 43 = the DeepFM pair scorer's per-history set-up / per-pair launches
         (JTM tree learning), and 40 .. 44 the launches of the grouped fp64 training step; under
         DM_DR_TIME_LAUNCHES=1 the Deep-Retrieval training step: 50 = forward GEMMs, 51 = softmax + cross-entropy, 52 = dX products,
-        53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam"""
+        53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam; and the M-step's path scores:
+        80 = pairs of a chunk, 81 = the (item, path) sort, 82 = segment heads, 83 = segment sums, 84 = sort by score, 85 = sort by item,
+        86 = the cut at C, 87 = codes / scores / offsets, 88 = occurrences"""
         n, ms = C.c_int(0), C.c_double(0)
         self._chk(N.lib().dm_kernel_timing_get_kind(self._h, int(kind), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -526,6 +526,33 @@ int dm_dr_beam_search_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, in
 int dm_dr_recommend_dev(dm_handle_t h, const int32_t *d_seq_ids, int64_t U, int beam, int topk, int32_t *d_out_ids,
                         double *d_out_scores, int32_t *d_out_counts);
 
+/* ---- Deep-Retrieval M-step: per-item path scores on the device ----
+ * CoordinateDescent.batchPathScore + aggregatePathScore + computeItemOccurrence (D/optim/CoordinateDescent.scala:117-163): one beam search with
+ * beam = num_candidate_path (C) per sample, and per target item the summed probability of every path its samples' beams hold.
+ * seq_ids [N x seq_len] internal ids (-1 = padding), targets [N] in [0, num_item).  The result is a CSR over ALL items: item v's candidates
+ * are out_codes / out_scores [out_item_off[v], out_item_off[v + 1]), at most C, descending by score, equal scores in ascending path code
+ * (code = sum_d node_d * num_node^(D-1-d)); an item that is never a target has an empty range.  A score is the fp64 sum of the path's
+ * probabilities over the item's samples in ASCENDING SAMPLE INDEX, left to right from the first term: the same inputs give the same bytes,
+ * whatever the chunk the call searched in.  out_item_off [num_item + 1]; out_occurrence [num_item] (samples per item) may be NULL;
+ * *out_total = entries written.  cap = capacity of out_codes / out_scores: when it is too small the call returns DM_ERR_INVALID, writes
+ * nothing to the arrays and leaves the needed size in *out_total; min(N, num_item) * C is always enough.
+ * trace_paths [N x C x D], trace_probs [N x C], trace_counts [N]: all NULL or all set; they receive every sample's beam as the call
+ * aggregated it (dm_dr_beam_search's output).  The samples are searched in chunks (a multiple of 32 768; DM_DR_MSTEP_CHUNK in the
+ * environment forces a size) and the node ids of one chunk only are held, unless a trace asks for all.
+ * Refused before anything is read or allocated: no Deep-Retrieval model DM_ERR_STATE; C outside [1, 2048], a null required array, N < 0,
+ * a partly given trace DM_ERR_INVALID; N * C >= 2^31 (pair indices are 32-bit) and ceil(log2 num_item) + ceil(log2 num_node^D) > 63 (item
+ * and path code share a 64-bit sort key) DM_ERR_UNSUPPORTED.  Host entry only: an id outside its range DM_ERR_INDEX.  N == 0: DM_OK, every
+ * offset 0.  After dm_dr_adam_step the call searches with re-derived weights, as every search does.  The handle stays usable. */
+int dm_dr_mstep_path_scores(dm_handle_t h, const int32_t *seq_ids, const int32_t *targets, int64_t N, int num_candidate_path,
+                            int64_t cap, int64_t *out_item_off, int64_t *out_codes, double *out_scores,
+                            int64_t *out_occurrence, int64_t *out_total,
+                            int32_t *trace_paths, double *trace_probs, int32_t *trace_counts);
+/* the same with device arrays (ids are NOT range-checked); out_total stays a host pointer; returns when the results are in place */
+int dm_dr_mstep_path_scores_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_targets, int64_t N, int num_candidate_path,
+                                int64_t cap, int64_t *d_out_item_off, int64_t *d_out_codes, double *d_out_scores,
+                                int64_t *d_out_occurrence, int64_t *out_total,
+                                int32_t *d_trace_paths, double *d_trace_probs, int32_t *d_trace_counts);
+
 /* ---- DeepFM: one training step on the device ----
  * LocalOptimizer.trainBatch with the DeepFM graph (T/optim/LocalOptimizer.scala:139-162, useMask = false; T/model/DeepFM.scala:11-45;
  * S/nn/FM.scala:24-71, S/nn/Linear.scala, S/nn/BCECriterionWithLogits.scala:27-64 averaged over the batch; S/optim/Adam.scala:19-73).
