@@ -62,6 +62,8 @@ struct BeamParams {
   const dm_h8 *wsplit;
   const dm_h8 *emb_split;    // the table pre-split for the one-wave-per-SIMD kernel: [row][E/32 k-steps][4 g][hi 8 | lo 8] halfs, row stride E*4 bytes
   float emb_scale, score_unscale, acc_scale, out_unscale;   // 2^sh_e, 2^(-2 sh_e), 2^(sh_e+sh_w), 2^-(sh_e+sh_w)
+  const float *g_table;      // [num_index][E]: row c = W1b (att.W emb[c]), what the W kernel's per-user setup computes for a history position
+                             //    holding code c (dm_build_g_table_kernel); null: the setup runs the two products itself
   int64_t num_index;
   // tree
   const uint32_t *exists_bits, *leaf_bits;

@@ -42,6 +42,12 @@ __device__ __forceinline__ void dmw_mfma_f32(f32x4 &acc, float a, float b) {
   asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
 #define DMW_PIN() __builtin_amdgcn_sched_barrier(0)
+// LDS traffic of ONE wave executes in order; this only stops the compiler from moving accesses across it
+__device__ __forceinline__ void dmw_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 // A tile's operand gathers are issued from assembly, so that the COMPILER does not count them: vector-memory loads return in
 // order, and its s_waitcnt placement at the loop header (the merge of the pre-header's and the back edge's pending loads) made
 // the score MFMAs of a tile wait for the gathers issued a few hundred cycles earlier for the tile AFTER it.  The kernel places
@@ -191,6 +197,90 @@ __device__ __forceinline__ void dmw_sort_phase(unsigned long long (&key)[8], int
   if constexpr (K >= 16) dmw_sort_inlane<4>(key);
   if constexpr (K >= 8) dmw_sort_inlane<2>(key);
   if constexpr (K >= 4) dmw_sort_inlane<1>(key);
+}
+
+// ---- the per-row setup product  G_j = W1b (att.W k_j)  in two stages on the fp32 matrix pipe:  T1 = K att_w^T,  G = T1 W1b^T.
+// Row j of G depends on history row k_j and the dense weights alone — not on the user, nor on which rows share the 16-row tile —
+// so the same code serves the W kernel's per-user setup and the builder of the per-row table (BeamParams::g_table), whose rows
+// are therefore the setup's values bit for bit.
+//
+// One stage: 16 x E times E x E, one 16-column tile at a time; the B fragments (L2-resident, shared by every user) are fetched
+// TWO tiles ahead of the tile being multiplied — one wave has nothing else to hide their latency with.  Lane (r, g) holds row r
+// of the left operand, columns 16 jc + 4 g .. + 3 in a[jc]; emit(nt, acc) receives rows 4 g .. 4 g + 3 of column 16 nt + r.
+template <int E, typename Emit>
+__device__ __forceinline__ void dmw_gemm16(const f32x4 *frag, const f32x4 (&a)[E / 16], int lane, Emit &&emit) {
+  constexpr int NJ = E / 16, NT = E / 16;
+  f32x4 bq[3][NJ];
+  // uniform base + one 32-bit lane offset (opaque: else the NJ * NT lane addresses are loop-invariant over the users, get
+  // hoisted and spilled, and every load then waits for the scratch reload of its own address)
+  unsigned lo16 = 16u * (unsigned)lane;
+  asm volatile("" : "+v"(lo16));
+  const char *fb = (const char *)frag;
+  auto fetch = [&](auto nt_c) {
+    constexpr int nt = decltype(nt_c)::value;
+#pragma unroll
+    for (int jc = 0; jc < NJ; jc++) bq[nt % 3][jc] = *(const f32x4 *)(fb + (size_t)((jc * NT + nt) * 1024) + lo16);
+  };
+  fetch(std::integral_constant<int, 0>{});
+  if constexpr (NT > 1) fetch(std::integral_constant<int, 1>{});
+  DMW_FOR(NT, nt)
+    if constexpr (nt + 2 < NT) fetch(std::integral_constant<int, nt + 2>{});
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    asm volatile("s_nop 1" : "+v"(acc));
+#pragma unroll
+    for (int jc = 0; jc < NJ; jc++)
+#pragma unroll
+      for (int t = 0; t < 4; t++) dmw_mfma_f32(acc, a[jc][t], bq[nt % 3][jc][t]);
+    asm volatile("s_nop 7\n\ts_nop 7" : "+v"(acc));
+    emit(nt, acc);
+  DMW_END
+}
+// the transpose between the stages, through T1s[16][E + 4] in LDS: the first stage's output (rows 4 g .. 4 g + 3 of a column per
+// lane) becomes the second stage's left operand (row r, four consecutive columns per lane)
+template <int E>
+__device__ __forceinline__ void dmw_t1_put(float *T1s, int r, int g, int nt, const f32x4 &acc) {
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++) T1s[(4 * g + rr) * (E + 4) + 16 * nt + r] = acc[rr];
+}
+template <int E>
+__device__ __forceinline__ void dmw_t1_get(const float *T1s, int r, int g, f32x4 (&ta)[E / 16]) {
+#pragma unroll
+  for (int jc = 0; jc < E / 16; jc++) ta[jc] = *(const f32x4 *)(T1s + r * (E + 4) + 16 * jc + 4 * g);
+}
+
+// The table of setup rows: out[c][0 .. E) = W1b (att.W emb[c]) without b1, for every row c of the fp32 table.  One wave per 16
+// table rows, grid-stride; each wave runs the setup's two stages on its rows as the W kernel does on a user's history rows.
+template <int E>
+__global__ __launch_bounds__(DMW_BLOCK) void dm_build_g_table_kernel(const float *emb, const f32x4 *afrag, const f32x4 *bfrag, int64_t n_rows, float *out) {
+  constexpr int NJ = E / 16;
+  __shared__ __attribute__((aligned(16))) float T1all[DMW_NWAVES][16 * (E + 4)];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  float *T1s = T1all[wave];
+  const int64_t n_tiles = (n_rows + 15) / 16;
+  for (int64_t t = (int64_t)blockIdx.x * DMW_NWAVES + wave; t < n_tiles; t += (int64_t)gridDim.x * DMW_NWAVES) {
+    const int64_t row = 16 * t + r;
+    f32x4 ka[NJ];
+    if (row < n_rows) {
+      const f32x4 *src = (const f32x4 *)(emb + row * E) + g;
+#pragma unroll
+      for (int jc = 0; jc < NJ; jc++) ka[jc] = src[4 * jc];
+    } else {
+#pragma unroll
+      for (int jc = 0; jc < NJ; jc++) ka[jc] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    dmw_gemm16<E>(afrag, ka, lane, [&](int nt, const f32x4 &acc) { dmw_t1_put<E>(T1s, r, g, nt, acc); });
+    dmw_wave_sync();
+    f32x4 ta[NJ];
+    dmw_t1_get<E>(T1s, r, g, ta);
+    dmw_wave_sync();          // T1 is in registers: the next tile of rows may overwrite it
+    dmw_gemm16<E>(bfrag, ta, lane, [&](int nt, const f32x4 &acc) {
+#pragma unroll
+      for (int rr = 0; rr < 4; rr++) {
+        const int64_t orow = 16 * t + 4 * g + rr;
+        if (orow < n_rows) out[orow * E + 16 * nt + r] = acc[rr];
+      }
+    });
+  }
 }
 
 struct BeamWLds { int b1, w2, slot0, slot_stride, x_kfrag, x_gfrag, y_keys, y_acode0, y_acode1, y_aval, misc, total; };
@@ -466,8 +556,8 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
           code = (t > p.max_code) ? -1 : t;
         }
         if (code < -1 || code >= p.num_index) code = -1;
-        misc[M_SEQ + lane] = code;
       }
+      if (lane < 16) misc[M_SEQ + lane] = code;          // positions L .. 15 read as pads
       const unsigned pm = (unsigned)__ballot(lane < L && code == -1);
       if (lane == 0) misc[M_PADMASK] = p.use_mask ? pm : 0u;
     }
@@ -486,69 +576,69 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
 #pragma unroll
         for (int jc = 0; jc < NJ; jc++) ka[jc] = (f32x4){0.f, 0.f, 0.f, 0.f};
       }
-      if (r < KCOLS) {
+      float *Gfw = (float *)(slotp + lo.x_gfrag);
+      float gm = 0.0f;
+      // (G + b1) of rows 4 g .. 4 g + 3, column 16 nt + r, into the fp32 planes; positions past the history are zero
+      auto put_g = [&](int r_, int g_, int nt, const f32x4 &acc) {
+        if (g_ < KQ) {
+          const float bb = B1[16 * nt + r_];
+#pragma unroll
+          for (int rr = 0; rr < 4; rr++) {
+            const float gv = (4 * g_ + rr < L) ? acc[rr] + bb : 0.0f;
+            Gfw[(g_ * NT + nt) * 64 + rr * 16 + r_] = gv;
+            gm = __builtin_fmaxf(gm, __builtin_fabsf(gv));
+          }
+        }
+      };
+      // with the per-row table (BeamParams::g_table) G is one more gather per history position, issued behind the key row's: lane
+      // (r, g) takes, for the positions 4 g .. 4 g + 3, the words 16 nt + r of their table rows — what the second product below
+      // would leave in its accumulators.  A pad's key row is zero, and so is its product.
+      const bool g_tab = p.g_table != nullptr;
+      // (an opaque copy of the lane id: the addresses computed from the real one are invariant over the users, get hoisted out
+      // of the user loop and spilled)
+      int lt = lane;
+      asm volatile("" : "+v"(lt));
+      const int rt = lt & 15, gt = lt >> 4;
+      if (g_tab) {
+        float gr[4][NT];
+#pragma unroll
+        for (int rr = 0; rr < 4; rr++) {
+          const int32_t gcode = misc[M_SEQ + 4 * gt + rr];
+          if (gcode >= 0) {
+            const float *src = p.g_table + (int64_t)gcode * E + rt;
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) gr[rr][nt] = src[16 * nt];
+          } else {
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) gr[rr][nt] = 0.0f;
+          }
+        }
+        DMW_FOR(NT, nt)
+          put_g(rt, gt, nt, (f32x4){gr[0][nt], gr[1][nt], gr[2][nt], gr[3][nt]});
+        DMW_END
+      }
+      if (rt < KCOLS) {
         dm_h8 *Khw = (dm_h8 *)(slotp + lo.x_kfrag);
 #pragma unroll
         for (int s = 0; s < NS; s++) {
           dm_h8 hi, lw;
           dm_split8(ka[2 * s], ka[2 * s + 1], p.emb_scale, hi, lw);
-          Khw[(s * 4 + g) * KCOLS + r] = hi;
-          Khw[((NS + s) * 4 + g) * KCOLS + r] = lw;
+          Khw[(s * 4 + gt) * KCOLS + rt] = hi;
+          Khw[((NS + s) * 4 + gt) * KCOLS + rt] = lw;
         }
       }
       SMARK(1);
-      float *T1s = (float *)(slotp + lo.y_keys);          // [16][E + 4]
-      // 16 x E times E x E on the fp32 matrix pipe, one 16-column tile at a time; the B fragments (L2-resident, shared by every
-      // user) are fetched TWO tiles ahead of the tile being multiplied — one wave has nothing else to hide their latency with
-      auto gemm16 = [&](const f32x4 *frag, const f32x4 (&a)[NJ], auto &&emit) {
-        f32x4 bq[3][NJ];
-        // uniform base + one 32-bit lane offset (opaque: else the NJ * NT lane addresses are loop-invariant over the users, get
-        // hoisted and spilled, and every load then waits for the scratch reload of its own address)
-        unsigned lo16 = 16u * (unsigned)lane;
-        asm volatile("" : "+v"(lo16));
-        const char *fb = (const char *)frag;
-        auto fetch = [&](auto nt_c) {
-          constexpr int nt = decltype(nt_c)::value;
-#pragma unroll
-          for (int jc = 0; jc < NJ; jc++) bq[nt % 3][jc] = *(const f32x4 *)(fb + (size_t)((jc * NT + nt) * 1024) + lo16);
-        };
-        fetch(std::integral_constant<int, 0>{});
-        if constexpr (NT > 1) fetch(std::integral_constant<int, 1>{});
-        DMW_FOR(NT, nt)
-          if constexpr (nt + 2 < NT) fetch(std::integral_constant<int, nt + 2>{});
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-          asm volatile("s_nop 1" : "+v"(acc));
-#pragma unroll
-          for (int jc = 0; jc < NJ; jc++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) dmw_mfma_f32(acc, a[jc][t], bq[nt % 3][jc][t]);
-          asm volatile("s_nop 7\n\ts_nop 7" : "+v"(acc));
-          emit(nt, acc);
-        DMW_END
-      };
-      gemm16(p.afrag, ka, [&](int nt, const f32x4 &acc) {
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) T1s[(4 * g + rr) * (E + 4) + 16 * nt + r] = acc[rr];
-      });
-      wsync();
-      SMARK(2);
-      f32x4 ta[NJ];
-#pragma unroll
-      for (int jc = 0; jc < NJ; jc++) ta[jc] = *(const f32x4 *)(T1s + r * (E + 4) + 16 * jc + 4 * g);
-      float *Gfw = (float *)(slotp + lo.x_gfrag);
-      float gm = 0.0f;
-      gemm16(p.bfrag, ta, [&](int nt, const f32x4 &acc) {
-        if (g < KQ) {
-          const float bb = B1[16 * nt + r];
-#pragma unroll
-          for (int rr = 0; rr < 4; rr++) {
-            const float gv = (4 * g + rr < L) ? acc[rr] + bb : 0.0f;
-            Gfw[(g * NT + nt) * 64 + rr * 16 + r] = gv;
-            gm = __builtin_fmaxf(gm, __builtin_fabsf(gv));
-          }
-        }
-      });
-      SMARK(3);
+      if (!g_tab) {
+        // T1 = K att_w^T;  G = T1 W1b^T  (dmw_gemm16), once per user
+        float *T1s = (float *)(slotp + lo.y_keys);          // [16][E + 4]
+        dmw_gemm16<E>(p.afrag, ka, lane, [&](int nt, const f32x4 &acc) { dmw_t1_put<E>(T1s, r, g, nt, acc); });
+        wsync();
+        SMARK(2);
+        f32x4 ta[NJ];
+        dmw_t1_get<E>(T1s, r, g, ta);
+        dmw_gemm16<E>(p.bfrag, ta, lane, [&](int nt, const f32x4 &acc) { put_g(r, g, nt, acc); });
+        SMARK(3);
+      }
       unsigned gbits = __float_as_uint(gm);
       gbits = gbits < 0x7f800000u ? gbits : 0x7f800000u;     // NaN counts as "out of range"
       for (int o = 32; o > 0; o >>= 1) { const unsigned t_ = (unsigned)__shfl_xor((int)gbits, o); gbits = t_ > gbits ? t_ : gbits; }
@@ -572,7 +662,7 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
           float gv[NQ][8];
 #pragma unroll
           for (int q = 0; q < NQ; q++) {
-            const int idx = lane + 64 * q;
+            const int idx = lt + 64 * q;
             const int nt_ = (idx >> 6) % NT, m_ = idx & 15, g_ = (idx >> 4) & 3;
             DMW_FOR(8, k)
               const int pos = (int)((dmw_fold_pos_nibbles(k) >> (4 * g_)) & 15u);
@@ -593,7 +683,7 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
             const dm_h2 h45 = __builtin_convertvector((f32x2_){x[4], x[5]}, dm_h2), h67 = __builtin_convertvector((f32x2_){x[6], x[7]}, dm_h2);
             dm_h8 o;
             o[0] = h01[0]; o[1] = h01[1]; o[2] = h23[0]; o[3] = h23[1]; o[4] = h45[0]; o[5] = h45[1]; o[6] = h67[0]; o[7] = h67[1];
-            ((dm_h8 *)Gfw)[lane + 64 * q] = o;
+            ((dm_h8 *)Gfw)[lt + 64 * q] = o;
           }
         } else {
           for (int i = lane; i < KQ * NT * 64; i += 64) Gfw[i] *= p.acc_scale;

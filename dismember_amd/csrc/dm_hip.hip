@@ -148,6 +148,7 @@ struct dm_ctx {
   std::vector<int> ev_kind;    // per pair: what it was recorded as (EvKind, host_request.hip.inc)
   bool time_direct = false;    // DM_TIME_DIRECT=1: the single-request path, which launches without an event pair, records one too (probes)
   bool direct_ok = true;       // host-mapped single-request path enabled (DM_NO_DIRECT=1 turns it off)
+  bool last_g_table = false;   // ... and whether that search's setup read the per-row table (dm_debug_g_table)
   char last_kernel[64] = "";   // the search kernel of the last beam search (measurement: dm_last_beam_kernel)
   SearchCounters *d_ctr = nullptr;
   unsigned long long *d_phase = nullptr;   // 8 debug counters
@@ -1048,6 +1049,7 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
   // the host-polled epilogue (results, system-scope fence, count as the flag) exists for the TDM final selection only: the mode-1 (OTM)
   // epilogue stores its counts before the ids and without a fence
   if (p.host_direct && p.mode != 0) return fail(h, DM_ERR_STATE, "launch_beam: the host-mapped single-request path is a mode-0 (TDM) path");
+  h->last_g_table = false;
   {   // f64 model trained since the f32 copies were made: refresh them, then take b2 again (fill_common read it before the rebuild)
     const int rc_ = ensure_f32_mirror(h);
     if (rc_ != DM_OK) return rc_;
@@ -1069,6 +1071,8 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       HIPCHK(h, hipMemsetAsync(h->defer.p, 0, 16, h->stream));
       p.defer_count = (unsigned long long *)h->defer.p;
       p.defer_users = (int32_t *)((char *)h->defer.p + 16);
+      { const int rc_g = g_table_for_search(h, &p.g_table); if (rc_g != DM_OK) return rc_g; }
+      h->last_g_table = p.g_table != nullptr;
       const char *const no_split = "the split-fp16 scorer needs an embedding size of 32, 64 or 128";
       int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
       if (rc != DM_OK) return rc;
@@ -1080,7 +1084,7 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       p2.user_count = (const unsigned long long *)h->defer.p;
       p2.user_list = (const int32_t *)((char *)h->defer.p + 16);
       p2.next_user = (unsigned long long *)((char *)h->defer.p + 8);
-      p2.defer_count = nullptr; p2.defer_users = nullptr;
+      p2.defer_count = nullptr; p2.defer_users = nullptr; p2.g_table = nullptr;      // (the LDS-fed kernel keeps its own setup)
       return dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_E<decltype(e)::value, true>(h, p2, pl2); });
     }
     return dispatch_E<32>(h, h->embed, "the split-fp16 scorer needs an embedding size of 32, 64 or 128",
@@ -1642,6 +1646,17 @@ int dm_kernel_timing_get(dm_handle_t h, int *launches, double *total_ms) {
   return DM_OK;
 }
 const char *dm_last_beam_kernel(dm_handle_t h) { return h ? h->last_kernel : ""; }
+// debug entry (not in the public header): did the last search on the one-wave-per-SIMD kernel read the setup table, is the owner's
+// table current, and its size
+extern "C" int dm_debug_g_table(dm_handle_t h, int *used_last, int *current, unsigned long long *bytes) {
+  if (!h || !used_last || !current || !bytes) return DM_ERR_INVALID;
+  dm_ctx *o = h->parent ? h->parent : h;
+  std::lock_guard<std::recursive_mutex> lk_(o->mu);
+  *used_last = h->last_g_table ? 1 : 0;
+  *current = (o->lazy.d_g_table && !o->lazy.g_table_dirty) ? 1 : 0;
+  *bytes = o->lazy.d_g_table ? (unsigned long long)o->lazy.g_table_bytes : 0ull;
+  return DM_OK;
+}
 int dm_kernel_timing_get_kind(dm_handle_t h, int kind, int *launches, double *total_ms) {
   if (!h || !launches || !total_ms) return DM_ERR_INVALID;
   HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -22,17 +22,21 @@ struct LazyCopies {
   int sh_r = 0; void *d_rows_split = nullptr; bool rows_split_dirty = true;
   // fp64 beam kernel: A / B fragments of att.W, W1a, W1b; l2.b read back with them
   void *d_frag64 = nullptr; double b2_64 = 0.0; bool frag64_dirty = true;
+  // one-wave-per-SIMD beam kernel: the per-row setup table, row c = W1b (att.W emb32[c]) in fp32 (ensure_g_table)
+  float *d_g_table = nullptr; size_t g_table_bytes = 0; bool g_table_dirty = true;
+  bool g_table_declined = false;    // DM_G_TABLE unset: the table was too large for the free memory; not asked again before the next load
   // f64 model whose weights moved: the f32 copies the throughput beam kernels read are stale (the buffers are install_weights')
   bool f32_mirror_dirty = false;
 
-  void loaded() { split_dirty = true; table_dense_change = true; }
+  void loaded() { split_dirty = true; table_dense_change = true; g_table_dirty = true; g_table_declined = false; }
   void released() {
     dm_release(d_wsplit, d_maxabs, d_emb_split, d_rows_split, d_frag64);
+    dm_release(d_g_table); g_table_bytes = 0; g_table_dirty = true; g_table_declined = false;
     emb_split_bytes = 0; table_dense_change = true; sh_e_valid = false; emb_split_need_full = true;
     split_dirty = true; rows_split_dirty = true; frag64_dirty = true; f32_mirror_dirty = false;
   }
   // dm_train_init: the weights did not move (the mirror flag stays), but changes of an earlier training run that are not yet in the
-  // split copies can no longer be found from the new run's active rows
+  // split copies can no longer be found from the new run's active rows.  The setup table stays as it is: it has no row-wise refresh
   void training_started() {
     if (split_dirty || emb_split_dirty) table_dense_change = true;
     active_rows_host = 0; split_dirty = true; frag64_dirty = true;
@@ -41,9 +45,12 @@ struct LazyCopies {
     active_rows_host = n_active;
     if (!sparse) table_dense_change = true;         // the split scorer's copies can no longer be refreshed row by row
     split_dirty = true; frag64_dirty = true; f32_mirror_dirty = f32_mirror_dirty || f64_model;
+    g_table_dirty = true;                           // att.W and W1b move in every step: every row of the setup table is stale
   }
-  void mirror_rebuilt() { f32_mirror_dirty = false; split_dirty = true; table_dense_change = true; }
-  void clone_view() {      // a clone's copy of its parent's state, taken after the parent brought its copies up to date
+  void mirror_rebuilt() { f32_mirror_dirty = false; split_dirty = true; table_dense_change = true; g_table_dirty = true; }
+  // a clone's copy of its parent's state, taken after the parent brought its copies up to date.  The setup table is not among them: a
+  // clone's search asks the owner for it, call by call (g_table_for_search), and never reads its own copy of these fields
+  void clone_view() {
     split_dirty = false; emb_split_dirty = false; rows_split_dirty = false; frag64_dirty = false; f32_mirror_dirty = false;
     table_dense_change = false; emb_split_need_full = false; emb_split_patch = false; active_rows_host = 0;
   }
@@ -223,6 +230,63 @@ static int ensure_split(dm_ctx *h) {
   }
   HIPCHK(h, hipGetLastError());
   z.emb_split_dirty = false;
+  return DM_OK;
+}
+
+// The setup table of the one-wave-per-SIMD kernel: row c = W1b (att.W emb32[c]), built by the kernel's own two-stage product
+// (dm_build_g_table_kernel, beam_kernel_w.hip.inc) from the f32 table and the fragment orders the kernel's setup reads.  There is no
+// row-wise refresh: att.W and W1b move in every Adam step, and with them every row.
+static int ensure_g_table(dm_ctx *h) {
+  std::lock_guard<std::recursive_mutex> lk_(h->mu);
+  int rc = ensure_f32_mirror(h);          // an f64 model builds from its f32 mirror
+  if (rc != DM_OK) return rc;
+  LazyCopies &z = h->lazy;
+  if (!z.g_table_dirty && z.d_g_table) return DM_OK;
+  const int E = h->embed;
+  const size_t bytes = (size_t)h->num_index * E * 4;
+  if (z.g_table_bytes != bytes || !z.d_g_table) {
+    dm_release(z.d_g_table); z.g_table_bytes = 0;
+    ALLOC(h, z.d_g_table, bytes);
+    z.g_table_bytes = bytes;
+  }
+  const int64_t waves = (h->num_index + 15) / 16, blocks = (waves + DMW_NWAVES - 1) / DMW_NWAVES;
+  const int grid = (int)std::min<int64_t>(blocks, (int64_t)h->n_cu * 8);
+  rc = dispatch_E<32>(h, E, "the setup table needs an embedding size of 32, 64 or 128", [&](auto e) {
+    hipLaunchKernelGGL((dm_build_g_table_kernel<decltype(e)::value>), dim3(grid), dim3(DMW_BLOCK), 0, h->stream, (const float *)h->d_emb32,
+                       (const f32x4 *)h->d_afrag, (const f32x4 *)h->d_bfrag, h->num_index, z.d_g_table);
+    HIPCHK(h, hipGetLastError());
+    return DM_OK;
+  });
+  if (rc != DM_OK) return rc;
+  z.g_table_dirty = false;
+  return DM_OK;
+}
+
+// The table a search on the one-wave-per-SIMD kernel reads, or null: the kernel then runs the two products per user.  DM_G_TABLE
+// (read per call: the tests run both routes in one process) = 0 never, 1 always (a table that cannot be allocated fails the search),
+// unset: unless the table is stale inside a training session (every Adam step would pay the whole rebuild) or its bytes exceed a
+// quarter of the free device memory (remembered until the next load).  A clone reads its owner's table, built on the owner's stream.
+static int g_table_for_search(dm_ctx *h, const float **table) {
+  *table = nullptr;
+  const char *e_ = getenv("DM_G_TABLE");
+  const int knob = (e_ && e_[0] == '0') ? 0 : (e_ && e_[0] == '1') ? 1 : -1;
+  if (knob == 0) return DM_OK;
+  dm_ctx *o = h->parent ? h->parent : h;
+  std::lock_guard<std::recursive_mutex> lk_(o->mu);
+  LazyCopies &z = o->lazy;
+  const bool stale = z.g_table_dirty || !z.d_g_table;
+  if (stale && knob < 0) {
+    if (o->train_ready || z.g_table_declined) return DM_OK;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+    if ((size_t)o->num_index * o->embed * 4 > free_b / 4) { z.g_table_declined = true; return DM_OK; }
+  }
+  if (stale) {
+    const int rc = ensure_g_table(o);
+    if (rc != DM_OK) { if (o != h) h->err = o->err; return rc; }
+    if (o != h) HIPCHK(h, hipStreamSynchronize(o->stream));
+  }
+  *table = z.d_g_table;
   return DM_OK;
 }
 

@@ -1008,6 +1008,15 @@ class Engine:
     def last_beam_kernel(self):
         return (N.lib().dm_last_beam_kernel(self._h) or b"").decode()
 
+    def g_table_state(self):
+        """dm_debug_g_table: whether the last search on the one-wave-per-SIMD kernel read the per-row setup table (DM_G_TABLE),
+        whether the owner's table is current, and its size in bytes."""
+        used, cur, nbytes = C.c_int(0), C.c_int(0), C.c_ulonglong(0)
+        fn = N.lib().dm_debug_g_table
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+        self._chk(fn(self._h, C.byref(used), C.byref(cur), C.byref(nbytes)))
+        return {"used_last": bool(used.value), "current": bool(cur.value), "bytes": nbytes.value}
+
     def last_scored_rows(self):
         r = C.c_int64(0)
         self._chk(N.lib().dm_last_scored_rows(self._h, C.byref(r)))
