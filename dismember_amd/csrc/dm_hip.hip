@@ -1594,6 +1594,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "dfm_jtm.hip.inc"
 #include "jtm_sharded.hip.inc"
 #include "train_grouped_host.hip.inc"
+#include "dfm_otm.hip.inc"
 #include "otm_train.hip.inc"
 #include "checkpoint.hip.inc"
 #include "tree_file.hip.inc"

@@ -25,6 +25,7 @@ enum EvKind {
   EV_ROWS = 30,           // general rows (rows_kernel.hip.inc)
   EV_DFM_USER = 40, EV_DFM_LEVEL = 41,
   EV_DFM_JTM_ROWS = 42, EV_DFM_JTM_PAIRS = 43,      // the pair scorer of JTM tree learning (dfm_jtm.hip.inc): per-history set-up, per-pair score
+  EV_DFM_OTM = 42,        // the fused OTM beam search of a DeepFM model (dfm_otm.hip.inc): a call is a search or a tree-learning step, never both
   EV_TG_SETUP = 40, EV_TG_ROWS = 41, EV_TG_WGRAD_A = 42, EV_TG_USER_BWD = 43, EV_TG_WGRAD_B = 44,
   // the Deep-Retrieval training step under DM_DR_TIME_LAUNCHES=1 (dr_train.hip.inc): forward GEMMs, softmax + cross-entropy, dX products,
   // dW / db products with their slab sums, embedding gradient (pairs, sort, segment sums), Adam

@@ -32,8 +32,30 @@ __device__ __forceinline__ unsigned long long otm64_desc_key(double s) {
   return ~asc;
 }
 
-// one workgroup per user: sortBy(score)(reverse).take(beam) is a STABLE sort (CandidateSearcher.scala:117-120), i.e. the
-// order of (descending key, position) pairs, which are unique; bitonic network over LDS
+// sortBy(score)(reverse).take(beam) is a STABLE sort (CandidateSearcher.scala:117-120), i.e. the order of (descending key, position)
+// pairs, which are unique; bitonic network over LDS.  Every thread of the workgroup calls it (uniform n, pcap = a power of two >= n);
+// on return pos[0 .. n) lists the positions of sc[0 .. n) in that order.  The ONE statement of the order: the fp64 / long-history
+// pipeline below and the fused DeepFM kernel (dfm_otm.hip.inc) both prune through it.
+template <typename T>
+__device__ __forceinline__ void otm64_sort_positions(unsigned long long *key, unsigned *pos, const T *sc, int n, int pcap) {
+  // a float widens to double exactly and in order (-0.0f < +0.0f, one NaN class): the fp64 key serves both score types
+  for (int i = threadIdx.x; i < pcap; i += blockDim.x) { key[i] = i < n ? otm64_desc_key((double)sc[i]) : ~0ull; pos[i] = i < n ? (unsigned)i : 0xFFFFFFFFu; }
+  __syncthreads();
+  for (int k = 2; k <= pcap; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int c = threadIdx.x; c < pcap / 2; c += blockDim.x) {
+        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1)), l = i + j;
+        const unsigned long long a = key[i], b = key[l];
+        const unsigned pa = pos[i], pb = pos[l];
+        const bool a_first = a < b || (a == b && pa < pb);
+        const bool asc = (i & k) == 0;
+        if (a_first != asc) { key[i] = b; key[l] = a; pos[i] = pb; pos[l] = pa; }
+      }
+      __syncthreads();
+    }
+}
+
+// one workgroup per user
 template <typename T>
 __global__ __launch_bounds__(256) void otm64_prune_expand_kernel(Otm64Prune<T> p) {
   extern __shared__ __attribute__((aligned(16))) char smem_o[];
@@ -46,22 +68,7 @@ __global__ __launch_bounds__(256) void otm64_prune_expand_kernel(Otm64Prune<T> p
     for (int i = threadIdx.x; i < p.n; i += blockDim.x) { const int32_t c = codes[i]; next[2 * i] = 2 * c + 1; next[2 * i + 1] = 2 * c + 2; }
     return;
   }
-  const T *sc = p.scores + u * p.stride;
-  // a float widens to double exactly and in order (-0.0f < +0.0f, one NaN class): the fp64 key serves both score types
-  for (int i = threadIdx.x; i < p.pcap; i += blockDim.x) { key[i] = i < p.n ? otm64_desc_key((double)sc[i]) : ~0ull; pos[i] = i < p.n ? (unsigned)i : 0xFFFFFFFFu; }
-  __syncthreads();
-  for (int k = 2; k <= p.pcap; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int c = threadIdx.x; c < p.pcap / 2; c += blockDim.x) {
-        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1)), l = i + j;
-        const unsigned long long a = key[i], b = key[l];
-        const unsigned pa = pos[i], pb = pos[l];
-        const bool a_first = a < b || (a == b && pa < pb);
-        const bool asc = (i & k) == 0;
-        if (a_first != asc) { key[i] = b; key[l] = a; pos[i] = pb; pos[l] = pa; }
-      }
-      __syncthreads();
-    }
+  otm64_sort_positions<T>(key, pos, p.scores + u * p.stride, p.n, p.pcap);
   for (int i = threadIdx.x; i < p.nb; i += blockDim.x) { const int32_t c = codes[pos[i]]; next[2 * i] = 2 * c + 1; next[2 * i + 1] = 2 * c + 2; }
 }
 

@@ -167,6 +167,11 @@ static int otm_targets_dev(dm_ctx *h, char *A, const OtmTgtArena &a, const int32
   const unsigned GU = (unsigned)((U + 255) / 256);
   HIPCHK(h, hipMemsetAsync(A + a.o_tnode, 0xFF, (size_t)levels * a.NTc * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(A + a.o_tlab, 0, (size_t)levels * a.NTc * 8, h->stream));
+  // DeepFM has no mask, and without one the reference feeds the sibling tensor to BOTH forwards (OTMTree.scala:156-161): posPreds(i) >=
+  // negPreds(i) compares a value with itself, so every node keeps its own label unless the logit is NaN.  No forward is run: the fold
+  // reads a zeroed prediction buffer
+  const bool dfm = h->scorer_kind == DM_KIND_DEEPFM;
+  if (dfm) HIPCHK(h, hipMemsetAsync(A + a.o_pred, 0, 2 * a.NTc * 8, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_seq, seq_codes, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_toff, target_off, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream));
   if (NT > 0) HIPCHK(h, hipMemcpyAsync(d_tin, target_nodes, (size_t)NT * 4, hipMemcpyHostToDevice, h->stream));
@@ -188,7 +193,7 @@ static int otm_targets_dev(dm_ctx *h, char *A, const OtmTgtArena &a, const int32
     p.cnode = a.tnode(A, li); p.clab = a.tlab(A, li); p.ccnt = a.tcnt(A, li); p.coff = d_coff;
     p.codes = (int32_t *)(A + a.o_ccodes); p.rseq = (int32_t *)(A + a.o_cseq); p.rmask = (unsigned *)(A + a.o_cmask); p.negl = (double *)(A + a.o_negl);
     p.pred = A + a.o_pred; p.pnode = a.tnode(A, li - 1); p.plab = a.tlab(A, li - 1); p.pcnt = a.tcnt(A, li - 1);
-    if (total > 0) {
+    if (total > 0 && !dfm) {
       hipLaunchKernelGGL(otm_tgt_rows_kernel, dim3(GU), dim3(256), 0, h->stream, p);
       // computePreds (:167-172): posPreds and negPreds as one launch (a row's value does not depend on its batch)
       // (f32 histories of 17 .. 32 positions: the general forward — the MFMA rows kernel holds one 16-position score tile)
@@ -207,28 +212,39 @@ static int otm_targets_dev(dm_ctx *h, char *A, const OtmTgtArena &a, const int32
 }
 
 // *agreed = level agreements this rank has taken part in (the caller completes the protocol when the call fails between two of them)
-static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+// dfm: the DeepFM scorer (dm_deepfm_otm_train_batch) — targets without a forward, the fused search of dfm_otm.hip.inc, the row step of
+// dfm_train.hip.inc per level; one rank
+static int otm_train_batch_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
                                 const dm_otm_train_opts *o, double *level_losses, int *n_levels, int *agreed, int *agree_total) {
-  int rc = train_check(h, "dm_otm_train_batch");
+  const std::string who = dfm ? "dm_deepfm_otm_train_batch" : "dm_otm_train_batch";
+  int rc = dfm ? dfm_train_check(h, who.c_str(), false) : train_check(h, who.c_str());
   if (rc != DM_OK) return rc;
   if (!seq_codes || !target_off || !o || !level_losses || U <= 0 || L <= 0 || L > DM_PIPE_MAXL)
-    return fail(h, DM_ERR_INVALID, "dm_otm_train_batch: bad arguments");
-  if ((rc = otm_check(h, U, L, o->beam, o->leaf_level, "dm_otm_train_batch")) != DM_OK) return rc;
+    return fail(h, DM_ERR_INVALID, who + ": bad arguments");
+  if (dfm) {
+    if ((rc = dfm_otm_check(h, who.c_str(), U, L, o->beam, o->leaf_level, o->use_mask)) != DM_OK) return rc;
+    if (h->comm && h->comm->nranks > 1)
+      return fail(h, DM_ERR_UNSUPPORTED, who + ": a communicator with " + std::to_string(h->comm->nranks) + " ranks is attached; the gradient exchange for DeepFM is not built");
+    if ((rc = dfm_train_check(h, who.c_str(), true)) != DM_OK) return rc;
+    // the row step's limits (dfm_train_fb_dev), before anything runs
+    if (U * 2 * o->beam > (int64_t)DRT_MAX_ROWS || U * 2 * o->beam * (int64_t)(L + 1) >= ((int64_t)1 << 31))
+      return fail(h, DM_ERR_UNSUPPORTED, who + ": a level's batch of U * 2 beam rows is too large for the DeepFM row step (at most 4 194 240 rows, and rows (L + 1) below 2^31): split the users");
+  } else if ((rc = otm_check(h, U, L, o->beam, o->leaf_level, who.c_str())) != DM_OK) return rc;
   int start, start_level;
   level_start_int(o->beam, &start, &start_level);
   const int levels = o->leaf_level - start_level;
-  if (levels < 1) return fail(h, DM_ERR_INVALID, "dm_otm_train_batch: the leaf level must lie below the beam's start level");
+  if (levels < 1) return fail(h, DM_ERR_INVALID, who + ": the leaf level must lie below the beam's start level");
   *agree_total = levels;
-  if (target_off[0] != 0) return fail(h, DM_ERR_INVALID, "dm_otm_train_batch: target_off[0] must be 0");
+  if (target_off[0] != 0) return fail(h, DM_ERR_INVALID, who + ": target_off[0] must be 0");
   for (int64_t u = 0; u < U; u++)
-    if (target_off[u + 1] < target_off[u]) return fail(h, DM_ERR_INVALID, "dm_otm_train_batch: target_off must be non-decreasing");
+    if (target_off[u + 1] < target_off[u]) return fail(h, DM_ERR_INVALID, who + ": target_off must be non-decreasing");
   const int64_t NT = target_off[U];
-  if (NT > 0 && !target_nodes) return fail(h, DM_ERR_INVALID, "dm_otm_train_batch: target_nodes is NULL");
+  if (NT > 0 && !target_nodes) return fail(h, DM_ERR_INVALID, who + ": target_nodes is NULL");
   const int64_t leaf_lo = ((int64_t)1 << o->leaf_level) - 1, leaf_hi = ((int64_t)2 << o->leaf_level) - 2;
   for (int64_t i = 0; i < NT; i++)
-    if (target_nodes[i] < leaf_lo || target_nodes[i] > leaf_hi) return fail(h, DM_ERR_INDEX, "dm_otm_train_batch: a target is not a node of the leaf level");
+    if (target_nodes[i] < leaf_lo || target_nodes[i] > leaf_hi) return fail(h, DM_ERR_INDEX, who + ": a target is not a node of the leaf level");
   for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_otm_train_batch: history code outside the embedding table");
+    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, who + ": history code outside the embedding table");
   HIPCHK(h, hipSetDevice(h->device));
   dm_otm_stats &st = h->otm_stats;
   st = dm_otm_stats{};
@@ -241,7 +257,7 @@ static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, 
   int cap = ((2 * o->beam + 15) / 16) * 16;
   if (cap < 32) cap = 32;
   SearchPlan pl{};
-  if (!pipe_search) {
+  if (!pipe_search && !dfm) {
     if ((rc = plan_search(h, o->beam, U, L, levels, false, &pl)) != DM_OK) return rc;
     cap = pl.cap;
   }
@@ -275,7 +291,8 @@ static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, 
   // ---- beam nodes with the weights fixed: the search's per-level trace IS beamSearchNodes
   int32_t *d_tc = (int32_t *)(A + o_tc), *d_tnn = (int32_t *)(A + o_tn), *d_ids = (int32_t *)(A + o_ids), *d_cnt = (int32_t *)(A + o_cnt);
   HIPCHK(h, hipMemsetAsync(d_tnn, 0, (size_t)U * levels * 4, h->stream));
-  if (pipe_search) rc = otm64_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, f64_search ? (double *)(A + o_sc) : nullptr,
+  if (dfm) rc = dfm_otm_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, (float *)(A + o_sc), d_cnt, levels, cap, d_tc, (float *)(A + o_ts), d_tnn);
+  else if (pipe_search) rc = otm64_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, f64_search ? (double *)(A + o_sc) : nullptr,
                                          f64_search ? nullptr : (float *)(A + o_sc), d_cnt, levels, cap, d_tc,
                                          f64_search ? (double *)(A + o_ts) : nullptr, f64_search ? nullptr : (float *)(A + o_ts), d_tnn);
   else rc = otm_search_dev(h, d_seq, U, L, o->beam, o->leaf_level, d_ids, (float *)(A + o_sc), d_cnt, levels, d_tc, (float *)(A + o_ts), d_tnn, pl, false);
@@ -300,10 +317,12 @@ static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, 
                        (const int32_t *)tn_(it), (const double *)tl_(it), (const int32_t *)tc_(it), b_codes, grouped ? (int32_t *)nullptr : b_seq,
                        grouped ? (unsigned *)nullptr : b_mask, b_lab);
     float lf = 0.f;
-    if (grouped) rc = train_fb_grouped_dev(h, d_seq, d_umask, b_codes, b_lab, U, nl, L, &lf);
+    double ld = 0.0;
+    if (dfm) rc = dfm_train_fb_dev(h, b_codes, b_seq, b_lab, B, &ld);      // (the row mask is unused: the graph has no mask input)
+    else if (grouped) rc = train_fb_grouped_dev(h, d_seq, d_umask, b_codes, b_lab, U, nl, L, &lf);
     else rc = train_fb_dev(h, b_codes, b_seq, b_mask, b_lab, B, L, &lf);
     const auto tb = clk::now();
-    double loss = h->last_loss;
+    double loss = dfm ? ld : h->last_loss;
     if (W > 1) {
       // one small all-reduce carries the ranks' status and their losses: a rank whose forward/backward failed tells the others BEFORE
       // anybody enters the gradient exchange (they would wait in it forever)
@@ -318,7 +337,7 @@ static int otm_train_batch_impl(dm_ctx *h, const int32_t *seq_codes, int64_t U, 
       loss = sl[1] / W;                             // totalLoss.sum / miniBatches.length (:130)
     } else if (rc != DM_OK) return rc;
     const auto tc2 = clk::now();
-    if ((rc = dm_adam_step(h, 1.0f / (float)W)) != DM_OK) return rc;
+    if ((rc = dfm ? dm_deepfm_adam_step(h, 1.0f) : dm_adam_step(h, 1.0f / (float)W)) != DM_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const auto td = clk::now();
     level_losses[it] = loss;
@@ -334,7 +353,7 @@ int dm_otm_train_batch(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L
                        const dm_otm_train_opts *opts, double *level_losses, int *n_levels) {
   if (!h) return DM_ERR_INVALID;
   int agreed = 0, total = 1, rc;
-  try { rc = otm_train_batch_impl(h, seq_codes, U, L, target_off, target_nodes, opts, level_losses, n_levels, &agreed, &total); }
+  try { rc = otm_train_batch_impl(h, false, seq_codes, U, L, target_off, target_nodes, opts, level_losses, n_levels, &agreed, &total); }
   catch (const std::exception &e) { rc = fail(h, DM_ERR_INVALID, std::string("dm_otm_train_batch: ") + e.what()); }
   // a data-parallel worker that failed OUTSIDE a level's agreement (validation, allocation, the beam search, the Adam step) still owes its
   // peers the next one: they are waiting in it.  (agreed == -1: everybody already left at an agreement; agreed == total: the peers are done.)
@@ -345,27 +364,37 @@ int dm_otm_train_batch(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L
   return rc;
 }
 
+// the same iteration with a DeepFM model (OTMTrainDeepModel.scala:41-47 with deep_model DeepFM): needs dm_deepfm_train_init; one rank
+int dm_deepfm_otm_train_batch(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+                              const dm_otm_train_opts *opts, double *level_losses, int *n_levels) {
+  if (!h) return DM_ERR_INVALID;
+  DM_OWNER_ONLY(h, "dm_deepfm_otm_train_batch");
+  int agreed = 0, total = 1;
+  try { return otm_train_batch_impl(h, true, seq_codes, U, L, target_off, target_nodes, opts, level_losses, n_levels, &agreed, &total); }
+  catch (const std::exception &e) { return fail(h, DM_ERR_INVALID, std::string("dm_deepfm_otm_train_batch: ") + e.what()); }
+}
+
 // parity instrumentation: the target lists alone, downloaded — OTMTree.optimalPseudoTargets / normalTargets for a batch: out_nodes / out_labels [levels][NT] in the CSR of target_off,
 // out_counts [levels][U]; level index li <-> tree level start_level + 1 + li.
-int dm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
-                          const dm_otm_train_opts *o, int32_t *out_nodes, double *out_labels, int32_t *out_counts) {
-  if (!h) return DM_ERR_INVALID;
-  DM_CLONE_ENTER(h);
-  if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_otm_pseudo_targets: weights not loaded");
-  DM_DIN_ONLY(h, "dm_otm_pseudo_targets");
+static int otm_pseudo_targets_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+                                   const dm_otm_train_opts *o, int32_t *out_nodes, double *out_labels, int32_t *out_counts) {
+  const std::string who = dfm ? "dm_deepfm_otm_pseudo_targets" : "dm_otm_pseudo_targets";
+  if (!h->w_loaded) return fail(h, DM_ERR_STATE, who + ": weights not loaded");
+  if (dfm) { const int rc_ = dfm_train_check(h, who.c_str(), false); if (rc_ != DM_OK) return rc_; }
+  else DM_DIN_ONLY(h, who);
   if (!seq_codes || !target_off || !o || !out_nodes || !out_labels || !out_counts || U <= 0 || L <= 0 || L > DM_PIPE_MAXL)
-    return fail(h, DM_ERR_INVALID, "dm_otm_pseudo_targets: bad arguments");
-  int rc = otm_check(h, U, L, o->beam, o->leaf_level, "dm_otm_pseudo_targets");
+    return fail(h, DM_ERR_INVALID, who + ": bad arguments");
+  int rc = dfm ? dfm_otm_check(h, who.c_str(), U, L, o->beam, o->leaf_level, o->use_mask) : otm_check(h, U, L, o->beam, o->leaf_level, who.c_str());
   if (rc != DM_OK) return rc;
   int start, start_level;
   level_start_int(o->beam, &start, &start_level);
   const int levels = o->leaf_level - start_level;
-  if (levels < 1 || target_off[0] != 0) return fail(h, DM_ERR_INVALID, "dm_otm_pseudo_targets: bad levels / target_off");
+  if (levels < 1 || target_off[0] != 0) return fail(h, DM_ERR_INVALID, who + ": bad levels / target_off");
   const int64_t NT = target_off[U];
   for (int64_t i = 0; i < NT; i++)
-    if (target_nodes[i] < 1 || target_nodes[i] >= h->num_index) return fail(h, DM_ERR_INDEX, "dm_otm_pseudo_targets: target outside the embedding table");
+    if (target_nodes[i] < 1 || target_nodes[i] >= h->num_index) return fail(h, DM_ERR_INDEX, who + ": target outside the embedding table");
   for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_otm_pseudo_targets: history code outside the embedding table");
+    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, who + ": history code outside the embedding table");
   HIPCHK(h, hipSetDevice(h->device));
   const OtmTgtArena ar = otm_tgt_arena(U, L, NT, levels);
   char *A = nullptr;
@@ -379,7 +408,21 @@ int dm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, in
   return DM_OK;
 }
 
-// what the last dm_otm_train_batch on this handle did: out6 = users, levels, rows of the pseudo-target forwards, rows trained,
+int dm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+                          const dm_otm_train_opts *o, int32_t *out_nodes, double *out_labels, int32_t *out_counts) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  return otm_pseudo_targets_impl(h, false, seq_codes, U, L, target_off, target_nodes, o, out_nodes, out_labels, out_counts);
+}
+// with a DeepFM model: no forward runs (otm_targets_dev says why); every label of target_mode 0 is clip(sum of child labels, 0, 1)
+int dm_deepfm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+                                 const dm_otm_train_opts *o, int32_t *out_nodes, double *out_labels, int32_t *out_counts) {
+  if (!h) return DM_ERR_INVALID;
+  DM_CLONE_ENTER(h);
+  return otm_pseudo_targets_impl(h, true, seq_codes, U, L, target_off, target_nodes, o, out_nodes, out_labels, out_counts);
+}
+
+// what the last dm_otm_train_batch / dm_deepfm_otm_train_batch on this handle did: out6 = users, levels, rows of the pseudo-target forwards, rows trained,
 // 0, 0; secs5 = pseudo targets, beam search (fixed weights), forward / backward (incl. the batch kernel), exchange, Adam
 int dm_otm_train_stats(dm_handle_t h, uint64_t *out6, double *secs5) {
   if (!h || !out6 || !secs5) return DM_ERR_INVALID;

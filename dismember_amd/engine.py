@@ -360,8 +360,8 @@ class Engine:
             ids = np.empty((U, 2 * beam), np.int32)
             sc = np.empty((U, 2 * beam), np.float32)
             cnt = np.empty(U, np.int32)
-        self._chk(N.lib().dm_otm_beam_search(self._h, _p(seq, N.i32p), U, L, int(beam), int(leaf_level), _p(ids, N.i32p),
-                                             _p(sc, N.f32p), _p(cnt, N.i32p)))
+        fn = N.lib().dm_deepfm_otm_beam_search if self.scorer == "deepfm" else N.lib().dm_otm_beam_search      # (the DeepFM twin: DESIGN.md §15)
+        self._chk(fn(self._h, _p(seq, N.i32p), U, L, int(beam), int(leaf_level), _p(ids, N.i32p), _p(sc, N.f32p), _p(cnt, N.i32p)))
         return ids, sc, cnt
 
     def otm_beam_search_f64(self, seq_codes, beam, leaf_level, trace_levels=None):
@@ -389,7 +389,8 @@ class Engine:
         return ids, sc, cnt, tc, ts, tn
 
     def otm_beam_search_trace(self, seq_codes, beam, leaf_level, trace_levels):
-        """dm_otm_beam_search_trace (float scores; arithmetic per the scorer mode): (ids, scores, counts, tc, ts, tn)."""
+        """dm_otm_beam_search_trace (float scores; arithmetic per the scorer mode; a DeepFM model: dm_deepfm_otm_beam_search_trace):
+        (ids, scores, counts, tc, ts, tn)."""
         seq = _i32(seq_codes)
         if seq.ndim == 1:
             seq = seq[None, :]
@@ -398,9 +399,9 @@ class Engine:
         ids = np.empty((U, 2 * beam), np.int32); sc = np.empty((U, 2 * beam), np.float32); cnt = np.empty(U, np.int32)
         tc = np.zeros((U, trace_levels, cap), np.int32); ts = np.zeros((U, trace_levels, cap), np.float32)
         tn = np.zeros((U, trace_levels), np.int32)
-        self._chk(N.lib().dm_otm_beam_search_trace(self._h, _p(seq, N.i32p), U, L, int(beam), int(leaf_level), _p(ids, N.i32p),
-                                                   _p(sc, N.f32p), _p(cnt, N.i32p), int(trace_levels), _p(tc, N.i32p),
-                                                   _p(ts, N.f32p), _p(tn, N.i32p)))
+        fn = N.lib().dm_deepfm_otm_beam_search_trace if self.scorer == "deepfm" else N.lib().dm_otm_beam_search_trace
+        self._chk(fn(self._h, _p(seq, N.i32p), U, L, int(beam), int(leaf_level), _p(ids, N.i32p), _p(sc, N.f32p), _p(cnt, N.i32p),
+                     int(trace_levels), _p(tc, N.i32p), _p(ts, N.f32p), _p(tn, N.i32p)))
         return ids, sc, cnt, tc, ts, tn
 
     def tdm_bruteforce_topk(self, seq_item_ids, topk, use_mask=True):
@@ -964,7 +965,8 @@ class Engine:
                                                  d_counts))
 
     def otm_beam_search_dev(self, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts):
-        self._chk(N.lib().dm_otm_beam_search_dev(self._h, d_seq, U, L, int(beam), int(leaf_level), d_ids, d_scores, d_counts))
+        fn = N.lib().dm_deepfm_otm_beam_search_dev if self.scorer == "deepfm" else N.lib().dm_otm_beam_search_dev
+        self._chk(fn(self._h, d_seq, U, L, int(beam), int(leaf_level), d_ids, d_scores, d_counts))
 
     def synchronize(self):
         self._chk(N.lib().dm_synchronize(self._h))
@@ -996,7 +998,7 @@ class Engine:
         the users the one-wave beam kernel deferred; under DM_DR_TIME_LAUNCHES=1 the sliced Deep-Retrieval search's launches, per
         layer d: 11 = layer 0, 10 + 2d = statistics, 11 + 2d = cut, 21 + 2d = the block version's second pass; 30 = general rows
         (din_forward); 40 / 41 = DeepFM user / level launches, 42 / 43 = the DeepFM pair scorer's per-history set-up / per-pair launches
-        (JTM tree learning), and 40 .. 44 the launches of the grouped fp64 training step; under
+        (JTM tree learning), 42 also the fused OTM beam search of a DeepFM model, and 40 .. 44 the launches of the grouped fp64 training step; under
         DM_DR_TIME_LAUNCHES=1 the Deep-Retrieval training step: 50 = forward GEMMs, 51 = softmax + cross-entropy, 52 = dX products,
         53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam; and the M-step's path scores:
         80 = pairs of a chunk, 81 = the (item, path) sort, 82 = segment heads, 83 = segment sums, 84 = sort by score, 85 = sort by item,

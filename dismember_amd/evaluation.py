@@ -155,7 +155,7 @@ def evaluate_otm(engine, sequences, labels, users, user_consumed, all_node_ids, 
     seqs = np.ascontiguousarray(sequences, np.int32)
     N = seqs.shape[0]
     if f64 is None:
-        f64 = engine.scorer_mode()["mode"] == "f64"
+        f64 = engine.scorer != "deepfm" and engine.scorer_mode()["mode"] == "f64"      # (a DeepFM model has one arithmetic, fp32: no scorer mode)
     allowed = all_node_ids if isinstance(all_node_ids, (set, frozenset)) else set(np.asarray(all_node_ids).tolist())
     batch = max(1, total_eval_batch_size // (beam_size * 2))
     total_loss, total = 0.0, OtmEvalResult()

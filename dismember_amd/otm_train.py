@@ -6,7 +6,9 @@ MiniBatch.batchTransform (otm/.../dataset/MiniBatch.scala:17-40).  Pseudo target
 offsets of computeTargets — a reference quirk, OTMTree.scala:115-128 — and clip(sum of children)), the beam nodes and the
 per-level label join all run on the device inside the library (csrc/otm_train.hip.inc); this class only flattens the batch.
 The arithmetic follows the loaded model: an f64 model (the reference's DIN[Double]) is searched by the fp64 beam kernel and
-trained by the fp64 kernels with fp64 Adam state; an f32 model runs the throughput kernels.
+trained by the fp64 kernels with fp64 Adam state; an f32 model runs the throughput kernels.  A DeepFM engine (`deep_model DeepFM`,
+examples/.../otm/OTMTrainDeepModel.scala:41-47) goes through the dm_deepfm_otm_* twins: no mask, the fused beam kernel, the DeepFM
+row step per level, one rank.
 """
 import ctypes as C
 
@@ -27,6 +29,12 @@ class OTMTrainer:
         self.e, self.leaf_level, self.beam, self.L = engine, int(leaf_level), int(beam), int(seq_len)
         self.start_level = lower_log2(beam)
         self.comm = comm
+        self.deepfm = engine.scorer == "deepfm"
+        if self.deepfm:
+            if comm is not None:
+                raise ValueError("OTMTrainer: a DeepFM model trains on one rank (the gradient exchange for DeepFM is not built)")
+            engine.deepfm_train_init(lr=lr)
+            return
         engine.train_init(lr=lr)
         if comm is not None:
             engine.attach_comm(comm)
@@ -34,6 +42,8 @@ class OTMTrainer:
     # ---- model evaluations
     def _forward(self, nodes, row_seqs):
         seqs = _i32(row_seqs).reshape(-1, self.L)
+        if self.deepfm:
+            return self.e.deepfm_forward(_i32(nodes), seqs)
         pad = np.flatnonzero(seqs.reshape(-1) == -1).astype(np.int32)
         return self.e.din_forward(_i32(nodes), seqs, pad)
 
@@ -43,7 +53,9 @@ class OTMTrainer:
         U = seqs.shape[0]
         levels = self.leaf_level - self.start_level
         cap = max(32, ((2 * self.beam + 15) // 16) * 16)
-        if self.e.dtype == np.float64 and self.e.scorer_mode()["mode"] == "f64":
+        if self.deepfm:
+            _, _, _, tc, ts, tn = self.e.otm_beam_search_trace(seqs, self.beam, self.leaf_level, levels)
+        elif self.e.dtype == np.float64 and self.e.scorer_mode()["mode"] == "f64":
             _, _, _, tc, ts, tn = self.e.otm_beam_search_f64(seqs, self.beam, self.leaf_level, trace_levels=levels)
         else:
             ids = np.empty((U, 2 * self.beam), np.int32); sc = np.empty((U, 2 * self.beam), np.float32); cnt = np.empty(U, np.int32)
@@ -62,7 +74,7 @@ class OTMTrainer:
         return seqs, off, flat
 
     def _opts(self, target_mode):
-        return N.OtmTrainOpts(self.beam, self.leaf_level, 1, {"pseudo": 0, "normal": 1}[target_mode])
+        return N.OtmTrainOpts(self.beam, self.leaf_level, 0 if self.deepfm else 1, {"pseudo": 0, "normal": 1}[target_mode])
 
     def optimal_pseudo_targets(self, target_nodes, seqs, target_mode="pseudo"):
         """OTMTree.optimalPseudoTargets (or normalTargets) on the device (dm_otm_pseudo_targets): list over the levels
@@ -71,8 +83,9 @@ class OTMTrainer:
         U, levels, NT = seqs.shape[0], self.leaf_level - self.start_level, max(int(off[-1]), 1)
         nodes = np.empty((levels, NT), np.int32); labels = np.empty((levels, NT), np.float64); counts = np.empty((levels, U), np.int32)
         opts = self._opts(target_mode)
-        self.e._chk(N.lib().dm_otm_pseudo_targets(self.e._h, _p(seqs, N.i32p), U, self.L, _p(off, N.i64p), _p(flat, N.i32p), C.byref(opts),
-                                                  _p(nodes, N.i32p), labels.ctypes.data_as(C.POINTER(C.c_double)), _p(counts, N.i32p)))
+        fn = N.lib().dm_deepfm_otm_pseudo_targets if self.deepfm else N.lib().dm_otm_pseudo_targets
+        self.e._chk(fn(self.e._h, _p(seqs, N.i32p), U, self.L, _p(off, N.i64p), _p(flat, N.i32p), C.byref(opts),
+                       _p(nodes, N.i32p), labels.ctypes.data_as(C.POINTER(C.c_double)), _p(counts, N.i32p)))
         out = []
         for lv in range(levels):
             per = []
@@ -94,8 +107,8 @@ class OTMTrainer:
         losses = (C.c_double * levels)()
         nl = C.c_int(0)
         opts = self._opts(target_mode)
-        self.e._chk(N.lib().dm_otm_train_batch(self.e._h, _p(seqs, N.i32p), seqs.shape[0], self.L, _p(off, N.i64p), _p(flat, N.i32p),
-                                               C.byref(opts), losses, C.byref(nl)))
+        fn = N.lib().dm_deepfm_otm_train_batch if self.deepfm else N.lib().dm_otm_train_batch
+        self.e._chk(fn(self.e._h, _p(seqs, N.i32p), seqs.shape[0], self.L, _p(off, N.i64p), _p(flat, N.i32p), C.byref(opts), losses, C.byref(nl)))
         return [float(losses[i]) for i in range(nl.value)]
 
     def last_stats(self):

@@ -8,9 +8,9 @@
 Each function is the body of the reference's `CommandApp` of the same name (examples/src/main/scala/com/mass/retrieval/):
 the conf file is read by dismember_amd.conf (same keys, same defaults, same "failed to find <key>" stop), the steps are the
 reference's, and every hot step is a library call — tree index + scorer weights in HBM, level-wise negative sampling, forward /
-backward / Adam, the batched evaluator, `JTM.optimize` in one call.  `deep_model` selects DIN or, for TDM, DeepFM (trained through
-`dm_deepfm_train_*`; OTM's `DeepFM[Double]` is not built).  What is NOT carried over: Java serialisation (the model file is
-`dm_save_model`'s flat checkpoint), HDFS paths and spectral clustering in `TDMClusterTree`.
+backward / Adam, the batched evaluator, `JTM.optimize` in one call.  `deep_model` selects DIN or DeepFM: TDM trains DeepFM through
+`dm_deepfm_train_*`, OTMTrainDeepModel through `dm_deepfm_otm_*` (fp32; OTMConstructTree with DeepFM is not built).  What is NOT
+carried over: Java serialisation (the model file is `dm_save_model`'s flat checkpoint), HDFS paths and spectral clustering in `TDMClusterTree`.
 
   tdm_initialize_tree   tdm/TDMInitializeTree.scala:14-48  -> TreeInit.generate (tdm/.../tree/TreeInit.scala:33-66)
   tdm_cluster_tree      tdm/TDMClusterTree.scala           -> RecursiveCluster.run on the device (dismember_amd/cluster.py; also
@@ -231,7 +231,8 @@ def _otm_sample(path):
 
 
 def otm_train_deep_model(conf_path, quiet=True, engine=None, max_iterations=None, time_recommend=True):
-    """OTMTrainDeepModel (examples/.../otm/OTMTrainDeepModel.scala:20-75): data set + mapping (LocalDataSet), DIN[Double] over the
+    """OTMTrainDeepModel (examples/.../otm/OTMTrainDeepModel.scala:20-75): data set + mapping (LocalDataSet), DIN[Double] (or, with
+    `deep_model DeepFM`, the DeepFM graph in fp32 through the dm_deepfm_otm_* entry points: DESIGN.md §15) over the
     complete tree of upperLog2(#items) levels, LocalOptimizer.optimize (otm/.../optim/LocalOptimizer.scala:55-110: per epoch a shuffle,
     batches of train_batch_size users, ONE library call per batch = pseudo targets + beam nodes + a gradient step per level), the
     evaluator at the progress interval and at the end of every epoch, OTM.saveModel (model checkpoint + `item node` mapping lines).
@@ -241,8 +242,8 @@ def otm_train_deep_model(conf_path, quiet=True, engine=None, max_iterations=None
     from .facade import OTM
     from .otm_train import OTMTrainer
     p = C.task_params("OTMTrainDeepModel", conf_path)
-    if p["deep_model"] != "din":
-        raise ValueError("DeepModel name should either be DeepFM or DIN (DeepFM is out of scope of this build)")
+    if p["deep_model"] not in ("din", "deepfm"):
+        raise ValueError("DeepModel name should either be DeepFM or DIN")
     if p["train_batch_size"] < p["thread_number"]:
         raise ValueError("requirement failed: train_batch_size >= thread_number")
     if not quiet:
@@ -258,7 +259,10 @@ def otm_train_deep_model(conf_path, quiet=True, engine=None, max_iterations=None
     leaf_level = od.upper_log2(len(mapping))
     ni = (1 << (leaf_level + 1)) - 1                                   # dataset.numTreeNode
     eng = engine or Engine(0)
-    eng.load_weights_din(_din_init(E, ni, p["seed"], dtype=np.float64), E, ni)
+    if p["deep_model"] == "deepfm":                                    # DeepFM.buildModel (otm/.../model/DeepFM.scala:10-49); f32, checkpoint kind 1
+        eng.load_weights_deepfm(_deepfm_init(E, L, ni, p["seed"]), E, L, ni)
+    else:
+        eng.load_weights_din(_din_init(E, ni, p["seed"], dtype=np.float64), E, ni)
     tr = OTMTrainer(eng, leaf_level=leaf_level, beam=beam, seq_len=L, lr=p["learning_rate"])
     allowed = ev.all_nodes(list(mapping.values()))
     tseq = np.array([t[0] for t in train], np.int32)
@@ -330,6 +334,8 @@ def otm_construct_tree(conf_path, quiet=True, engine=None):
         print("\n".join("%s: %s" % kv for kv in sorted(p.items())))
     eng = engine or Engine(0)
     eng.load_model(p["model_path"])
+    if eng.scorer == "deepfm":
+        raise ValueError("OTMConstructTree with a DeepFM model: the child-weight twin of dm_otm_child_weights is not built (DESIGN.md §15)")
     mapping = od.load_mapping(p["mapping_path"])
     sample = _otm_sample(p["data_path"])
     seqs = od.item_sequences(sample, mapping, p["label_num"], p["min_seq_len"], p["seq_len"], p["split_ratio"])

@@ -110,8 +110,8 @@ int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, cons
  * otherwise); dm_get_leaf_embeddings, dm_cluster_tree_model, dm_save_model / dm_load_model work as for DIN; every entry point that
  * evaluates DIN (dm_din_forward, dm_otm_*, dm_tdm_bruteforce_topk, dm_jtm_*, dm_train_*, dm_adam_step, dm_tdm_make_train_batch,
  * dm_tdm_sample_train_batch_dev, dm_set_scorer_mode) returns DM_ERR_UNSUPPORTED and leaves the handle usable (training and its
- * sampler have DeepFM entry points of their own, below, and so has JTM's scoring: dm_deepfm_jtm_*; OTM tree learning with DeepFM
- * stays refused — the reference's is a DeepFM[Double]). */
+ * sampler have DeepFM entry points of their own, below, and so has JTM's scoring: dm_deepfm_jtm_*; OTM's beam search and training
+ * iteration: dm_deepfm_otm_*, below; OTMConstructTree's child weights with DeepFM stay refused). */
 enum { DM_KIND_DIN = 0, DM_KIND_DEEPFM = 1 };
 int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_index, const void *compact, int64_t n_elems);
 int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len);
@@ -419,6 +419,40 @@ int dm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, in
 /* measurement — the last dm_otm_train_batch on this handle: out6 = users, levels, rows of the pseudo-target forwards, rows trained, 0, 0;
  * secs5 = pseudo targets, beam search, forward / backward, gradient exchange, Adam (seconds) */
 int dm_otm_train_stats(dm_handle_t h, uint64_t *out6, double *secs5);
+
+/* ---- OTM with the DeepFM scorer (examples/.../otm/OTMTrainDeepModel.scala:41-47 builds O/model/DeepFM.scala:10-49; fp32 like the loader,
+ * where the reference runs DeepFM[Double]; the contract is the one dm_otm_beam_search states for f32 models).  The dm_otm_* entry points keep
+ * refusing a DeepFM handle (DM_ERR_UNSUPPORTED); these are their twins.
+ * All of them: DM_ERR_STATE on a DIN model; L must be the model's seq_len (DM_ERR_INVALID); beam <= 512 (DM_ERR_UNSUPPORTED above: the
+ * prune sorts in LDS); there is no mask (O/model/OTM.scala:14-22,32,58: useMask = false) — opts->use_mask must be 0 (DM_ERR_INVALID).
+ *
+ * dm_deepfm_otm_beam_search         OTM.recommend's search: CandidateSearcher.beamSearch (O/model/CandidateSearcher.scala:58-80, buildBeamNodes
+ *                                   :109-122) as ONE kernel, one workgroup per user; arguments, outputs and DM_ERR_INDEX as dm_otm_beam_search
+ * dm_deepfm_otm_beam_search_trace   + every level's candidates (OTMTree.beamSearchNodes, O/tree/OTMTree.scala:67-91,174-212); layouts of
+ *                                   dm_otm_beam_search_trace (cap = 2 beam rounded up to 16, at least 32)
+ * dm_deepfm_otm_beam_search_dev     device-resident request, as dm_otm_beam_search_dev (codes outside the table count as padding)
+ * Two runs, any batch mates and any grid give the same bytes; dm_clone clones serve them. */
+int dm_deepfm_otm_beam_search(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, int beam, int leaf_level,
+                              int32_t *out_node_ids, float *out_scores, int32_t *out_counts);
+int dm_deepfm_otm_beam_search_trace(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, int beam, int leaf_level,
+                                    int32_t *out_node_ids, float *out_scores, int32_t *out_counts, int max_levels,
+                                    int32_t *trace_codes, float *trace_scores, int32_t *trace_counts);
+int dm_deepfm_otm_beam_search_dev(dm_handle_t h, const int32_t *d_seq_codes, int64_t U, int L, int beam, int leaf_level,
+                                  int32_t *d_out_node_ids, float *d_out_scores, int32_t *d_out_counts);
+/* OTMTree.optimalPseudoTargets (O/tree/OTMTree.scala:27-46) / normalTargets (:50-63), arguments and outputs of dm_otm_pseudo_targets.
+ * Without a mask computeChildrenScores feeds the sibling tensor to both forwards (:156-161), so posPreds(i) >= negPreds(i) compares a
+ * value with itself and every node keeps its own label: no forward is run, and target_mode 0 gives, per level, the targets' ancestors in
+ * first-appearance order with clip(sum of child labels, 0, 1).  (The reference differs only where a logit is NaN.) */
+int dm_deepfm_otm_pseudo_targets(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+                                 const dm_otm_train_opts *opts, int32_t *out_nodes, double *out_labels, int32_t *out_counts);
+/* LocalOptimizer.optimize's body for one batch (O/optim/LocalOptimizer.scala:55-109), arguments of dm_otm_train_batch: the targets as
+ * above, the beam nodes from ONE fused traced search with the weights fixed, then per level MiniBatch.batchTransform -> the DeepFM row
+ * step (dm_deepfm_train_forward_backward_dev) -> dm_deepfm_adam_step with grad_scale 1.  Needs dm_deepfm_train_init (DM_ERR_STATE);
+ * owner only; a communicator with more than one rank is DM_ERR_UNSUPPORTED (the gradient exchange for DeepFM is not built), and so is a
+ * batch whose U * 2 beam rows exceed the row step's limits (4 194 240 rows, rows (L + 1) < 2^31).  dm_otm_train_stats reads the same
+ * block (rows of the pseudo-target forwards: 0). */
+int dm_deepfm_otm_train_batch(dm_handle_t h, const int32_t *seq_codes, int64_t U, int L, const int64_t *target_off, const int32_t *target_nodes,
+                              const dm_otm_train_opts *opts, double *level_losses, int *n_levels);
 
 /* Level-wise negative sampling + batch expansion, ON THE DEVICE: NegativeSampler.sample
  * (tdm/.../utils/NegativeSampler.scala:76-158: uniform and sample_with_probability modes) + MiniBatch.convert
