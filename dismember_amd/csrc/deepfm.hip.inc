@@ -17,12 +17,21 @@
 // since |e + s|^2 - |e|^2 - sum |k_j|^2 = 2 e.s + |s|^2 - sum |k_j|^2.  A level of the search is therefore ONE product per user,
 // [children x E] . [E x (T + 1)]: column 0 is the user's s, columns 1 .. T are W1a (shared by all users), padded to 16 / 32 / 48.
 //
+// Every kernel that evaluates this form calls the same device functions, defined here once:
+//   dfm_user_setup         (s, c, a) of one user by one workgroup of 1, 2 or 4 waves: dfm_user_kernel, dfm_otm_beam_kernel (dfm_otm.hip.inc)
+//   dfm_stage_frag         W1a's B fragments (and w2p) into LDS, once per workgroup; dfm_frag_bytes: their size, in HBM and in LDS
+//   dfm_tile_gather        16 node rows HBM -> VGPR in A-fragment layout
+//   dfm_tile_score         the product, the epilogue and the row sums of a 16-row tile: dfm_level_kernel, dfm_otm_beam_kernel
+// (dfm_jtm_pairs_kernel, dfm_jtm.hip.inc, shares the staging and the gather and restates the product: see there)
+// so a (row, user) pair gets the same bytes from each of them (tests/test_gpu_deepfm_shared_tile.py).
+//
 // Summation orders (fixed; no atomics on floats; two runs give the same bits):
 //   s[e], sum_j k_j[e]^2   history order j = 0 .. L-1, one thread per feature
 //   c                      d[e] = s[e]^2 - sum_j k_j[e]^2 per feature (the cancellation happens per feature, on small numbers), then the
-//                          xor-shuffle tree over the 64 lanes of each wave and wave 0 + wave 1
+//                          xor-shuffle tree over the 64 lanes: features 0 .. 63 and 64 .. 127 each through one wave-sum, whichever wave
+//                          executes it; c = 0.5 (red0 + red1) + b2
 //   a[t]                   lane-strided partial sums over vec(K) in index order, then the xor-shuffle tree
-//   level kernel           v_mfma_f32_16x16x4_f32 over k = 0 .. Ep-1 in steps of 4 (exact fp32 fma chain per output), the epilogue per column,
+//   tile score             v_mfma_f32_16x16x4_f32 over k = 0 .. Ep-1 in steps of 4 (exact fp32 fma chain per output), the epilogue per column,
 //                          column tiles added in order, then the xor-shuffle tree over the 16 lanes that hold a row's columns
 
 #define DFM_MAXL 32
@@ -58,7 +67,47 @@ __global__ void dfm_jtm_derive_kernel(const float *l1_w, int E, int L, int NCT, 
   }
 }
 
-// ---- per user: s [U][E], aux [U][NC]: aux[0] = c, aux[n] = a[n - 1] for n = 1 .. T, 0 beyond.  One workgroup of 256 per user.
+// ---- per user: s [E], aux [NC]: aux[0] = c, aux[n] = a[n - 1] for n = 1 .. T, 0 beyond.  Called by every thread of a workgroup of nthr = 64,
+// 128 or 256 threads for ONE user's L history codes (-1 or outside the table = a zero row).  K: LDS, L E floats, written before the first
+// of the two barriers in here and read between them: dead only after the second, so between(), which runs just before it, must not
+// touch K (the OTM kernel fills its frontier there and lets its sort overlap K afterwards).  S, aux, red (2 floats): global or LDS, the
+// caller's choice; c is written after the second barrier.  No sum's order depends on nthr.
+template <typename F>
+__device__ __forceinline__ void dfm_user_setup(const float *emb, const float *l1_w, const float *l1_b, float b2, int64_t num_index, int E, int L, int NC,
+                                               const int32_t *kcode, float *K, int nthr, float *S, float *aux, float *red, F between) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
+  const int T = L + 1, n = L * E;
+  for (int i = tid; i < n; i += nthr) {
+    const int32_t c = kcode[i / E];
+    K[i] = (c >= 0 && c < num_index) ? emb[(int64_t)c * E + i % E] : 0.0f;
+  }
+  __syncthreads();
+  for (int hf = wave; hf < 2; hf += nw) {      // features 0 .. 63, 64 .. 127 (E <= 128)
+    const int e = 64 * hf + lane;
+    float d = 0.0f;
+    if (e < E) {
+      float s = 0.0f, q = 0.0f;
+      for (int j = 0; j < L; j++) { const float v = K[j * E + e]; s += v; q = fmaf(v, v, q); }
+      S[e] = s;
+      d = fmaf(s, s, -q);
+    }
+    d = dm_wave_sum(d);
+    if (lane == 0) red[hf] = d;
+  }
+  for (int t = wave; t < T; t += nw) {
+    const float *w = l1_w + (int64_t)t * T * E + E;      // W1s[t]: the L history blocks of row t
+    float part = 0.0f;
+    for (int i = lane; i < n; i += 64) part = fmaf(w[i], K[i], part);
+    part = dm_wave_sum(part);
+    if (lane == 0) aux[1 + t] = part + l1_b[t];
+  }
+  for (int i = T + 1 + tid; i < NC; i += nthr) aux[i] = 0.0f;
+  between();
+  __syncthreads();
+  if (tid == 0) aux[0] = 0.5f * (red[0] + red[1]) + b2;
+}
+
+// One workgroup of 256 per user: S [U][E], aux [U][NC].
 struct DfmUser {
   const float *emb, *l1_w, *l1_b;      // l1_w [T][T E]
   float b2;
@@ -72,42 +121,77 @@ __global__ __launch_bounds__(256) void dfm_user_kernel(DfmUser p) {
   __shared__ float K[DFM_MAXL * 128];
   __shared__ float red[2];
   const int64_t u = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int E = p.E, L = p.L, T = L + 1, n = L * E;
-  for (int i = tid; i < n; i += 256) {
-    const int32_t c = p.kcode[u * L + i / E];
-    K[i] = (c >= 0 && c < p.num_index) ? p.emb[(int64_t)c * E + i % E] : 0.0f;
-  }
-  __syncthreads();
-  if (tid < 128) {                     // E <= 128: waves 0 and 1
-    float d = 0.0f;
-    if (tid < E) {
-      float s = 0.0f, q = 0.0f;
-      for (int j = 0; j < L; j++) { const float v = K[j * E + tid]; s += v; q = fmaf(v, v, q); }
-      p.S[u * E + tid] = s;
-      d = fmaf(s, s, -q);
-    }
-    d = dm_wave_sum(d);
-    if (lane == 0) red[wave] = d;
-  }
-  for (int t = wave; t < T; t += 4) {
-    const float *w = p.l1_w + (int64_t)t * T * E + E;      // W1s[t]: the L history blocks of row t
-    float part = 0.0f;
-    for (int i = lane; i < n; i += 64) part = fmaf(w[i], K[i], part);
-    part = dm_wave_sum(part);
-    if (lane == 0) p.aux[u * p.NC + 1 + t] = part + p.l1_b[t];
-  }
-  for (int i = T + 1 + tid; i < p.NC; i += 256) p.aux[u * p.NC + i] = 0.0f;
-  __syncthreads();
-  if (tid == 0) p.aux[u * p.NC] = 0.5f * (red[0] + red[1]) + p.b2;
+  dfm_user_setup(p.emb, p.l1_w, p.l1_b, p.b2, p.num_index, p.E, p.L, p.NC, p.kcode + u * p.L, K, 256, p.S + u * p.E, p.aux + u * p.NC, red, [] {});
 }
 
-// ---- one level: sc[u][row] for the rows < counts[u] of cur[u][stride].  One wave per (user, 16-row tile); the children's rows go
-// HBM -> VGPR straight into A-fragment layout (lane (g, r): row r, features 16 jc + 4 g .. + 3 as one float4 per jc: k-step (jc, t) of
-// the MFMA takes feature 16 jc + 4 g + t from lane group g — the B fragments above follow the same map); W1a's fragments are staged once
-// per workgroup in LDS (NCT E 64 bytes: 24 KB at E = 128, L = 32) and read back as one conflict-free ds_read_b128 per lane and (ct, jc);
-// column 0 of tile 0 is the user's s, held by the lanes r = 0.
+// ---- the 16-row tile.  One wave scores 16 rows against [s ; W1a] (T + 1 columns, padded to NCT tiles of 16).  The rows go HBM -> VGPR
+// straight into A-fragment layout (lane (g, r): row r, features 16 jc + 4 g .. + 3 as one float4 per jc: k-step (jc, t) of the MFMA takes
+// feature 16 jc + 4 g + t from lane group g — the B fragments above follow the same map); W1a's fragments are staged once per workgroup
+// in LDS (NCT E 64 bytes: 24 KB at E = 128, L = 32) and read back as one conflict-free ds_read_b128 per lane and (ct, jc).
 // C layout: lane (g, r) holds rows 4 g .. 4 g + 3 of column 16 ct + r.
+static size_t dfm_frag_bytes(int E, int NCT) { return (size_t)NCT * E * 64; }
+
+// frag [NCT][E / 16][64] -> wl, and w2p [NCT * 16] -> w2l where the caller keeps it in LDS (else null); the caller's barrier follows
+template <int E, int NCT>
+__device__ __forceinline__ void dfm_stage_frag(const f32x4 *frag, f32x4 *wl, const float *w2p, float *w2l, int nthr) {
+  for (int i = threadIdx.x; i < NCT * (E / 16) * 64; i += nthr) wl[i] = frag[i];
+  if (w2l)
+    for (int i = threadIdx.x; i < NCT * 16; i += nthr) w2l[i] = w2p[i];
+}
+
+// row `code` of the table for lane (g, .); a code < 0 or >= num_index is a zero row.  next(jc, row) runs behind the load of qa[jc], row =
+// "not a zero row": what a caller reads per feature block beside the row (the level kernel's s, the pair kernel's e.s) keeps its place
+// between the gathers.
+struct DfmNothing { __device__ __forceinline__ void operator()(int, bool) const {} };
+
+template <int E, typename F = DfmNothing>
+__device__ __forceinline__ void dfm_tile_gather(const float *emb, int32_t code, int64_t num_index, int g, f32x4 (&qa)[E / 16], F next = F{}) {
+  if (code >= num_index) code = -1;
+#pragma unroll
+  for (int jc = 0; jc < E / 16; jc++) {
+    qa[jc] = code >= 0 ? *(const f32x4 *)(emb + (int64_t)code * E + 16 * jc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    next(jc, code >= 0);
+  }
+}
+
+// tot[rr] = sum over the columns of  col == 0 ? x : w2[col] relu(x),  x = (row . column) + aux(rr, col),  for rows 4 g + rr of the tile, in
+// every lane (g, .).  b0(jc, staged) is the B fragment of column tile 0: *staged (DfmStagedB0) where column 0 is W1a's zero column, and
+// with the lanes r = 0 holding the user's s (features 16 jc + 4 g ..) where it is the user's.  aux(rr, col): aux[user of row 4 g + rr][col].
+struct DfmStagedB0 { __device__ __forceinline__ f32x4 operator()(int, const f32x4 *staged) const { return *staged; } };
+
+template <int E, int NCT, typename B0, typename Aux>
+__device__ __forceinline__ void dfm_tile_score(const f32x4 (&qa)[E / 16], const f32x4 *wl, const float *w2, int lane, B0 b0, Aux aux, float (&tot)[4]) {
+  constexpr int NJ = E / 16;
+  const int r = lane & 15;
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++) tot[rr] = 0.0f;
+#pragma unroll
+  for (int ct = 0; ct < NCT; ct++) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int jc = 0; jc < NJ; jc++) {
+      const f32x4 *staged = wl + (ct * NJ + jc) * 64 + lane;
+      const f32x4 b = ct == 0 ? b0(jc, staged) : *staged;
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[jc][t], b[t], acc, 0, 0, 0);
+    }
+    const int col = 16 * ct + r;
+    const float wv = w2[col];
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+      const float x = acc[rr] + aux(rr, col);
+      tot[rr] += col == 0 ? x : wv * fmaxf(x, 0.0f);
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) tot[rr] += __shfl_xor(tot[rr], o);
+  }
+}
+
+// ---- one level: sc[u][row] for the rows < counts[u] of cur[u][stride].  One wave per (user, 16-row tile); column 0 of tile 0 is the
+// user's s, held by the lanes r = 0.
 struct DfmLevel {
   const float *emb;
   const f32x4 *frag;                   // [NCT][E / 16][64]
@@ -124,7 +208,7 @@ __global__ __launch_bounds__(256) void dfm_level_kernel(DfmLevel p) {
   constexpr int NJ = E / 16, NC = NCT * 16;
   extern __shared__ __attribute__((aligned(16))) char smem_dfm[];
   f32x4 *wl = (f32x4 *)smem_dfm;
-  for (int i = threadIdx.x; i < NCT * NJ * 64; i += 256) wl[i] = p.frag[i];
+  dfm_stage_frag<E, NCT>(p.frag, wl, nullptr, nullptr, 256);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
   const int tpu = p.stride / 16;
@@ -134,38 +218,18 @@ __global__ __launch_bounds__(256) void dfm_level_kernel(DfmLevel p) {
     const int row0 = (int)(w % tpu) * 16;
     const int n = min(p.counts[u], p.stride);
     if (row0 >= n) continue;           // (wave-uniform) rows at or past counts[u] are neither gathered nor stored
-    int32_t code = row0 + r < n ? p.codes[u * p.stride + row0 + r] : -1;
-    if (code >= p.num_index) code = -1;
     f32x4 qa[NJ], sf[NJ];
-#pragma unroll
-    for (int jc = 0; jc < NJ; jc++) {
-      qa[jc] = code >= 0 ? *(const f32x4 *)(p.emb + (int64_t)code * E + 16 * jc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    dfm_tile_gather<E>(p.emb, row0 + r < n ? p.codes[u * p.stride + row0 + r] : -1, p.num_index, g, qa, [&](int jc, bool) {
       sf[jc] = r == 0 ? *(const f32x4 *)(p.S + u * E + 16 * jc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    float tot[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ct = 0; ct < NCT; ct++) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int jc = 0; jc < NJ; jc++) {
-        f32x4 b = wl[(ct * NJ + jc) * 64 + lane];
-        if (ct == 0) b = r == 0 ? sf[jc] : b;
-#pragma unroll
-        for (int t = 0; t < 4; t++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[jc][t], b[t], acc, 0, 0, 0);
-      }
-      const int col = 16 * ct + r;
-      const float av = p.aux[u * NC + col], wv = p.w2p[col];
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) {
-        const float x = acc[rr] + av;
-        tot[rr] += col == 0 ? x : wv * fmaxf(x, 0.0f);
-      }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) tot[rr] += __shfl_xor(tot[rr], o);
-    }
+    });
+    // (the select per component: given a whole-vector select the compiler sinks the LDS read under it, behind a branch of its own per jc,
+    // and the MFMAs wait for every read; the parent's ISA, which this form reproduces, reads ahead in pairs)
+    const auto b0 = [&](int jc, const f32x4 *staged) {
+      const f32x4 b = *staged;
+      return (f32x4){r == 0 ? sf[jc][0] : b[0], r == 0 ? sf[jc][1] : b[1], r == 0 ? sf[jc][2] : b[2], r == 0 ? sf[jc][3] : b[3]};
+    };
+    float tot[4];
+    dfm_tile_score<E, NCT>(qa, wl, p.w2p, lane, b0, [&](int, int col) { return p.aux[u * NC + col]; }, tot);
     if (r == 0) {
 #pragma unroll
       for (int rr = 0; rr < 4; rr++)
@@ -264,7 +328,7 @@ int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_i
   h->d_compact = d; h->d_emb32 = (float *)d; h->dtype = DM_F32; h->embed = Ep; h->embed_log = E; h->num_index = num_index;
   h->scorer_kind = DM_KIND_DEEPFM; h->dfm_L = L;
   const int NCT = dfm_col_tiles(L);
-  ALLOC(h, h->d_dfm_frag, (size_t)NCT * Ep * 64);
+  ALLOC(h, h->d_dfm_frag, dfm_frag_bytes(Ep, NCT));
   ALLOC(h, h->d_dfm_w2p, (size_t)NCT * 16 * 4);
   ALLOC(h, h->d_dfm_fragS, (size_t)NCT * L * Ep * 64);
   const DfmBlocks b = dfm_blocks(h);
@@ -295,30 +359,33 @@ static int dfm_download_model(dm_ctx *h, std::vector<float> &out) {
   return DM_OK;
 }
 
+// What every DeepFM entry point checks first (after the NULL check and its DM_CLONE_ENTER / DM_OWNER_ONLY): a DeepFM model is loaded, the
+// caller asks for no mask (the graph has no mask input) and *L is the model's (L == nullptr: not known yet).  The one wording of these
+// refusals.
+static int dfm_check_L(dm_ctx *h, const char *who, int L) {
+  if (L == h->dfm_L) return DM_OK;
+  return fail(h, DM_ERR_INVALID, std::string(who) + ": L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
+}
+static int dfm_enter(dm_ctx *h, const char *who, const int *L, int use_mask) {
+  if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": weights not loaded");
+  if (h->scorer_kind != DM_KIND_DEEPFM)
+    return fail(h, DM_ERR_STATE, std::string(who) + ": the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model; DIN trains through dm_train_*)");
+  if (use_mask != 0) return fail(h, DM_ERR_INVALID, std::string(who) + ": the DeepFM graph has no mask input (use_mask must be 0; OTM.scala:14-22 serves it with useMask = false)");
+  return L ? dfm_check_L(h, who, *L) : DM_OK;
+}
+
 int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, int64_t B, int L, float *logits) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
-  if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_deepfm_forward: weights not loaded");
-  if (h->scorer_kind != DM_KIND_DEEPFM) return fail(h, DM_ERR_STATE, "dm_deepfm_forward: the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model)");
+  int rc = dfm_enter(h, "dm_deepfm_forward", &L, 0);
+  if (rc != DM_OK) return rc;
   if (!codes || !seqs || !logits || B < 0) return fail(h, DM_ERR_INVALID, "dm_deepfm_forward: bad arguments");
-  if (L != h->dfm_L) return fail(h, DM_ERR_INVALID, "dm_deepfm_forward: L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
   if (B == 0) return DM_OK;
-  // LookupTable.embeddingLookup validates every index first (LookupTable.scala:29-53)
-  for (int64_t i = 0; i < B; i++)
-    if (codes[i] != -1 && (codes[i] < 0 || codes[i] >= h->num_index)) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)i, codes[i]);
-      return fail(h, DM_ERR_INDEX, b);
-    }
-  for (int64_t i = 0; i < B * L; i++)
-    if (seqs[i] != -1 && (seqs[i] < 0 || seqs[i] >= h->num_index)) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)(i / L), seqs[i]);
-      return fail(h, DM_ERR_INDEX, b);
-    }
+  if ((rc = check_lookup_ids(h, codes, B, 1, "row")) != DM_OK || (rc = check_lookup_ids(h, seqs, B * L, L, "row")) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   ReqArena ar(h);
   const size_t o_codes = ar.add((size_t)B * 4), o_seqs = ar.add((size_t)B * L * 4), o_out = ar.add((size_t)B * 4);
-  int rc = ar.commit(h);
-  if (rc != DM_OK) return rc;
+  if ((rc = ar.commit(h)) != DM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(ar.ptr<int32_t>(o_codes), codes, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(ar.ptr<int32_t>(o_seqs), seqs, (size_t)B * L * 4, hipMemcpyHostToDevice, h->stream));
   const DfmBlocks b = dfm_blocks(h);
@@ -339,7 +406,7 @@ int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, 
 // ---- the level pipeline's scorer
 template <int E, int NCT>
 static int dfm_launch_level(dm_ctx *h, const DfmLevel &p) {
-  const size_t lds = (size_t)NCT * E * 64;
+  const size_t lds = dfm_frag_bytes(E, NCT);
   const int64_t waves = p.U * (p.stride / 16);
   int64_t blocks = (waves + 3) / 4;
   if (blocks > (int64_t)h->n_cu * 4) blocks = (int64_t)h->n_cu * 4;
@@ -379,10 +446,7 @@ struct TdmPlDeepFM : TdmPlScorer {
     DfmLevel p;
     p.emb = h->d_emb32; p.frag = (const f32x4 *)h->d_dfm_frag; p.w2p = h->d_dfm_w2p; p.S = S; p.aux = aux; p.codes = cur; p.counts = ncur;
     p.sc = sc; p.stride = stride; p.U = Un; p.num_index = h->num_index;
-    return dispatch_E(h, E, "unsupported embed size", [&](auto e) {
-      constexpr int E_ = decltype(e)::value;
-      return NCT == 1 ? dfm_launch_level<E_, 1>(h, p) : NCT == 2 ? dfm_launch_level<E_, 2>(h, p) : dfm_launch_level<E_, 3>(h, p);
-    });
+    return dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_launch_level<decltype(e)::value, decltype(n)::value>(h, p); });
   }
 };
 

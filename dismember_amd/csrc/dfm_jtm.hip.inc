@@ -5,7 +5,11 @@
 //   per history (dfm_jtm_rows_kernel):  s = sum_j k_j      c = (|s|^2 - sum_j |k_j|^2) / 2 + l2.b      a = W1s vec(K) + l1.b
 //   per pair    (dfm_jtm_pairs_kernel): logit = e.s + c + sum_t l2.W[t] relu(W1a[t].e + a[t])
 // S [H][E] and aux [H][NCT 16] (aux[0] = c, aux[1 .. T] = a, 0 beyond) have dfm_user_kernel's layout.  history(pair) = pair / seq_div,
-// as in din_rows_dev.  The set-up results live for one slice of histories (DFM_JTM_SLICE), never for a catalogue.
+// as in din_rows_dev.  The pair kernel stages W1a's fragments and gathers its rows through deepfm.hip.inc (dfm_stage_frag,
+// dfm_tile_gather) and keeps a product and epilogue of its own, a restatement of dfm_tile_score's with its orders: through
+// dfm_tile_score itself the kernel measured 1.4 % slower (DESIGN.md section 15).  The per-history set-up is its own algorithm (MFMA
+// over 16 histories), not dfm_user_setup.  The set-up results live for one slice of histories
+// (DFM_JTM_SLICE), never for a catalogue.
 //
 // Summation orders (fixed; no atomics; a history's (s, c, a) depends on its L codes only and a pair's logit on its (code, history) only:
 // neither on the tile mates, nor on the position in the tile, nor on seq_div or the slicing):
@@ -16,7 +20,7 @@
 //   e.s                    fma chain over the lane's features in (jc, t) order, then xor 16, xor 32
 //   W1a[t].e               v_mfma_f32_16x16x4_f32 over k = 0 .. E-1 in steps of 4
 //   logit                  per column w2 relu(. + a) (column 0: c), column tiles added in order, the xor tree over the 16 lanes that hold a
-//                          pair's columns, + e.s last
+//                          pair's columns (dfm_tile_score's orders, deepfm.hip.inc), + e.s last
 
 #define DFM_JTM_SLICE ((int64_t)1 << 18)      // histories per set-up pass: 144 MB of s and aux at E = 128, L <= 14
 // DM_DFM_JTM_SLICE=<positive integer>: histories per set-up pass, read per call like DM_JTM_MAX_PAIRS (tests: slice edges at sizes a test
@@ -101,10 +105,8 @@ __global__ __launch_bounds__(256) void dfm_jtm_rows_kernel(DfmJtmRows p) {
   }
 }
 
-// ---- per pair: one wave per 16 consecutive pairs.  The node rows are gathered by code straight into A-fragment layout and W1a's
-// fragments are staged once per workgroup in LDS, both as in dfm_level_kernel; e.s is a VALU dot against S[history(pair)] (column 0 of
-// the product is W1a's zero column here: tile mates have different histories); the epilogue reads aux[history(row)][column] per C-layout
-// row.
+// ---- per pair: one wave per 16 consecutive pairs.  e.s is a VALU dot against S[history(pair)] (column 0 of the
+// product is W1a's zero column here: tile mates have different histories); aux is read per C-layout row, aux[history(row)][column].
 struct DfmJtmPairs {
   const float *emb;
   const f32x4 *frag;                   // [NCT][E / 16][64] (d_dfm_frag: column 0 zero, columns 1 .. T = W1a)
@@ -121,28 +123,23 @@ __global__ __launch_bounds__(256) void dfm_jtm_pairs_kernel(DfmJtmPairs p) {
   constexpr int NJ = E / 16, NC = NCT * 16;
   extern __shared__ __attribute__((aligned(16))) char smem_dfj[];
   f32x4 *wl = (f32x4 *)smem_dfj;
-  for (int i = threadIdx.x; i < NCT * NJ * 64; i += 256) wl[i] = p.frag[i];
+  dfm_stage_frag<E, NCT>(p.frag, wl, nullptr, nullptr, 256);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
   const int64_t tiles = (p.P + 15) / 16;
   for (int64_t w = (int64_t)blockIdx.x * 4 + wave; w < tiles; w += (int64_t)gridDim.x * 4) {
     const int64_t pr = w * 16 + r;
     const bool live = pr < p.P;          // pairs at or past P are neither gathered nor stored
-    int32_t code = live ? p.codes[pr] : -1;
-    if (code >= p.num_index) code = -1;
+    const int32_t code = live ? p.codes[pr] : -1;
     const int64_t hh = live ? pr / p.seq_div : 0;
     f32x4 qa[NJ];
     float es = 0.0f;
+    dfm_tile_gather<E>(p.emb, code, p.num_index, g, qa, [&](int jc, bool row) {
+      if (!row) return;      // (a zero row: e.s = 0, S is not read)
+      const f32x4 sv = *(const f32x4 *)(p.S + hh * E + 16 * jc + 4 * g);
 #pragma unroll
-    for (int jc = 0; jc < NJ; jc++) {
-      qa[jc] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (code >= 0) {
-        qa[jc] = *(const f32x4 *)(p.emb + (int64_t)code * E + 16 * jc + 4 * g);
-        const f32x4 sv = *(const f32x4 *)(p.S + hh * E + 16 * jc + 4 * g);
-#pragma unroll
-        for (int t = 0; t < 4; t++) es = fmaf(qa[jc][t], sv[t], es);
-      }
-    }
+      for (int t = 0; t < 4; t++) es = fmaf(qa[jc][t], sv[t], es);
+    });
     es += __shfl_xor(es, 16);
     es += __shfl_xor(es, 32);            // e.s of pair r, in all four lane groups
     float tot[4] = {0.f, 0.f, 0.f, 0.f};
@@ -192,7 +189,7 @@ static int dfm_jtm_launch(dm_ctx *h, const DfmJtmRows &r, const DfmJtmPairs &p) 
     const int rc = tm.stop();
     if (rc != DM_OK) return rc;
   }
-  const size_t lds = (size_t)NCT * E * 64;
+  const size_t lds = dfm_frag_bytes(E, NCT);
   int64_t blocks = ((p.P + 15) / 16 + 3) / 4;
   if (blocks > (int64_t)h->n_cu * 4) blocks = (int64_t)h->n_cu * 4;
   LaunchTimer tm(h, EV_DFM_JTM_PAIRS);
@@ -222,22 +219,16 @@ static int dfm_pairs_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seq
     const int64_t p0 = h0 * seq_div;
     r.hcode = d_seqs + h0 * L; r.H = std::min(Hs, H - h0);
     p.codes = d_codes + p0; p.out = d_out + p0; p.P = std::min(P - p0, r.H * seq_div);
-    rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) {
-      constexpr int E_ = decltype(e)::value;
-      return NCT == 1 ? dfm_jtm_launch<E_, 1>(h, r, p) : NCT == 2 ? dfm_jtm_launch<E_, 2>(h, r, p) : dfm_jtm_launch<E_, 3>(h, r, p);
-    });
+    rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_jtm_launch<decltype(e)::value, decltype(n)::value>(h, r, p); });
     if (rc != DM_OK) return rc;
   }
   return DM_OK;
 }
 
-// what every DeepFM tree-learning entry point checks first (after the NULL check and DM_CLONE_ENTER); L < 0: not known yet
+// what every DeepFM tree-learning entry point checks first (after the NULL check and DM_CLONE_ENTER): dfm_enter (L < 0: not known yet), one rank
 static int dfm_jtm_enter(dm_ctx *h, const char *who, int use_mask, int L) {
-  if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": weights not loaded");
-  if (h->scorer_kind != DM_KIND_DEEPFM) return fail(h, DM_ERR_STATE, std::string(who) + ": the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model)");
-  if (use_mask != 0) return fail(h, DM_ERR_INVALID, std::string(who) + ": the DeepFM graph has no mask input (use_mask must be 0)");
-  if (L >= 0 && L != h->dfm_L)
-    return fail(h, DM_ERR_INVALID, std::string(who) + ": L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
+  const int rc = dfm_enter(h, who, L < 0 ? nullptr : &L, use_mask);
+  if (rc != DM_OK) return rc;
   if (h->comm && h->comm->nranks > 1)
     return fail(h, DM_ERR_UNSUPPORTED, std::string(who) + ": a communicator with " + std::to_string(h->comm->nranks) + " ranks is attached; DeepFM tree learning runs on one rank");
   return DM_OK;
@@ -246,28 +237,16 @@ static int dfm_jtm_enter(dm_ctx *h, const char *who, int use_mask, int L) {
 int dm_deepfm_pairs_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, int64_t P, int L, int seq_div, float *logits) {
   if (!h) return DM_ERR_INVALID;
   DM_CLONE_ENTER(h);
-  if (!h->w_loaded) return fail(h, DM_ERR_STATE, "dm_deepfm_pairs_forward: weights not loaded");
-  if (h->scorer_kind != DM_KIND_DEEPFM) return fail(h, DM_ERR_STATE, "dm_deepfm_pairs_forward: the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model)");
+  int rc = dfm_enter(h, "dm_deepfm_pairs_forward", &L, 0);
+  if (rc != DM_OK) return rc;
   if (!codes || !seqs || !logits || P < 0 || seq_div < 1) return fail(h, DM_ERR_INVALID, "dm_deepfm_pairs_forward: bad arguments");
-  if (L != h->dfm_L) return fail(h, DM_ERR_INVALID, "dm_deepfm_pairs_forward: L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
   if (P == 0) return DM_OK;
   const int64_t H = (P + seq_div - 1) / seq_div;
-  // LookupTable.embeddingLookup validates every index first (LookupTable.scala:29-53)
-  for (int64_t i = 0; i < P; i++)
-    if (codes[i] != -1 && (codes[i] < 0 || codes[i] >= h->num_index)) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), pair %lld got %d", (long long)h->num_index, (long long)i, codes[i]);
-      return fail(h, DM_ERR_INDEX, b);
-    }
-  for (int64_t i = 0; i < H * L; i++)
-    if (seqs[i] != -1 && (seqs[i] < 0 || seqs[i] >= h->num_index)) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), history %lld got %d", (long long)h->num_index, (long long)(i / L), seqs[i]);
-      return fail(h, DM_ERR_INDEX, b);
-    }
+  if ((rc = check_lookup_ids(h, codes, P, 1, "pair")) != DM_OK || (rc = check_lookup_ids(h, seqs, H * L, L, "history")) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   ReqArena ar(h);
   const size_t o_codes = ar.add((size_t)P * 4), o_seqs = ar.add((size_t)H * L * 4), o_out = ar.add((size_t)P * 4);
-  int rc = ar.commit(h);
-  if (rc != DM_OK) return rc;
+  if ((rc = ar.commit(h)) != DM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(ar.ptr<int32_t>(o_codes), codes, (size_t)P * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(ar.ptr<int32_t>(o_seqs), seqs, (size_t)H * L * 4, hipMemcpyHostToDevice, h->stream));
   if ((rc = dfm_pairs_dev(h, ar.ptr<int32_t>(o_codes), ar.ptr<int32_t>(o_seqs), P, L, ar.ptr<float>(o_out), seq_div)) != DM_OK) return rc;

@@ -7,13 +7,13 @@
 // set-up, every level's prune / expand / score, the results — fits in one workgroup.  One workgroup per user, grid-stride over the users
 // (they cost the same: a static assignment), no communication between workgroups; the only seams are __syncthreads.
 //
-// Per workgroup : W1a's B fragments (d_dfm_frag, [0 ; W1a ; 0]) and w2p staged in LDS, as dfm_level_kernel does.
-// Per user      : the body of dfm_user_kernel with its summation orders (history rows into LDS, S[E], aux[0] = c, aux[1 .. T] = W1s vec(K) + b1),
-//                 results kept in LDS; a -1 code and a code outside the table are zero rows.
+// Per workgroup : W1a's B fragments (d_dfm_frag, [0 ; W1a ; 0]) and w2p staged in LDS (dfm_stage_frag).
+// Per user      : dfm_user_setup (history rows into LDS, S[E], aux[0] = c, aux[1 .. T] = W1s vec(K) + b1), results kept in LDS; a -1 code
+//                 and a code outside the table are zero rows.
 // Frontier      : nodes 2^s - 1 .. 2^(s+1) - 2 with score 0, s = floor(log2 beam) (OTMTree.initializeBeam).
 // Per level     : prune (first level: keep all; then otm64_sort_positions — the stable (Double.compare descending, position) order — and
 //                 take min(beam, n)), expand (children 2c+1, 2c+2 in kept order), score (a wave takes the 16-row tiles wave, wave + nwaves, ..;
-//                 rows HBM -> VGPR in A-fragment layout; the product and epilogue of dfm_level_kernel; scores to LDS), emit (trace slot and,
+//                 dfm_tile_gather and dfm_tile_score with the user's S / aux and w2p in LDS; scores to LDS), emit (trace slot and,
 //                 on the last level, the outputs, in expansion order: what the reference returns before OTM.recommend sorts).
 // A user's scores depend on the user alone: not on batch mates, the grid, or which wave took which tile (a tile's arithmetic is a
 // function of its 16 rows and the user's S / aux).  No atomics.
@@ -38,7 +38,7 @@ struct DfmOtm {
 
 static inline size_t dfm_otm_lds(int E, int NCT, int L, int cap2, int pcap) {
   const size_t un = std::max((size_t)L * E * 4, (size_t)pcap * 12);
-  return (size_t)NCT * E * 64 + (size_t)NCT * 16 * 4 * 2 + (size_t)E * 4 + 16 + (size_t)cap2 * 12 + ((un + 15) & ~(size_t)15);
+  return dfm_frag_bytes(E, NCT) + (size_t)NCT * 16 * 4 * 2 + (size_t)E * 4 + 16 + (size_t)cap2 * 12 + ((un + 15) & ~(size_t)15);
 }
 
 template <int E, int NCT>
@@ -47,9 +47,9 @@ __global__ __launch_bounds__(256) void dfm_otm_beam_kernel(DfmOtm p) {
   extern __shared__ __attribute__((aligned(16))) char smem_dfo[];
   const int nthr = blockDim.x, nw = nthr >> 6;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
-  const int L = p.L, T = L + 1, nk = L * E, cap2 = p.cap2;
+  const int cap2 = p.cap2;
   f32x4 *wl = (f32x4 *)smem_dfo;
-  float *w2l = (float *)(smem_dfo + (size_t)NCT * E * 64);
+  float *w2l = (float *)(wl + NCT * NJ * 64);
   float *Sl = w2l + NC, *auxl = Sl + E, *red = auxl + NC;
   int32_t *cA = (int32_t *)(red + 4), *cB = cA + cap2;
   float *scl = (float *)(cB + cap2);
@@ -57,41 +57,15 @@ __global__ __launch_bounds__(256) void dfm_otm_beam_kernel(DfmOtm p) {
   float *K = (float *)un;
   unsigned long long *key = (unsigned long long *)un;
   const f32x4 *Sl4 = (const f32x4 *)Sl;
-  for (int i = tid; i < NCT * NJ * 64; i += nthr) wl[i] = p.frag[i];
-  for (int i = tid; i < NC; i += nthr) w2l[i] = p.w2p[i];
+  dfm_stage_frag<E, NCT>(p.frag, wl, p.w2p, w2l, nthr);
   if (blockIdx.x == 0 && tid == 0) *p.rows = p.rows_total;
   for (int64_t u = blockIdx.x; u < p.U; u += gridDim.x) {
     __syncthreads();                   // the staging above; the last user's emit has read its codes and scores
-    // ---- the user: dfm_user_kernel's body, same summation orders (a sum's order does not depend on the workgroup's width)
-    for (int i = tid; i < nk; i += nthr) {
-      const int32_t c = p.seq[u * L + i / E];
-      K[i] = (c >= 0 && c < p.num_index) ? p.emb[(int64_t)c * E + i % E] : 0.0f;
-    }
-    __syncthreads();
-    for (int hf = wave; hf < 2; hf += nw) {      // features 0 .. 63, 64 .. 127: one wave each, as waves 0 and 1 there
-      const int e = 64 * hf + lane;
-      float d = 0.0f;
-      if (e < E) {
-        float s = 0.0f, q = 0.0f;
-        for (int j = 0; j < L; j++) { const float v = K[j * E + e]; s += v; q = fmaf(v, v, q); }
-        Sl[e] = s;
-        d = fmaf(s, s, -q);
-      }
-      d = dm_wave_sum(d);
-      if (lane == 0) red[hf] = d;
-    }
-    for (int t = wave; t < T; t += nw) {
-      const float *w = p.l1_w + (int64_t)t * T * E + E;      // W1s[t]: the L history blocks of row t
-      float part = 0.0f;
-      for (int i = lane; i < nk; i += 64) part = fmaf(w[i], K[i], part);
-      part = dm_wave_sum(part);
-      if (lane == 0) auxl[1 + t] = part + p.l1_b[t];
-    }
-    for (int i = T + 1 + tid; i < NC; i += nthr) auxl[i] = 0.0f;
+    // ---- the user; the frontier goes in before the set-up's second barrier (the history rows are dead behind it: the sort takes their place)
     int n = p.start + 1;
-    for (int i = tid; i < n; i += nthr) { cA[i] = p.start + i; scl[i] = 0.0f; }
-    __syncthreads();                   // (the history rows are dead from here on: the sort takes their place)
-    if (tid == 0) auxl[0] = 0.5f * (red[0] + red[1]) + p.b2;
+    dfm_user_setup(p.emb, p.l1_w, p.l1_b, p.b2, p.num_index, E, p.L, NC, p.seq + u * p.L, K, nthr, Sl, auxl, red, [&] {
+      for (int i = tid; i < n; i += nthr) { cA[i] = p.start + i; scl[i] = 0.0f; }
+    });
     int32_t *cur = cA, *nxt = cB;
     for (int level = p.level0; level < p.leaf_level; level++) {
       // ---- prune + expand
@@ -106,41 +80,16 @@ __global__ __launch_bounds__(256) void dfm_otm_beam_kernel(DfmOtm p) {
         otm64_sort_positions<float>(key, pos, scl, n, pc);
         for (int i = tid; i < nb; i += nthr) { const int32_t c = cur[pos[i]]; nxt[2 * i] = 2 * c + 1; nxt[2 * i + 1] = 2 * c + 2; }
       }
-      __syncthreads();                 // (also: auxl[0] on the first level)
+      __syncthreads();                 // (also: aux[0] = c on the first level)
       { int32_t *t_ = cur; cur = nxt; nxt = t_; }
       n = 2 * nb;
-      // ---- score: dfm_level_kernel's tile, with the user's S / aux and the codes in LDS
+      // ---- score: column 0 of tile 0 is the user's s, read from LDS by the lanes r = 0 (feature 16 jc + 4 g + t)
       for (int row0 = 16 * wave; row0 < n; row0 += 16 * nw) {
-        int32_t code = row0 + r < n ? cur[row0 + r] : -1;       // rows at or past the count are neither gathered nor stored
-        if (code >= p.num_index) code = -1;
         f32x4 qa[NJ];
-#pragma unroll
-        for (int jc = 0; jc < NJ; jc++)
-          qa[jc] = code >= 0 ? *(const f32x4 *)(p.emb + (int64_t)code * E + 16 * jc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        float tot[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ct = 0; ct < NCT; ct++) {
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int jc = 0; jc < NJ; jc++) {
-            // column 0 of tile 0 is the user's s, held by the lanes r = 0: feature 16 jc + 4 g + t
-            const f32x4 b = (ct == 0 && r == 0) ? Sl4[4 * jc + g] : wl[(ct * NJ + jc) * 64 + lane];
-#pragma unroll
-            for (int t = 0; t < 4; t++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[jc][t], b[t], acc, 0, 0, 0);
-          }
-          const int col = 16 * ct + r;
-          const float av = auxl[col], wv = w2l[col];
-#pragma unroll
-          for (int rr = 0; rr < 4; rr++) {
-            const float x = acc[rr] + av;
-            tot[rr] += col == 0 ? x : wv * fmaxf(x, 0.0f);
-          }
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; rr++) {
-#pragma unroll
-          for (int o = 1; o < 16; o <<= 1) tot[rr] += __shfl_xor(tot[rr], o);
-        }
+        dfm_tile_gather<E>(p.emb, row0 + r < n ? cur[row0 + r] : -1, p.num_index, g, qa);       // rows at or past the count are neither gathered nor stored
+        float tot[4];
+        dfm_tile_score<E, NCT>(qa, wl, w2l, lane, [&](int jc, const f32x4 *staged) { return *(r == 0 ? Sl4 + 4 * jc + g : staged); },
+                               [&](int, int col) { return auxl[col]; }, tot);
         if (r == 0) {
 #pragma unroll
           for (int rr = 0; rr < 4; rr++)
@@ -190,15 +139,12 @@ static int dfm_otm_launch(dm_ctx *h, const DfmOtm &p, int nthr, size_t lds) {
   return tm.stop();
 }
 
-// what every DeepFM OTM entry point checks first (after the NULL check and, for the searches, DM_CLONE_ENTER)
+// what every DeepFM OTM entry point checks first (after the NULL check and, for the searches, DM_CLONE_ENTER): dfm_enter, then the search's shape
 static int dfm_otm_check(dm_ctx *h, const char *who, int64_t U, int L, int beam, int leaf_level, int use_mask) {
-  if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": weights not loaded");
-  if (h->scorer_kind != DM_KIND_DEEPFM) return fail(h, DM_ERR_STATE, std::string(who) + ": the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model)");
-  if (use_mask != 0) return fail(h, DM_ERR_INVALID, std::string(who) + ": DeepFM has no mask (OTM.scala:14-22 serves it with useMask = false): use_mask must be 0");
+  const int rc = dfm_enter(h, who, &L, use_mask);
+  if (rc != DM_OK) return rc;
   if (U < 0 || L <= 0 || L > DFM_MAXL || beam <= 0 || leaf_level <= 0 || leaf_level > 30)
     return fail(h, DM_ERR_INVALID, std::string(who) + ": bad arguments (L must be 1..32)");
-  if (L != h->dfm_L)
-    return fail(h, DM_ERR_INVALID, std::string(who) + ": L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
   if ((((int64_t)1) << (leaf_level + 1)) - 1 > h->num_index) return fail(h, DM_ERR_INDEX, std::string(who) + ": leaf level exceeds the embedding table");
   if (beam > DFM_OTM_MAX_BEAM) return fail(h, DM_ERR_UNSUPPORTED, std::string(who) + ": beam too large for the LDS sort (at most 512 with a DeepFM model)");
   return DM_OK;
@@ -232,10 +178,7 @@ static int dfm_otm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L,
   const size_t lds = dfm_otm_lds(E, NCT, L, p.cap2, pcap);
   const int tiles = (2 * beam + 15) / 16;
   const int nthr = tiles <= 1 ? 64 : tiles == 2 ? 128 : 256;      // 1, 2 or 4 waves
-  return dispatch_E(h, E, "unsupported embed size", [&](auto e) {
-    constexpr int E_ = decltype(e)::value;
-    return NCT == 1 ? dfm_otm_launch<E_, 1>(h, p, nthr, lds) : NCT == 2 ? dfm_otm_launch<E_, 2>(h, p, nthr, lds) : dfm_otm_launch<E_, 3>(h, p, nthr, lds);
-  });
+  return dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_otm_launch<decltype(e)::value, decltype(n)::value>(h, p, nthr, lds); });
 }
 
 // host-buffer front end of dm_deepfm_otm_beam_search[_trace]

@@ -296,8 +296,8 @@ __global__ __launch_bounds__(256) void dfm_seg_heads_kernel(const unsigned long 
 // ---------------------------------------------------------------------------------------------------------------- host
 // (launch kinds under DM_DFM_TIME_LAUNCHES=1: EV_DFT_* in host_request.hip.inc)
 static int dfm_train_check(dm_ctx *h, const char *who, bool need_init) {
-  if (!h->w_loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": weights not loaded");
-  if (h->scorer_kind != DM_KIND_DEEPFM) return fail(h, DM_ERR_STATE, std::string(who) + ": the loaded scorer is DIN (dm_load_weights_deepfm loads a DeepFM model; DIN trains through dm_train_*)");
+  const int rc = dfm_enter(h, who, nullptr, 0);
+  if (rc != DM_OK) return rc;
   if (need_init && !h->dfm_tr) return fail(h, DM_ERR_STATE, std::string(who) + ": call dm_deepfm_train_init first");
   return DM_OK;
 }
@@ -394,10 +394,7 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
     DfmTrainRows p;
     p.emb = h->d_emb32; p.l1_b = b.l1_b; p.l2_w = b.l2_w; p.l2_b = b.l2_b; p.fragF = (const f32x4 *)t->fragF; p.fragB = (const f32x4 *)t->fragB;
     p.idx = idx; p.labels = d_labels; p.B = B; p.T = T; p.dH = dH; p.dX = dX; p.ploss = ar.ptr<double>(o_pl); p.pg = ar.ptr<float>(o_pg);
-    rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) {
-      constexpr int E_ = decltype(e)::value;
-      return NCT == 1 ? dfm_launch_train_rows<E_, 1>(h, p, nb, detail) : NCT == 2 ? dfm_launch_train_rows<E_, 2>(h, p, nb, detail) : dfm_launch_train_rows<E_, 3>(h, p, nb, detail);
-    });
+    rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_launch_train_rows<decltype(e)::value, decltype(n)::value>(h, p, nb, detail); });
     if (rc != DM_OK) return rc;
     hipLaunchKernelGGL(dfm_train_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)p.ploss, (const float *)p.pg, nb, NC, T, B, ar.ptr<double>(o_loss), g_l2w, g_l2b);
     HIPCHK(h, hipGetLastError());
@@ -437,8 +434,7 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
 
 static int dfm_train_fb_args(dm_ctx *h, const void *codes, const void *seqs, const void *labels, int64_t B, int L) {
   if (B <= 0 || !codes || !seqs || !labels) return fail(h, DM_ERR_INVALID, "dm_deepfm_train_forward_backward: B must be positive and the arrays non-null");
-  if (L != h->dfm_L) return fail(h, DM_ERR_INVALID, "dm_deepfm_train_forward_backward: L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L) + " (l1.W is sized by it)");
-  return DM_OK;
+  return dfm_check_L(h, "dm_deepfm_train_forward_backward", L);
 }
 
 int dm_deepfm_train_forward_backward_dev(dm_handle_t h, const int32_t *d_codes, const int32_t *d_seqs, const float *d_labels, int64_t B, int L, double *out_loss) {
@@ -459,14 +455,7 @@ int dm_deepfm_train_forward_backward(dm_handle_t h, const int32_t *codes, const 
   if ((rc = dfm_train_fb_args(h, codes, seqs, labels, B, L)) != DM_OK) return rc;
   if (B * (int64_t)(L + 1) >= ((int64_t)1 << 31) || B > (int64_t)DRT_MAX_ROWS)
     return fail(h, DM_ERR_UNSUPPORTED, "dm_deepfm_train_forward_backward: batch too large (at most 4 194 240 rows, and B (L + 1) below 2^31): split it and accumulate on the host");
-  // LookupTable.embeddingLookup validates every index first (LookupTable.scala:29-53)
-  for (int64_t i = 0; i < B * (L + 1); i++) {
-    const int32_t id = i < B ? codes[i] : seqs[i - B];
-    if (id < -1 || id >= h->num_index) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)(i < B ? i : (i - B) / L), id);
-      return fail(h, DM_ERR_INDEX, b);
-    }
-  }
+  if ((rc = check_lookup_ids(h, codes, B, 1, "row")) != DM_OK || (rc = check_lookup_ids(h, seqs, B * L, L, "row")) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   dm_dfm_train *t = h->dfm_tr;
   const size_t b_codes = DevArena::up((size_t)B * 4), b_seqs = DevArena::up((size_t)B * L * 4), b_lab = DevArena::up((size_t)B * 4);
@@ -554,10 +543,8 @@ extern "C" int dm_debug_deepfm_train_padded(dm_handle_t h, int what, float *out,
 
 // ---- the sampler's twins: the rows of dm_tdm_make_train_batch / dm_tdm_sample_train_batch_dev without a mask (the graph has none)
 static int dfm_sample_check(dm_ctx *h, const char *who, int64_t T, int L, const int32_t *neg_counts, int n_counts, const dm_sample_opts *o, int64_t *per) {
-  int rc = dfm_train_check(h, who, false);
+  const int rc = dfm_enter(h, who, &L, o ? o->use_mask : 0);
   if (rc != DM_OK) return rc;
-  if (o && o->use_mask != 0) return fail(h, DM_ERR_INVALID, std::string(who) + ": the DeepFM graph has no mask (use_mask must be 0)");
-  if (L != h->dfm_L) return fail(h, DM_ERR_INVALID, std::string(who) + ": L = " + std::to_string(L) + " but the model was built for seq_len " + std::to_string(h->dfm_L));
   return sample_check(h, DM_KIND_DEEPFM, T, L, neg_counts, n_counts, o, per);
 }
 

@@ -221,6 +221,25 @@ static int dispatch_E(dm_ctx *h, int E, const char *unsupported, F &&f) {
   return fail(h, DM_ERR_UNSUPPORTED, unsupported);
 }
 
+// The DeepFM kernel templates are also instantiated per number of 16-column tiles: f(integral_constant<E>, integral_constant<NCT>), NCT = 1 .. 3
+template <typename F>
+static int dispatch_E_NCT(dm_ctx *h, int E, int NCT, const char *unsupported, F &&f) {
+  return dispatch_E(h, E, unsupported, [&](auto e) {
+    return NCT == 1 ? f(e, std::integral_constant<int, 1>{}) : NCT == 2 ? f(e, std::integral_constant<int, 2>{}) : f(e, std::integral_constant<int, 3>{});
+  });
+}
+
+// LookupTable.embeddingLookup validates every index first (LookupTable.scala:29-53): -1 is the padding index, anything else outside
+// [0, num_index) fails with the reference's message, which names `noun` i / div (the row, pair or history that holds ids[i])
+static int check_lookup_ids(dm_ctx *h, const int32_t *ids, int64_t n, int64_t div, const char *noun) {
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] < -1 || ids[i] >= h->num_index) {
+      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), %s %lld got %d", (long long)h->num_index, noun, (long long)(i / div), ids[i]);
+      return fail(h, DM_ERR_INDEX, b);
+    }
+  return DM_OK;
+}
+
 // ------------------------------------------------------------ small kernels
 __global__ void dm_f64_to_f32_kernel(const double *in, float *out, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -867,17 +886,8 @@ int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, con
   if (!codes || !seqs || !logits || B < 0 || L <= 0 || L > 32 || n_pad < 0 || (n_pad > 0 && !pad_flat_idx))
     return fail(h, DM_ERR_INVALID, "dm_din_forward: bad arguments (L must be 1..32)");
   if (B == 0) return DM_OK;
-  // LookupTable.embeddingLookup validates every index first (LookupTable.scala:29-53)
-  for (int64_t i = 0; i < B; i++)
-    if (codes[i] != -1 && (codes[i] < 0 || codes[i] >= h->num_index)) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)i, codes[i]);
-      return fail(h, DM_ERR_INDEX, b);
-    }
-  for (int64_t i = 0; i < B * L; i++)
-    if (seqs[i] != -1 && (seqs[i] < 0 || seqs[i] >= h->num_index)) {
-      char b[160]; snprintf(b, sizeof b, "embeddingLookup failed, valid index range is [0, %lld), row %lld got %d", (long long)h->num_index, (long long)(i / L), seqs[i]);
-      return fail(h, DM_ERR_INDEX, b);
-    }
+  int rc;
+  if ((rc = check_lookup_ids(h, codes, B, 1, "row")) != DM_OK || (rc = check_lookup_ids(h, seqs, B * L, L, "row")) != DM_OK) return rc;
   for (int64_t i = 0; i < n_pad; i++)
     if (pad_flat_idx[i] < 0 || pad_flat_idx[i] >= B * L) return fail(h, DM_ERR_INDEX, "dm_din_forward: mask index outside [0, B*L)");
   HIPCHK(h, hipSetDevice(h->device));
@@ -886,7 +896,6 @@ int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, con
   void *d_out = nullptr;
   const size_t esz = h->dtype == DM_F32 ? 4 : 8;
   DevTemps t(h);
-  int rc;
   if ((rc = t.alloc(d_codes, B * 4)) != DM_OK || (rc = t.alloc(d_seqs, B * L * 4)) != DM_OK || (rc = t.alloc(d_mask, B * 4)) != DM_OK ||
       (rc = t.alloc(d_out, B * esz)) != DM_OK) return rc;
   if (hipMemcpyAsync(d_codes, codes, B * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
