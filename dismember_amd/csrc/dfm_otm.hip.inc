@@ -188,28 +188,18 @@ static int dfm_otm_search_host(dm_ctx *h, const char *who, const int32_t *seq_co
   if (rc != DM_OK) return rc;
   if (U == 0) return DM_OK;          // an empty batch is not an error
   if (!seq_codes || !out_node_ids || !out_scores || !out_counts) return fail(h, DM_ERR_INVALID, std::string(who) + ": bad arguments");
-  for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, std::string(who) + ": history code outside the embedding table");
+  if ((rc = check_table_ids(h, who, "history code", seq_codes, U * L, -1)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   int cap;
   frontier_caps(beam, &cap, nullptr);
-  const size_t stride = (size_t)2 * beam, nt = tn ? (size_t)U * max_levels : 0;
-  // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
-  ReqArena ar(h);
-  const size_t o_seq = ar.add((size_t)U * L * 4), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * 4), o_cnt = ar.add((size_t)U * 4);
-  const size_t o_tc = ar.add(nt * cap * 4), o_ts = ar.add(nt * cap * 4), o_tn = ar.add(nt * 4);
-  if ((rc = ar.commit(h)) != DM_OK) return rc;
-  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_cnt = ar.ptr<int32_t>(o_cnt);
-  float *d_sc = ar.ptr<float>(o_sc);
-  int32_t *d_tc = tn ? ar.ptr<int32_t>(o_tc) : nullptr, *d_tn = tn ? ar.ptr<int32_t>(o_tn) : nullptr;
-  float *d_ts = tn ? ar.ptr<float>(o_ts) : nullptr;
-  const HostOut outs[6] = {{out_node_ids, d_ids, stride * 4}, {out_scores, d_sc, stride * 4}, {out_counts, d_cnt, 4},
-                           {tc, d_tc, (size_t)max_levels * cap * 4}, {ts, d_ts, (size_t)max_levels * cap * 4}, {tn, d_tn, (size_t)max_levels * 4}};
-  HIPCHK(h, hipMemcpyAsync(d_seq, seq_codes, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream));
-  if (tn) HIPCHK(h, hipMemsetAsync(d_tc, 0, ar.need - o_tc, h->stream));   // trace codes, scores and counts are adjacent
-  if ((rc = dfm_otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_sc, d_cnt, max_levels, cap, d_tc, d_ts, d_tn)) != DM_OK) return rc;
-  HIPCHK(h, download_all(h, outs, tn ? 6 : 3, U, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  ReqLayout lay(h, h->req, 2, U, (size_t)L * 4, (size_t)2 * beam, 4);
+  if (tn) lay.trace(max_levels, cap, 4);
+  if ((rc = lay.commit(out_node_ids, out_scores, out_counts, tc, ts, tn)) != DM_OK) return rc;
+  HIPCHK(h, lay.upload(seq_codes));
+  if (tn) HIPCHK(h, lay.clear_trace());
+  if ((rc = dfm_otm_search_dev(h, lay.d<int32_t>(lay.SEQ), U, L, beam, leaf_level, lay.d<int32_t>(lay.IDS), lay.d<float>(lay.SCORES), lay.d<int32_t>(lay.COUNTS),
+                               max_levels, cap, lay.d<int32_t>(lay.TC), lay.d<float>(lay.TS), lay.d<int32_t>(lay.TN))) != DM_OK) return rc;
+  HIPCHK(h, lay.finish());
   return DM_OK;
 }
 

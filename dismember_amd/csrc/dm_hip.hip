@@ -240,6 +240,14 @@ static int check_lookup_ids(dm_ctx *h, const int32_t *ids, int64_t n, int64_t di
   return DM_OK;
 }
 
+// The OTM and training entry points' own check of host ids: every ids[i] in [lowest, num_index), or "<who>: <noun> outside the
+// embedding table".  lowest = -1 admits the padding id; node codes that must exist (targets) pass 1.
+static int check_table_ids(dm_ctx *h, const char *who, const char *noun, const int32_t *ids, int64_t n, int32_t lowest) {
+  for (int64_t i = 0; i < n; i++)
+    if (ids[i] < lowest || ids[i] >= h->num_index) return fail(h, DM_ERR_INDEX, std::string(who) + ": " + noun + " outside the embedding table");
+  return DM_OK;
+}
+
 // ------------------------------------------------------------ small kernels
 __global__ void dm_f64_to_f32_kernel(const double *in, float *out, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1284,47 +1292,37 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
   const int mb = host_max_beam(opts, coff, U);
   int cap;
   frontier_caps(mb, &cap, nullptr);
-  const size_t topk = (size_t)opts->topk, b_seq = (size_t)U * L * 4;
+  const size_t topk = (size_t)opts->topk;
   const int64_t nc = coff ? coff[U] : 0;
-  // request arena: [seq | ids | scores | counts | consumed_off | consumed_ids]
-  ReqArena ar(h);
-  const size_t o_seq = ar.add(b_seq), o_ids = ar.add(U * topk * 4), o_sc = ar.add(U * topk * 4), o_cnt = ar.add((size_t)U * 4), o_end = ar.need;
-  const size_t o_coff = coff ? ar.add((size_t)(U + 1) * 8) : 0, o_cids = coff ? ar.add((size_t)(nc > 0 ? nc : 1) * 4) : 0;
-  int rc = ar.commit(h);
+  // trace buffers (parity instrumentation) are per call, not arena space: a large trace does not enlarge h->req for good
+  ReqLayout lay(h, h->req, 2, U, (size_t)L * 4, topk, 4);
+  if (tn) lay.trace(max_levels, cap, 4, true);
+  if (coff) lay.extras((size_t)(U + 1) * 8, (size_t)(nc > 0 ? nc : 1) * 4);
+  int rc = lay.commit(out_ids, out_scores, out_counts, tc, ts, tn);
   if (rc != DM_OK) return rc;
-  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_counts = ar.ptr<int32_t>(o_cnt), *d_cids = coff ? ar.ptr<int32_t>(o_cids) : nullptr;
-  int64_t *d_coff = coff ? ar.ptr<int64_t>(o_coff) : nullptr;
-  float *d_scores = ar.ptr<float>(o_sc);
-  HostOut outs[6] = {{out_ids, d_ids, topk * 4}, {out_scores, d_scores, topk * 4}, {out_counts, d_counts, 4}};
-  // small requests (the reference's one-user-per-call serving loop): the request goes up and the three result arrays come down
-  // through ONE pinned staging block — a pageable copy costs 10-15 us each, and a single-user search is 60 us of kernel
-  const bool staged = !coff && !tn && o_end <= (256u << 10);
-  if (staged && (rc = ensure_stage(h)) != DM_OK) return rc;
-  if (staged) memcpy(h->h_stage, seq, b_seq);
-  if (staged && h->direct_ok && U <= 8) {
-    // Single-request path (the reference's serving loop: one user per call, examples/.../tdm/package.scala:114-124).  The staging
-    // block is host-mapped: the kernel reads the request from it and writes the results into it; the host polls the counts.
-    volatile int32_t *m_cnt = (volatile int32_t *)(h->h_stage + o_cnt);
-    for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
+  int32_t *d_seq = lay.d<int32_t>(lay.SEQ), *d_ids = lay.d<int32_t>(lay.IDS), *d_counts = lay.d<int32_t>(lay.COUNTS), *d_cids = lay.d<int32_t>(lay.X1);
+  int64_t *d_coff = lay.d<int64_t>(lay.X0);
+  float *d_scores = lay.d<float>(lay.SCORES);
+  if (lay.fits_stage() && (rc = lay.stage(seq)) != DM_OK) return rc;
+  if (lay.staged && h->direct_ok && U <= 8) {
+    // Single-request path (the reference's serving loop: one user per call, examples/.../tdm/package.scala:114-124)
+    lay.arm_direct();
     bool direct = true;
-    rc = tdm_search_dev(h, (const int32_t *)h->d_stage, U, L, opts, mb, nullptr, nullptr, (int32_t *)(h->d_stage + o_ids),
-                        (float *)(h->d_stage + o_sc), (int32_t *)(h->d_stage + o_cnt), 0, nullptr, nullptr, nullptr, false, &direct);
+    rc = tdm_search_dev(h, lay.stage_ptr(d_seq), U, L, opts, mb, nullptr, nullptr, lay.stage_ptr(d_ids), lay.stage_ptr(d_scores),
+                        lay.stage_ptr(d_counts), 0, nullptr, nullptr, nullptr, false, &direct);
     if (rc != DM_OK) return rc;
-    if (direct) {
-      if ((rc = wait_host_direct(h, m_cnt, U, "tdm beam search")) == DM_OK) copy_from_stage(h, outs, 3, U);
-      return rc;
-    }
+    if (direct) return lay.wait_direct("tdm beam search");
     // the plan did not allow it (one-wave-per-SIMD kernel, too many users for the grid): fall through to the staged path
   }
-  if (hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq, b_seq, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
+  if (lay.upload(seq) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
   int64_t off[18];
-  const int n_chunks = (staged || coff || tn || level_pipeline(h, mb, L)) ? 1 : host_pipe_plan(topk * 8, U, off);
+  const int n_chunks = (lay.staged || coff || tn || level_pipeline(h, mb, L)) ? 1 : host_pipe_plan(lay.result_bytes_per_user(), U, off);
   if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
     int launched;
     rc = launch_chunks(h, n_chunks, off, [&](int k, int64_t u0, int64_t uk) {
       return tdm_search_dev(h, d_seq + u0 * L, uk, L, opts, mb, nullptr, nullptr, d_ids + u0 * topk, d_scores + u0 * topk, d_counts + u0, 0, nullptr, nullptr, nullptr, k > 0);
     }, &launched);
-    const hipError_t e = download_chunks(h, outs, 3, off, launched);
+    const hipError_t e = download_chunks(h, lay.outs, 3, off, launched);
     if (rc == DM_OK && e != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string("tdm beam search (pipelined download): ") + hipGetErrorString(e));
     return rc;
   }
@@ -1332,29 +1330,17 @@ static int tdm_search_host(dm_ctx *h, const int32_t *seq, int64_t U, int L, cons
     if (hipMemcpyAsync(d_coff, coff, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
     if (nc > 0 && hipMemcpyAsync(d_cids, cids, (size_t)nc * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
   }
-  // the search and its download; d_tc / d_ts / d_tn: device trace buffers or null
-  auto finish = [&](int32_t *d_tc, float *d_ts, int32_t *d_tn) -> int {
-    int rc_f = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tc, d_ts, d_tn, false);
-    if (rc_f != DM_OK) return rc_f;
-    hipError_t e = staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("tdm beam search: ") + hipGetErrorString(e));
-    if (staged) copy_from_stage(h, outs, 3, U);
-    return DM_OK;
-  };
-  if (tn) {      // trace buffers (parity instrumentation) are per call; the guard exists on this path only
-    DevTemps trace(h);
-    int32_t *d_tc = nullptr, *d_tn = nullptr; float *d_ts = nullptr;
-    const size_t nt = (size_t)U * max_levels;
-    if ((rc = trace.alloc(d_tc, nt * cap * 4)) != DM_OK) return rc;
-    if ((rc = trace.alloc(d_ts, nt * cap * 4)) != DM_OK) return rc;
-    if ((rc = trace.alloc(d_tn, nt * 4)) != DM_OK) return rc;
-    if (hipMemsetAsync(d_tn, 0, nt * 4, h->stream) != hipSuccess || hipMemsetAsync(d_tc, 0, nt * cap * 4, h->stream) != hipSuccess ||
-        hipMemsetAsync(d_ts, 0, nt * cap * 4, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "memset failed");
-    outs[3] = {tc, d_tc, (size_t)max_levels * cap * 4}; outs[4] = {ts, d_ts, (size_t)max_levels * cap * 4}; outs[5] = {tn, d_tn, (size_t)max_levels * 4};
-    return finish(d_tc, d_ts, d_tn);
+  DevTemps trace(h);
+  int32_t *d_tc = nullptr, *d_tn = nullptr; float *d_ts = nullptr;
+  if (tn) {
+    if ((rc = trace.alloc(d_tc, lay.array_bytes(lay.TC))) != DM_OK || (rc = trace.alloc(d_ts, lay.array_bytes(lay.TS))) != DM_OK ||
+        (rc = trace.alloc(d_tn, lay.array_bytes(lay.TN))) != DM_OK) return rc;
+    lay.trace_at(d_tc, d_ts, d_tn);
+    if (lay.clear_trace() != hipSuccess) return fail(h, DM_ERR_HIP, "memset failed");
   }
-  return finish(nullptr, nullptr, nullptr);
+  if ((rc = tdm_search_dev(h, d_seq, U, L, opts, mb, d_coff, d_cids, d_ids, d_scores, d_counts, tn ? max_levels : 0, d_tc, d_ts, d_tn, false)) != DM_OK) return rc;
+  const hipError_t e = lay.finish();
+  return e == hipSuccess ? DM_OK : fail(h, DM_ERR_HIP, std::string("tdm beam search: ") + hipGetErrorString(e));
 }
 
 int dm_tdm_beam_search(dm_handle_t h, const int32_t *seq_item_ids, int64_t U, int L, const dm_tdm_search_opts *opts,
@@ -1438,28 +1424,21 @@ static int otm_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L
   if (rc != DM_OK) return rc;
   if (U == 0) return DM_OK;          // an empty batch is not an error
   if (!seq_codes || !out_node_ids || !out_scores || !out_counts) return fail(h, DM_ERR_INVALID, "dm_otm_beam_search: bad arguments");
-  for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_otm_beam_search: history code outside the embedding table");
+  if ((rc = check_table_ids(h, "dm_otm_beam_search", "history code", seq_codes, U * L, -1)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   int start, level;
   level_start_int(beam, &start, &level);
   SearchPlan pl;
   if ((rc = plan_search(h, beam, U, L, leaf_level - level, false, &pl)) != DM_OK) return rc;
-  const size_t stride = (size_t)2 * beam, nt = tn ? (size_t)U * max_levels : 0;
-  // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
-  ReqArena ar(h);
-  const size_t o_seq = ar.add((size_t)U * L * 4), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * 4), o_cnt = ar.add((size_t)U * 4);
-  const size_t o_tc = ar.add(nt * pl.cap * 4), o_ts = ar.add(nt * pl.cap * 4), o_tn = ar.add(nt * 4);
-  if ((rc = ar.commit(h)) != DM_OK) return rc;
-  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_counts = ar.ptr<int32_t>(o_cnt);
-  float *d_scores = ar.ptr<float>(o_sc);
-  int32_t *d_tc = tn ? ar.ptr<int32_t>(o_tc) : nullptr, *d_tn = tn ? ar.ptr<int32_t>(o_tn) : nullptr;
-  float *d_ts = tn ? ar.ptr<float>(o_ts) : nullptr;
-  const HostOut outs[6] = {{out_node_ids, d_ids, stride * 4}, {out_scores, d_scores, stride * 4}, {out_counts, d_counts, 4},
-                           {tc, d_tc, (size_t)max_levels * pl.cap * 4}, {ts, d_ts, (size_t)max_levels * pl.cap * 4}, {tn, d_tn, (size_t)max_levels * 4}};
-  HIPCHK(h, hipMemcpyAsync(d_seq, seq_codes, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream));
+  const size_t stride = (size_t)2 * beam;
+  ReqLayout lay(h, h->req, 2, U, (size_t)L * 4, stride, 4);
+  if (tn) lay.trace(max_levels, pl.cap, 4);
+  if ((rc = lay.commit(out_node_ids, out_scores, out_counts, tc, ts, tn)) != DM_OK) return rc;
+  int32_t *d_seq = lay.d<int32_t>(lay.SEQ), *d_ids = lay.d<int32_t>(lay.IDS), *d_counts = lay.d<int32_t>(lay.COUNTS);
+  float *d_scores = lay.d<float>(lay.SCORES);
+  HIPCHK(h, lay.upload(seq_codes));
   int64_t off[18];
-  const int n_chunks = tn ? 1 : host_pipe_plan(stride * 8, U, off);
+  const int n_chunks = tn ? 1 : host_pipe_plan(lay.result_bytes_per_user(), U, off);
   if (n_chunks > 1) {      // chunks of users, downloads under the kernels behind them (host_pipe_plan)
     int launched;
     rc = launch_chunks(h, n_chunks, off, [&](int k, int64_t u0, int64_t uk) {
@@ -1467,15 +1446,13 @@ static int otm_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int L
       const int rc_ = plan_search(h, beam, uk, L, leaf_level - level, false, &plk);
       return rc_ != DM_OK ? rc_ : otm_search_dev(h, d_seq + u0 * L, uk, L, beam, leaf_level, d_ids + u0 * stride, d_scores + u0 * stride, d_counts + u0, 0, nullptr, nullptr, nullptr, plk, k > 0);
     }, &launched);
-    const hipError_t e = download_chunks(h, outs, 3, off, launched);
+    const hipError_t e = download_chunks(h, lay.outs, 3, off, launched);
     if (rc == DM_OK && e != hipSuccess) rc = fail(h, DM_ERR_HIP, std::string("dm_otm_beam_search (pipelined download): ") + hipGetErrorString(e));
-    if (rc != DM_OK) return rc;
-  } else {
-    if (tn) HIPCHK(h, hipMemsetAsync(d_tn, 0, nt * 4, h->stream));
-    if ((rc = otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts, max_levels, d_tc, d_ts, d_tn, pl, false)) != DM_OK) return rc;
-    HIPCHK(h, download_all(h, outs, tn ? 6 : 3, U, h->stream));
+    return rc;
   }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (tn) HIPCHK(h, lay.clear_trace());
+  if ((rc = otm_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, d_scores, d_counts, max_levels, lay.d<int32_t>(lay.TC), lay.d<float>(lay.TS), lay.d<int32_t>(lay.TN), pl, false)) != DM_OK) return rc;
+  HIPCHK(h, lay.finish());
   return DM_OK;
 }
 

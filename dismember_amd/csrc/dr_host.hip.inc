@@ -493,19 +493,11 @@ int dm_dr_beam_search(dm_handle_t h, const int32_t *seq_ids, int64_t U, int beam
   dm_dr_state *s = h->dr;
   if ((rc = dr_check_ids(h, seq_ids, U * s->L)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t b_seq = (size_t)U * s->L * 4, b_paths = (size_t)U * beam * s->D * 4, b_probs = (size_t)U * beam * 8, b_cnt = (size_t)U * 4;
-  if ((rc = s->io.reserve(h, DevArena::up(b_seq) + DevArena::up(b_paths) + DevArena::up(b_probs) + DevArena::up(b_cnt))) != DM_OK) return rc;
-  char *base = (char *)s->io.p;
-  int32_t *d_seq = (int32_t *)base;
-  double *d_probs = (double *)(base + DevArena::up(b_seq));
-  int32_t *d_paths = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_probs));
-  int32_t *d_cnt = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_probs) + DevArena::up(b_paths));
-  HIPCHK(h, hipMemcpyAsync(d_seq, seq_ids, b_seq, hipMemcpyHostToDevice, h->stream));
-  if ((rc = dm_dr_beam_search_dev(h, d_seq, U, beam, d_paths, d_probs, d_cnt)) != DM_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(out_paths, d_paths, b_paths, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_probs, d_probs, b_probs, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_counts, d_cnt, b_cnt, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  ReqLayout lay(h, s->io, 0, U, (size_t)s->L * 4, (size_t)beam, 8, (size_t)s->D);          // ids = paths [U][beam][D], scores = probs
+  if ((rc = lay.commit(out_paths, out_probs, out_counts)) != DM_OK) return rc;
+  HIPCHK(h, lay.upload(seq_ids));
+  if ((rc = dm_dr_beam_search_dev(h, lay.d<int32_t>(lay.SEQ), U, beam, lay.d<int32_t>(lay.IDS), lay.d<double>(lay.SCORES), lay.d<int32_t>(lay.COUNTS))) != DM_OK) return rc;
+  HIPCHK(h, lay.finish());
   return DM_OK;
 }
 
@@ -583,32 +575,22 @@ int dm_dr_recommend(dm_handle_t h, const int32_t *seq_ids, int64_t U, int beam, 
   dm_dr_state *s = h->dr;
   if ((rc = dr_check_ids(h, seq_ids, U * s->L)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t b_seq = (size_t)U * s->L * 4, b_ids = (size_t)U * topk * 4, b_sc = (size_t)U * topk * 8, b_cnt = (size_t)U * 4;
-  if ((rc = s->io.reserve(h, DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids) + DevArena::up(b_cnt))) != DM_OK) return rc;
-  char *base = (char *)s->io.p;
-  int32_t *d_seq = (int32_t *)base;
-  double *d_sc = (double *)(base + DevArena::up(b_seq));
-  int32_t *d_ids = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_sc));
-  int32_t *d_cnt = (int32_t *)(base + DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids));
-  if (U <= 8 && h->direct_ok && DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids) + DevArena::up(b_cnt) <= (256u << 10)) {
+  ReqLayout lay(h, s->io, 0, U, (size_t)s->L * 4, (size_t)topk, 8);
+  if ((rc = lay.commit(out_ids, out_scores, out_counts)) != DM_OK) return rc;
+  int32_t *d_seq = lay.d<int32_t>(lay.SEQ), *d_ids = lay.d<int32_t>(lay.IDS), *d_cnt = lay.d<int32_t>(lay.COUNTS);
+  double *d_sc = lay.d<double>(lay.SCORES);
+  if (U <= 8 && h->direct_ok && lay.fits_stage()) {
     // single requests (DeepRetrieval.recommend's serving loop, examples/.../dr/package.scala:107-111): request and results live in the
-    // host-mapped pinned staging block — the kernels read and write it in place, no copy on either side of the three launches
-    if ((rc = ensure_stage(h)) != DM_OK) return rc;
-    char *hb = h->h_stage, *db = h->d_stage;      // the block as the host / the kernels address it
-    memcpy(hb, seq_ids, b_seq);
-    double *m_sc = (double *)(hb + DevArena::up(b_seq));
-    int32_t *m_ids = (int32_t *)(hb + DevArena::up(b_seq) + DevArena::up(b_sc)), *m_cnt = (int32_t *)(hb + DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids));
-    if ((rc = dr_recommend_dev(h, (const int32_t *)db, U, beam, topk, (int32_t *)(db + DevArena::up(b_seq) + DevArena::up(b_sc)), (double *)(db + DevArena::up(b_seq)),
-                               (int32_t *)(db + DevArena::up(b_seq) + DevArena::up(b_sc) + DevArena::up(b_ids)))) != DM_OK) return rc;
+    // host-mapped pinned staging block — the kernels read and write it in place, no copy on either side of the three launches.
+    // The stream is synchronized; no counts are polled.
+    if ((rc = lay.stage(seq_ids)) != DM_OK) return rc;
+    if ((rc = dr_recommend_dev(h, lay.stage_ptr(d_seq), U, beam, topk, lay.stage_ptr(d_ids), lay.stage_ptr(d_sc), lay.stage_ptr(d_cnt))) != DM_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    memcpy(out_ids, m_ids, b_ids); memcpy(out_scores, m_sc, b_sc); memcpy(out_counts, m_cnt, b_cnt);
+    lay.copy_from_stage();
     return DM_OK;
   }
-  HIPCHK(h, hipMemcpyAsync(d_seq, seq_ids, b_seq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, lay.upload(seq_ids));
   if ((rc = dr_recommend_dev(h, d_seq, U, beam, topk, d_ids, d_sc, d_cnt)) != DM_OK) return rc;
-  HIPCHK(h, hipMemcpyAsync(out_ids, d_ids, b_ids, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_scores, d_sc, b_sc, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(out_counts, d_cnt, b_cnt, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, lay.finish());
   return DM_OK;
 }

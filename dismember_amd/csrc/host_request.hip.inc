@@ -1,6 +1,7 @@
-// Host-request layer (host code only): the mechanisms the host-buffer beam-search front ends share (tdm_search_host, otm_search_host in
-// dm_hip.hip, otm64_search_host in otm64.hip.inc) and the event pair around one launch.  A front end states its own policy — which
-// requests are staged, served in place or cut into chunks — and calls these.
+// Host-request layer (host code only): what the six host-buffer search front ends share — tdm_search_host and otm_search_host
+// (dm_hip.hip), otm64_search_host (otm64.hip.inc), dfm_otm_search_host (dfm_otm.hip.inc), dm_dr_beam_search and dm_dr_recommend
+// (dr_host.hip.inc) — and the event pair around one launch.  ReqLayout owns the layout of a request and its invariants; a front end
+// keeps its own checks and its own policy — which requests are staged, served in place or cut into chunks — and calls the layout.
 
 // ---- frontier sizing of a beam search: cap = slots of a level's candidate list (2 * beam in whole 16-row tiles, at least two tiles),
 // pcap = the sort's power of two above it
@@ -80,38 +81,112 @@ struct ReqArena : DevArena {
 // ---- one result array of a request: `bytes_per_user` bytes per user at `dev` (in the arena, or a per-call buffer) go to `host`
 struct HostOut { void *host; const void *dev; size_t bytes_per_user; };
 
-// plain download: every array on `stream`; the caller synchronizes
-static hipError_t download_all(dm_ctx *h, const HostOut *outs, int n, int64_t U, hipStream_t stream) {
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < n && e == hipSuccess; i++) e = hipMemcpyAsync(outs[i].host, outs[i].dev, outs[i].bytes_per_user * (size_t)U, hipMemcpyDeviceToHost, stream);
-  return e;
-}
+// ---- request layout: the arrays of one host-buffer request in a grow-only buffer, in the one order
+//   [seq | ids | scores | counts | trace codes | trace scores | trace counts | extra 0 | extra 1]
+// and the three things that order is for:
+//   1. the pinned staging block (ensure_stage) mirrors the head [seq .. counts]: an array at arena offset o is staged at h_stage + o,
+//      and the single-request kernels address it as d_stage + o (stage_ptr);
+//   2. ids, scores and counts are adjacent, so a staged download is ONE copy;
+//   3. trace codes, scores and counts are adjacent, so ONE memset clears them (the kernels write the live slots only).
+// Arena sizes, device pointers and the HostOut table come from the same bytes[] and cannot disagree.  A front end constructs it,
+// names the optional arrays (trace, extras), commits, and states its policy in terms of fits_stage() / stage() / arm_direct().
+struct ReqLayout {
+  enum { SEQ, IDS, SCORES, COUNTS, TC, TS, TN, X0, X1, N };
+  dm_ctx *h; DevArena ar; int64_t U;
+  size_t bytes[N] = {};          // per user (X0, X1: the whole array); 0 = the array is absent
+  char *dev[N] = {};             // null where absent
+  size_t head_bytes = 0;         // [seq .. counts]
+  bool trace_external = false, staged = false;
+  HostOut outs[6] = {};          // ids, scores, counts, trace codes, trace scores, trace counts
 
-// The pinned staging block (ensure_stage) mirrors the head of the arena: a buffer at arena offset o is staged at h_stage + o, and the
-// single-request kernels address it as d_stage + o.
-static char *stage_of(const dm_ctx *h, const void *dev) { return h->h_stage + ((const char *)dev - (const char *)h->req.p); }
-static void copy_from_stage(const dm_ctx *h, const HostOut *outs, int n, int64_t U) {
-  for (int i = 0; i < n; i++) memcpy(outs[i].host, stage_of(h, outs[i].dev), outs[i].bytes_per_user * (size_t)U);
-}
-// staged download: outs[0] .. outs[n - 1] are adjacent in the arena and come down as ONE block; the caller synchronizes, then copy_from_stage()
-static hipError_t download_staged(dm_ctx *h, const HostOut *outs, int n, int64_t U) {
-  const char *first = (const char *)outs[0].dev, *end = (const char *)outs[n - 1].dev + outs[n - 1].bytes_per_user * (size_t)U;
-  return hipMemcpyAsync(stage_of(h, first), first, (size_t)(end - first), hipMemcpyDeviceToHost, h->stream);
-}
+  // ids [U][stride][id_width] int32, scores [U][stride] of score_bytes (4 or 8), counts [U]; buf grows by need / slack_div (0: exactly)
+  ReqLayout(dm_ctx *h_, DevGrow &buf, size_t slack_div, int64_t U_, size_t seq_bytes, size_t stride, size_t score_bytes, size_t id_width = 1)
+      : h(h_), ar(buf, slack_div), U(U_) {
+    bytes[SEQ] = seq_bytes; bytes[IDS] = stride * id_width * 4; bytes[SCORES] = stride * score_bytes; bytes[COUNTS] = 4;
+  }
+  // level traces [U][max_levels][cap]; external: the caller owns the three buffers (trace_at), the arena holds none
+  void trace(int max_levels, int cap, size_t score_bytes, bool external = false) {
+    bytes[TC] = (size_t)max_levels * cap * 4; bytes[TS] = (size_t)max_levels * cap * score_bytes; bytes[TN] = (size_t)max_levels * 4;
+    trace_external = external;
+  }
+  void extras(size_t bytes0, size_t bytes1) { bytes[X0] = bytes0; bytes[X1] = bytes1; }
+  size_t array_bytes(int a) const { return a >= X0 ? bytes[a] : bytes[a] * (size_t)U; }
+  size_t result_bytes_per_user() const { return bytes[IDS] + bytes[SCORES]; }
 
-// ---- single-request path: the kernel writes whole result rows into the host-mapped staging block and publishes each user's count
-// last; the caller has set the counts to -1 and launched.  Polls the counts; every 4096 spins a look at the stream: idle (or failed)
-// with counts still missing is a kernel fault.
-static int wait_host_direct(dm_ctx *h, volatile int32_t *m_cnt, int64_t U, const char *who) {
-  auto all_in = [&] { bool ok = true; for (int64_t u = 0; u < U; u++) ok = ok && m_cnt[u] >= 0; return ok; };
-  for (long spin = 0; !all_in(); spin++)
-    if ((spin & 0xFFF) == 0xFFF && hipStreamQuery(h->stream) != hipErrorNotReady) {
-      const hipError_t e = hipStreamSynchronize(h->stream);
-      if (!all_in()) return fail(h, DM_ERR_HIP, std::string(who) + " (single-request path): " + (e != hipSuccess ? hipGetErrorString(e) : "kernel finished without results"));
+  // host_* : where the result arrays go (trace ones null without a trace)
+  int commit(void *host_ids, void *host_scores, void *host_counts, void *host_tc = nullptr, void *host_ts = nullptr, void *host_tn = nullptr) {
+    size_t off[N];
+    for (int a = 0; a < N; a++) {
+      off[a] = ar.add(trace_external && a >= TC && a <= TN ? 0 : array_bytes(a));
+      if (a == COUNTS) head_bytes = ar.need;
     }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  return DM_OK;
-}
+    const int rc = ar.commit(h);
+    if (rc != DM_OK) return rc;
+    for (int a = 0; a < N; a++) dev[a] = bytes[a] ? ar.base + off[a] : nullptr;
+    void *const host[6] = {host_ids, host_scores, host_counts, host_tc, host_ts, host_tn};
+    for (int i = 0; i < 6; i++) outs[i] = {host[i], dev[IDS + i], bytes[IDS + i]};
+    return DM_OK;
+  }
+  void trace_at(void *d_tc, void *d_ts, void *d_tn) {
+    dev[TC] = (char *)d_tc; dev[TS] = (char *)d_ts; dev[TN] = (char *)d_tn;
+    for (int i = 3; i < 6; i++) outs[i].dev = dev[IDS + i];
+  }
+  template <typename T> T *d(int a) const { return (T *)dev[a]; }
+  bool has_trace() const { return bytes[TN] != 0; }
+  int n_outs() const { return has_trace() ? 6 : 3; }
+
+  // small requests go up and come down through ONE pinned block: a pageable copy costs 10-15 us each, a single-user search 60 us
+  bool fits_stage() const { return !has_trace() && !bytes[X0] && !bytes[X1] && head_bytes <= (256u << 10); }
+  int stage(const void *seq) {
+    const int rc = ensure_stage(h);
+    if (rc != DM_OK) return rc;
+    memcpy(h->h_stage, seq, array_bytes(SEQ));
+    staged = true;
+    return DM_OK;
+  }
+  char *host_view(const void *p) const { return h->h_stage + ((const char *)p - ar.base); }
+  template <typename T> T *stage_ptr(T *p) const { return (T *)(h->d_stage + ((const char *)p - ar.base)); }
+  void copy_from_stage() const {
+    for (int i = 0; i < 3; i++) memcpy(outs[i].host, host_view(outs[i].dev), outs[i].bytes_per_user * (size_t)U);
+  }
+  hipError_t upload(const void *seq) const {
+    return hipMemcpyAsync(dev[SEQ], staged ? (const void *)h->h_stage : seq, array_bytes(SEQ), hipMemcpyHostToDevice, h->stream);
+  }
+  hipError_t clear_trace() const {
+    if (!trace_external) return hipMemsetAsync(dev[TC], 0, (size_t)(dev[TN] + array_bytes(TN) - dev[TC]), h->stream);
+    hipError_t e = hipSuccess;
+    for (int a = TC; a <= TN && e == hipSuccess; a++) e = hipMemsetAsync(dev[a], 0, array_bytes(a), h->stream);
+    return e;
+  }
+  // after the search: the download (one block when staged), the synchronize, and the way out of the staging block
+  hipError_t finish() const {
+    hipError_t e = hipSuccess;
+    if (staged) e = hipMemcpyAsync(host_view(dev[IDS]), dev[IDS], (size_t)(dev[COUNTS] + array_bytes(COUNTS) - dev[IDS]), hipMemcpyDeviceToHost, h->stream);
+    else for (int i = 0; i < n_outs() && e == hipSuccess; i++) e = hipMemcpyAsync(outs[i].host, outs[i].dev, outs[i].bytes_per_user * (size_t)U, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && staged) copy_from_stage();
+    return e;
+  }
+  // single-request path: the kernel reads the request from the host-mapped staging block and writes whole result rows into it,
+  // publishing each user's count last.  arm_direct() sets the counts to -1 before the launch; wait_direct() polls them (every 4096
+  // spins a look at the stream: idle or failed with counts still missing is a kernel fault) and copies the results out.
+  void arm_direct() const {
+    volatile int32_t *m_cnt = (volatile int32_t *)host_view(dev[COUNTS]);
+    for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
+  }
+  int wait_direct(const char *who) const {
+    volatile int32_t *m_cnt = (volatile int32_t *)host_view(dev[COUNTS]);
+    auto all_in = [&] { bool ok = true; for (int64_t u = 0; u < U; u++) ok = ok && m_cnt[u] >= 0; return ok; };
+    for (long spin = 0; !all_in(); spin++)
+      if ((spin & 0xFFF) == 0xFFF && hipStreamQuery(h->stream) != hipErrorNotReady) {
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        if (!all_in()) return fail(h, DM_ERR_HIP, std::string(who) + " (single-request path): " + (e != hipSuccess ? hipGetErrorString(e) : "kernel finished without results"));
+      }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    copy_from_stage();
+    return DM_OK;
+  }
+};
 
 // ---- pipelined download of a request cut into chunks of users (host_pipe_plan in dm_hip.hip says why and how).
 // fn(k, u0, uk) enqueues the search of chunk k = users [u0, u0 + uk); a chunk k > 0 keeps the scored-rows counter counting

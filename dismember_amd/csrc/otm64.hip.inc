@@ -433,52 +433,33 @@ static int otm64_search_host(dm_ctx *h, const int32_t *seq_codes, int64_t U, int
     return fail(h, DM_ERR_STATE, "fp64 OTM beam search needs f64 weights (dm_load_weights_din with DM_F64)");
   if (U == 0) return DM_OK;
   if (!seq_codes || !out_node_ids || !out_counts || (!out_sc64 && !out_sc32)) return fail(h, DM_ERR_INVALID, "dm_otm_beam_search (fp64): bad arguments");
-  for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_otm_beam_search: history code outside the embedding table");
+  if ((rc = check_table_ids(h, "dm_otm_beam_search", "history code", seq_codes, U * L, -1)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   int cap;
   frontier_caps(beam, &cap, nullptr);
-  const size_t stride = (size_t)2 * beam, ssz = out_sc64 ? 8 : 4, tsz = ts64 ? 8 : 4, b_seq = (size_t)U * L * 4, nt = tn ? (size_t)U * max_levels : 0;
-  // request arena: [seq | ids | scores | counts | trace codes | trace scores | trace counts]
-  ReqArena ar(h);
-  const size_t o_seq = ar.add(b_seq), o_ids = ar.add(U * stride * 4), o_sc = ar.add(U * stride * ssz), o_cnt = ar.add((size_t)U * 4), o_end = ar.need;
-  const size_t o_tc = ar.add(nt * cap * 4), o_ts = ar.add(nt * cap * tsz), o_tn = ar.add(nt * 4);
-  if ((rc = ar.commit(h)) != DM_OK) return rc;
-  int32_t *d_seq = ar.ptr<int32_t>(o_seq), *d_ids = ar.ptr<int32_t>(o_ids), *d_cnt = ar.ptr<int32_t>(o_cnt);
-  void *d_sc = ar.ptr<char>(o_sc);
-  int32_t *d_tc = tn ? ar.ptr<int32_t>(o_tc) : nullptr, *d_tn = tn ? ar.ptr<int32_t>(o_tn) : nullptr;
-  void *d_ts = tn ? ar.ptr<char>(o_ts) : nullptr;
-  const HostOut outs[6] = {{out_node_ids, d_ids, stride * 4}, {out_sc64 ? (void *)out_sc64 : (void *)out_sc32, d_sc, stride * ssz}, {out_counts, d_cnt, 4},
-                           {tc, d_tc, (size_t)max_levels * cap * 4}, {ts64 ? (void *)ts64 : (void *)ts32, d_ts, (size_t)max_levels * cap * tsz}, {tn, d_tn, (size_t)max_levels * 4}};
-  // small requests (OTM.recommend's one-user-per-call loop, examples/.../otm/package.scala:101-105): the request goes up and the
-  // results come down through ONE pinned staging block
-  const bool staged = !tn && o_end <= (256u << 10);
-  if (staged && (rc = ensure_stage(h)) != DM_OK) return rc;
-  if (staged) memcpy(h->h_stage, seq_codes, b_seq);
-  if (staged && h->direct_ok && U <= 8) {
-    // Single-request path (OTM.recommend's serving loop): the staging block is host-mapped — the fused kernel reads the request from
-    // it and writes ids / scores / counts into it (whole rows, then a system-scope fence, then the count as the flag); the host polls.
-    volatile int32_t *m_cnt = (volatile int32_t *)(h->h_stage + o_cnt);
-    for (int64_t u = 0; u < U; u++) m_cnt[u] = -1;
+  ReqLayout lay(h, h->req, 2, U, (size_t)L * 4, (size_t)2 * beam, out_sc64 ? 8 : 4);
+  if (tn) lay.trace(max_levels, cap, ts64 ? 8 : 4);
+  if ((rc = lay.commit(out_node_ids, out_sc64 ? (void *)out_sc64 : (void *)out_sc32, out_counts, tc, ts64 ? (void *)ts64 : (void *)ts32, tn)) != DM_OK) return rc;
+  int32_t *d_seq = lay.d<int32_t>(lay.SEQ), *d_ids = lay.d<int32_t>(lay.IDS), *d_cnt = lay.d<int32_t>(lay.COUNTS);
+  char *d_sc = lay.d<char>(lay.SCORES), *d_ts = lay.d<char>(lay.TS);
+  // small requests: OTM.recommend's one-user-per-call loop, examples/.../otm/package.scala:101-105
+  if (lay.fits_stage() && (rc = lay.stage(seq_codes)) != DM_OK) return rc;
+  if (lay.staged && h->direct_ok && U <= 8) {
+    lay.arm_direct();
     bool done = false;
-    void *k_sc = h->d_stage + o_sc;          // the same block as the kernel addresses it
-    rc = beam64_search_dev(h, (const int32_t *)h->d_stage, U, L, beam, leaf_level, (int32_t *)(h->d_stage + o_ids), out_sc64 ? (double *)k_sc : nullptr,
-                           out_sc64 ? nullptr : (float *)k_sc, (int32_t *)(h->d_stage + o_cnt), 0, cap, nullptr, nullptr, nullptr, nullptr, &done, true);
+    void *k_sc = lay.stage_ptr(d_sc);
+    rc = beam64_search_dev(h, lay.stage_ptr(d_seq), U, L, beam, leaf_level, lay.stage_ptr(d_ids), out_sc64 ? (double *)k_sc : nullptr,
+                           out_sc64 ? nullptr : (float *)k_sc, lay.stage_ptr(d_cnt), 0, cap, nullptr, nullptr, nullptr, nullptr, &done, true);
     if (rc != DM_OK) return rc;
-    if (done) {
-      if ((rc = wait_host_direct(h, m_cnt, U, "fp64 OTM beam search")) == DM_OK) copy_from_stage(h, outs, 3, U);
-      return rc;
-    }
+    if (done) return lay.wait_direct("fp64 OTM beam search");
     // the fused kernel did not take it (pipeline fallback): the staged path below
   }
-  HIPCHK(h, hipMemcpyAsync(d_seq, staged ? (const void *)h->h_stage : (const void *)seq_codes, b_seq, hipMemcpyHostToDevice, h->stream));
-  if (tn) HIPCHK(h, hipMemsetAsync(d_tc, 0, ar.need - o_tc, h->stream));   // trace codes, scores and counts are adjacent
+  HIPCHK(h, lay.upload(seq_codes));
+  if (tn) HIPCHK(h, lay.clear_trace());
   rc = otm64_search_dev(h, d_seq, U, L, beam, leaf_level, d_ids, out_sc64 ? (double *)d_sc : nullptr, out_sc64 ? nullptr : (float *)d_sc,
-                        d_cnt, max_levels, cap, d_tc, ts64 ? (double *)d_ts : nullptr, (tn && !ts64) ? (float *)d_ts : nullptr, d_tn);
+                        d_cnt, max_levels, cap, lay.d<int32_t>(lay.TC), ts64 ? (double *)d_ts : nullptr, (tn && !ts64) ? (float *)d_ts : nullptr, lay.d<int32_t>(lay.TN));
   if (rc != DM_OK) return rc;
-  HIPCHK(h, staged ? download_staged(h, outs, 3, U) : download_all(h, outs, tn ? 6 : 3, U, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (staged) copy_from_stage(h, outs, 3, U);
+  HIPCHK(h, lay.finish());
   return DM_OK;
 }
 

@@ -243,8 +243,7 @@ static int otm_train_batch_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, i
   const int64_t leaf_lo = ((int64_t)1 << o->leaf_level) - 1, leaf_hi = ((int64_t)2 << o->leaf_level) - 2;
   for (int64_t i = 0; i < NT; i++)
     if (target_nodes[i] < leaf_lo || target_nodes[i] > leaf_hi) return fail(h, DM_ERR_INDEX, who + ": a target is not a node of the leaf level");
-  for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, who + ": history code outside the embedding table");
+  if ((rc = check_table_ids(h, who.c_str(), "history code", seq_codes, U * L, -1)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   dm_otm_stats &st = h->otm_stats;
   st = dm_otm_stats{};
@@ -391,10 +390,8 @@ static int otm_pseudo_targets_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes
   const int levels = o->leaf_level - start_level;
   if (levels < 1 || target_off[0] != 0) return fail(h, DM_ERR_INVALID, who + ": bad levels / target_off");
   const int64_t NT = target_off[U];
-  for (int64_t i = 0; i < NT; i++)
-    if (target_nodes[i] < 1 || target_nodes[i] >= h->num_index) return fail(h, DM_ERR_INDEX, who + ": target outside the embedding table");
-  for (int64_t i = 0; i < U * L; i++)
-    if (seq_codes[i] != -1 && (seq_codes[i] < 0 || seq_codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, who + ": history code outside the embedding table");
+  if ((rc = check_table_ids(h, who.c_str(), "target", target_nodes, NT, 1)) != DM_OK ||
+      (rc = check_table_ids(h, who.c_str(), "history code", seq_codes, U * L, -1)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
   const OtmTgtArena ar = otm_tgt_arena(U, L, NT, levels);
   char *A = nullptr;

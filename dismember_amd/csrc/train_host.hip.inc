@@ -238,10 +238,8 @@ int dm_train_forward_backward(dm_handle_t h, const int32_t *codes, const int32_t
   if (rc != DM_OK) return rc;
   if (!codes || !seqs || !labels || B <= 0 || L <= 0 || L > DM_PIPE_MAXL || n_pad < 0 || (n_pad > 0 && !pad_flat_idx))
     return fail(h, DM_ERR_INVALID, "dm_train_forward_backward: bad arguments (L must be 1..32)");
-  for (int64_t i = 0; i < B; i++)
-    if (codes[i] != -1 && (codes[i] < 0 || codes[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_train_forward_backward: item index outside the embedding table");
-  for (int64_t i = 0; i < B * L; i++)
-    if (seqs[i] != -1 && (seqs[i] < 0 || seqs[i] >= h->num_index)) return fail(h, DM_ERR_INDEX, "dm_train_forward_backward: history index outside the embedding table");
+  if ((rc = check_table_ids(h, "dm_train_forward_backward", "item index", codes, B, -1)) != DM_OK ||
+      (rc = check_table_ids(h, "dm_train_forward_backward", "history index", seqs, B * L, -1)) != DM_OK) return rc;
   for (int64_t i = 0; i < n_pad; i++)
     if (pad_flat_idx[i] < 0 || pad_flat_idx[i] >= B * L) return fail(h, DM_ERR_INDEX, "dm_train_forward_backward: mask index outside [0, B*L)");
   HIPCHK(h, hipSetDevice(h->device));
