@@ -85,6 +85,8 @@ SIGNATURES = {
     "dm_deepfm_train_forward_backward": (C.c_int, [C.c_void_p, i32p, i32p, f32p, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
     "dm_deepfm_train_forward_backward_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                                        C.POINTER(C.c_double)]),
+    "dm_deepfm_train_forward_backward_grouped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                               C.POINTER(C.c_double)]),
     "dm_deepfm_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
     "dm_deepfm_train_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dm_deepfm_train_download": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_int64]),

@@ -95,6 +95,84 @@ struct DfmTrainRows {
 
 #define DFM_WAVE_LDS_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
+// ---- what dfm_train_rows_kernel and the user-grouped dfm_tg_rows_kernel (dfm_train_grouped.hip.inc) share: a tile's epilogue and the
+// workgroup's partials.  acc: H of the tile in the C layout; fm: of row r in every lane (., r); dhl: the wave's 16 x (16 NCT + 1) floats of
+// LDS.  Adds the tile to lsum / gsum / pw2, stores dH (and g, where the caller keeps it), returns pass 2's operands grow and dhb
+struct DfmTrainEpi { const float *l1_b, *l2_w, *labels; float *dH, *g /* [B], or NULL */; int64_t B; int T; float fB, b2; };
+template <int NCT>
+__device__ __forceinline__ void dfm_train_epilogue(const DfmTrainEpi &q, const f32x4 (&acc)[NCT], float fm, int64_t row0, int r, int g, float *dhl, double &lsum,
+                                                   float &gsum, float (&pw2)[NCT], float &grow, float (&dhb)[4 * NCT]) {
+  constexpr int NC = NCT * 16, LDH = NC + 1;
+  // ---- epilogue in the C layout: lane (g, r) holds rows 4 g .. 4 g + 3 of column 16 ct + r
+  float zl[4] = {0.f, 0.f, 0.f, 0.f}, hv[NCT][4], aw[NCT][4], gr[4];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ct++) {
+    const int col = 16 * ct + r;
+    const float b1 = col < q.T ? q.l1_b[col] : 0.0f, w2 = col < q.T ? q.l2_w[col] : 0.0f;
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+      const float zp = acc[ct][rr] + b1;
+      hv[ct][rr] = fmaxf(zp, 0.0f);
+      aw[ct][rr] = zp > 0.0f ? w2 : 0.0f;
+      zl[rr] = fmaf(w2, hv[ct][rr], zl[rr]);
+    }
+  }
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) zl[rr] += __shfl_xor(zl[rr], o);
+    const int64_t row = row0 + 4 * g + rr;
+    const float z = __shfl(fm, 4 * g + rr) + (zl[rr] + q.b2);
+    float loss = 0.0f, gz = 0.0f;
+    if (row < q.B) {
+      const float y = q.labels[row], e = expf(-fabsf(z));
+      loss = (fmaxf(z, 0.0f) - z * y) + log1pf(e);
+      gz = ((z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e)) - y) / q.fB;
+      if (q.g && r == 0) q.g[row] = gz;
+    }
+    gr[rr] = gz;
+    if (r == 0) { lsum += (double)loss; gsum += gz; }
+  }
+#pragma unroll
+  for (int ct = 0; ct < NCT; ct++) {
+    const int col = 16 * ct + r;
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+      const float dh = gr[rr] * aw[ct][rr];
+      dhl[(4 * g + rr) * LDH + col] = dh;
+      if (row0 + 4 * g + rr < q.B) q.dH[(row0 + 4 * g + rr) * NC + col] = dh;
+      pw2[ct] = fmaf(gr[rr], hv[ct][rr], pw2[ct]);
+    }
+  }
+  DFM_WAVE_LDS_SYNC();
+  // ---- pass 2: dX_i^T = W1_i^T dH^T; lane (g, r) supplies dH[row r][unit 4 ks + g] and receives row r, features 16 jn + 4 g ..
+  grow = 0.0f;
+#pragma unroll
+  for (int rr = 0; rr < 4; rr++) {
+    const float t = __shfl(gr[rr], (r >> 2) * 16);
+    if ((r & 3) == rr) grow = t;
+  }
+#pragma unroll
+  for (int ks = 0; ks < 4 * NCT; ks++) dhb[ks] = dhl[r * LDH + 4 * ks + g];
+}
+template <int NCT>
+__device__ __forceinline__ void dfm_train_partials(double lsum, float gsum, float (&pw2)[NCT], double *wloss, float (*wpg)[1 + 16 * NCT], double *ploss, float *pg) {
+  constexpr int NC = NCT * 16;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
+  // ---- the workgroup's partials: lanes (g, 0) hold the loss and g of their rows, lanes (g, r) the g_l2W part of column 16 ct + r
+  lsum += __shfl_xor(lsum, 16); lsum += __shfl_xor(lsum, 32);
+  gsum += __shfl_xor(gsum, 16); gsum += __shfl_xor(gsum, 32);
+#pragma unroll
+  for (int ct = 0; ct < NCT; ct++) {
+    pw2[ct] += __shfl_xor(pw2[ct], 16); pw2[ct] += __shfl_xor(pw2[ct], 32);
+    if (g == 0) wpg[wave][1 + 16 * ct + r] = pw2[ct];
+  }
+  if (lane == 0) { wloss[wave] = lsum; wpg[wave][0] = gsum; }
+  __syncthreads();
+  if (threadIdx.x < 1 + NC) pg[(int64_t)blockIdx.x * (1 + NC) + threadIdx.x] = ((wpg[0][threadIdx.x] + wpg[1][threadIdx.x]) + wpg[2][threadIdx.x]) + wpg[3][threadIdx.x];
+  if (threadIdx.x == 0) ploss[blockIdx.x] = ((wloss[0] + wloss[1]) + wloss[2]) + wloss[3];
+}
+
 template <int E, int NCT>
 __global__ __launch_bounds__(256) void dfm_train_rows_kernel(DfmTrainRows p) {
   constexpr int NJ = E / 16, NC = NCT * 16, LDH = NC + 1;
@@ -104,7 +182,7 @@ __global__ __launch_bounds__(256) void dfm_train_rows_kernel(DfmTrainRows p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
   const int T = p.T;
   const int64_t tiles = (p.B + 15) / 16;
-  const float fB = (float)p.B, b2 = p.l2_b[0];
+  const DfmTrainEpi q{p.l1_b, p.l2_w, p.labels, p.dH, nullptr, p.B, p.T, (float)p.B, p.l2_b[0]};
   double lsum = 0.0;
   float gsum = 0.0f, pw2[NCT];
 #pragma unroll
@@ -147,56 +225,10 @@ __global__ __launch_bounds__(256) void dfm_train_rows_kernel(DfmTrainRows p) {
     ss += __shfl_xor(ss, 16); ss += __shfl_xor(ss, 32);
     sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
     const float fm = 0.5f * (ss - sq);                 // of row r, in every lane (., r)
-    // ---- epilogue in the C layout: lane (g, r) holds rows 4 g .. 4 g + 3 of column 16 ct + r
-    float zl[4] = {0.f, 0.f, 0.f, 0.f}, hv[NCT][4], aw[NCT][4], gr[4];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ct++) {
-      const int col = 16 * ct + r;
-      const float b1 = col < T ? p.l1_b[col] : 0.0f, w2 = col < T ? p.l2_w[col] : 0.0f;
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) {
-        const float zp = acc[ct][rr] + b1;
-        hv[ct][rr] = fmaxf(zp, 0.0f);
-        aw[ct][rr] = zp > 0.0f ? w2 : 0.0f;
-        zl[rr] = fmaf(w2, hv[ct][rr], zl[rr]);
-      }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) zl[rr] += __shfl_xor(zl[rr], o);
-      const int64_t row = row0 + 4 * g + rr;
-      const float z = __shfl(fm, 4 * g + rr) + (zl[rr] + b2);
-      float loss = 0.0f, gz = 0.0f;
-      if (row < p.B) {
-        const float y = p.labels[row], e = expf(-fabsf(z));
-        loss = (fmaxf(z, 0.0f) - z * y) + log1pf(e);
-        gz = ((z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e)) - y) / fB;
-      }
-      gr[rr] = gz;
-      if (r == 0) { lsum += (double)loss; gsum += gz; }
-    }
-#pragma unroll
-    for (int ct = 0; ct < NCT; ct++) {
-      const int col = 16 * ct + r;
-#pragma unroll
-      for (int rr = 0; rr < 4; rr++) {
-        const float dh = gr[rr] * aw[ct][rr];
-        dhl[wave][(4 * g + rr) * LDH + col] = dh;
-        if (row0 + 4 * g + rr < p.B) p.dH[(row0 + 4 * g + rr) * NC + col] = dh;
-        pw2[ct] = fmaf(gr[rr], hv[ct][rr], pw2[ct]);
-      }
-    }
-    DFM_WAVE_LDS_SYNC();
-    // ---- pass 2: dX_i^T = W1_i^T dH^T; lane (g, r) supplies dH[row r][unit 4 ks + g] and receives row r, features 16 jn + 4 g ..
-    float grow = 0.0f, dhb[4 * NCT];
-#pragma unroll
-    for (int rr = 0; rr < 4; rr++) {
-      const float t = __shfl(gr[rr], (r >> 2) * 16);
-      if ((r & 3) == rr) grow = t;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4 * NCT; ks++) dhb[ks] = dhl[wave][r * LDH + 4 * ks + g];
+    // ---- epilogue in the C layout, then pass 2: dX_i^T = W1_i^T dH^T; lane (g, r) supplies dH[row r][unit 4 ks + g] and receives row r,
+    // features 16 jn + 4 g ..
+    float grow, dhb[4 * NCT];
+    dfm_train_epilogue<NCT>(q, acc, fm, row0, r, g, dhl[wave], lsum, gsum, pw2, grow, dhb);
     for (int i = 0; i < T; i++) {
       const int32_t id = in ? ids[i] : -1;
       float *dst = p.dX + (myrow * T + i) * E + 4 * g;
@@ -217,18 +249,7 @@ __global__ __launch_bounds__(256) void dfm_train_rows_kernel(DfmTrainRows p) {
     }
     DFM_WAVE_LDS_SYNC();               // the next tile overwrites dhl
   }
-  // ---- the workgroup's partials: lanes (g, 0) hold the loss and g of their rows, lanes (g, r) the g_l2W part of column 16 ct + r
-  lsum += __shfl_xor(lsum, 16); lsum += __shfl_xor(lsum, 32);
-  gsum += __shfl_xor(gsum, 16); gsum += __shfl_xor(gsum, 32);
-#pragma unroll
-  for (int ct = 0; ct < NCT; ct++) {
-    pw2[ct] += __shfl_xor(pw2[ct], 16); pw2[ct] += __shfl_xor(pw2[ct], 32);
-    if (g == 0) wpg[wave][1 + 16 * ct + r] = pw2[ct];
-  }
-  if (lane == 0) { wloss[wave] = lsum; wpg[wave][0] = gsum; }
-  __syncthreads();
-  if (threadIdx.x < 1 + NC) p.pg[(int64_t)blockIdx.x * (1 + NC) + threadIdx.x] = ((wpg[0][threadIdx.x] + wpg[1][threadIdx.x]) + wpg[2][threadIdx.x]) + wpg[3][threadIdx.x];
-  if (threadIdx.x == 0) p.ploss[blockIdx.x] = ((wloss[0] + wloss[1]) + wloss[2]) + wloss[3];
+  dfm_train_partials<NCT>(lsum, gsum, pw2, wloss, wpg, p.ploss, p.pg);
 }
 
 // workgroup partials -> loss (mean, double), g_l2b, g_l2W, workgroup 0 first; one block of 64 threads (1 + NC <= 49)
@@ -347,6 +368,33 @@ int dm_deepfm_train_free(dm_handle_t h) {
   return DM_OK;
 }
 
+// ---- what the row step and the user-grouped step (dfm_train_grouped.hip.inc) share on the host
+// zeroGradParameters for the table: the rows the last batch reached, of either step (the dense blocks are overwritten by every step)
+static int dfm_train_clear_prev(dm_ctx *h, dm_dfm_train *t) {
+  if (t->vec.prev_m <= 0) return DM_OK;
+  hipLaunchKernelGGL((drt_seg_rows_kernel<float, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->vec.prev.p, nullptr,
+                     t->vec.prev_m, h->num_index, nullptr, h->embed, (float *)t->vec.grad);
+  HIPCHK(h, hipGetLastError());
+  t->vec.forget();
+  return DM_OK;
+}
+// g_emb: the m slots idx[i] -> dX[i] sorted by destination row, chunk sums, one wave per destination; the rows are remembered and marked active
+static int dfm_train_emb_grad(dm_ctx *h, dm_dfm_train *t, const int32_t *idx, int64_t m, float *dX, const DrtSortBufs &sb, bool detail) {
+  const int E = h->embed;
+  const int64_t NI = h->num_index;
+  int rc;
+  LaunchTimer tm(h, EV_DFT_EMB, detail);
+  if (tm.rc != DM_OK) return tm.rc;
+  const unsigned long long *ks;
+  const int32_t *vs;
+  if ((rc = drt_sort_slots(h, idx, m, NI, sb, ks, vs)) != DM_OK) return rc;
+  hipLaunchKernelGGL(dfm_seg_chunks_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NI, dX, E);
+  hipLaunchKernelGGL(dfm_seg_heads_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NI, (const float *)dX, E, (float *)t->vec.grad);
+  HIPCHK(h, hipGetLastError());
+  if ((rc = t->vec.remember(h, ks, m)) != DM_OK || (rc = t->vec.mark_active(h, drt_blocks(h, m, 256), idx, m)) != DM_OK) return rc;
+  return tm.stop();
+}
+
 template <int E, int NCT>
 static int dfm_launch_train_rows(dm_ctx *h, const DfmTrainRows &p, int nb, bool timed) {
   LaunchTimer tm(h, EV_DFT_ROWS, timed);
@@ -380,12 +428,7 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
   float *grad = (float *)t->vec.grad;
   float *g_l1w = grad + NI * E, *g_l1b = g_l1w + (int64_t)T * T * E, *g_l2w = g_l1b + T, *g_l2b = g_l2w + T;
   // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
-  if (t->vec.prev_m > 0) {
-    hipLaunchKernelGGL((drt_seg_rows_kernel<float, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->vec.prev.p, nullptr,
-                       t->vec.prev_m, NI, nullptr, E, grad);
-    HIPCHK(h, hipGetLastError());
-    t->vec.forget();
-  }
+  if ((rc = dfm_train_clear_prev(h, t)) != DM_OK) return rc;
   hipLaunchKernelGGL(dfm_train_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seqs, B, L, NI, idx);
   HIPCHK(h, hipGetLastError());
   // ---- forward, loss, dH, dX
@@ -409,23 +452,14 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
     if ((rc = drt_launch_gemm<float>(h, g, EV_DFT_DW, detail)) != DM_OK) return rc;
     LaunchTimer tm(h, EV_DFT_DW, detail);
     if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (cols + 1), 256)), dim3(256), 0, h->stream, (const float *)part, (int)slabs, T, cols, g_l1w, g_l1b);
+    hipLaunchKernelGGL(drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (cols + 1), 256)), dim3(256), 0, h->stream, (const float *)part, (int)slabs, T, cols, g_l1w, g_l1b, (int64_t)cols);
     HIPCHK(h, hipGetLastError());
     if ((rc = tm.stop()) != DM_OK) return rc;
   }
   // ---- g_emb: sort the B T slots by destination row, chunk sums, one wave per destination
   {
-    LaunchTimer tm(h, EV_DFT_EMB, detail);
-    if (tm.rc != DM_OK) return tm.rc;
     const DrtSortBufs sb{ar.ptr<unsigned long long>(o_k0), ar.ptr<unsigned long long>(o_k1), ar.ptr<int32_t>(o_v0), ar.ptr<int32_t>(o_v1), ar.ptr<uint32_t>(o_tmp)};
-    const unsigned long long *ks;
-    const int32_t *vs;
-    if ((rc = drt_sort_slots(h, idx, m, NI, sb, ks, vs)) != DM_OK) return rc;
-    hipLaunchKernelGGL(dfm_seg_chunks_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NI, dX, E);
-    hipLaunchKernelGGL(dfm_seg_heads_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NI, (const float *)dX, E, grad);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = t->vec.remember(h, ks, m)) != DM_OK || (rc = t->vec.mark_active(h, drt_blocks(h, m, 256), idx, m)) != DM_OK) return rc;
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    if ((rc = dfm_train_emb_grad(h, t, idx, m, dX, sb, detail)) != DM_OK) return rc;
   }
   if (out_loss) HIPCHK(h, hipMemcpyAsync(out_loss, ar.ptr<double>(o_loss), 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));

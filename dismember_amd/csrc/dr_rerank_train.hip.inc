@@ -464,7 +464,7 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
     LaunchTimer tm(h, EV_DRR_DW, detail);
     if (tm.rc != DM_OK) return tm.rc;
     hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)E * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, E, cols,
-                       gg + NI * E, gg + NI * E + (int64_t)E * cols);
+                       gg + NI * E, gg + NI * E + (int64_t)E * cols, (int64_t)cols);
     HIPCHK(h, hipGetLastError());
     if ((rc = tm.stop()) != DM_OK) return rc;
   }

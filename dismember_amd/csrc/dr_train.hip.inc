@@ -211,16 +211,16 @@ __global__ __launch_bounds__(256) void drt_gemm_kernel(DrtGemmParams<T> p) {
     }
 }
 
-// slabs [S][K][cols + 1] -> dW [K][cols] and db [K], slab 0 first
+// slabs [S][K][cols + 1] -> dW [K][cols] (row stride ldw: a column range of a wider matrix) and db [K] (or NULL: dropped), slab 0 first
 template <typename T>
-__global__ void drt_slab_sum_kernel(const T *part, int S, int K, int cols, T *gw, T *gb) {
+__global__ void drt_slab_sum_kernel(const T *part, int S, int K, int cols, T *gw, T *gb, int64_t ldw) {
   const int64_t n = (int64_t)K * (cols + 1);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     T s = part[i];
     for (int z = 1; z < S; z++) s += part[(int64_t)z * n + i];
     const int64_t k = i / (cols + 1);
     const int c = (int)(i % (cols + 1));
-    if (c < cols) gw[k * cols + c] = s; else gb[k] = s;
+    if (c < cols) gw[k * ldw + c] = s; else if (gb) gb[k] = s;
   }
 }
 
@@ -429,7 +429,7 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
       LaunchTimer tm(h, EV_DRT_DW, detail);
       if (tm.rc != DM_OK) return tm.rc;
       hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)K * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, K, cols,
-                         grad + off, grad + off + (int64_t)K * cols);
+                         grad + off, grad + off + (int64_t)K * cols, (int64_t)cols);
       HIPCHK(h, hipGetLastError());
       if ((rc = tm.stop()) != DM_OK) return rc;
       off += (int64_t)K * cols + K;

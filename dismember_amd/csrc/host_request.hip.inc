@@ -36,6 +36,9 @@ enum EvKind {
   // the DeepFM training step under DM_DFM_TIME_LAUNCHES=1 (dfm_train.hip.inc): the fused rows kernel (forward, loss, dH, dX), the l1.W / l1.b
   // product with its slab sum, embedding gradient (pairs, sort, segment sums), Adam
   EV_DFT_ROWS = 70, EV_DFT_DW = 71, EV_DFT_EMB = 72, EV_DFT_ADAM = 73,
+  // its user-grouped form (dfm_train_grouped.hip.inc): the per-user set-up, the rows kernel, the per-user backward; its two l1.W products
+  // are EV_DFT_DW and its embedding gradient EV_DFT_EMB
+  EV_DFG_SETUP = 74, EV_DFG_ROWS = 75, EV_DFG_USER_BWD = 76,
   EV_DRR_FWD = 60, EV_DRR_SAMPLE = 61, EV_DRR_SOFTMAX = 62, EV_DRR_SMGRAD = 63, EV_DRR_DX = 64, EV_DRR_DW = 65, EV_DRR_EMB = 66, EV_DRR_ADAM = 67,
   // the Deep-Retrieval M-step's path scores under DM_DR_TIME_LAUNCHES=1 (dr_mstep.hip.inc): pairs of a chunk, the (item, path) sort, segment
   // heads (flags + compaction), segment sums, the sort by score, the sort by item (with its key kernel), the cut at C (flags + compaction),

@@ -306,7 +306,8 @@ static int otm_train_batch_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, i
   unsigned *b_mask = (unsigned *)(A + o_bmask);
   float *b_lab = (float *)(A + o_blab);
   // the level batch replicates a user's history over the user's candidates: the fp64 model trains on it user by user (train_grouped_f64.hip.inc)
-  const bool grouped = f64 && L <= DM_MAXL && tg_enabled();
+  // ... and a DeepFM model under DM_DFM_TRAIN_GROUPED=1 (read per call; dfm_train_grouped.hip.inc).  The row step stays the default
+  const bool grouped = dfm ? dfm_train_grouped_enabled() : f64 && L <= DM_MAXL && tg_enabled();
   for (int it = 0; it < levels; it++) {
     const int nl = n_lv[(size_t)it];
     const int64_t B = U * nl;
@@ -317,7 +318,8 @@ static int otm_train_batch_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, i
                        grouped ? (unsigned *)nullptr : b_mask, b_lab);
     float lf = 0.f;
     double ld = 0.0;
-    if (dfm) rc = dfm_train_fb_dev(h, b_codes, b_seq, b_lab, B, &ld);      // (the row mask is unused: the graph has no mask input)
+    if (dfm && grouped) rc = dfm_train_fb_grouped_dev(h, d_seq, b_codes, b_lab, U, nl, &ld);
+    else if (dfm) rc = dfm_train_fb_dev(h, b_codes, b_seq, b_lab, B, &ld);      // (the row mask is unused: the graph has no mask input)
     else if (grouped) rc = train_fb_grouped_dev(h, d_seq, d_umask, b_codes, b_lab, U, nl, L, &lf);
     else rc = train_fb_dev(h, b_codes, b_seq, b_mask, b_lab, B, L, &lf);
     const auto tb = clk::now();

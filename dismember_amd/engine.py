@@ -805,6 +805,34 @@ class Engine:
         self._chk(N.lib().dm_deepfm_train_forward_backward_dev(self._h, d_codes, d_seqs, d_labels, int(B), int(L), C.byref(loss)))
         return loss.value
 
+    def deepfm_train_forward_backward_grouped(self, seq_codes, codes, labels):
+        """The same step on a user-grouped batch (dm_deepfm_train_forward_backward_grouped_dev): seq_codes [U][L],
+        codes / labels [U][R] — a user's R candidate rows share the user's history, which is read once.  Uploads and calls the device
+        entry (ids are not range-checked: one outside [0, num_index) reads as -1); -> the mean loss (float64)."""
+        seq = _i32(seq_codes)
+        U, L = seq.shape if seq.ndim == 2 else (0, 1)
+        codes = _i32(codes).reshape(U, -1) if U else _i32(codes).reshape(0, 1)
+        R = codes.shape[1]
+        lab = np.ascontiguousarray(labels, np.float32).reshape(U, R)
+        al = lambda v: (v + 255) & ~255
+        buf = self.dev_alloc(al(U * L * 4) + 2 * al(U * R * 4) + 256)
+        try:
+            d_seq = C.c_void_p(buf.value)
+            d_codes = C.c_void_p(buf.value + al(U * L * 4))
+            d_lab = C.c_void_p(d_codes.value + al(U * R * 4))
+            if U and R:
+                self.h2d(d_seq, seq); self.h2d(d_codes, codes); self.h2d(d_lab, lab)
+            return self.deepfm_train_forward_backward_grouped_dev(d_seq, d_codes, d_lab, U, R, L)
+        finally:
+            self.dev_free(buf)
+
+    def deepfm_train_forward_backward_grouped_dev(self, d_seq_codes, d_codes, d_labels, U, R, L):
+        """the same on device arrays: d_seq_codes [U][L], d_codes / d_labels [U * R] user-major -> the mean loss"""
+        loss = C.c_double(0)
+        self._chk(N.lib().dm_deepfm_train_forward_backward_grouped_dev(self._h, d_seq_codes, d_codes, d_labels, int(U), int(R), int(L),
+                                                                       C.byref(loss)))
+        return loss.value
+
     def deepfm_make_train_batch(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, with_prob=False, tolerance=20):
         """make_train_batch for a DeepFM model (no mask): (codes [R], seqs [R, L], labels [R])."""
         seq = _i32(seq_item_ids)

@@ -605,6 +605,15 @@ int dm_deepfm_train_free(dm_handle_t h);                                /* the m
 int dm_deepfm_train_forward_backward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, const float *labels, int64_t B, int L, double *out_loss);
 /* the same on device arrays, NOT range-checked (an id outside [0, num_index) is read as -1); out_loss is still a host pointer */
 int dm_deepfm_train_forward_backward_dev(dm_handle_t h, const int32_t *d_codes, const int32_t *d_seqs, const float *d_labels, int64_t B, int L, double *out_loss);
+/* the same step on a user-grouped batch: U histories d_seq_codes [U][L] and rows_per_user candidate rows per user,
+ * d_codes / d_labels [U * rows_per_user] user-major; row u * rows_per_user + r reads history u, B = U * rows_per_user.  Every history is
+ * read once per user, never once per row; the gradient is the row step's on the expanded rows up to float32 rounding (other, fixed
+ * summation orders).  Device arrays, NOT range-checked (an id outside [0, num_index) is read as -1); out_loss is a host pointer or NULL.
+ * U <= 0, rows_per_user <= 0, a null array or L != the model's seq_len: DM_ERR_INVALID; before dm_deepfm_train_init: DM_ERR_STATE;
+ * B > 4 194 240 or B + U L >= 2^31: DM_ERR_UNSUPPORTED.  dm_deepfm_otm_train_batch takes it for its level batches under
+ * DM_DFM_TRAIN_GROUPED=1 (read per call). */
+int dm_deepfm_train_forward_backward_grouped_dev(dm_handle_t h, const int32_t *d_seq_codes, const int32_t *d_codes, const float *d_labels, int64_t U,
+                                                 int rows_per_user, int L, double *out_loss);
 /* Adam.optimize (S/optim/Adam.scala:19-73) over the vector with dm_dr_adam_step's rules: the embedding rows a gradient has ever reached plus
  * the dense blocks, or the whole vector when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 - the same bytes
  * either way.  Rebuilds every copy the searches read and tells the clones: serving continues with the new weights. */
