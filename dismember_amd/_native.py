@@ -87,6 +87,8 @@ SIGNATURES = {
                                                        C.POINTER(C.c_double)]),
     "dm_deepfm_train_forward_backward_grouped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                                                C.POINTER(C.c_double)]),
+    "dm_deepfm_train_forward_backward_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                                           C.POINTER(C.c_double)]),
     "dm_deepfm_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
     "dm_deepfm_train_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dm_deepfm_train_download": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_int64]),
@@ -94,6 +96,8 @@ SIGNATURES = {
                                              i32p, i32p, f32p, C.c_int64, i64p]),
     "dm_deepfm_sample_train_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, i32p, C.c_int,
                                                    C.POINTER(SampleOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, i64p]),
+    "dm_deepfm_sample_train_batch_csr_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, i32p, C.c_int,
+                                                       C.POINTER(SampleOpts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, i64p]),
     "dm_din_forward": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "dm_tdm_beam_search": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, C.POINTER(SearchOpts), i64p, i32p, i32p,
                                      f32p, i32p]),

@@ -598,6 +598,22 @@ int dm_deepfm_sample_train_batch_dev(dm_handle_t h, const int32_t *d_seq_item_id
   return sample_dev(h, d_seq_item_ids, d_target_item_ids, T, L, neg_counts, opts, d_codes, d_seqs, nullptr, d_labels, cap, n_rows);
 }
 
+int dm_deepfm_sample_train_batch_csr_dev(dm_handle_t h, const int32_t *d_seq_item_ids, const int32_t *d_target_item_ids, int64_t T, int L,
+                                         const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *d_codes,
+                                         int32_t *d_seq_codes, int64_t *d_row_off, float *d_labels, int64_t cap, int64_t *n_rows) {
+  if (!h || !n_rows) return DM_ERR_INVALID;
+  DM_OWNER_ONLY(h, "dm_deepfm_sample_train_batch_csr_dev");
+  int64_t per = 0;
+  int rc = dfm_sample_check(h, "dm_deepfm_sample_train_batch_csr_dev", T, L, neg_counts, n_counts, opts, &per);
+  if (rc != DM_OK) return rc;
+  *n_rows = T * per;
+  if (!d_codes) return DM_OK;                        // size query: an upper bound, the row twin's
+  if (!d_seq_item_ids || !d_target_item_ids || !d_seq_codes || !d_row_off || !d_labels || cap < T * per)
+    return fail(h, DM_ERR_INVALID, "dm_deepfm_sample_train_batch_csr_dev: output buffers too small");
+  HIPCHK(h, hipSetDevice(h->device));
+  return sample_dev(h, d_seq_item_ids, d_target_item_ids, T, L, neg_counts, opts, d_codes, nullptr, nullptr, d_labels, cap, n_rows, d_seq_codes, d_row_off);
+}
+
 int dm_deepfm_make_train_batch(dm_handle_t h, const int32_t *seq_item_ids, const int32_t *target_item_ids, int64_t T, int L,
                                const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *out_codes,
                                int32_t *out_seqs, float *out_labels, int64_t cap, int64_t *n_rows) {

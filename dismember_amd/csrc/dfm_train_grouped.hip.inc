@@ -20,11 +20,48 @@
 //   dfm_train_sum_kernel, drt_gemm_kernel<float> (twice: the B rows through [codes] for block 0 and l1.b, the U users through [seq] for
 //   blocks 1 .. L), drt_slab_sum_kernel, drt_sort_slots + dfm_seg_chunks_kernel + dfm_seg_heads_kernel over the B + U L slots
 // Nothing of size B x L E is read or written.  No floating-point atomics; every sum has a fixed order.
+//
+// Ragged (CSR) form (dm_deepfm_train_forward_backward_csr_dev; DESIGN.md §17): rows row_off[u] .. row_off[u + 1] of codes / labels belong to
+// user u, a user may have none.  The same kernels with CSR = true: the rows kernel reads the user of a row from row_user [B] where the
+// rectangular instance divides by R, the user-backward kernel walks row_off[u] .. row_off[u + 1] (lanes of a tile have different trip
+// counts; still no cross-lane sum, rows ascending).  Two more kernels:
+//   dfm_tg_check_off_kernel  row_off[0] == 0, non-decreasing, row_off[U] == B: the first offending user by an integer atomicMin, read back
+//                            before any other kernel dereferences through the offsets
+//   dfm_tg_idx_csr_kernel    dfm_tg_idx_kernel, plus row_user by a binary search of row_off per row, and -1 for all L history slots of a
+//                            user without rows (it scatters nothing, and dfm_train_emb_grad never marks its history)
 
 __global__ void dfm_tg_idx_kernel(const int32_t *codes, const int32_t *seq, int64_t B, int64_t UL, int64_t num_index, int32_t *idx) {
   const int64_t n = B + UL;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const int32_t id = i < B ? codes[i] : seq[i - B];
+    idx[i] = (id >= 0 && id < num_index) ? id : -1;
+  }
+}
+
+// first u whose offsets are wrong: 0 for row_off[0] != 0, u for row_off[u + 1] < row_off[u], U for row_off[U] != B; *bad starts at ~0
+__global__ void dfm_tg_check_off_kernel(const int64_t *row_off, int64_t U, int64_t B, unsigned long long *bad) {
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u <= U; u += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = row_off[u];
+    const bool wrong = u == U ? a != B : ((u == 0 && a != 0) || row_off[u + 1] < a);
+    if (wrong) atomicMin(bad, (unsigned long long)u);
+  }
+}
+
+// row_off has passed dfm_tg_check_off_kernel: 0 = row_off[0] <= .. <= row_off[U] = B
+__global__ void dfm_tg_idx_csr_kernel(const int32_t *codes, const int32_t *seq, const int64_t *row_off, int64_t B, int64_t U, int L, int64_t num_index,
+                                      int32_t *idx, int32_t *row_user) {
+  const int64_t n = B + U * L;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    int32_t id;
+    if (i < B) {
+      id = codes[i];
+      int64_t lo = 0, hi = U;            // the last u with row_off[u] <= i: row_off[lo] <= i < row_off[hi] throughout
+      while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (row_off[mid] <= i) lo = mid; else hi = mid; }
+      row_user[i] = (int32_t)lo;
+    } else {
+      const int64_t u = (i - B) / L;
+      id = row_off[u + 1] > row_off[u] ? seq[i - B] : -1;
+    }
     idx[i] = (id >= 0 && id < num_index) ? id : -1;
   }
 }
@@ -41,6 +78,8 @@ struct DfmTgParams {
   float *DH;                           // [U][NC]
   double *ploss;                       // [gridDim.x] of the rows kernel
   float *pg;                           // [gridDim.x][1 + NC]: g_l2b, g_l2W
+  const int32_t *row_user;             // CSR instances only: [B] the user of a row
+  const int64_t *row_off;              // CSR instances only: [U + 1]
 };
 
 template <int E, int NCT>
@@ -93,7 +132,7 @@ __global__ __launch_bounds__(256) void dfm_tg_setup_kernel(DfmTgParams p) {
   }
 }
 
-template <int E, int NCT>
+template <int E, int NCT, bool CSR = false>
 __global__ __launch_bounds__(256) void dfm_tg_rows_kernel(DfmTgParams p) {
   constexpr int NJ = E / 16, NC = NCT * 16, LDH = NC + 1;
   __shared__ float dhl[4][16 * LDH];
@@ -109,7 +148,8 @@ __global__ __launch_bounds__(256) void dfm_tg_rows_kernel(DfmTgParams p) {
   for (int64_t tile = (int64_t)blockIdx.x * 4 + wave; tile < tiles; tile += (int64_t)gridDim.x * 4) {
     const int64_t row0 = tile * 16, myrow = row0 + r;
     const bool in = myrow < p.B;
-    const int64_t myu = in ? myrow / p.R : 0;
+    int64_t myu = 0;
+    if constexpr (CSR) { if (in) myu = p.row_user[myrow]; } else myu = in ? myrow / p.R : 0;
     const int32_t id = in ? p.idx[myrow] : -1;
     // ---- pass 1, block 0 only: H = Hh[u] + x_c W1_0^T, buf = bufh[u] + x_c
     f32x4 bh[NJ], x[NJ], acc[NCT];
@@ -125,7 +165,9 @@ __global__ __launch_bounds__(256) void dfm_tg_rows_kernel(DfmTgParams p) {
 #pragma unroll
     for (int rr = 0; rr < 4; rr++) {                    // each of the lane's four C-layout rows reads its own user
       const int64_t row = row0 + 4 * g + rr;
-      const float *hh = p.Hh + (row < p.B ? row / p.R : 0) * NC + r;
+      int64_t ru = 0;
+      if constexpr (CSR) { if (row < p.B) ru = p.row_user[row]; } else ru = row < p.B ? row / p.R : 0;
+      const float *hh = p.Hh + ru * NC + r;
 #pragma unroll
       for (int ct = 0; ct < NCT; ct++) acc[ct][rr] = row < p.B ? hh[16 * ct] : 0.0f;
     }
@@ -162,7 +204,7 @@ __global__ __launch_bounds__(256) void dfm_tg_rows_kernel(DfmTgParams p) {
   dfm_train_partials<NCT>(lsum, gsum, pw2, wloss, wpg, p.ploss, p.pg);
 }
 
-template <int E, int NCT>
+template <int E, int NCT, bool CSR = false>
 __global__ __launch_bounds__(256) void dfm_tg_user_bwd_kernel(DfmTgParams p) {
   constexpr int NJ = E / 16, NC = NCT * 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
@@ -179,8 +221,10 @@ __global__ __launch_bounds__(256) void dfm_tg_user_bwd_kernel(DfmTgParams p) {
 #pragma unroll
     for (int ks = 0; ks < 4 * NCT; ks++) dhb[ks] = 0.0f;
     if (in) {
-      const int64_t rlo = myu * R;
-      for (int q = 0; q < R; q++) {
+      int64_t rlo = myu * R;
+      int nr = R;                      // (CSR: the lanes of a tile have different trip counts; nothing in the loop crosses lanes)
+      if constexpr (CSR) { rlo = p.row_off[myu]; nr = (int)(p.row_off[myu + 1] - rlo); }
+      for (int q = 0; q < nr; q++) {
         const int64_t row = rlo + q;
         const float gv = p.g[row];
         const int32_t id = p.idx[row];
@@ -232,13 +276,13 @@ __global__ __launch_bounds__(256) void dfm_tg_user_bwd_kernel(DfmTgParams p) {
 // ---------------------------------------------------------------------------------------------------------------- host
 static inline bool dfm_train_grouped_enabled() { const char *e = getenv("DM_DFM_TRAIN_GROUPED"); return e && strcmp(e, "1") == 0; }
 
-template <int E, int NCT>
+template <int E, int NCT, bool CSR>
 static int dfm_tg_launch(dm_ctx *h, const DfmTgParams &p, int which, unsigned nb, bool timed) {
   LaunchTimer tm(h, which == 0 ? EV_DFG_SETUP : which == 1 ? EV_DFG_ROWS : EV_DFG_USER_BWD, timed);
   if (tm.rc != DM_OK) return tm.rc;
   if (which == 0) hipLaunchKernelGGL((dfm_tg_setup_kernel<E, NCT>), dim3(nb), dim3(256), 0, h->stream, p);
-  else if (which == 1) hipLaunchKernelGGL((dfm_tg_rows_kernel<E, NCT>), dim3(nb), dim3(256), 0, h->stream, p);
-  else hipLaunchKernelGGL((dfm_tg_user_bwd_kernel<E, NCT>), dim3(nb), dim3(256), 0, h->stream, p);
+  else if (which == 1) hipLaunchKernelGGL((dfm_tg_rows_kernel<E, NCT, CSR>), dim3(nb), dim3(256), 0, h->stream, p);
+  else hipLaunchKernelGGL((dfm_tg_user_bwd_kernel<E, NCT, CSR>), dim3(nb), dim3(256), 0, h->stream, p);
   HIPCHK(h, hipGetLastError());
   return tm.stop();
 }
@@ -249,13 +293,22 @@ static bool dfm_tg_too_large(int64_t U, int64_t R, int L) {
   return B > (int64_t)DRT_MAX_ROWS || B + U * (int64_t)L >= ((int64_t)1 << 31);
 }
 
-static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_codes, const float *d_labels, int64_t U, int R, double *out_loss) {
+static bool dfm_tg_csr_too_large(int64_t U, int64_t B, int L) {
+  return U > (int64_t)DRT_MAX_ROWS || B > (int64_t)DRT_MAX_ROWS || B + U * (int64_t)L >= ((int64_t)1 << 31);
+}
+
+// d_row_off == nullptr: the rectangular batch, B = U R.  Otherwise the ragged one: rows row_off[u] .. row_off[u + 1] are user u's, R is unused
+static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int64_t *d_row_off, const int32_t *d_codes, const float *d_labels, int64_t U, int R,
+                                    int64_t B_csr, double *out_loss) {
   dm_dfm_train *t = h->dfm_tr;
+  const bool csr = d_row_off != nullptr;
   const int E = h->embed, L = h->dfm_L, T = L + 1, NCT = dfm_train_col_tiles(L), NC = 16 * NCT;
   // B + U L slots are sorted with 32-bit values; the slabs of the l1.W products are a grid's z
-  if (dfm_tg_too_large(U, R, L))
+  if (csr && dfm_tg_csr_too_large(U, B_csr, L))
+    return fail(h, DM_ERR_UNSUPPORTED, "dm_deepfm_train_forward_backward_csr: batch too large (at most 4 194 240 rows and as many users, and B + U L below 2^31): split it and accumulate on the host");
+  if (!csr && dfm_tg_too_large(U, R, L))
     return fail(h, DM_ERR_UNSUPPORTED, "dm_deepfm_train_forward_backward_grouped: batch too large (at most 4 194 240 rows, and U rows_per_user + U L below 2^31): split it and accumulate on the host");
-  const int64_t NI = h->num_index, B = U * R, UL = U * L, m = B + UL;
+  const int64_t NI = h->num_index, B = csr ? B_csr : U * R, UL = U * L, m = B + UL;
   const bool detail = dfm_time_launches();
   const int64_t slabs_b = (B + DRT_SLAB - 1) / DRT_SLAB, slabs_u = (U + DRT_SLAB - 1) / DRT_SLAB;
   int nb = (int)std::min<int64_t>(((B + 15) / 16 + 3) / 4, 1024);            // workgroups of the rows kernel: a function of (U, R) alone
@@ -269,14 +322,31 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int32
   const size_t o_tmp = ar.add(dev_sort_scratch_bytes(m));
   const size_t o_part = ar.add(std::max((size_t)slabs_b * T * ((size_t)E + 1), (size_t)slabs_u * T * ((size_t)L * E + 1)) * 4);
   const size_t o_pl = ar.add((size_t)nb * 8), o_pg = ar.add((size_t)nb * (1 + NC) * 4), o_loss = ar.add(8);
+  const size_t o_ru = csr ? ar.add((size_t)B * 4) : 0, o_bad = csr ? ar.add(8) : 0;
   if ((rc = ar.commit(h)) != DM_OK) return rc;
+  // ---- the offsets, before anything dereferences through them (and before the gradient is touched)
+  if (csr) {
+    unsigned long long *d_bad = ar.ptr<unsigned long long>(o_bad), bad = 0;
+    HIPCHK(h, hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
+    hipLaunchKernelGGL(dfm_tg_check_off_kernel, dim3(drt_blocks(h, U + 1, 256)), dim3(256), 0, h->stream, d_row_off, U, B, d_bad);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (bad != ~0ull) {
+      char msg[256];
+      if (bad == (unsigned long long)U) snprintf(msg, sizeof msg, "dm_deepfm_train_forward_backward_csr: row_off[U] must equal B = %lld (user %lld)", (long long)B, (long long)U);
+      else snprintf(msg, sizeof msg, "dm_deepfm_train_forward_backward_csr: row_off must start at 0 and never decrease (first offending user %llu)", bad);
+      return fail(h, DM_ERR_INVALID, msg);
+    }
+  }
   int32_t *idx = ar.ptr<int32_t>(o_idx);
   float *dX = ar.ptr<float>(o_dx), *part = ar.ptr<float>(o_part);
   float *grad = (float *)t->vec.grad;
   float *g_l1w = grad + NI * E, *g_l1b = g_l1w + (int64_t)T * T * E, *g_l2w = g_l1b + T, *g_l2b = g_l2w + T;
   // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
   if ((rc = dfm_train_clear_prev(h, t)) != DM_OK) return rc;
-  hipLaunchKernelGGL(dfm_tg_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seq, B, UL, NI, idx);
+  if (csr) hipLaunchKernelGGL(dfm_tg_idx_csr_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seq, d_row_off, B, U, L, NI, idx, ar.ptr<int32_t>(o_ru));
+  else hipLaunchKernelGGL(dfm_tg_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seq, B, UL, NI, idx);
   HIPCHK(h, hipGetLastError());
   // ---- per user, per row, per user
   DfmTgParams p;
@@ -287,9 +357,12 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int32
     p.Hh = ar.ptr<float>(o_hh); p.bufh = ar.ptr<float>(o_bufh); p.sqh = ar.ptr<float>(o_sqh);
     p.dH = ar.ptr<float>(o_dh); p.g = ar.ptr<float>(o_g); p.dX = dX; p.DH = ar.ptr<float>(o_DH);
     p.ploss = ar.ptr<double>(o_pl); p.pg = ar.ptr<float>(o_pg);
+    p.row_user = csr ? ar.ptr<const int32_t>(o_ru) : nullptr; p.row_off = d_row_off;
     for (int which = 0; which < 3; which++) {
       rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) {
-        return dfm_tg_launch<decltype(e)::value, decltype(n)::value>(h, p, which, (unsigned)(which == 1 ? nb : nbu), detail); });
+        const unsigned nbw = (unsigned)(which == 1 ? nb : nbu);
+        return csr ? dfm_tg_launch<decltype(e)::value, decltype(n)::value, true>(h, p, which, nbw, detail)
+                   : dfm_tg_launch<decltype(e)::value, decltype(n)::value, false>(h, p, which, nbw, detail); });
       if (rc != DM_OK) return rc;
     }
     hipLaunchKernelGGL(dfm_train_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)p.ploss, (const float *)p.pg, nb, NC, T, B, ar.ptr<double>(o_loss), g_l2w, g_l2b);
@@ -340,5 +413,18 @@ int dm_deepfm_train_forward_backward_grouped_dev(dm_handle_t h, const int32_t *d
     return fail(h, DM_ERR_INVALID, "dm_deepfm_train_forward_backward_grouped: U and rows_per_user must be positive and the arrays non-null");
   if ((rc = dfm_check_L(h, "dm_deepfm_train_forward_backward_grouped", L)) != DM_OK) return rc;
   HIPCHK(h, hipSetDevice(h->device));
-  return dfm_train_fb_grouped_dev(h, d_seq_codes, d_codes, d_labels, U, rows_per_user, out_loss);
+  return dfm_train_fb_grouped_dev(h, d_seq_codes, nullptr, d_codes, d_labels, U, rows_per_user, 0, out_loss);
+}
+
+int dm_deepfm_train_forward_backward_csr_dev(dm_handle_t h, const int32_t *d_seq_codes, const int64_t *d_row_off, const int32_t *d_codes, const float *d_labels,
+                                             int64_t U, int64_t B, int L, double *out_loss) {
+  if (!h) return DM_ERR_INVALID;
+  DM_OWNER_ONLY(h, "dm_deepfm_train_forward_backward_csr");
+  int rc = dfm_train_check(h, "dm_deepfm_train_forward_backward_csr", true);
+  if (rc != DM_OK) return rc;
+  if (U <= 0 || B <= 0 || !d_seq_codes || !d_row_off || !d_codes || !d_labels)
+    return fail(h, DM_ERR_INVALID, "dm_deepfm_train_forward_backward_csr: U and B must be positive and the arrays non-null");
+  if ((rc = dfm_check_L(h, "dm_deepfm_train_forward_backward_csr", L)) != DM_OK) return rc;
+  HIPCHK(h, hipSetDevice(h->device));
+  return dfm_train_fb_grouped_dev(h, d_seq_codes, d_row_off, d_codes, d_labels, U, 0, B, out_loss);
 }

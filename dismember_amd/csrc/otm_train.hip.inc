@@ -318,7 +318,7 @@ static int otm_train_batch_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, i
                        grouped ? (unsigned *)nullptr : b_mask, b_lab);
     float lf = 0.f;
     double ld = 0.0;
-    if (dfm && grouped) rc = dfm_train_fb_grouped_dev(h, d_seq, b_codes, b_lab, U, nl, &ld);
+    if (dfm && grouped) rc = dfm_train_fb_grouped_dev(h, d_seq, nullptr, b_codes, b_lab, U, nl, 0, &ld);
     else if (dfm) rc = dfm_train_fb_dev(h, b_codes, b_seq, b_lab, B, &ld);      // (the row mask is unused: the graph has no mask input)
     else if (grouped) rc = train_fb_grouped_dev(h, d_seq, d_umask, b_codes, b_lab, U, nl, L, &lf);
     else rc = train_fb_dev(h, b_codes, b_seq, b_mask, b_lab, B, L, &lf);

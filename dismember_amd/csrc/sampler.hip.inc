@@ -34,7 +34,7 @@ struct SampleParams {
   int32_t *tcode;              // [T] target code or -1
   int64_t *row_off;            // [T + 1] first row of every target (exclusive scan of the row counts)
   // outputs
-  int32_t *codes, *seqs; uint32_t *rowmask; float *labels;
+  int32_t *codes, *seqs; uint32_t *rowmask; float *labels;      // seqs == nullptr: the per-row history stores are skipped (the CSR twin)
   int64_t cap;
 };
 
@@ -49,6 +49,19 @@ __device__ __forceinline__ unsigned long long dm_sample_draw(unsigned long long 
                          (ctr * 0xD6E8FEB86659FD93ull));
 }
 __device__ __forceinline__ int dm_code_level(int64_t code) { return 63 - __clzll((unsigned long long)(code + 1)); }
+// a raw history id as the code the training steps read (TDMTree.idToCode; 0 = padding -> -1)
+__device__ __forceinline__ int32_t dm_sample_hist_code(const SampleParams &p, int32_t id) {
+  if (id == 0) return -1;
+  if (id < p.non_leaf_offset && id >= 0 && p.id_to_code[id] >= 0) return p.id_to_code[id];
+  const int32_t tt = (int32_t)((uint32_t)id - (uint32_t)p.non_leaf_offset);
+  return tt > p.max_code ? -1 : tt;
+}
+// the CSR twin's histories: every target's, once, whether it yields rows or not
+__global__ void dm_sample_hist_kernel(SampleParams p, int32_t *seq_codes) {
+  const int64_t n = p.T * p.L;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    seq_codes[i] = dm_sample_hist_code(p, p.seq_ids[i]);
+}
 
 // target ids -> codes and row counts (pathNodes of an unknown / padding target is empty: no rows)
 __global__ void dm_sample_plan_kernel(SampleParams p, int64_t *cnt) {
@@ -159,19 +172,16 @@ __global__ __launch_bounds__(256) void dm_sample_kernel(SampleParams p) {
     }
     // history codes + mask of the target (TDMTree.idToCode), replicated over the n + 1 rows
     int32_t hc = -1;
-    if (lane < p.L) {
-      const int32_t id = p.seq_ids[t * p.L + lane];
-      if (id == 0) hc = -1;
-      else if (id < p.non_leaf_offset && id >= 0 && p.id_to_code[id] >= 0) hc = p.id_to_code[id];
-      else { const int32_t tt = (int32_t)((uint32_t)id - (uint32_t)p.non_leaf_offset); hc = tt > p.max_code ? -1 : tt; }
-    }
+    if (lane < p.L) hc = dm_sample_hist_code(p, p.seq_ids[t * p.L + lane]);
     const unsigned long long pm = __ballot(lane < p.L && hc == -1);
     hm = p.use_mask ? (unsigned)pm : 0u;
-    for (int r = 0; r <= n; r++) {
-      const int64_t q = q0 + r;
-      if (q >= p.cap) break;
-      if (lane < p.L) p.seqs[q * p.L + lane] = hc;
-      if (lane == 0 && p.rowmask) p.rowmask[q] = hm;
+    if (p.seqs || p.rowmask) {                         // (neither: the CSR twin, dm_sample_hist_kernel writes the history once per target)
+      for (int r = 0; r <= n; r++) {
+        const int64_t q = q0 + r;
+        if (q >= p.cap) break;
+        if (lane < p.L && p.seqs) p.seqs[q * p.L + lane] = hc;
+        if (lane == 0 && p.rowmask) p.rowmask[q] = hm;
+      }
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -249,10 +259,11 @@ static int sample_check(dm_ctx *h, int kind, int64_t T, int L, const int32_t *ne
   return DM_OK;
 }
 
-// all request / output pointers are device pointers; *n_rows = rows produced (a host sync)
+// all request / output pointers are device pointers; *n_rows = rows produced (a host sync).  d_seq_codes / d_row_off (both or neither; then
+// d_seqs is null): the CSR form, histories [T][L] once per target and the plan's offsets [T + 1]
 static int sample_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int64_t T, int L, const int32_t *neg_counts,
                       const dm_sample_opts *o, int32_t *d_codes, int32_t *d_seqs, uint32_t *d_rowmask, float *d_labels, int64_t cap,
-                      int64_t *n_rows) {
+                      int64_t *n_rows, int32_t *d_seq_codes = nullptr, int64_t *d_row_off = nullptr) {
   const int nl = h->max_level + 1;
   std::vector<int32_t> neg(nl), lvl_off(nl + 1, 0);
   int negmax = 1;
@@ -286,11 +297,17 @@ static int sample_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int
       hipLaunchKernelGGL(dm_sample_kernel, dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
       HIPCHK(h, hipGetLastError());
     }
+    if (d_seq_codes) {
+      hipLaunchKernelGGL(dm_sample_hist_kernel, dim3((unsigned)std::min<int64_t>((T * L + 255) / 256, 1024)), dim3(256), 0, h->stream, p, d_seq_codes);
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipMemcpyAsync(d_row_off, p.row_off, (size_t)(T + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+    }
     long long total = 0;
     HIPCHK(h, hipMemcpyAsync(&total, p.row_off + T, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     *n_rows = total;
   } else {
+    if (d_row_off) HIPCHK(h, hipMemsetAsync(d_row_off, 0, 8, h->stream));
     *n_rows = 0;
   }
   return DM_OK;

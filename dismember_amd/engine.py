@@ -833,6 +833,81 @@ class Engine:
                                                                        C.byref(loss)))
         return loss.value
 
+    def deepfm_train_forward_backward_csr(self, seq_codes, row_off, codes, labels):
+        """The same step on a ragged user-grouped batch (dm_deepfm_train_forward_backward_csr_dev): seq_codes [U][L],
+        row_off [U + 1] (int64), codes / labels [B] — rows row_off[u] .. row_off[u + 1] are user u's and share its history; a user may
+        have none.  Checks the offsets here (ValueError), uploads and calls the device entry, which checks them again on the device
+        (ids are not range-checked: one outside [0, num_index) reads as -1); -> the mean loss (float64)."""
+        seq = _i32(seq_codes)
+        U, L = seq.shape if seq.ndim == 2 else (0, 1)
+        off = np.ascontiguousarray(row_off, np.int64).ravel()
+        codes = _i32(codes).ravel()
+        B = codes.size
+        lab = np.ascontiguousarray(labels, np.float32).ravel()
+        if off.size != U + 1 or lab.size != B:
+            raise ValueError("deepfm_train_forward_backward_csr: row_off must hold U + 1 offsets and labels one value per row")
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != B:
+            bad = 0 if off[0] != 0 else int(np.flatnonzero(np.diff(off) < 0)[0]) if (np.diff(off) < 0).any() else U
+            raise ValueError("deepfm_train_forward_backward_csr: row_off must start at 0, never decrease and end at B = %d "
+                             "(first offending user %d)" % (B, bad))
+        al = lambda v: (v + 255) & ~255
+        buf = self.dev_alloc(al(U * L * 4) + al((U + 1) * 8) + 2 * al(B * 4) + 256)
+        try:
+            d_seq = C.c_void_p(buf.value)
+            d_off = C.c_void_p(buf.value + al(U * L * 4))
+            d_codes = C.c_void_p(d_off.value + al((U + 1) * 8))
+            d_lab = C.c_void_p(d_codes.value + al(B * 4))
+            if U:
+                self.h2d(d_seq, seq); self.h2d(d_off, off)
+            if B:
+                self.h2d(d_codes, codes); self.h2d(d_lab, lab)
+            return self.deepfm_train_forward_backward_csr_dev(d_seq, d_off, d_codes, d_lab, U, B, L)
+        finally:
+            self.dev_free(buf)
+
+    def deepfm_train_forward_backward_csr_dev(self, d_seq_codes, d_row_off, d_codes, d_labels, U, B, L):
+        """the same on device arrays: d_seq_codes [U][L], d_row_off [U + 1] int64, d_codes / d_labels [B] -> the mean loss"""
+        loss = C.c_double(0)
+        self._chk(N.lib().dm_deepfm_train_forward_backward_csr_dev(self._h, d_seq_codes, d_row_off, d_codes, d_labels, int(U), int(B), int(L),
+                                                                   C.byref(loss)))
+        return loss.value
+
+    def deepfm_sample_train_batch_csr(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, with_prob=False, tolerance=20):
+        """dm_deepfm_sample_train_batch_csr_dev, downloaded (for the tests): (codes [R], labels [R], seq_codes [T, L], row_off [T + 1])."""
+        seq = _i32(seq_item_ids)
+        tgt = _i32(target_item_ids).ravel()
+        T, L = seq.shape
+        neg = _i32(neg_counts)
+        o = N.SampleOpts(int(start_level), int(bool(with_prob)), int(tolerance), 0, int(seed))
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_deepfm_sample_train_batch_csr_dev(self._h, None, None, T, L, _p(neg, N.i32p), neg.size, C.byref(o), None, None,
+                                                               None, None, 0, C.byref(n)))
+        R = max(n.value, 1)
+        al = lambda v: (v + 255) & ~255
+        buf = self.dev_alloc(2 * al(T * L * 4) + al(T * 4) + 2 * al(R * 4) + al((T + 1) * 8) + 256)
+        try:
+            base = buf.value
+            d_seq = C.c_void_p(base); base += al(T * L * 4)
+            d_tgt = C.c_void_p(base); base += al(T * 4)
+            d_codes = C.c_void_p(base); base += al(R * 4)
+            d_sc = C.c_void_p(base); base += al(T * L * 4)
+            d_off = C.c_void_p(base); base += al((T + 1) * 8)
+            d_lab = C.c_void_p(base)
+            if T:
+                self.h2d(d_seq, seq); self.h2d(d_tgt, tgt)
+            self._chk(N.lib().dm_deepfm_sample_train_batch_csr_dev(self._h, d_seq, d_tgt, T, L, _p(neg, N.i32p), neg.size, C.byref(o), d_codes,
+                                                                   d_sc, d_off, d_lab, R, C.byref(n)))
+            R = n.value
+            codes = np.empty(R, np.int32); lab = np.empty(R, np.float32); sc = np.empty((T, L), np.int32); off = np.empty(T + 1, np.int64)
+            if R:
+                self.d2h(codes, d_codes); self.d2h(lab, d_lab)
+            self.d2h(off, d_off)
+            if T:
+                self.d2h(sc, d_sc)
+            return codes, lab, sc, off
+        finally:
+            self.dev_free(buf)
+
     def deepfm_make_train_batch(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, with_prob=False, tolerance=20):
         """make_train_batch for a DeepFM model (no mask): (codes [R], seqs [R, L], labels [R])."""
         seq = _i32(seq_item_ids)
@@ -851,10 +926,16 @@ class Engine:
         return codes[:R], seqs[:R], lab[:R]
 
     def deepfm_train_step_sampled(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, with_prob=False, tolerance=20,
-                                  return_rows=False):
+                                  return_rows=False, grouped=False):
         """train_step_sampled for a DeepFM model: dm_deepfm_sample_train_batch_dev expands the targets on the device straight into
         the buffers of dm_deepfm_train_forward_backward_dev.  Returns the mean BCE loss of the expanded rows (with return_rows: and
-        the rows (codes, seqs, labels), downloaded)."""
+        the rows (codes, seqs, labels), downloaded).
+        grouped: dm_deepfm_sample_train_batch_csr_dev into the buffers of dm_deepfm_train_forward_backward_csr_dev instead (DESIGN.md
+        §17) — the same rows from the same seed, every target's history written and read once; the [R][L] row histories are never
+        carved (return_rows then gives (codes, seq_codes [T, L], labels, row_off [T + 1]))."""
+        if grouped:
+            return self._deepfm_train_step_sampled_csr(seq_item_ids, target_item_ids, neg_counts, start_level, seed, with_prob, tolerance,
+                                                       return_rows)
         seq = _i32(seq_item_ids)
         tgt = _i32(target_item_ids).ravel()
         T, L = seq.shape
@@ -889,6 +970,44 @@ class Engine:
         if R:
             self.d2h(codes, d_codes); self.d2h(seqs, d_seqs); self.d2h(lab, d_lab)
         return loss.value, (codes, seqs, lab)
+
+    def _deepfm_train_step_sampled_csr(self, seq_item_ids, target_item_ids, neg_counts, start_level, seed, with_prob, tolerance, return_rows):
+        seq = _i32(seq_item_ids)
+        tgt = _i32(target_item_ids).ravel()
+        T, L = seq.shape
+        neg = _i32(neg_counts)
+        o = N.SampleOpts(int(start_level), int(bool(with_prob)), int(tolerance), 0, int(seed))
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_deepfm_sample_train_batch_csr_dev(self._h, None, None, T, L, _p(neg, N.i32p), neg.size, C.byref(o), None, None,
+                                                               None, None, 0, C.byref(n)))
+        R = max(n.value, 1)
+        al = lambda v: (v + 255) & ~255
+        need = 2 * al(T * L * 4) + al(T * 4) + 2 * al(R * 4) + al((T + 1) * 8)          # the six sub-buffers as carved below: no [R][L]
+        if getattr(self, "_samp_bytes", 0) < need:
+            if getattr(self, "_samp_buf", None):
+                self.dev_free(self._samp_buf)
+            self._samp_buf, self._samp_bytes = self.dev_alloc(need + need // 2), need + need // 2
+        base = self._samp_buf.value
+        d_seq = C.c_void_p(base); base += al(T * L * 4)
+        d_tgt = C.c_void_p(base); base += al(T * 4)
+        d_codes = C.c_void_p(base); base += al(R * 4)
+        d_sc = C.c_void_p(base); base += al(T * L * 4)
+        d_off = C.c_void_p(base); base += al((T + 1) * 8)
+        d_lab = C.c_void_p(base)
+        self.h2d(d_seq, seq); self.h2d(d_tgt, tgt)
+        self._chk(N.lib().dm_deepfm_sample_train_batch_csr_dev(self._h, d_seq, d_tgt, T, L, _p(neg, N.i32p), neg.size, C.byref(o), d_codes,
+                                                               d_sc, d_off, d_lab, R, C.byref(n)))
+        R = n.value
+        loss = C.c_double(0)
+        if R:
+            self._chk(N.lib().dm_deepfm_train_forward_backward_csr_dev(self._h, d_sc, d_off, d_codes, d_lab, T, R, L, C.byref(loss)))
+        if not return_rows:
+            return loss.value
+        codes = np.empty(R, np.int32); lab = np.empty(R, np.float32); sc = np.empty((T, L), np.int32); off = np.empty(T + 1, np.int64)
+        if R:
+            self.d2h(codes, d_codes); self.d2h(lab, d_lab)
+        self.d2h(sc, d_sc); self.d2h(off, d_off)
+        return loss.value, (codes, sc, lab, off)
 
     def deepfm_adam_step(self, grad_scale=1.0):
         self._chk(N.lib().dm_deepfm_adam_step(self._h, float(grad_scale)))

@@ -9,6 +9,8 @@ the touched embedding rows, re-summed in rank order, inside the library) makes e
 gradient, and every replica applies the same Adam step, so replicas stay bit-identical without a parameter broadcast
 (never a ring over the 17 GB table).
 """
+import os
+
 import numpy as np
 
 
@@ -18,15 +20,20 @@ class TDMTrainer:
     comm: dismember_amd.comm.Comm (or None for a single worker).  sampler: "device" draws the negatives on the GPU
     (dm_tdm_sample_train_batch_dev; rows never visit the host), "host" uses dm_tdm_make_train_batch.
     An engine that holds a DeepFM model is driven through its own entry points (Engine.deepfm_*), without a mask — the graph has none,
-    tdm/.../model/TDM.scala:26-29 — and without a communicator: gradient exchange for DeepFM is not built."""
+    tdm/.../model/TDM.scala:26-29 — and without a communicator: gradient exchange for DeepFM is not built.
+    grouped (DeepFM with the device sampler only; a DIN engine ignores it, the host sampler keeps the row step): True trains with the
+    ragged user-grouped step (Engine.deepfm_train_step_sampled(grouped=True): a target's history is read once, not once per row;
+    other summation orders than the row step's, so not its bytes), False with the row step, None reads DM_DFM_TRAIN_GROUPED ("1" = on)
+    once, here."""
 
     def __init__(self, engine, neg_counts, start_level=1, use_mask=True, lr=1e-3, comm=None, seed=0, sampler="device",
-                 with_prob=False, tolerance=20):
+                 with_prob=False, tolerance=20, grouped=None):
         self.e, self.neg, self.start, self.use_mask = engine, np.asarray(neg_counts, np.int32), start_level, use_mask
         self.comm, self.seed, self.it, self.sampler, self.with_prob = comm, seed, 0, sampler, bool(with_prob)
         self.tolerance = int(tolerance)                   # model.sample_tolerance (NegativeSampler.scala:116-145)
         self.sync_s, self.sync_calls = 0.0, 0             # wall time spent in the gradient exchange (bench.py reports it)
         self.deepfm = engine.scorer == "deepfm"
+        self.grouped = (os.environ.get("DM_DFM_TRAIN_GROUPED") == "1") if grouped is None else bool(grouped)
         if self.deepfm:
             if comm is not None:
                 raise ValueError("TDMTrainer: gradient exchange for a DeepFM model is not built (comm must be None)")
@@ -45,7 +52,7 @@ class TDMTrainer:
         if self.deepfm:
             if self.sampler == "device":
                 loss = self.e.deepfm_train_step_sampled(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
-                                                        with_prob=self.with_prob, tolerance=self.tolerance)
+                                                        with_prob=self.with_prob, tolerance=self.tolerance, grouped=self.grouped)
             else:
                 codes, seqs, y = self.e.deepfm_make_train_batch(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
                                                                 with_prob=self.with_prob, tolerance=self.tolerance)

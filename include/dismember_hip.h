@@ -614,6 +614,14 @@ int dm_deepfm_train_forward_backward_dev(dm_handle_t h, const int32_t *d_codes, 
  * DM_DFM_TRAIN_GROUPED=1 (read per call). */
 int dm_deepfm_train_forward_backward_grouped_dev(dm_handle_t h, const int32_t *d_seq_codes, const int32_t *d_codes, const float *d_labels, int64_t U,
                                                  int rows_per_user, int L, double *out_loss);
+/* the same step on a ragged user-grouped batch: rows d_row_off[u] .. d_row_off[u + 1] of d_codes / d_labels [B] belong
+ * to user u and read d_seq_codes[u]; a user may have no rows (its history is then never read).  The offsets are validated on the device
+ * before anything is read through them: d_row_off[0] == 0, non-decreasing, d_row_off[U] == B, else DM_ERR_INVALID naming the first offending
+ * user.  With uniform offsets the bytes of dm_deepfm_train_forward_backward_grouped_dev.  Device arrays, ids NOT range-checked (an id outside
+ * [0, num_index) is read as -1); out_loss is a host pointer or NULL.  U <= 0, B <= 0, a null array or L != the model's seq_len:
+ * DM_ERR_INVALID; before dm_deepfm_train_init: DM_ERR_STATE; U or B > 4 194 240 or B + U L >= 2^31: DM_ERR_UNSUPPORTED. */
+int dm_deepfm_train_forward_backward_csr_dev(dm_handle_t h, const int32_t *d_seq_codes, const int64_t *d_row_off, const int32_t *d_codes, const float *d_labels,
+                                             int64_t U, int64_t B, int L, double *out_loss);
 /* Adam.optimize (S/optim/Adam.scala:19-73) over the vector with dm_dr_adam_step's rules: the embedding rows a gradient has ever reached plus
  * the dense blocks, or the whole vector when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 - the same bytes
  * either way.  Rebuilds every copy the searches read and tells the clones: serving continues with the new weights. */
@@ -631,6 +639,12 @@ int dm_deepfm_make_train_batch(dm_handle_t h, const int32_t *seq_item_ids, const
 int dm_deepfm_sample_train_batch_dev(dm_handle_t h, const int32_t *d_seq_item_ids, const int32_t *d_target_item_ids, int64_t T, int L,
                                      const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *d_codes,
                                      int32_t *d_seqs, float *d_labels, int64_t cap, int64_t *n_rows);
+/* dm_deepfm_sample_train_batch_dev in the form dm_deepfm_train_forward_backward_csr_dev reads: the same d_codes / d_labels from the same seed,
+ * d_seq_codes [T][L] = every target's history as codes, written once per target (also for a target that yields no rows), d_row_off [T + 1] =
+ * the first row of every target.  No [cap][L] histories are written.  Size query (d_codes == NULL), checks and refusals: the row twin's. */
+int dm_deepfm_sample_train_batch_csr_dev(dm_handle_t h, const int32_t *d_seq_item_ids, const int32_t *d_target_item_ids, int64_t T, int L,
+                                         const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *d_codes,
+                                         int32_t *d_seq_codes, int64_t *d_row_off, float *d_labels, int64_t cap, int64_t *n_rows);
 
 /* ---- Deep-Retrieval E-step: one training step of the LAYER model on the device ----
  * D/model/LayerModel.scala:22-49, D/dataset/MiniBatch.scala:18-50, D/loss/CrossEntropyLayer.scala, D/optim/LocalOptimizer.scala:58-116.

@@ -125,11 +125,13 @@ EXTENTS = {
     "dm_deepfm_train_forward_backward": {"codes": "B", "seqs": "B * L", "labels": "B", "out_loss": "1"},
     "dm_deepfm_train_forward_backward_dev": {"out_loss": "1"},
     "dm_deepfm_train_forward_backward_grouped_dev": {"out_loss": "1"},
+    "dm_deepfm_train_forward_backward_csr_dev": {"out_loss": "1"},
     "dm_deepfm_train_param_count": {"n": "1"},
     "dm_deepfm_train_download": {"out": "n"},
     "dm_deepfm_make_train_batch": {"seq_item_ids": "T * L", "target_item_ids": "T", "neg_counts": "n_counts", "out_codes": "cap",
                                    "out_seqs": "cap * L", "out_labels": "cap", "n_rows": "1"},
     "dm_deepfm_sample_train_batch_dev": {"neg_counts": "n_counts", "n_rows": "1"},
+    "dm_deepfm_sample_train_batch_csr_dev": {"neg_counts": "n_counts", "n_rows": "1"},
     "dm_dr_load_path_items": {"item_off": "n_paths + 1"},
     "dm_dr_rerank_forward_backward": {"targets": "B", "out_loss": "1"},
     "dm_dr_rerank_forward_backward_dev": {"out_loss": "1"},
