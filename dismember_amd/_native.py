@@ -133,6 +133,11 @@ SIGNATURES = {
     "dm_deepfm_otm_beam_search_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dm_deepfm_otm_pseudo_targets": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, i64p, i32p, C.POINTER(OtmTrainOpts), i32p, C.POINTER(C.c_double), i32p]),
     "dm_deepfm_otm_train_batch": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, i64p, i32p, C.POINTER(OtmTrainOpts), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "dm_deepfm_otm_child_weights": (C.c_int, [C.c_void_p, i64p, i32p, i32p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_double)]),
+    "dm_deepfm_otm_tree_prepare": (C.c_int, [C.c_void_p, i64p, i32p, C.c_int64, C.c_int]),
+    "dm_deepfm_otm_tree_weights": (C.c_int, [C.c_void_p, i32p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_double)]),
+    "dm_deepfm_otm_tree_release": (C.c_int, [C.c_void_p]),
     "dm_train_init": (C.c_int, [C.c_void_p, C.POINTER(AdamOpts)]),
     "dm_train_forward_backward": (C.c_int, [C.c_void_p, i32p, i32p, i32p, C.c_int64, f32p, C.c_int64, C.c_int, f32p]),
     "dm_adam_step": (C.c_int, [C.c_void_p, C.c_float]),

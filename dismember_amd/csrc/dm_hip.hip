@@ -123,6 +123,7 @@ struct dm_ctx {
   float *d_dfm_w2p = nullptr;
   float *d_dfm_fragS = nullptr; // DeepFM: W1s as MFMA B fragments (dfm_jtm_derive_kernel), for the per-history set-up of the pair scorer
   struct dm_dfm_train *dfm_tr = nullptr;   // DeepFM training state (dm_deepfm_train_init, dfm_train.hip.inc): the owner's, never mirrored by a clone
+  struct dm_dfm_otm_tree *dfm_otree = nullptr;   // DeepFM: what dm_deepfm_otm_tree_prepare keeps (dfm_otm_tree.hip.inc): the owner's, dropped with the weights
   LazyCopies lazy;             // the copies rebuilt on first use after a weight change, and their stale flags (lazy_copies.hip.inc)
   int scorer_mode = DM_SCORER_AUTO;      // dm_set_scorer_mode
   bool beam_w = true;          // split scorer on the one-wave-per-SIMD kernel (beam_kernel_w.hip.inc); DM_BEAM_W=0 in the environment selects the LDS-fed kernel
@@ -457,9 +458,11 @@ static void free_training(dm_ctx *h) {
   h->train_ready = false; h->touch_cap = 0; h->touch_ub = 0;
 }
 static void dfm_train_release(dm_ctx *h);
+static void dfm_otm_tree_release(dm_ctx *h);
 static void free_weights(dm_ctx *h) {
   model_changed(h);
   dfm_train_release(h);
+  dfm_otm_tree_release(h);
   if (h->emb32_owned) dm_release(h->d_emb32);
   h->d_emb32 = nullptr; h->emb32_owned = false;
   dm_release(h->d_compact, h->d_wfrag, h->d_afrag, h->d_bfrag, h->d_attA, h->d_w1aA, h->d_w1bA, h->d_b1, h->d_w2, h->d_att_wT_t, h->d_l1T_t);
@@ -1582,6 +1585,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "jtm_sharded.hip.inc"
 #include "train_grouped_host.hip.inc"
 #include "dfm_otm.hip.inc"
+#include "dfm_otm_tree.hip.inc"
 #include "otm_train.hip.inc"
 #include "checkpoint.hip.inc"
 #include "tree_file.hip.inc"

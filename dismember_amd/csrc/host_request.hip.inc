@@ -17,7 +17,7 @@ static void frontier_caps(int max_beam, int *cap, int *pcap) {
 // ---- what an event pair is recorded as (dm_kernel_timing_get_kind).  The numbers are read by tools and tests: they do not change.
 // Deep-Retrieval's sliced search numbers its launches per layer d: EV_DR_STATS + 2 d = the statistics of layer d >= 1, EV_DR_CUT + 2 d =
 // its cut (d = 0: the layer-0 launch), EV_DR_BLOCK + 2 d = the block version's second pass over the users the one-wave cut flagged.
-// 40 .. 43 mean two things: the grouped fp64 training step of a DIN model and the serving / tree-learning launches of a DeepFM model (a
+// 40 .. 45 mean two things: the grouped fp64 training step of a DIN model and the serving / tree-learning launches of a DeepFM model (a
 // handle holds one).
 enum EvKind {
   EV_MAIN = 0,            // a search's main kernel, a whole Deep-Retrieval search, and every launch nobody asks for by kind
@@ -27,6 +27,7 @@ enum EvKind {
   EV_DFM_USER = 40, EV_DFM_LEVEL = 41,
   EV_DFM_JTM_ROWS = 42, EV_DFM_JTM_PAIRS = 43,      // the pair scorer of JTM tree learning (dfm_jtm.hip.inc): per-history set-up, per-pair score
   EV_DFM_OTM = 42,        // the fused OTM beam search of a DeepFM model (dfm_otm.hip.inc): a call is a search or a tree-learning step, never both
+  EV_DFM_OTM_TREE_SCORE = 44, EV_DFM_OTM_TREE_SUM = 45,      // OTM tree construction with a DeepFM model (dfm_otm_tree.hip.inc): unit scores, segment sums + chain
   EV_TG_SETUP = 40, EV_TG_ROWS = 41, EV_TG_WGRAD_A = 42, EV_TG_USER_BWD = 43, EV_TG_WGRAD_B = 44,
   // the Deep-Retrieval training step under DM_DR_TIME_LAUNCHES=1 (dr_train.hip.inc): forward GEMMs, softmax + cross-entropy, dX products,
   // dW / db products with their slab sums, embedding gradient (pairs, sort, segment sums), Adam

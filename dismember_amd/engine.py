@@ -293,6 +293,51 @@ class Engine:
         self._chk(N.lib().dm_deepfm_pairs_forward(self._h, _p(codes, N.i32p), _p(seqs, N.i32p), P, int(L), seq_div, _p(out, N.f32p)))
         return out
 
+    # ---- OTM tree construction with a DeepFM model (csrc/dfm_otm_tree.hip.inc)
+    @staticmethod
+    def _otm_tree_rows(row_off, row_codes):
+        off = np.ascontiguousarray(row_off, np.int64).ravel()
+        rows = _i32(row_codes)
+        n = off.size - 1
+        R = int(off[-1]) if off.size else 0
+        if n < 0:
+            raise ValueError("row_off needs n_items + 1 entries")
+        L = rows.shape[-1] if rows.ndim == 2 else rows.size // max(R, 1)
+        rows = rows.ravel()
+        if rows.size < R * L:
+            raise ValueError("row_off ends at row %d but row_codes holds %d values of L = %d" % (R, rows.size, L))
+        return off, rows, n, int(L)
+
+    def deepfm_otm_child_weights(self, row_off, row_codes, item_node, old_level, level, L=None, use_mask=False):
+        """dm_deepfm_otm_child_weights: weights [n_items, 2^(level - old_level)] float64 of TreeConstruction.aggregateWeights with the
+        DeepFM graph; item i owns the histories row_off[i] .. row_off[i + 1] of row_codes [rows, L] (NODE codes, -1 = padding) and sits
+        in node item_node[i] of old_level."""
+        off, rows, n, Lr = self._otm_tree_rows(row_off, row_codes)
+        node = _i32(item_node).ravel()
+        if node.size != n:
+            raise ValueError("item_node holds %d entries for %d items" % (node.size, n))
+        w = np.empty((max(n, 1), 1 << max(0, min(int(level) - int(old_level), 8))), np.float64)
+        self._chk(N.lib().dm_deepfm_otm_child_weights(self._h, _p(off, N.i64p), _p(rows, N.i32p), _p(node, N.i32p), n, int(Lr if L is None else L),
+                                                      int(old_level), int(level), int(use_mask), w.ctypes.data_as(C.POINTER(C.c_double))))
+        return w[:n]
+
+    def deepfm_otm_tree_prepare(self, row_off, row_codes, L=None):
+        """dm_deepfm_otm_tree_prepare: the histories of a catalogue go up once and their per-history part of the score stays on the
+        device for deepfm_otm_tree_weights; a second prepare replaces the first."""
+        off, rows, n, Lr = self._otm_tree_rows(row_off, row_codes)
+        self._chk(N.lib().dm_deepfm_otm_tree_prepare(self._h, _p(off, N.i64p), _p(rows, N.i32p), n, int(Lr if L is None else L)))
+
+    def deepfm_otm_tree_weights(self, item_node, old_level, level):
+        """dm_deepfm_otm_tree_weights: one gap step on the prepared catalogue; the bytes of deepfm_otm_child_weights."""
+        node = _i32(item_node).ravel()
+        n = node.size
+        w = np.empty((max(n, 1), 1 << max(0, min(int(level) - int(old_level), 8))), np.float64)
+        self._chk(N.lib().dm_deepfm_otm_tree_weights(self._h, _p(node, N.i32p), n, int(old_level), int(level), w.ctypes.data_as(C.POINTER(C.c_double))))
+        return w[:n]
+
+    def deepfm_otm_tree_release(self):
+        self._chk(N.lib().dm_deepfm_otm_tree_release(self._h))
+
     # ---- beam search
     @staticmethod
     def _csr(consumed, U):
@@ -1145,7 +1190,8 @@ class Engine:
         the users the one-wave beam kernel deferred; under DM_DR_TIME_LAUNCHES=1 the sliced Deep-Retrieval search's launches, per
         layer d: 11 = layer 0, 10 + 2d = statistics, 11 + 2d = cut, 21 + 2d = the block version's second pass; 30 = general rows
         (din_forward); 40 / 41 = DeepFM user / level launches, 42 / 43 = the DeepFM pair scorer's per-history set-up / per-pair launches
-        (JTM tree learning), 42 also the fused OTM beam search of a DeepFM model, and 40 .. 44 the launches of the grouped fp64 training step; under
+        (JTM tree learning), 42 also the fused OTM beam search of a DeepFM model, 44 / 45 the unit scores / segment sums of OTM tree construction with a DeepFM
+        model, and 40 .. 44 the launches of the grouped fp64 training step; under
         DM_DR_TIME_LAUNCHES=1 the Deep-Retrieval training step: 50 = forward GEMMs, 51 = softmax + cross-entropy, 52 = dX products,
         53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam; and the M-step's path scores:
         80 = pairs of a chunk, 81 = the (item, path) sort, 82 = segment heads, 83 = segment sums, 84 = sort by score, 85 = sort by item,

@@ -9,7 +9,7 @@ Each function is the body of the reference's `CommandApp` of the same name (exam
 the conf file is read by dismember_amd.conf (same keys, same defaults, same "failed to find <key>" stop), the steps are the
 reference's, and every hot step is a library call — tree index + scorer weights in HBM, level-wise negative sampling, forward /
 backward / Adam, the batched evaluator, `JTM.optimize` in one call.  `deep_model` selects DIN or DeepFM: TDM trains DeepFM through
-`dm_deepfm_train_*`, OTMTrainDeepModel through `dm_deepfm_otm_*` (fp32; OTMConstructTree with DeepFM is not built).  What is NOT
+`dm_deepfm_train_*`, OTMTrainDeepModel through `dm_deepfm_otm_*` and OTMConstructTree through `dm_deepfm_otm_tree_*` (fp32).  What is NOT
 carried over: Java serialisation (the model file is `dm_save_model`'s flat checkpoint), HDFS paths and spectral clustering in `TDMClusterTree`.
 
   tdm_initialize_tree   tdm/TDMInitializeTree.scala:14-48  -> TreeInit.generate (tdm/.../tree/TreeInit.scala:33-66)
@@ -323,9 +323,11 @@ def otm_train_deep_model(conf_path, quiet=True, engine=None, max_iterations=None
     return out
 
 
-def otm_construct_tree(conf_path, quiet=True, engine=None):
+def otm_construct_tree(conf_path, quiet=True, engine=None, deepfm=False):
     """OTMConstructTree (examples/.../otm/OTMConstructTree.scala:17-45): the trained model + the mapping file -> TreeConstruction.run
-    (otm/.../tree/TreeConstruction.scala:44-101) over the items' training histories -> the new `item node` mapping written back."""
+    (otm/.../tree/TreeConstruction.scala:44-101) over the items' training histories -> the new `item node` mapping written back.
+    A DeepFM checkpoint runs with deepfm=True (fp32, no mask: DESIGN.md §18; the command line passes it); without the keyword it is
+    refused, as before the DeepFM child weights were built."""
     from . import otm_data as od
     from .engine import Engine
     from .otm_tree import TreeConstruction
@@ -334,12 +336,15 @@ def otm_construct_tree(conf_path, quiet=True, engine=None):
         print("\n".join("%s: %s" % kv for kv in sorted(p.items())))
     eng = engine or Engine(0)
     eng.load_model(p["model_path"])
-    if eng.scorer == "deepfm":
-        raise ValueError("OTMConstructTree with a DeepFM model: the child-weight twin of dm_otm_child_weights is not built (DESIGN.md §15)")
+    dfm = eng.scorer == "deepfm"
+    if dfm and not deepfm:
+        raise ValueError("OTMConstructTree with a DeepFM model: dm_otm_child_weights evaluates DIN; its DeepFM child-weight twin "
+                         "dm_deepfm_otm_child_weights runs with otm_construct_tree(..., deepfm=True) (DESIGN.md §18)")
     mapping = od.load_mapping(p["mapping_path"])
     sample = _otm_sample(p["data_path"])
     seqs = od.item_sequences(sample, mapping, p["label_num"], p["min_seq_len"], p["seq_len"], p["split_ratio"])
-    tc = TreeConstruction(eng, mapping, seqs, gap=p["gap"], seq_len=p["seq_len"], use_mask=p["use_mask"])
+    tc = TreeConstruction(eng, mapping, seqs, gap=p["gap"], seq_len=p["seq_len"],
+                          use_mask=p["use_mask"] and not dfm)               # (the DeepFM graph has no mask input, OTM.scala:14-22)
     t0 = time.perf_counter()
     result = tc.run()
     dt = time.perf_counter() - t0
@@ -352,11 +357,16 @@ def otm_construct_tree(conf_path, quiet=True, engine=None):
 from .cluster import tdm_cluster_tree  # noqa: E402,F401  (reachable as tasks.tdm_cluster_tree; not in TASK_FUNCS: see README.md)
 
 
+def _otm_construct_tree_cli(conf_path, quiet=True):
+    """the command-line task: whatever scorer the checkpoint holds"""
+    return otm_construct_tree(conf_path, quiet=quiet, deepfm=True)
+
+
 TASK_FUNCS = {
     "TDMInitializeTree": tdm_initialize_tree, "JTMInitializeTree": tdm_initialize_tree,
     "TDMTrainDeepModel": tdm_train_deep_model, "JTMTrainDeepModel": tdm_train_deep_model,
     "JTMTreeLearning": jtm_tree_learning,
-    "OTMTrainDeepModel": otm_train_deep_model, "OTMConstructTree": otm_construct_tree,
+    "OTMTrainDeepModel": otm_train_deep_model, "OTMConstructTree": _otm_construct_tree_cli,
 }
 
 

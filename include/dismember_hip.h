@@ -111,7 +111,7 @@ int dm_load_weights_din(dm_handle_t h, int dtype, int E, int64_t num_index, cons
  * evaluates DIN (dm_din_forward, dm_otm_*, dm_tdm_bruteforce_topk, dm_jtm_*, dm_train_*, dm_adam_step, dm_tdm_make_train_batch,
  * dm_tdm_sample_train_batch_dev, dm_set_scorer_mode) returns DM_ERR_UNSUPPORTED and leaves the handle usable (training and its
  * sampler have DeepFM entry points of their own, below, and so has JTM's scoring: dm_deepfm_jtm_*; OTM's beam search and training
- * iteration: dm_deepfm_otm_*, below; OTMConstructTree's child weights with DeepFM stay refused). */
+ * iteration: dm_deepfm_otm_*, below; OTMConstructTree's child weights: dm_deepfm_otm_child_weights / dm_deepfm_otm_tree_*, below). */
 enum { DM_KIND_DIN = 0, DM_KIND_DEEPFM = 1 };
 int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_index, const void *compact, int64_t n_elems);
 int dm_get_scorer_kind(dm_handle_t h, int *kind, int *seq_len);
@@ -314,6 +314,25 @@ int dm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *r
                          int64_t n_items, int L, int old_level, int level, int use_mask, double *weights);
 int dm_otm_rebalance(dm_handle_t h, const double *weights, const int32_t *old_node, int64_t n, int32_t node, int old_level,
                      int level, int max_assign, int32_t *out_node);
+/* The same child weights with a DeepFM model (TreeConstruction.scala:215-230 builds Table(nodes, seq) when useMask = false): fp32 model,
+ * double sums.  dm_deepfm_otm_child_weights has dm_otm_child_weights' signature (use_mask must be 0, L the model's, one rank); the
+ * histories go up once per call and are never expanded into pairs: the per-history part of the score is computed once, the per-node
+ * part once per (item, 16 chain nodes).  A (row, chain node) logit is dm_deepfm_pairs_forward's byte for byte; an item's rows are
+ * summed in segments of 256 (DM_DFM_OTM_TREE_SEG), the segment sums left to right: with at most 256 rows this is strict row order.
+ * An item's weights depend on its own rows and node only.
+ * The prepared form, on the owning handle: dm_deepfm_otm_tree_prepare uploads the histories of a catalogue and keeps their per-history
+ * part on the device (a second prepare replaces the first); dm_deepfm_otm_tree_weights runs one gap step on it and returns the same
+ * bytes as the one-shot call — DM_ERR_STATE if nothing is prepared, if n_items differs or if the model changed since the prepare (a
+ * load, an Adam step); dm_deepfm_otm_tree_release drops it (a weight release and dm_destroy do too).
+ * DM_ERR_STATE on a DIN model; DM_ERR_INVALID for null arguments, n_items < 0, level <= old_level, level - old_level > 8, an item_node
+ * that is not a node of old_level, use_mask != 0, an L that is not the model's; DM_ERR_INDEX when 2^(level + 1) - 1 > num_index or a
+ * history code lies outside [-1, num_index); DM_ERR_UNSUPPORTED with a communicator of more than one rank.  Every refusal comes before
+ * anything is allocated and leaves the handle usable. */
+int dm_deepfm_otm_child_weights(dm_handle_t h, const int64_t *row_off, const int32_t *row_codes, const int32_t *item_node,
+                                int64_t n_items, int L, int old_level, int level, int use_mask, double *weights);
+int dm_deepfm_otm_tree_prepare(dm_handle_t h, const int64_t *row_off, const int32_t *row_codes, int64_t n_items, int L);
+int dm_deepfm_otm_tree_weights(dm_handle_t h, const int32_t *item_node, int64_t n_items, int old_level, int level, double *weights);
+int dm_deepfm_otm_tree_release(dm_handle_t h);
 
 /* ---- training step (tdm/src/main/scala/com/mass/tdm/optim/LocalOptimizer.scala:58-187) ------------------
  * One handle == one worker (the reference's per-thread model clone).  A step is

@@ -112,7 +112,10 @@ EXTENTS = {
     "dm_jtm_rebalance_all": {"weights": "n * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))", "old_node": "n", "item_node": "n", "out_node": "n"},
     "dm_otm_rebalance_all": {"weights": "n * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))", "old_node": "n", "item_node": "n", "out_node": "n"},
     "dm_otm_child_weights": {"row_off": "n_items + 1", "item_node": "n_items", "weights": "n_items * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))"},
-    "dm_otm_rebalance": {"weights": "n * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))", "old_node": "n", "out_node": "n"},
+    "dm_deepfm_otm_child_weights": {"row_off": "n_items + 1", "item_node": "n_items", "weights": "n_items * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))"},
+    "dm_deepfm_otm_tree_prepare": {"row_off": "n_items + 1"},
+    "dm_deepfm_otm_tree_weights": {"item_node": "n_items", "weights": "n_items * ((jlong)1 << (level > old_level && level - old_level < 32 ? level - old_level : 0))"},
+    "dm_otm_rebalance": {"weights": "n * ((jlong)1<< (level > old_level && level - old_level < 32 ? level - old_level : 0))", "old_node": "n", "out_node": "n"},
     "dm_train_forward_backward": {"codes": "B", "seqs": "B * L", "pad_flat_idx": "n_pad", "labels": "B", "loss": "1"},
     "dm_comm_create_all": {"devices": "n", "out": "n"},
     "dm_comm_allreduce_f64": {"vals": "n"},
