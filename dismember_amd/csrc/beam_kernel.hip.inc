@@ -48,6 +48,11 @@ typedef _Float16 dm_h2 __attribute__((ext_vector_type(2)));
 #define DM_NWAVES 8
 #define DM_MAXL 16
 #define DM_PIPE_MAXL 32        // history positions of the per-level pipelines (otm64.hip.inc, tdm_pipeline.hip.inc): 17 .. 32 take those
+// Per-level existence bounds of a loaded tree (dm_level_bounds_bits): entry l is the largest existing code of level l when the
+// level's existing codes are exactly [2^l - 1, last] ("exists" is then code <= last), 2^l - 2 for an empty level, and
+// DM_LEVEL_USE_BITS for a level with a gap — only the bitmap answers there
+#define DM_N_LEVEL_BOUNDS 32
+#define DM_LEVEL_USE_BITS (-2)
 
 struct BeamParams {
   // weights
@@ -68,6 +73,8 @@ struct BeamParams {
   // tree
   const uint32_t *exists_bits, *leaf_bits;
   const int32_t *node_id, *id_to_code;
+  const int32_t *level_last; // [DM_N_LEVEL_BOUNDS] per-level existence bounds (dm_level_bounds_bits), read by the one-wave-per-SIMD kernel;
+                             //    null (DM_LEVEL_BOUNDS=0, or no tree): every existence test reads exists_bits
   int64_t n_slots;
   int32_t non_leaf_offset, max_code, max_level;
   int leaf_fast;             // 1: every leaf sits at max_level and nothing else does (TreeBuilder.flattenLeaves)

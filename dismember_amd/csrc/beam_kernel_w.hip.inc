@@ -283,13 +283,14 @@ __global__ __launch_bounds__(DMW_BLOCK) void dm_build_g_table_kernel(const float
   }
 }
 
-struct BeamWLds { int b1, w2, slot0, slot_stride, x_kfrag, x_gfrag, y_keys, y_acode0, y_acode1, y_aval, misc, total; };
+struct BeamWLds { int b1, w2, lb, slot0, slot_stride, x_kfrag, x_gfrag, y_keys, y_acode0, y_acode1, y_aval, misc, total; };
 __host__ __device__ inline BeamWLds dm_beamw_lds(int E, int cap, int pcap, int kq) {
   const int kcols = kq >= 4 ? 16 : 12;
   BeamWLds l;
   int o = 0;
   l.b1 = o; o += E * 4;
   l.w2 = o; o += E * 4;
+  l.lb = o; o += DM_N_LEVEL_BOUNDS * 4;          // the tree's per-level existence bounds (BeamParams::level_last)
   l.slot0 = o;
   int s = 0;
   l.x_kfrag = s; s += (E / 16) * 4 * kcols * 16;          // K as fp16 hi / lo planes, A-fragment order of the 16x16x32 shape
@@ -398,6 +399,7 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int CAP = p.cap, L = p.L;
   float *B1 = (float *)(smem + lo.b1), *W2 = (float *)(smem + lo.w2);
+  int *LB = (int *)(smem + lo.lb);
   char *slotp = smem + lo.slot0 + wave * lo.slot_stride;
   unsigned long long *keys = (unsigned long long *)(slotp + lo.y_keys);
   float *A_val = (float *)(slotp + lo.y_aval);
@@ -413,6 +415,9 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
     asm volatile("" : "=a"(wreg[i]) : "0"(t));
   }
   for (int i = tid; i < E; i += DMW_BLOCK) { B1[i] = p.b1[i]; W2[i] = p.w2[i] * p.out_unscale; }
+  // the existence bounds of the tree's levels, staged once (a by-value array indexed by a level would live in scratch); without
+  // them — OTM, DM_LEVEL_BOUNDS=0 — every level reads "use the bits"
+  if (tid < DM_N_LEVEL_BOUNDS) LB[tid] = (p.mode == 0 && p.level_last) ? p.level_last[tid] : DM_LEVEL_USE_BITS;
   __syncthreads();                 // b1 / w2: the only workgroup-wide barrier
   const float scale2 = (float)(1.4426950408889634 * (double)p.sm_scale) * p.score_unscale;
   unsigned long long my_rows = 0;
@@ -730,11 +735,22 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
     }
     // initial frontier: codes [start, 2*start+1) that exist, pred 0 (Recommender.scala:53-56)
     int n_cand;
+    int lv0;          // the level of the initial frontier
     {
       const int start = misc[M_START];
       const int n_iter0 = misc[M_NITER];
       int32_t *A0 = (int32_t *)(slotp + lo.y_acode0);
       int base = 0;
+      // the start level's bound (the user's own level: widened beams start at different ones): its existing codes are the run
+      // start .. last, so the frontier is start .. min(2 start, last) — no bit loads, no scan
+      lv0 = 31 - __clz(__builtin_amdgcn_readfirstlane(start) + 1);
+      const int last0 = __builtin_amdgcn_readfirstlane(LB[lv0]);
+      if (last0 != DM_LEVEL_USE_BITS) {
+        const int hi0 = 2 * start < last0 ? 2 * start : last0;
+        base = (n_iter0 > 0 && hi0 >= start) ? hi0 - start + 1 : 0;
+#pragma unroll 1
+        for (int i = lane; i < base; i += 64) { A0[i] = start + i; A_val[i] = 0.0f; }
+      } else
       for (int r0 = 0; r0 < CAP / 2; r0 += 256) {
         unsigned bits = 0;
 #pragma unroll
@@ -783,6 +799,9 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
       // opens with a scratch reload)
       int ln = lane;
       asm volatile("" : "+v"(ln));
+      // the existence bound of the children's level (wave-uniform; DM_LEVEL_USE_BITS: the level has none, or OTM)
+      const int clv = lv0 + it + 1;
+      const int lastc = __builtin_amdgcn_readfirstlane(LB[clv < DM_N_LEVEL_BOUNDS ? clv : DM_N_LEVEL_BOUNDS - 1]);
       // ---- P1: split leaves / non-leaves, in order (Recommender.scala:62-70) ----
       if (p.mode == 0) {
         if (p.leaf_fast) {
@@ -857,15 +876,37 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
       // ---- P3: children 2c+1, 2c+2 of the beam, in beam order, existence-filtered (:88-92) ----
       // eight children (four parents) per lane and round: the existence bits of a whole 512-slot frontier are one round of loads
       for (int r0 = 0; r0 < 2 * nb; r0 += 512) {
-        unsigned bits = 0;
+        unsigned bits = 0, vbits = 0;
         int64_t ch[8];
         bool ok[8];
+        // the four parents' LDS reads as TWO rounds, not eight: every key position is read without a condition (an unsorted
+        // level selects the slot's own index instead; the key area is the wave's own LDS either way) — under `do_sort ? :` each
+        // key read sat in a branch of its own with a wait behind it, one dependent round trip after the other
+        // (the scheduling barriers keep the rounds apart: left alone the scheduler waits for one read before it issues the next)
+        int ppic[4];
+        uint32_t pkey[4];
+        int32_t ppc[4];
+#pragma unroll
+        for (int j2 = 0; j2 < 4; j2++) {
+          const int pi = (r0 >> 1) + 4 * ln + j2;
+          ppic[j2] = pi < nb ? pi : 0;
+        }
+        DMW_PIN();
+#pragma unroll
+        for (int j2 = 0; j2 < 4; j2++) pkey[j2] = ((const uint32_t *)keys)[2 * ppic[j2]];
+        DMW_PIN();
+#pragma unroll
+        for (int j2 = 0; j2 < 4; j2++) ppic[j2] = do_sort ? (int)DMW_KEY_POS(pkey[j2]) : ppic[j2];
+        DMW_PIN();
+#pragma unroll
+        for (int j2 = 0; j2 < 4; j2++) ppc[j2] = Acur[ppic[j2]];
+        DMW_PIN();
 #pragma unroll
         for (int j2 = 0; j2 < 4; j2++) {
           const int pi = (r0 >> 1) + 4 * ln + j2;
           const bool valid = pi < nb;
-          const int pic = valid ? pi : 0;
-          const int32_t pc = do_sort ? Acur[DMW_KEY_POS(keys[pic])] : Acur[pic];
+          vbits |= valid ? (3u << (2 * j2)) : 0u;
+          const int32_t pc = ppc[j2];
 #pragma unroll
           for (int h = 0; h < 2; h++) {
             const int64_t c = (int64_t)pc * 2 + 1 + h;
@@ -873,7 +914,12 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
             ok[2 * j2 + h] = valid && c < p.num_index && (p.mode != 0 || c < p.n_slots);
           }
         }
-        if (p.mode == 0) {
+        const bool bounded = lastc != DM_LEVEL_USE_BITS;          // (never in mode 1: its LB reads "use the bits")
+        if (bounded) {
+          // the level's existing codes are the run first .. lastc: no load, the answer is a compare
+#pragma unroll
+          for (int j = 0; j < 8; j++) ok[j] = ok[j] && ch[j] <= (int64_t)lastc;
+        } else if (p.mode == 0) {
           uint32_t w[8];
 #pragma unroll
           for (int j = 0; j < 8; j++) w[j] = ok[j] ? p.exists_bits[ch[j] >> 5] : 0u;
@@ -882,12 +928,22 @@ __global__ __launch_bounds__(DMW_BLOCK, 1) void dm_beam_w_kernel(BeamParams p) {
         }
 #pragma unroll
         for (int j = 0; j < 8; j++) bits |= ok[j] ? (1u << j) : 0u;
-        int total;
-        const int before = scan8(bits, total);
+        if (bounded && __ballot(bits != vbits) == 0ull) {
+          // every child of this round's parents exists: the ordered compaction is the identity (lane ln's eight children are
+          // elements 8 ln .. 8 ln + 7 of the round, and the parents of a round are a prefix of its slots)
+          const int rem = 2 * nb - r0;
 #pragma unroll
-        for (int j = 0; j < 8; j++)
-          if ((bits >> j) & 1u) Anext[nchild + before + __popc(bits & ((1u << j) - 1))] = (int32_t)ch[j];
-        nchild += total;
+          for (int j = 0; j < 8; j++)
+            if ((bits >> j) & 1u) Anext[nchild + 8 * ln + j] = (int32_t)ch[j];
+          nchild += rem < 512 ? rem : 512;
+        } else {
+          int total;
+          const int before = scan8(bits, total);
+#pragma unroll
+          for (int j = 0; j < 8; j++)
+            if ((bits >> j) & 1u) Anext[nchild + before + __popc(bits & ((1u << j) - 1))] = (int32_t)ch[j];
+          nchild += total;
+        }
       }
       n_cand = nchild;
       cur ^= 1;

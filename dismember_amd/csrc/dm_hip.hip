@@ -97,6 +97,8 @@ struct dm_ctx {
   int max_level = 0;
   int64_t n_slots = 0, n_leaf_nodes = 0;
   uint32_t *d_exists = nullptr, *d_leaf = nullptr;
+  int32_t *d_level_last = nullptr;                          // per-level existence bounds (dm_level_bounds_bits), [DM_N_LEVEL_BOUNDS]
+  std::array<int32_t, DM_N_LEVEL_BOUNDS> level_last{};      //   and their host copy
   int32_t *d_node_id = nullptr, *d_id_to_code = nullptr, *d_leaf_codes = nullptr;
   int32_t non_leaf_offset = -1, max_code = -1;
   std::vector<int32_t> h_id_to_code;
@@ -448,7 +450,7 @@ static const char *scorer_name(const dm_ctx *h) { return h->scorer_kind == DM_KI
 
 static void free_tree(dm_ctx *h) {
   model_changed(h);
-  dm_release(h->d_lv_codes, h->d_lv_cdf, h->d_lv_start, h->d_exists, h->d_leaf, h->d_node_id, h->d_leaf_codes);
+  dm_release(h->d_lv_codes, h->d_lv_cdf, h->d_lv_start, h->d_exists, h->d_leaf, h->d_node_id, h->d_leaf_codes, h->d_level_last);
   h->tree_loaded = false;
 }
 // the training state of dm_train_init: its buffers, and the flags that say they exist
@@ -477,6 +479,7 @@ static void free_weights(dm_ctx *h) {
 // the pre-split table, the f32 mirror of an f64 model, the fp64 fragments).  One list drives the mirror and the clone's tear-down.
 #define DM_SHARED_FIELDS(X)                                                                                                              \
   X(tree_loaded) X(ids_loaded) X(leaves_at_max_only) X(max_level) X(n_slots) X(n_leaf_nodes) X(d_exists) X(d_leaf) X(d_node_id)          \
+  X(d_level_last) X(level_last)                                                                                                          \
   X(d_id_to_code) X(d_leaf_codes) X(non_leaf_offset) X(max_code) X(w_loaded) X(dtype) X(embed) X(embed_log) X(num_index) X(d_compact)    \
   X(d_emb32) X(d_wfrag) X(d_afrag) X(d_bfrag) X(d_attA) X(d_w1aA) X(d_w1bA) X(d_b1) X(d_w2) X(b2) X(d_att_wT_t) X(d_l1T_t) X(d_tail32)   \
   X(lazy) X(d_lv_codes) X(d_lv_cdf) X(d_lv_start) X(scorer_kind) X(dfm_L) X(d_dfm_frag) X(d_dfm_w2p) X(d_dfm_fragS)
@@ -533,6 +536,39 @@ int dm_level_start(int candidate_num, int *start_code, int *level) {
   return level_start_int(candidate_num, start_code, level);
 }
 
+// Per-level existence bounds of the bitmap `ex` over codes [0, n_slots): out[l], l = 0 .. DM_N_LEVEL_BOUNDS - 1, is the largest
+// existing code of level l when the level's existing codes are exactly the prefix [2^l - 1, last] of its code range (every
+// left-filled heap, TreeBuilder's trees among them), 2^l - 2 when the level holds no node, and DM_LEVEL_USE_BITS when the level has
+// a gap.  With a bound, "code c of level l exists" is c <= out[l]: a compare against a number that holds while the tree is loaded.
+static void dm_level_bounds_bits(const uint32_t *ex, int64_t n_slots, int32_t *out) {
+  for (int l = 0; l < DM_N_LEVEL_BOUNDS; l++) {
+    const int64_t first = ((int64_t)1 << l) - 1, end = std::min<int64_t>(2 * first + 1, n_slots);
+    if (l > 30) { out[l] = DM_LEVEL_USE_BITS; continue; }          // (no int32 code lives there)
+    int64_t count = 0, last = first - 1;
+    for (int64_t c = first; c < end;) {
+      const uint32_t w = ex[c >> 5] >> (c & 31);
+      const int span = (int)std::min<int64_t>(32 - (c & 31), end - c);
+      const uint32_t m = span == 32 ? w : (w & ((1u << span) - 1u));
+      if (m) { count += __builtin_popcount(m); last = c + 31 - __builtin_clz(m); }
+      c += span;
+    }
+    out[l] = count == 0 ? (int32_t)(first - 1) : count == last - first + 1 ? (int32_t)last : DM_LEVEL_USE_BITS;
+  }
+}
+// debug (not part of the public header): the bounds of a list of node codes, without a handle or a device
+extern "C" int dm_debug_level_bounds(const int32_t *codes, int64_t n_nodes, int32_t *out) {
+  if (!codes || !out || n_nodes < 0) return DM_ERR_INVALID;
+  int64_t mc = -1;
+  for (int64_t i = 0; i < n_nodes; i++) {
+    if (codes[i] < 0) return DM_ERR_INVALID;
+    if (codes[i] > mc) mc = codes[i];
+  }
+  std::vector<uint32_t> ex((size_t)((mc + 1 + 31) / 32 + 1), 0);
+  for (int64_t i = 0; i < n_nodes; i++) ex[(size_t)(codes[i] >> 5)] |= 1u << (codes[i] & 31);
+  dm_level_bounds_bits(ex.data(), mc + 1, out);
+  return DM_OK;
+}
+
 int dm_load_tree_tdm(dm_handle_t h, const int32_t *codes, const int32_t *node_ids, const uint8_t *is_leaf,
                      int64_t n_nodes, int max_level) {
   if (!h) return DM_ERR_INVALID;
@@ -563,6 +599,9 @@ int dm_load_tree_tdm(dm_handle_t h, const int32_t *codes, const int32_t *node_id
   ALLOC(h, h->d_leaf, words * 4);
   ALLOC(h, h->d_node_id, n_slots * 4);
   ALLOC(h, h->d_leaf_codes, leaf_codes.size() * 4);
+  ALLOC(h, h->d_level_last, DM_N_LEVEL_BOUNDS * 4);
+  dm_level_bounds_bits(ex.data(), n_slots, h->level_last.data());
+  HIPCHK(h, hipMemcpy(h->d_level_last, h->level_last.data(), DM_N_LEVEL_BOUNDS * 4, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_exists, ex.data(), words * 4, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_leaf, lf.data(), words * 4, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(h->d_node_id, nid.data(), n_slots * 4, hipMemcpyHostToDevice));
@@ -1092,6 +1131,9 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       p.defer_count = (unsigned long long *)h->defer.p;
       p.defer_users = (int32_t *)((char *)h->defer.p + 16);
       { const int rc_g = g_table_for_search(h, &p.g_table); if (rc_g != DM_OK) return rc_g; }
+      // DM_LEVEL_BOUNDS (read per call, like DM_G_TABLE: the tests run both routes in one process) = 0: the existence tests of
+      // the expand and of the initial frontier read the bitmap on every level; unset or 1: the per-level bounds where a level has one
+      { const char *e_ = getenv("DM_LEVEL_BOUNDS"); p.level_last = (e_ && e_[0] == '0') ? nullptr : h->d_level_last; }
       h->last_g_table = p.g_table != nullptr;
       const char *const no_split = "the split-fp16 scorer needs an embedding size of 32, 64 or 128";
       int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
