@@ -65,9 +65,7 @@ __global__ void dm_mark_active_kernel(const int32_t *a, int64_t na, const int32_
   }
 }
 int TrainVec::mark_active(dm_ctx *h, unsigned grid, const int32_t *a, int64_t na, const int32_t *b, int64_t nb) {
-  hipLaunchKernelGGL(dm_mark_active_kernel, dim3(grid), dim3(256), 0, h->stream, a, na, b, nb, active_bits, active_list, active_cnt, rows);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, dm_mark_active_kernel, dim3(grid), dim3(256), 0, a, na, b, nb, active_bits, active_list, active_cnt, rows);
 }
 
 int TrainVec::remember(dm_ctx *h, const unsigned long long *sorted_keys, int64_t m) {
@@ -86,35 +84,32 @@ AdamPlan TrainVec::plan_step(unsigned long long active) {
   const double clr = opts.lr / (1 + t * opts.lr_decay);
   t += 1;
   const double bc1 = 1 - pow(opts.beta1, t), bc2 = 1 - pow(opts.beta2, t);
-  const char *fd_ = getenv("DM_ADAM_DENSE");
-  const bool force_dense = fd_ && fd_[0] == '1';
+  const bool force_dense = env_on("DM_ADAM_DENSE");
   return AdamPlan{clr * sqrt(bc2) / bc1, (int64_t)active, !force_dense && opts.eps > 0 && (int64_t)active * 4 < rows};
 }
 
 // The launches of one planned step.  Rows path: the listed rows, then the tail — dense, or one value per table row (the criterion's
 // softmax_b: tail_by_row, the same list with E = 1).  KEEP puts the gradient back (the accumulating criterion never clears it).
 template <typename T, bool KEEP>
-static void adam_step_vec(dm_ctx *h, const TrainVec &v, const AdamPlan &p, void *weights, float grad_scale, bool tail_by_row, unsigned tail_grid) {
+static int adam_step_vec(dm_ctx *h, const TrainVec &v, const AdamPlan &p, void *weights, float grad_scale, bool tail_by_row, unsigned tail_grid) {
   const dm_adam_opts &o = v.opts;
   const T gs = (T)grad_scale, b1 = (T)o.beta1, c1 = (T)(1 - o.beta1), b2 = (T)o.beta2, c2 = (T)(1 - o.beta2), eps = (T)o.eps, ns = (T)(-p.step);
   T *w = (T *)weights, *g = (T *)v.grad, *s_ = (T *)v.s, *r_ = (T *)v.r;
   const int64_t table = v.rows * v.E;
-  if (!p.rows_path) {
-    hipLaunchKernelGGL((dm_adam_kernel<T, KEEP>), dim3(8192), dim3(256), 0, h->stream, w, g, s_, r_, v.n, gs, b1, c1, b2, c2, eps, ns);
-    return;
-  }
-  if (p.act) hipLaunchKernelGGL((dm_adam_rows_kernel<T, KEEP>), dim3(4096), dim3(256), 0, h->stream, w, g, s_, r_, v.active_list, p.act, v.E, gs, b1, c1, b2, c2, eps, ns);
+  if (!p.rows_path) return LAUNCH(h, (dm_adam_kernel<T, KEEP>), dim3(8192), dim3(256), 0, w, g, s_, r_, v.n, gs, b1, c1, b2, c2, eps, ns);
+  int rc = DM_OK;
+  if (p.act) rc = LAUNCH(h, (dm_adam_rows_kernel<T, KEEP>), dim3(4096), dim3(256), 0, w, g, s_, r_, v.active_list, p.act, v.E, gs, b1, c1, b2, c2, eps, ns);
+  if (rc != DM_OK) return rc;
   if (!tail_by_row)
-    hipLaunchKernelGGL((dm_adam_kernel<T, KEEP>), dim3(tail_grid), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, v.n - table, gs, b1, c1, b2, c2, eps, ns);
-  else if (p.act)
-    hipLaunchKernelGGL((dm_adam_rows_kernel<T, KEEP>), dim3(tail_grid), dim3(256), 0, h->stream, w + table, g + table, s_ + table, r_ + table, v.active_list, p.act, 1, gs, b1, c1,
-                       b2, c2, eps, ns);
+    return LAUNCH(h, (dm_adam_kernel<T, KEEP>), dim3(tail_grid), dim3(256), 0, w + table, g + table, s_ + table, r_ + table, v.n - table, gs, b1, c1, b2, c2, eps, ns);
+  if (p.act)
+    return LAUNCH(h, (dm_adam_rows_kernel<T, KEEP>), dim3(tail_grid), dim3(256), 0, w + table, g + table, s_ + table, r_ + table, v.active_list, p.act, 1, gs, b1, c1, b2, c2,
+                  eps, ns);
+  return DM_OK;
 }
 static int adam_step(dm_ctx *h, const TrainVec &v, const AdamPlan &p, void *weights, bool f64, bool keep, float grad_scale, bool tail_by_row, unsigned tail_grid) {
-  if (f64) keep ? adam_step_vec<double, true>(h, v, p, weights, grad_scale, tail_by_row, tail_grid) : adam_step_vec<double, false>(h, v, p, weights, grad_scale, tail_by_row, tail_grid);
-  else keep ? adam_step_vec<float, true>(h, v, p, weights, grad_scale, tail_by_row, tail_grid) : adam_step_vec<float, false>(h, v, p, weights, grad_scale, tail_by_row, tail_grid);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  if (f64) return keep ? adam_step_vec<double, true>(h, v, p, weights, grad_scale, tail_by_row, tail_grid) : adam_step_vec<double, false>(h, v, p, weights, grad_scale, tail_by_row, tail_grid);
+  return keep ? adam_step_vec<float, true>(h, v, p, weights, grad_scale, tail_by_row, tail_grid) : adam_step_vec<float, false>(h, v, p, weights, grad_scale, tail_by_row, tail_grid);
 }
 
 #else

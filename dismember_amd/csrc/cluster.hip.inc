@@ -638,8 +638,9 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
   }
   int32_t *perm[2] = {nullptr, nullptr}, *d_codes = nullptr;
   unsigned long long *keys[2] = {nullptr, nullptr};
+  int rc;
   CL_GET(perm[0], n); CL_GET(perm[1], n); CL_GET(d_codes, n);
-  hipLaunchKernelGGL(cl_iota_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, sm, perm[0], n);
+  if ((rc = LAUNCH(h, cl_iota_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, perm[0], n)) != DM_OK) return rc;
   HIPCHK(h, hipMemsetAsync(d_codes, 0, (size_t)n * 4, sm));
   int cur = 0, level = 0;
   constexpr int CUT = ClCut<EP>::items;
@@ -676,19 +677,16 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
     L.keys = keys[0]; L.vals = perm[cur ^ 1];
     // seeding
     auto t0 = clk::now();
-    hipLaunchKernelGGL(cl_seed0_kernel<EP>, dim3((unsigned)SR), dim3(64), 0, sm, L);
-    hipLaunchKernelGGL(cl_seed_dist_kernel<EP>, dim3((unsigned)T), dim3(CL_TB), 0, sm, L);
-    hipLaunchKernelGGL(cl_seed_pick_kernel<EP>, dim3((unsigned)SR), dim3(CL_TB), 0, sm, L);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, cl_seed0_kernel<EP>, dim3((unsigned)SR), dim3(64), 0, L)) != DM_OK || (rc = LAUNCH(h, cl_seed_dist_kernel<EP>, dim3((unsigned)T), dim3(CL_TB), 0, L)) != DM_OK ||
+        (rc = LAUNCH(h, cl_seed_pick_kernel<EP>, dim3((unsigned)SR), dim3(CL_TB), 0, L)) != DM_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(sm));
     st.seeding_s += secs(t0); st.bytes_streamed += (int64_t)row_bytes;
     // Lloyd
     t0 = clk::now();
     for (int it = 0; it < max_iter; it++) {
       HIPCHK(h, hipMemsetAsync(L.any_active, 0, 4, sm));
-      hipLaunchKernelGGL(cl_lloyd_tile_kernel<EP>, dim3((unsigned)T), dim3(CL_TB), 0, sm, L);
-      hipLaunchKernelGGL(cl_lloyd_reduce_kernel<EP>, dim3((unsigned)SR), dim3(CL_TB), 0, sm, L);
-      HIPCHK(h, hipGetLastError());
+      if ((rc = LAUNCH(h, cl_lloyd_tile_kernel<EP>, dim3((unsigned)T), dim3(CL_TB), 0, L)) != DM_OK ||
+          (rc = LAUNCH(h, cl_lloyd_reduce_kernel<EP>, dim3((unsigned)SR), dim3(CL_TB), 0, L)) != DM_OK) return rc;
       int32_t any = 0;
       HIPCHK(h, hipMemcpyAsync(&any, L.any_active, 4, hipMemcpyDeviceToHost, sm));
       HIPCHK(h, hipStreamSynchronize(sm));
@@ -698,9 +696,8 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
     st.lloyd_s += secs(t0);
     // split
     t0 = clk::now();
-    hipLaunchKernelGGL(cl_best_kernel<EP>, dim3((unsigned)std::min(S / 256 + 1, 1024)), dim3(256), 0, sm, L);
-    hipLaunchKernelGGL(cl_dist_key_kernel<EP>, dim3((unsigned)T), dim3(CL_TB), 0, sm, L);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, cl_best_kernel<EP>, dim3((unsigned)std::min(S / 256 + 1, 1024)), dim3(256), 0, L)) != DM_OK ||
+        (rc = LAUNCH(h, cl_dist_key_kernel<EP>, dim3((unsigned)T), dim3(CL_TB), 0, L)) != DM_OK) return rc;
     int sbits = 0;
     while ((1 << sbits) < S) sbits++;
     int where = 0;
@@ -727,9 +724,7 @@ static int cluster_run(dm_ctx *h, const float *d_X, int64_t n, int E, int R, int
     P.X = d_X; P.n = n; P.level = level; P.S = S; P.R = R; P.max_iter = max_iter; P.tol = tol; P.seed = seed; P.perm = perm[cur]; P.seg_off = d_seg_off;
     P.codes = d_codes; P.tr = tr;
     const size_t lds = (size_t)CUT * EP * 4 + (size_t)CUT * (4 + 4 + 2 + 2);
-    HIPCHK(h, hipFuncSetAttribute((const void *)cl_lds_subtree_kernel<EP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(cl_lds_subtree_kernel<EP>, dim3((unsigned)S), dim3(CL_TB), lds, sm, P);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH_LDS(h, cl_lds_subtree_kernel<EP>, dim3((unsigned)S), dim3(CL_TB), lds, P)) != DM_OK) return rc;
     HIPCHK(h, hipStreamSynchronize(sm));
     st.lds_s += secs(t0); st.bytes_streamed += (int64_t)row_bytes;
     st.levels_lds = max_level - level;
@@ -829,9 +824,8 @@ static int cluster_gather_model(dm_ctx *h, const char *who, const int32_t *item_
   CL_GET(*d_out, (size_t)n * ocols);
   HIPCHK(h, hipMemcpy(d_rows, codes.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   const int cols = h->embed_log > 0 ? h->embed_log : h->embed;
-  hipLaunchKernelGGL(cl_gather_rows_kernel, dim3((unsigned)std::min<int64_t>((n * ocols + 255) / 256, 8192)), dim3(256), 0, h->stream,
-                     (const float *)h->d_emb32, h->embed, cols, (const int32_t *)d_rows, n, ocols, *d_out);
-  HIPCHK(h, hipGetLastError());
+  const int rc_g = LAUNCH(h, cl_gather_rows_kernel, dim3((unsigned)std::min<int64_t>((n * ocols + 255) / 256, 8192)), dim3(256), 0, h->d_emb32, h->embed, cols, d_rows, n, ocols, *d_out);
+  if (rc_g != DM_OK) return rc_g;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DM_OK;
 }
@@ -851,9 +845,8 @@ int dm_cluster_tree_model(dm_handle_t h, const int32_t *item_ids, int64_t n, int
     int32_t *d_first, first = 0x7fffffff;
     CL_GET(d_first, 1);
     HIPCHK(h, hipMemcpy(d_first, &first, 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(cl_nonfinite_kernel, dim3((unsigned)std::min<int64_t>((n * h->embed + 255) / 256, 8192)), dim3(256), 0, h->stream,
-                       (const float *)d_X, n, h->embed, d_first);
-    HIPCHK(h, hipGetLastError());
+    const int rc_n = LAUNCH(h, cl_nonfinite_kernel, dim3((unsigned)std::min<int64_t>((n * h->embed + 255) / 256, 8192)), dim3(256), 0, d_X, n, h->embed, d_first);
+    if (rc_n != DM_OK) return rc_n;
     HIPCHK(h, hipMemcpyAsync(&first, d_first, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (first != 0x7fffffff)

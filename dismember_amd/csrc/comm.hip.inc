@@ -432,8 +432,7 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
       HIPCHK(h, hipSetDevice(h->device));
       int rc = sync_grow(h, 16 + 16 * (size_t)W);
       if (rc != DM_OK) return rc;
-      hipLaunchKernelGGL(dm_sync_record_kernel, dim3(1), dim3(64), 0, h->stream, h->d_touch_cnt, (unsigned long long)h->touch_cap, (unsigned long long *)h->sync.p);
-      HIPCHK(h, hipGetLastError());
+      if ((rc = LAUNCH(h, dm_sync_record_kernel, dim3(1), dim3(64), 0, h->d_touch_cnt, h->touch_cap, (unsigned long long *)h->sync.p)) != DM_OK) return rc;
     }
     ncclResult_t e = ncclGroupStart();
     for (int i = 0; i < nh && e == ncclSuccess; i++)
@@ -538,9 +537,9 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
     }
     S.bytes_sent = sendbuf.size(); S.bytes_recv = off;
     char *dense = (char *)h->train.grad + (size_t)(h->num_index * E) * es;
-    if (f64) hipLaunchKernelGGL(dm_sum_blocks_kernel<double>, dim3(64), dim3(256), 0, h->stream, (double *)dense, (const double *)lay[0].dense_all, nd, W);
-    else hipLaunchKernelGGL(dm_sum_blocks_kernel<float>, dim3(64), dim3(256), 0, h->stream, (float *)dense, (const float *)lay[0].dense_all, nd, W);
-    HIPCHK(h, hipGetLastError());
+    const int rc_s = f64 ? LAUNCH(h, dm_sum_blocks_kernel<double>, dim3(64), dim3(256), 0, (double *)dense, (const double *)lay[0].dense_all, nd, W)
+                         : LAUNCH(h, dm_sum_blocks_kernel<float>, dim3(64), dim3(256), 0, (float *)dense, (const float *)lay[0].dense_all, nd, W);
+    if (rc_s != DM_OK) return rc_s;
     HIPCHK(h, hipStreamSynchronize(h->stream));      // recv is read by the copies above
     S.host_syncs++;
   }
@@ -550,9 +549,9 @@ static int sync_gradients_impl(dm_ctx **hs, int nh) {
     HIPCHK(h, hipSetDevice(h->device));
     const uint64_t mine = cnt[h->comm->rank];
     if (mine) {
-      if (f64) hipLaunchKernelGGL(dm_zero_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (double *)h->train.grad, h->d_touch_list, (int64_t)mine, (int)E);
-      else hipLaunchKernelGGL(dm_zero_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (float *)h->train.grad, h->d_touch_list, (int64_t)mine, (int)E);
-      HIPCHK(h, hipGetLastError());
+      const int rc_z = f64 ? LAUNCH(h, dm_zero_rows_kernel<double>, dim3(1024), dim3(256), 0, (double *)h->train.grad, h->d_touch_list, mine, E)
+                           : LAUNCH(h, dm_zero_rows_kernel<float>, dim3(1024), dim3(256), 0, (float *)h->train.grad, h->d_touch_list, mine, E);
+      if (rc_z != DM_OK) return rc_z;
     }
     size_t ro = 0, go = 0;
     for (int r = 0; r < W; r++) {

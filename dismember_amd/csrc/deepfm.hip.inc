@@ -332,9 +332,11 @@ int dm_load_weights_deepfm(dm_handle_t h, int dtype, int E, int L, int64_t num_i
   ALLOC(h, h->d_dfm_w2p, (size_t)NCT * 16 * 4);
   ALLOC(h, h->d_dfm_fragS, (size_t)NCT * L * Ep * 64);
   const DfmBlocks b = dfm_blocks(h);
-  hipLaunchKernelGGL(dfm_derive_kernel, dim3(32), dim3(256), 0, h->stream, b.l1_w, b.l2_w, Ep, L + 1, NCT, h->d_dfm_frag, h->d_dfm_w2p);
-  hipLaunchKernelGGL(dfm_jtm_derive_kernel, dim3(256), dim3(256), 0, h->stream, b.l1_w, Ep, L, NCT, h->d_dfm_fragS);
-  HIPCHK(h, hipGetLastError());
+  {
+    int rc = LAUNCH(h, dfm_derive_kernel, dim3(32), dim3(256), 0, b.l1_w, b.l2_w, Ep, L + 1, NCT, h->d_dfm_frag, h->d_dfm_w2p);
+    if (rc == DM_OK) rc = LAUNCH(h, dfm_jtm_derive_kernel, dim3(256), dim3(256), 0, b.l1_w, Ep, L, NCT, h->d_dfm_fragS);
+    if (rc != DM_OK) return rc;
+  }
   HIPCHK(h, hipMemcpyAsync(&h->b2, b.l2_b, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->w_loaded = true;
@@ -393,11 +395,9 @@ int dm_deepfm_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, 
   p.emb = h->d_emb32; p.l1_w = b.l1_w; p.l1_b = b.l1_b; p.l2_w = b.l2_w; p.b2 = h->b2;
   p.codes = ar.ptr<int32_t>(o_codes); p.seqs = ar.ptr<int32_t>(o_seqs); p.E = h->embed; p.L = L; p.B = B; p.out = ar.ptr<float>(o_out);
   const size_t lds = (size_t)4 * (L + 1) * h->embed * 4;      // at most 4 x 33 x 128 floats = 66 KB
-  HIPCHK(h, hipFuncSetAttribute((const void *)dfm_forward_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   int64_t blocks = (B + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(dfm_forward_kernel, dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = LAUNCH_LDS(h, dfm_forward_kernel, dim3((unsigned)blocks), dim3(256), lds, p)) != DM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(logits, p.out, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DM_OK;
@@ -411,11 +411,7 @@ static int dfm_launch_level(dm_ctx *h, const DfmLevel &p) {
   int64_t blocks = (waves + 3) / 4;
   if (blocks > (int64_t)h->n_cu * 4) blocks = (int64_t)h->n_cu * 4;
   if (blocks < 1) blocks = 1;
-  LaunchTimer tm(h, EV_DFM_LEVEL);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dfm_level_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  return timed(h, EV_DFM_LEVEL, true, [&] { return LAUNCH(h, (dfm_level_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), lds, p); });
 }
 
 struct TdmPlDeepFM : TdmPlScorer {
@@ -436,11 +432,7 @@ struct TdmPlDeepFM : TdmPlScorer {
     DfmUser p;
     p.emb = h->d_emb32; p.l1_w = b.l1_w; p.l1_b = b.l1_b; p.b2 = h->b2; p.kcode = kcode; p.E = E; p.L = L; p.NC = NCT * 16;
     p.num_index = h->num_index; p.S = S; p.aux = aux;
-    LaunchTimer tm(h, EV_DFM_USER);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(dfm_user_kernel, dim3((unsigned)Un), dim3(256), 0, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    return tm.stop();
+    return timed(h, EV_DFM_USER, true, [&] { return LAUNCH(h, dfm_user_kernel, dim3((unsigned)Un), dim3(256), 0, p); });
   }
   int score(dm_ctx *h, const int32_t *cur, const int32_t *ncur, float *sc, int64_t Un) override {
     DfmLevel p;

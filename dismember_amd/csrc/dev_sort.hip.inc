@@ -115,10 +115,10 @@ static hipError_t dev_select_flagged(hipStream_t st, const A *in, const B *in2, 
                                      uint32_t *scratch) {
   if (n <= 0) return hipMemsetAsync(d_count, 0, 8, st);
   const int64_t tiles = (n + DSORT_TILE - 1) / DSORT_TILE;
-  hipLaunchKernelGGL((dsel_count_kernel<A, B>), dim3((unsigned)tiles), dim3(DSORT_TB), 0, st, flag, n, scratch);
-  hipLaunchKernelGGL(dsort_scan_kernel, dim3(1), dim3(1024), 0, st, scratch, tiles, d_count);
-  hipLaunchKernelGGL((dsel_scatter_kernel<A, B>), dim3((unsigned)tiles), dim3(DSORT_TB), 0, st, in, in2, flag, n, (const uint32_t *)scratch, out, out2);
-  return hipGetLastError();
+  hipError_t e = launch_on(st, dsel_count_kernel<A, B>, dim3((unsigned)tiles), dim3(DSORT_TB), 0, flag, n, scratch);
+  if (e == hipSuccess) e = launch_on(st, dsort_scan_kernel, dim3(1), dim3(1024), 0, scratch, tiles, d_count);
+  if (e == hipSuccess) e = launch_on(st, dsel_scatter_kernel<A, B>, dim3((unsigned)tiles), dim3(DSORT_TB), 0, in, in2, flag, n, scratch, out, out2);
+  return e;
 }
 
 // ---- radix sort, 8 bits per pass
@@ -201,12 +201,14 @@ static hipError_t dev_radix_sort_pairs(hipStream_t st, unsigned long long *k0, i
   for (int shift = begin_bit; shift < end_bit; shift += 8) {
     const int bits = end_bit - shift < 8 ? end_bit - shift : 8;
     const unsigned mask = (1u << bits) - 1u;
-    hipLaunchKernelGGL(dsort_hist_kernel, dim3((unsigned)tiles), dim3(DSORT_TB), 0, st, (const unsigned long long *)ks[cur], m, shift, mask, tiles, scratch);
-    hipLaunchKernelGGL(dsort_digit_scan_kernel, dim3(256), dim3(256), 0, st, scratch, tiles, scratch + 256 * tiles);
-    hipLaunchKernelGGL(dsort_scatter_kernel, dim3((unsigned)tiles), dim3(DSORT_TB), 0, st, (const unsigned long long *)ks[cur], (const int32_t *)vs[cur], m, shift, mask,
-                       tiles, (const uint32_t *)scratch, (const uint32_t *)(scratch + 256 * tiles), ks[cur ^ 1], vs[cur ^ 1]);
+    hipError_t e = launch_on(st, dsort_hist_kernel, dim3((unsigned)tiles), dim3(DSORT_TB), 0, ks[cur], m, shift, mask, tiles, scratch);
+    if (e == hipSuccess) e = launch_on(st, dsort_digit_scan_kernel, dim3(256), dim3(256), 0, scratch, tiles, scratch + 256 * tiles);
+    if (e == hipSuccess)
+      e = launch_on(st, dsort_scatter_kernel, dim3((unsigned)tiles), dim3(DSORT_TB), 0, ks[cur], vs[cur], m, shift, mask, tiles, scratch, scratch + 256 * tiles,
+                    ks[cur ^ 1], vs[cur ^ 1]);
+    if (e != hipSuccess) return e;
     cur ^= 1;
   }
   *where = cur;
-  return hipGetLastError();
+  return hipSuccess;
 }

@@ -26,7 +26,7 @@
 // DM_DFM_JTM_SLICE=<positive integer>: histories per set-up pass, read per call like DM_JTM_MAX_PAIRS (tests: slice edges at sizes a test
 // can afford); unset or invalid: DFM_JTM_SLICE
 static int64_t dfm_jtm_slice() {
-  const char *e = getenv("DM_DFM_JTM_SLICE");
+  const char *e = env_str("DM_DFM_JTM_SLICE");
   if (!e || !*e) return DFM_JTM_SLICE;
   char *end = nullptr;
   const long long v = strtoll(e, &end, 10);
@@ -177,26 +177,18 @@ __global__ __launch_bounds__(256) void dfm_jtm_pairs_kernel(DfmJtmPairs p) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
+// the two launches of the pair scorer: the per-history set-up (OTM tree construction, dfm_otm_tree.hip.inc, runs it on its own) and the pairs
 template <int E, int NCT>
-static int dfm_jtm_launch(dm_ctx *h, const DfmJtmRows &r, const DfmJtmPairs &p) {
-  {
-    int64_t blocks = ((r.H + 15) / 16 + 3) / 4;
-    if (blocks > (int64_t)h->n_cu * 8) blocks = (int64_t)h->n_cu * 8;
-    LaunchTimer tm(h, EV_DFM_JTM_ROWS);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL((dfm_jtm_rows_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), 0, h->stream, r);
-    HIPCHK(h, hipGetLastError());
-    const int rc = tm.stop();
-    if (rc != DM_OK) return rc;
-  }
-  const size_t lds = dfm_frag_bytes(E, NCT);
+static int dfm_jtm_launch_rows(dm_ctx *h, const DfmJtmRows &r) {
+  int64_t blocks = ((r.H + 15) / 16 + 3) / 4;
+  if (blocks > (int64_t)h->n_cu * 8) blocks = (int64_t)h->n_cu * 8;
+  return timed(h, EV_DFM_JTM_ROWS, true, [&] { return LAUNCH(h, (dfm_jtm_rows_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), 0, r); });
+}
+template <int E, int NCT>
+static int dfm_jtm_launch_pairs(dm_ctx *h, const DfmJtmPairs &p) {
   int64_t blocks = ((p.P + 15) / 16 + 3) / 4;
   if (blocks > (int64_t)h->n_cu * 4) blocks = (int64_t)h->n_cu * 4;
-  LaunchTimer tm(h, EV_DFM_JTM_PAIRS);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dfm_jtm_pairs_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  return timed(h, EV_DFM_JTM_PAIRS, true, [&] { return LAUNCH(h, (dfm_jtm_pairs_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), dfm_frag_bytes(E, NCT), p); });
 }
 
 // logits of P pairs on device buffers, asynchronous on the handle's stream: d_seqs holds ceil(P / seq_div) histories of CODES
@@ -219,7 +211,10 @@ static int dfm_pairs_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seq
     const int64_t p0 = h0 * seq_div;
     r.hcode = d_seqs + h0 * L; r.H = std::min(Hs, H - h0);
     p.codes = d_codes + p0; p.out = d_out + p0; p.P = std::min(P - p0, r.H * seq_div);
-    rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_jtm_launch<decltype(e)::value, decltype(n)::value>(h, r, p); });
+    rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) {
+      const int r_ = dfm_jtm_launch_rows<decltype(e)::value, decltype(n)::value>(h, r);
+      return r_ != DM_OK ? r_ : dfm_jtm_launch_pairs<decltype(e)::value, decltype(n)::value>(h, p);
+    });
     if (rc != DM_OK) return rc;
   }
   return DM_OK;

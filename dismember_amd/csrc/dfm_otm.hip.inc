@@ -125,18 +125,14 @@ __global__ __launch_bounds__(256) void dfm_otm_beam_kernel(DfmOtm p) {
 // ------------------------------------------------------------------------------------------------ host
 template <int E, int NCT>
 static int dfm_otm_launch(dm_ctx *h, const DfmOtm &p, int nthr, size_t lds) {
-  HIPCHK(h, hipFuncSetAttribute((const void *)dfm_otm_beam_kernel<E, NCT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIPCHK(h, lds_opt_in(dfm_otm_beam_kernel<E, NCT>, lds));      // before the occupancy query, which is asked about the same LDS
   int occ = 0;
   HIPCHK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)dfm_otm_beam_kernel<E, NCT>, nthr, lds));
   if (occ < 1) occ = 1;
   int64_t grid = std::min<int64_t>(p.U, (int64_t)h->n_cu * occ);      // every workgroup resident: equal users, equal shares
-  { const char *e_ = getenv("DM_DFM_OTM_GRID"); if (e_ && atoi(e_) > 0) grid = std::min(atoi(e_), 65535); }      // (tests: a second, partial round of the user loop)
+  if (const long long g_ = env_int("DM_DFM_OTM_GRID")) grid = std::min<int64_t>(g_, 65535);      // (tests: a second, partial round of the user loop)
   snprintf(h->last_kernel, sizeof(h->last_kernel), "dfm_otm_beam_kernel<%d, %d>", E, NCT);
-  LaunchTimer tm(h, EV_DFM_OTM);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dfm_otm_beam_kernel<E, NCT>), dim3((unsigned)grid), dim3((unsigned)nthr), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  return timed(h, EV_DFM_OTM, true, [&] { return LAUNCH(h, (dfm_otm_beam_kernel<E, NCT>), dim3((unsigned)grid), dim3((unsigned)nthr), lds, p); });
 }
 
 // what every DeepFM OTM entry point checks first (after the NULL check and, for the searches, DM_CLONE_ENTER): dfm_enter, then the search's shape

@@ -28,7 +28,7 @@
 // DM_DFM_OTM_TREE_SEG=<1 .. 256>: rows per segment, read per call like DM_JTM_MAX_PAIRS (tests: segment edges at sizes a test can afford);
 // unset or invalid: DFM_OTM_TREE_SEG
 static int dfm_otm_tree_seg() {
-  const char *e = getenv("DM_DFM_OTM_TREE_SEG");
+  const char *e = env_str("DM_DFM_OTM_TREE_SEG");
   if (!e || !*e) return DFM_OTM_TREE_SEG;
   char *end = nullptr;
   const long long v = strtoll(e, &end, 10);
@@ -209,26 +209,13 @@ static int dfm_otm_seg_list(dm_ctx *h, const int64_t *row_off, int64_t n_items, 
 }
 
 template <int E, int NCT>
-static int dfm_otm_tree_launch_rows(dm_ctx *h, const DfmJtmRows &r) {
-  int64_t blocks = ((r.H + 15) / 16 + 3) / 4;
-  if (blocks > (int64_t)h->n_cu * 8) blocks = (int64_t)h->n_cu * 8;
-  LaunchTimer tm(h, EV_DFM_JTM_ROWS);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dfm_jtm_rows_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), 0, h->stream, r);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
-}
-
-template <int E, int NCT>
 static int dfm_otm_tree_launch_score(dm_ctx *h, const DfmOtmTreeScore &p) {
   int64_t blocks = (p.n_units + 3) / 4;
   if (blocks > (int64_t)h->n_cu * 16) blocks = (int64_t)h->n_cu * 16;
-  { const char *e_ = getenv("DM_DFM_OTM_TREE_GRID"); if (e_ && atoi(e_) > 0) blocks = std::min(atoi(e_), 65535); }      // (tests: several rounds of the unit loop)
-  LaunchTimer tm(h, EV_DFM_OTM_TREE_SCORE);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dfm_otm_tree_score_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), dfm_frag_bytes(E, NCT), h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  if (const long long g_ = env_int("DM_DFM_OTM_TREE_GRID")) blocks = std::min<int64_t>(g_, 65535);      // (tests: several rounds of the unit loop)
+  return timed(h, EV_DFM_OTM_TREE_SCORE, true, [&] {
+    return LAUNCH(h, (dfm_otm_tree_score_kernel<E, NCT>), dim3((unsigned)blocks), dim3(256), dfm_frag_bytes(E, NCT), p);
+  });
 }
 
 // the set-up of H histories (codes on the device) into S / aux
@@ -238,7 +225,7 @@ static int dfm_otm_tree_setup(dm_ctx *h, const int32_t *d_hcode, int64_t H, floa
   DfmJtmRows r;
   r.emb = h->d_emb32; r.fragS = (const f32x4 *)h->d_dfm_fragS; r.l1_b = b.l1_b; r.b2 = h->b2; r.L = h->dfm_L; r.num_index = h->num_index;
   r.hcode = d_hcode; r.H = H; r.S = S; r.aux = aux;
-  return dispatch_E_NCT(h, h->embed, dfm_col_tiles(h->dfm_L), "unsupported embed size", [&](auto e, auto n) { return dfm_otm_tree_launch_rows<decltype(e)::value, decltype(n)::value>(h, r); });
+  return dispatch_E_NCT(h, h->embed, dfm_col_tiles(h->dfm_L), "unsupported embed size", [&](auto e, auto n) { return dfm_jtm_launch_rows<decltype(e)::value, decltype(n)::value>(h, r); });
 }
 
 // The gap step on device arrays, asynchronous on the handle's stream: weights [n_items][1 << gap] double.  Items go in chunks of whole
@@ -278,12 +265,10 @@ static int dfm_otm_tree_steps(dm_ctx *h, const int64_t *row_off, const DfmOtmSeg
       rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_otm_tree_launch_score<decltype(e)::value, decltype(n)::value>(h, p); });
       if (rc != DM_OK) return rc;
     }
-    LaunchTimer tm(h, EV_DFM_OTM_TREE_SUM);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(dfm_otm_tree_sum_kernel, dim3((unsigned)(((i1 - i0) * nchild + 255) / 256)), dim3(256), 0, h->stream, sl.d_seg_off, s0, i0, i1 - i0, gap,
-                       (const double *)part.p, d_w);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    rc = timed(h, EV_DFM_OTM_TREE_SUM, true, [&] {
+      return LAUNCH(h, dfm_otm_tree_sum_kernel, dim3((unsigned)(((i1 - i0) * nchild + 255) / 256)), dim3(256), 0, sl.d_seg_off, s0, i0, i1 - i0, gap, (const double *)part.p, d_w);
+    });
+    if (rc != DM_OK) return rc;
     i0 = i1;
   }
   return DM_OK;

@@ -44,7 +44,7 @@ static void dfm_train_release(dm_ctx *h) {
 }
 
 static int dfm_train_col_tiles(int L) { return (L + 1 + 15) / 16; }      // ceil(T / 16): 1 for L <= 15, 2 for L <= 31, 3 at 32
-static inline bool dfm_time_launches() { const char *e = getenv("DM_DFM_TIME_LAUNCHES"); return e && e[0] == '1'; }
+static inline bool dfm_time_launches() { return env_on("DM_DFM_TIME_LAUNCHES"); }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
 // The one statement of both fragment orders of l1.W [T][T E] (columns t >= T are zero), NJ = E / 16, lane = (g, r):
@@ -327,11 +327,11 @@ static int dfm_train_check(dm_ctx *h, const char *who, bool need_init) {
 static int dfm_rederive(dm_ctx *h) {
   const DfmBlocks b = dfm_blocks(h);
   const int E = h->embed, T = h->dfm_L + 1;
-  hipLaunchKernelGGL(dfm_derive_kernel, dim3(32), dim3(256), 0, h->stream, b.l1_w, b.l2_w, E, T, dfm_col_tiles(h->dfm_L), h->d_dfm_frag, h->d_dfm_w2p);
-  hipLaunchKernelGGL(dfm_jtm_derive_kernel, dim3(256), dim3(256), 0, h->stream, b.l1_w, E, h->dfm_L, dfm_col_tiles(h->dfm_L), h->d_dfm_fragS);
-  if (h->dfm_tr)
-    hipLaunchKernelGGL(dfm_train_derive_kernel, dim3(256), dim3(256), 0, h->stream, b.l1_w, E, T, dfm_train_col_tiles(h->dfm_L), h->dfm_tr->fragF, h->dfm_tr->fragB);
-  HIPCHK(h, hipGetLastError());
+  int rc = LAUNCH(h, dfm_derive_kernel, dim3(32), dim3(256), 0, b.l1_w, b.l2_w, E, T, dfm_col_tiles(h->dfm_L), h->d_dfm_frag, h->d_dfm_w2p);
+  if (rc == DM_OK) rc = LAUNCH(h, dfm_jtm_derive_kernel, dim3(256), dim3(256), 0, b.l1_w, E, h->dfm_L, dfm_col_tiles(h->dfm_L), h->d_dfm_fragS);
+  if (rc == DM_OK && h->dfm_tr)
+    rc = LAUNCH(h, dfm_train_derive_kernel, dim3(256), dim3(256), 0, b.l1_w, E, T, dfm_train_col_tiles(h->dfm_L), h->dfm_tr->fragF, h->dfm_tr->fragB);
+  if (rc != DM_OK) return rc;
   HIPCHK(h, hipMemcpyAsync(&h->b2, b.l2_b, 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DM_OK;
@@ -372,36 +372,30 @@ int dm_deepfm_train_free(dm_handle_t h) {
 // zeroGradParameters for the table: the rows the last batch reached, of either step (the dense blocks are overwritten by every step)
 static int dfm_train_clear_prev(dm_ctx *h, dm_dfm_train *t) {
   if (t->vec.prev_m <= 0) return DM_OK;
-  hipLaunchKernelGGL((drt_seg_rows_kernel<float, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->vec.prev.p, nullptr,
-                     t->vec.prev_m, h->num_index, nullptr, h->embed, (float *)t->vec.grad);
-  HIPCHK(h, hipGetLastError());
-  t->vec.forget();
-  return DM_OK;
+  const int rc = LAUNCH(h, (drt_seg_rows_kernel<float, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, (const unsigned long long *)t->vec.prev.p, nullptr,
+                        t->vec.prev_m, h->num_index, nullptr, h->embed, (float *)t->vec.grad);
+  if (rc == DM_OK) t->vec.forget();
+  return rc;
 }
 // g_emb: the m slots idx[i] -> dX[i] sorted by destination row, chunk sums, one wave per destination; the rows are remembered and marked active
 static int dfm_train_emb_grad(dm_ctx *h, dm_dfm_train *t, const int32_t *idx, int64_t m, float *dX, const DrtSortBufs &sb, bool detail) {
   const int E = h->embed;
   const int64_t NI = h->num_index;
-  int rc;
-  LaunchTimer tm(h, EV_DFT_EMB, detail);
-  if (tm.rc != DM_OK) return tm.rc;
-  const unsigned long long *ks;
-  const int32_t *vs;
-  if ((rc = drt_sort_slots(h, idx, m, NI, sb, ks, vs)) != DM_OK) return rc;
-  hipLaunchKernelGGL(dfm_seg_chunks_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NI, dX, E);
-  hipLaunchKernelGGL(dfm_seg_heads_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NI, (const float *)dX, E, (float *)t->vec.grad);
-  HIPCHK(h, hipGetLastError());
-  if ((rc = t->vec.remember(h, ks, m)) != DM_OK || (rc = t->vec.mark_active(h, drt_blocks(h, m, 256), idx, m)) != DM_OK) return rc;
-  return tm.stop();
+  return timed(h, EV_DFT_EMB, detail, [&] {
+    const unsigned long long *ks;
+    const int32_t *vs;
+    int rc;
+    if ((rc = drt_sort_slots(h, idx, m, NI, sb, ks, vs)) != DM_OK) return rc;
+    if ((rc = LAUNCH(h, dfm_seg_chunks_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, ks, vs, m, NI, dX, E)) != DM_OK) return rc;
+    if ((rc = LAUNCH(h, dfm_seg_heads_kernel, dim3(drt_blocks(h, m, 4)), dim3(256), 0, ks, vs, m, NI, dX, E, (float *)t->vec.grad)) != DM_OK) return rc;
+    if ((rc = t->vec.remember(h, ks, m)) != DM_OK) return rc;
+    return t->vec.mark_active(h, drt_blocks(h, m, 256), idx, m);
+  });
 }
 
 template <int E, int NCT>
-static int dfm_launch_train_rows(dm_ctx *h, const DfmTrainRows &p, int nb, bool timed) {
-  LaunchTimer tm(h, EV_DFT_ROWS, timed);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dfm_train_rows_kernel<E, NCT>), dim3((unsigned)nb), dim3(256), 0, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+static int dfm_launch_train_rows(dm_ctx *h, const DfmTrainRows &p, int nb, bool on) {
+  return timed(h, EV_DFT_ROWS, on, [&] { return LAUNCH(h, (dfm_train_rows_kernel<E, NCT>), dim3((unsigned)nb), dim3(256), 0, p); });
 }
 
 static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, const float *d_labels, int64_t B, double *out_loss) {
@@ -414,7 +408,7 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
   const bool detail = dfm_time_launches();
   const int64_t slabs = (B + DRT_SLAB - 1) / DRT_SLAB;
   int nb = (int)std::min<int64_t>(((B + 15) / 16 + 3) / 4, 1024);            // workgroups of the rows kernel: a function of B alone
-  { const char *e_ = getenv("DM_DFM_TRAIN_GRID"); if (e_ && atoi(e_) > 0) nb = std::min(atoi(e_), 65535); }      // (tests: a second, partial round of the grid-stride loop)
+  if (const long long g_ = env_int("DM_DFM_TRAIN_GRID")) nb = (int)std::min<long long>(g_, 65535);      // (tests: a second, partial round of the grid-stride loop)
   int rc;
   DevArena ar(t->ws, 8);
   const size_t o_idx = ar.add((size_t)m * 4), o_dh = ar.add((size_t)B * NC * 4), o_dx = ar.add((size_t)m * E * 4);
@@ -429,8 +423,7 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
   float *g_l1w = grad + NI * E, *g_l1b = g_l1w + (int64_t)T * T * E, *g_l2w = g_l1b + T, *g_l2b = g_l2w + T;
   // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
   if ((rc = dfm_train_clear_prev(h, t)) != DM_OK) return rc;
-  hipLaunchKernelGGL(dfm_train_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seqs, B, L, NI, idx);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = LAUNCH(h, dfm_train_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, d_codes, d_seqs, B, L, NI, idx)) != DM_OK) return rc;
   // ---- forward, loss, dH, dX
   {
     const DfmBlocks b = dfm_blocks(h);
@@ -439,8 +432,7 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
     p.idx = idx; p.labels = d_labels; p.B = B; p.T = T; p.dH = dH; p.dX = dX; p.ploss = ar.ptr<double>(o_pl); p.pg = ar.ptr<float>(o_pg);
     rc = dispatch_E_NCT(h, E, NCT, "unsupported embed size", [&](auto e, auto n) { return dfm_launch_train_rows<decltype(e)::value, decltype(n)::value>(h, p, nb, detail); });
     if (rc != DM_OK) return rc;
-    hipLaunchKernelGGL(dfm_train_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)p.ploss, (const float *)p.pg, nb, NC, T, B, ar.ptr<double>(o_loss), g_l2w, g_l2b);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, dfm_train_sum_kernel, dim3(1), dim3(64), 0, p.ploss, p.pg, nb, NC, T, B, ar.ptr<double>(o_loss), g_l2w, g_l2b)) != DM_OK) return rc;
   }
   // ---- g_l1W, g_l1b: dH^T [T x B] . [X | 1] [B x (T E + 1)] in slabs of the batch, added in slab order
   {
@@ -450,11 +442,10 @@ static int dfm_train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_
     g.B = h->d_emb32; g.gidx = idx; g.Lg = T; g.E = E; g.gcols = cols;
     g.C = part; g.ldc = cols + 1; g.c_slab = (int64_t)T * (cols + 1); g.M = T; g.N = cols + 1; g.Kd = B; g.slab = DRT_SLAB;
     if ((rc = drt_launch_gemm<float>(h, g, EV_DFT_DW, detail)) != DM_OK) return rc;
-    LaunchTimer tm(h, EV_DFT_DW, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (cols + 1), 256)), dim3(256), 0, h->stream, (const float *)part, (int)slabs, T, cols, g_l1w, g_l1b, (int64_t)cols);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    rc = timed(h, EV_DFT_DW, detail, [&] {
+      return LAUNCH(h, drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (cols + 1), 256)), dim3(256), 0, part, (int)slabs, T, cols, g_l1w, g_l1b, cols);
+    });
+    if (rc != DM_OK) return rc;
   }
   // ---- g_emb: sort the B T slots by destination row, chunk sums, one wave per destination
   {
@@ -516,11 +507,9 @@ int dm_deepfm_adam_step(dm_handle_t h, float grad_scale) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const AdamPlan plan = t->vec.plan_step(act);
   model_changed(h);                 // before the first launch: a step that fails half-way has still moved weights
-  LaunchTimer tm(h, EV_DFT_ADAM, dfm_time_launches());
-  if (tm.rc != DM_OK) return tm.rc;
-  if ((rc = adam_step(h, t->vec, plan, h->d_compact, false, false, grad_scale, false, 1024)) != DM_OK) return rc;
+  rc = timed(h, EV_DFT_ADAM, dfm_time_launches(), [&] { return adam_step(h, t->vec, plan, h->d_compact, false, false, grad_scale, false, 1024); });
+  if (rc != DM_OK) return rc;
   t->vec.forget();                  // the step zeroed every gradient it visited, and it visited every row a batch has reached
-  if ((rc = tm.stop()) != DM_OK) return rc;
   if ((rc = dfm_rederive(h)) != DM_OK) return rc;
   model_changed(h);
   return DM_OK;

@@ -274,17 +274,15 @@ __global__ __launch_bounds__(256) void dfm_tg_user_bwd_kernel(DfmTgParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static inline bool dfm_train_grouped_enabled() { const char *e = getenv("DM_DFM_TRAIN_GROUPED"); return e && strcmp(e, "1") == 0; }
+static inline bool dfm_train_grouped_enabled() { return env_on("DM_DFM_TRAIN_GROUPED"); }
 
 template <int E, int NCT, bool CSR>
-static int dfm_tg_launch(dm_ctx *h, const DfmTgParams &p, int which, unsigned nb, bool timed) {
-  LaunchTimer tm(h, which == 0 ? EV_DFG_SETUP : which == 1 ? EV_DFG_ROWS : EV_DFG_USER_BWD, timed);
-  if (tm.rc != DM_OK) return tm.rc;
-  if (which == 0) hipLaunchKernelGGL((dfm_tg_setup_kernel<E, NCT>), dim3(nb), dim3(256), 0, h->stream, p);
-  else if (which == 1) hipLaunchKernelGGL((dfm_tg_rows_kernel<E, NCT, CSR>), dim3(nb), dim3(256), 0, h->stream, p);
-  else hipLaunchKernelGGL((dfm_tg_user_bwd_kernel<E, NCT, CSR>), dim3(nb), dim3(256), 0, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+static int dfm_tg_launch(dm_ctx *h, const DfmTgParams &p, int which, unsigned nb, bool on) {
+  return timed(h, which == 0 ? EV_DFG_SETUP : which == 1 ? EV_DFG_ROWS : EV_DFG_USER_BWD, on, [&] {
+    return which == 0   ? LAUNCH(h, (dfm_tg_setup_kernel<E, NCT>), dim3(nb), dim3(256), 0, p)
+           : which == 1 ? LAUNCH(h, (dfm_tg_rows_kernel<E, NCT, CSR>), dim3(nb), dim3(256), 0, p)
+                        : LAUNCH(h, (dfm_tg_user_bwd_kernel<E, NCT, CSR>), dim3(nb), dim3(256), 0, p);
+  });
 }
 
 static bool dfm_tg_too_large(int64_t U, int64_t R, int L) {
@@ -313,7 +311,7 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int64
   const int64_t slabs_b = (B + DRT_SLAB - 1) / DRT_SLAB, slabs_u = (U + DRT_SLAB - 1) / DRT_SLAB;
   int nb = (int)std::min<int64_t>(((B + 15) / 16 + 3) / 4, 1024);            // workgroups of the rows kernel: a function of (U, R) alone
   int nbu = (int)std::min<int64_t>(((U + 15) / 16 + 3) / 4, 1024);           // ... and of the two user kernels
-  { const char *e_ = getenv("DM_DFM_TRAIN_GRID"); if (e_ && atoi(e_) > 0) { nb = std::min(atoi(e_), 65535); nbu = std::min(atoi(e_), 65535); } }      // (tests: partial rounds)
+  if (const long long g_ = env_int("DM_DFM_TRAIN_GRID")) nb = nbu = (int)std::min<long long>(g_, 65535);      // (tests: partial rounds)
   int rc;
   DevArena ar(t->ws, 8);
   const size_t o_idx = ar.add((size_t)m * 4), o_hh = ar.add((size_t)U * NC * 4), o_bufh = ar.add((size_t)U * E * 4), o_sqh = ar.add((size_t)U * 4);
@@ -328,8 +326,7 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int64
   if (csr) {
     unsigned long long *d_bad = ar.ptr<unsigned long long>(o_bad), bad = 0;
     HIPCHK(h, hipMemsetAsync(d_bad, 0xFF, 8, h->stream));
-    hipLaunchKernelGGL(dfm_tg_check_off_kernel, dim3(drt_blocks(h, U + 1, 256)), dim3(256), 0, h->stream, d_row_off, U, B, d_bad);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, dfm_tg_check_off_kernel, dim3(drt_blocks(h, U + 1, 256)), dim3(256), 0, d_row_off, U, B, d_bad)) != DM_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (bad != ~0ull) {
@@ -345,9 +342,9 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int64
   float *g_l1w = grad + NI * E, *g_l1b = g_l1w + (int64_t)T * T * E, *g_l2w = g_l1b + T, *g_l2b = g_l2w + T;
   // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
   if ((rc = dfm_train_clear_prev(h, t)) != DM_OK) return rc;
-  if (csr) hipLaunchKernelGGL(dfm_tg_idx_csr_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seq, d_row_off, B, U, L, NI, idx, ar.ptr<int32_t>(o_ru));
-  else hipLaunchKernelGGL(dfm_tg_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, d_codes, d_seq, B, UL, NI, idx);
-  HIPCHK(h, hipGetLastError());
+  rc = csr ? LAUNCH(h, dfm_tg_idx_csr_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, d_codes, d_seq, d_row_off, B, U, L, NI, idx, ar.ptr<int32_t>(o_ru))
+           : LAUNCH(h, dfm_tg_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, d_codes, d_seq, B, UL, NI, idx);
+  if (rc != DM_OK) return rc;
   // ---- per user, per row, per user
   DfmTgParams p;
   {
@@ -365,8 +362,7 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int64
                    : dfm_tg_launch<decltype(e)::value, decltype(n)::value, false>(h, p, which, nbw, detail); });
       if (rc != DM_OK) return rc;
     }
-    hipLaunchKernelGGL(dfm_train_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)p.ploss, (const float *)p.pg, nb, NC, T, B, ar.ptr<double>(o_loss), g_l2w, g_l2b);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, dfm_train_sum_kernel, dim3(1), dim3(64), 0, p.ploss, p.pg, nb, NC, T, B, ar.ptr<double>(o_loss), g_l2w, g_l2b)) != DM_OK) return rc;
   }
   // ---- g_l1W, g_l1b: dH^T [T x B] . [Xc | 1] into block 0 and l1.b, then DH^T [T x U] . Xh into blocks 1 .. L; slabs added in slab order
   {
@@ -376,22 +372,18 @@ static int dfm_train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const int64
     g.B = h->d_emb32; g.gidx = idx; g.Lg = 1; g.E = E; g.gcols = E;
     g.C = part; g.ldc = E + 1; g.c_slab = (int64_t)T * (E + 1); g.M = T; g.N = E + 1; g.Kd = B; g.slab = DRT_SLAB;
     if ((rc = drt_launch_gemm<float>(h, g, EV_DFT_DW, detail)) != DM_OK) return rc;
-    {
-      LaunchTimer tm(h, EV_DFT_DW, detail);
-      if (tm.rc != DM_OK) return tm.rc;
-      hipLaunchKernelGGL(drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (E + 1), 256)), dim3(256), 0, h->stream, (const float *)part, (int)slabs_b, T, E, g_l1w, g_l1b, ldw);
-      HIPCHK(h, hipGetLastError());
-      if ((rc = tm.stop()) != DM_OK) return rc;
-    }
+    rc = timed(h, EV_DFT_DW, detail, [&] {
+      return LAUNCH(h, drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (E + 1), 256)), dim3(256), 0, part, (int)slabs_b, T, E, g_l1w, g_l1b, ldw);
+    });
+    if (rc != DM_OK) return rc;
     const int cols = L * E;            // (the ones column of this product is computed and dropped: l1.b came with the rows)
     g.A = p.DH; g.gidx = idx + B; g.Lg = L; g.gcols = cols;
     g.ldc = cols + 1; g.c_slab = (int64_t)T * (cols + 1); g.N = cols + 1; g.Kd = U;
     if ((rc = drt_launch_gemm<float>(h, g, EV_DFT_DW, detail)) != DM_OK) return rc;
-    LaunchTimer tm(h, EV_DFT_DW, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (cols + 1), 256)), dim3(256), 0, h->stream, (const float *)part, (int)slabs_u, T, cols, g_l1w + E, (float *)nullptr, ldw);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    rc = timed(h, EV_DFT_DW, detail, [&] {
+      return LAUNCH(h, drt_slab_sum_kernel<float>, dim3(drt_blocks(h, (int64_t)T * (cols + 1), 256)), dim3(256), 0, part, (int)slabs_u, T, cols, g_l1w + E, nullptr, ldw);
+    });
+    if (rc != DM_OK) return rc;
   }
   // ---- g_emb: sort the B + U L slots by destination row, chunk sums, one wave per destination
   {

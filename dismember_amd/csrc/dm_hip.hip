@@ -427,9 +427,9 @@ int dm_create(int device_id, dm_handle_t *out) {
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device_id) != hipSuccess) { delete h; return fail(nullptr, DM_ERR_HIP, "hipGetDeviceProperties failed"); }
   h->n_cu = prop.multiProcessorCount;
-  { const char *e_ = getenv("DM_BEAM_W"); if (e_) h->beam_w = e_[0] == '1'; }
-  { const char *e_ = getenv("DM_NO_DIRECT"); if (e_ && e_[0] == '1') h->direct_ok = false; }
-  { const char *e_ = getenv("DM_TIME_DIRECT"); if (e_ && e_[0] == '1') h->time_direct = true; }
+  if (env_str("DM_BEAM_W")) h->beam_w = env_on("DM_BEAM_W");
+  if (env_on("DM_NO_DIRECT")) h->direct_ok = false;
+  if (env_on("DM_TIME_DIRECT")) h->time_direct = true;
   if (hipStreamCreate(&h->stream) != hipSuccess) { delete h; return fail(nullptr, DM_ERR_HIP, "hipStreamCreate failed"); }
   if (dm_alloc(h, (void **)&h->d_ctr, sizeof(SearchCounters)) != DM_OK) { delete h; return fail(nullptr, DM_ERR_HIP, "hipMalloc failed"); }
   (void)hipMemset(h->d_ctr, 0, sizeof(SearchCounters));
@@ -794,8 +794,8 @@ int dm_fill_tree_normal(dm_handle_t h, float *d_emb, int E, int depth, float rho
     const int64_t first = ((int64_t)1 << l) - 1, count = (int64_t)1 << l;
     int64_t blocks = (count * E / 2 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(dm_fill_tree_level_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, d_emb, E, first, count, rho, std, (unsigned long long)seed);
-    HIPCHK(h, hipGetLastError());
+    const int rc = LAUNCH(h, dm_fill_tree_level_kernel, dim3((unsigned)blocks), dim3(256), 0, d_emb, E, first, count, rho, std, seed);
+    if (rc != DM_OK) return rc;
   }
   return DM_OK;
 }
@@ -805,9 +805,7 @@ int dm_fill_normal(dm_handle_t h, float *d_ptr, int64_t n, float mean, float std
   if (!d_ptr || n < 0) return fail(h, DM_ERR_INVALID, "dm_fill_normal: bad arguments");
   HIPCHK(h, hipSetDevice(h->device));
   if (n == 0) return DM_OK;
-  hipLaunchKernelGGL(dm_fill_normal_kernel<float>, dim3(4096), dim3(256), 0, h->stream, d_ptr, n, mean, std, (unsigned long long)seed);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, dm_fill_normal_kernel<float>, dim3(4096), dim3(256), 0, d_ptr, n, mean, std, seed);
 }
 
 int dm_fill_normal_f64(dm_handle_t h, double *d_ptr, int64_t n, float mean, float std, uint64_t seed) {
@@ -815,9 +813,7 @@ int dm_fill_normal_f64(dm_handle_t h, double *d_ptr, int64_t n, float mean, floa
   if (!d_ptr || n < 0) return fail(h, DM_ERR_INVALID, "dm_fill_normal_f64: bad arguments");
   HIPCHK(h, hipSetDevice(h->device));
   if (n == 0) return DM_OK;
-  hipLaunchKernelGGL(dm_fill_normal_kernel<double>, dim3(4096), dim3(256), 0, h->stream, d_ptr, n, mean, std, (unsigned long long)seed);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, dm_fill_normal_kernel<double>, dim3(4096), dim3(256), 0, d_ptr, n, mean, std, seed);
 }
 
 static bool fwd64_ready(dm_ctx *h, int L);                 // train_host.hip.inc
@@ -831,7 +827,7 @@ static int din_forward_t(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seq
     // f64 models, batches of rows: the matrix-pipe forward (train_host.hip.inc: rows_fwd64 — the training kernel's forward half on
     // v_mfma_f64_16x16x4_f64) instead of the one-wave-per-row kernel below, which stays for single rows and for clones
     // (round 6: 34 M rows/s -> 10x; dm_din_forward, OTM child weights, evaluators).  DM_FWD64_SCALAR=1 keeps the scalar kernel.
-    static const bool scalar_only = [] { const char *e_ = getenv("DM_FWD64_SCALAR"); return e_ && e_[0] == '1'; }();
+    static const bool scalar_only = env_on("DM_FWD64_SCALAR");
     if (!scalar_only && (B_request > 0 ? B_request : B) >= 256 && fwd64_ready(h, L)) return rows_fwd64(h, d_codes, d_seqs, d_rowmask, B, L, (double *)d_out);
   }
   DinFwdParams<T> p;
@@ -847,36 +843,26 @@ static int din_forward_t(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seq
   int64_t blocks = (B + 3) / 4;
   if (blocks > 8192) blocks = 8192;
   size_t lds = (size_t)4 * (3 * E + 32) * sizeof(T);
-  hipLaunchKernelGGL(dm_din_forward_kernel<T>, dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, dm_din_forward_kernel<T>, dim3((unsigned)blocks), dim3(256), lds, p);
 }
 
 template <int E>
 static int launch_rows_E(dm_ctx *h, const RowsParams &p) {
   const int lds = 2 * E * E * 4;
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_din_rows_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   int64_t tiles = (p.B + 15) / 16;
   int64_t blocks = (tiles + DM_NWAVES - 1) / DM_NWAVES;
   if (blocks > h->n_cu) blocks = h->n_cu;
   if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(dm_din_rows_kernel<E>, dim3((unsigned)blocks), dim3(DM_BLOCK), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH_LDS(h, dm_din_rows_kernel<E>, dim3((unsigned)blocks), dim3(DM_BLOCK), lds, p);
 }
 
-// HIP-event pair of kind 30 around a general-rows launch (dm_kernel_timing_get_kind: the roofline of JTM's scorer in bench.py)
-struct RowsTimer : LaunchTimer { explicit RowsTimer(dm_ctx *h_) : LaunchTimer(h_, EV_ROWS) {} };
-
+// the two launches below: an event pair of kind 30 around a general-rows launch (dm_kernel_timing_get_kind: the roofline of JTM's scorer
+// in bench.py)
 template <int E, int LC>
 static int launch_rows_split_EL(dm_ctx *h, const RowsSplitParams &p, int64_t blocks) {
   const int lds = 4 * E * E * 2 + DM_NWAVES * 2 * (DM_MAXL + 2) * 16 * 4 + 2 * E * 4;      // weight planes + the per-wave index staging + b1, w2
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_din_rows_split_l_kernel<E, LC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RowsTimer tm(h);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dm_din_rows_split_l_kernel<E, LC>), dim3((unsigned)blocks), dim3(DM_BLOCK), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  HIPCHK(h, lds_opt_in(dm_din_rows_split_l_kernel<E, LC>, lds));      // (a host call: ahead of the event pair, not inside it)
+  return timed(h, EV_ROWS, true, [&] { return LAUNCH(h, (dm_din_rows_split_l_kernel<E, LC>), dim3((unsigned)blocks), dim3(DM_BLOCK), lds, p); });
 }
 
 // History lengths with a counted-load instance (rows_kernel.hip.inc: dm_din_rows_split_l_kernel); every other length takes the generic
@@ -887,7 +873,7 @@ static int launch_rows_split_E(dm_ctx *h, const RowsSplitParams &p) {
   int64_t blocks = (tiles + DM_NWAVES - 1) / DM_NWAVES;
   if (blocks > h->n_cu) blocks = h->n_cu;
   if (blocks < 1) blocks = 1;
-  static const bool generic_only = [] { const char *e_ = getenv("DM_ROWS_GENERIC"); return e_ && e_[0] == '1'; }();
+  static const bool generic_only = env_on("DM_ROWS_GENERIC");
   if (!generic_only) {
     switch (p.L) {
       case 8: return launch_rows_split_EL<E, 8>(h, p, blocks);
@@ -897,12 +883,8 @@ static int launch_rows_split_E(dm_ctx *h, const RowsSplitParams &p) {
     }
   }
   const int lds = 4 * E * E * 2;
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_din_rows_split_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  RowsTimer tm(h);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL(dm_din_rows_split_kernel<E>, dim3((unsigned)blocks), dim3(DM_BLOCK), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  HIPCHK(h, lds_opt_in(dm_din_rows_split_kernel<E>, lds));
+  return timed(h, EV_ROWS, true, [&] { return LAUNCH(h, dm_din_rows_split_kernel<E>, dim3((unsigned)blocks), dim3(DM_BLOCK), lds, p); });
 }
 
 // f32 general-rows forward on device buffers (asynchronous on the handle's stream)
@@ -954,7 +936,7 @@ int dm_din_forward(dm_handle_t h, const int32_t *codes, const int32_t *seqs, con
   if (n_pad > 0) {
     if (t.alloc(d_pad, n_pad * 4) != DM_OK) return DM_ERR_HIP;
     if (hipMemcpyAsync(d_pad, pad_flat_idx, n_pad * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
-    hipLaunchKernelGGL(dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, h->stream, d_pad, n_pad, L, d_mask);
+    if ((rc = LAUNCH(h, dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, d_pad, n_pad, L, d_mask)) != DM_OK) return rc;
   }
   rc = h->dtype == DM_F32 ? (L <= DM_MAXL ? din_rows_dev(h, d_codes, d_seqs, d_mask, B, L, (float *)d_out)
                                           : din_forward_t<float>(h, d_codes, d_seqs, d_mask, B, L, (float *)d_out))
@@ -991,8 +973,7 @@ static bool split_for_call(const dm_ctx *h, int64_t U, int max_beam) {
 // A/B runs (DM_LONG_PIPELINE=1).
 static bool long_history_pipeline(const dm_ctx *h, int max_beam, int L) {
   if (L <= DM_MAXL) return false;
-  const char *e_ = getenv("DM_LONG_PIPELINE");          // read per call: the tests run both routes in one process
-  if (e_ && e_[0] == '1') return true;
+  if (env_on("DM_LONG_PIPELINE")) return true;          // read per call: the tests run both routes in one process
   int cap, pcap;
   frontier_caps(max_beam, &cap, &pcap);
   // (sized for the split scorer's layout; the fp32-input layout of the same request is no larger)
@@ -1057,29 +1038,23 @@ template <int E, int KQ, bool SPLIT, int KT = 1>
 static int launch_beam_EK(dm_ctx *h, const BeamParams &p_in, const SearchPlan &pl) {
   BeamParams p = p_in;
   p.static_users = (p.mode != 2 && !p.user_list && p.U <= (int64_t)pl.grid * pl.nteams) ? 1 : 0;
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam_kernel<E, KQ, SPLIT, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
   if (pl.ev_kind == EV_MAIN) {
     if (KT == 1) snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_kernel<%d, %d, %s>", E, KQ, SPLIT ? "true" : "false");
     else snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_kernel<%d, %d, %s, %d>", E, KQ, SPLIT ? "true" : "false", KT);
   }
-  LaunchTimer tm(h, pl.ev_kind, !(p.host_direct && !h->time_direct));       // single-request path: the launch and nothing else
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dm_beam_kernel<E, KQ, SPLIT, KT>), dim3(pl.grid), dim3(DM_BLOCK), pl.lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  HIPCHK(h, lds_opt_in(dm_beam_kernel<E, KQ, SPLIT, KT>, pl.lds));
+  return timed(h, pl.ev_kind, !(p.host_direct && !h->time_direct), [&] {      // single-request path: the launch and nothing else
+    return LAUNCH(h, (dm_beam_kernel<E, KQ, SPLIT, KT>), dim3(pl.grid), dim3(DM_BLOCK), pl.lds, p);
+  });
 }
 
 // FOLD: the attention-combine product in one MFMA per feature tile — its three terms per history position fit the 32 contraction
 // slots of v_mfma_f32_16x16x32_f16 exactly when 3 L <= 32 (beam_kernel_w.hip.inc, dmw_fold_slot)
 template <int E, int KQ, bool FOLD>
 static int launch_beam_w_EK(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam_w_kernel<E, KQ, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
   snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam_w_kernel<%d, %d, %s>", E, KQ, FOLD ? "true" : "false");
-  LaunchTimer tm(h);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dm_beam_w_kernel<E, KQ, FOLD>), dim3(pl.grid), dim3(DMW_BLOCK), pl.lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  HIPCHK(h, lds_opt_in(dm_beam_w_kernel<E, KQ, FOLD>, pl.lds));
+  return timed(h, EV_MAIN, true, [&] { return LAUNCH(h, (dm_beam_w_kernel<E, KQ, FOLD>), dim3(pl.grid), dim3(DMW_BLOCK), pl.lds, p); });
 }
 template <int E>
 static int launch_beam_w_E(dm_ctx *h, const BeamParams &p, const SearchPlan &pl) {
@@ -1133,7 +1108,7 @@ static int launch_beam(dm_ctx *h, BeamParams &p, const SearchPlan &pl) {
       { const int rc_g = g_table_for_search(h, &p.g_table); if (rc_g != DM_OK) return rc_g; }
       // DM_LEVEL_BOUNDS (read per call, like DM_G_TABLE: the tests run both routes in one process) = 0: the existence tests of
       // the expand and of the initial frontier read the bitmap on every level; unset or 1: the per-level bounds where a level has one
-      { const char *e_ = getenv("DM_LEVEL_BOUNDS"); p.level_last = (e_ && e_[0] == '0') ? nullptr : h->d_level_last; }
+      p.level_last = env_off("DM_LEVEL_BOUNDS") ? nullptr : h->d_level_last;
       h->last_g_table = p.g_table != nullptr;
       const char *const no_split = "the split-fp16 scorer needs an embedding size of 32, 64 or 128";
       int rc = dispatch_E<32>(h, h->embed, no_split, [&](auto e) { return launch_beam_w_E<decltype(e)::value>(h, p, pl); });
@@ -1282,7 +1257,7 @@ static int tdm_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, con
 // Chunk k covers users [off[k], off[k + 1]): equal chunks of about 24 MB of results, then a SHORT last one (its download is the only
 // one nothing hides; 8 192 users still fill the persistent grid eight users deep).  n = 1: the request is not cut.
 static int host_pipe_plan(size_t bytes_per_user, int64_t U, int64_t *off /* [18] */) {
-  static const bool disabled = [] { const char *e = getenv("DM_HOST_PIPELINE"); return e && e[0] == '0'; }();
+  static const bool disabled = env_off("DM_HOST_PIPELINE");
   off[0] = 0; off[1] = U;
   const size_t out_bytes = bytes_per_user * (size_t)U;
   if (disabled || U < 16384 || out_bytes < (32u << 20)) return 1;

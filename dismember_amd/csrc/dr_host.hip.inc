@@ -66,21 +66,17 @@ static void dm_dr_free(dm_dr_state *s) {
 }
 
 template <typename T>
-static int dr_launch_gemm(dm_ctx *h, const DrGemmParams<T> &p, bool timed = true) {
+static int dr_launch_gemm(dm_ctx *h, const DrGemmParams<T> &p, bool on = true) {
   if (p.M <= 0 || p.N <= 0) return DM_OK;
   dim3 grid((unsigned)((p.N + DR_TN - 1) / DR_TN), (unsigned)((p.M + DR_TM - 1) / DR_TM));
-  LaunchTimer tm(h, EV_MAIN, timed);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL(dr_gemm_kernel<T>, grid, dim3(256), 0, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  return timed(h, EV_MAIN, on, [&] { return LAUNCH(h, dr_gemm_kernel<T>, grid, dim3(256), 0, p); });
 }
 // A search is several launches (history GEMM, layer 0, statistics and cut per layer).  An event pair around EACH of them (what
 // dm_kernel_timing_get_kind reports by kind) drains the GPU between two kernels: measured 0.39 -> 0.32 ms per 1 024 users, 0.63 -> 0.55 per
 // 4 096, 2.12 -> 2.07 per 16 384 without them — back-to-back kernels overlap their tails.  So by default ONE pair brackets the whole
 // search (EV_MAIN: its device time), and the per-launch pairs are recorded only under DM_DR_TIME_LAUNCHES=1 (read per call: bench.py and
 // tools/dr_bench.py time the search without, then run a breakdown pass with).
-static inline bool dr_time_launches() { const char *e = getenv("DM_DR_TIME_LAUNCHES"); return e && e[0] == '1'; }
+static inline bool dr_time_launches() { return env_on("DM_DR_TIME_LAUNCHES"); }
 
 // the history columns of every layer, [D*K x L*E], out of the W_d (the training step refreshes these alone: its dX product reads them)
 template <typename T>
@@ -128,37 +124,34 @@ static int dr_derive(dm_ctx *h, dm_dr_state *s) {
       if ((rc = dr_launch_gemm<T>(h, g)) != DM_OK) return rc;
       void *&rm = s->d_rowmax[d * (d - 1) / 2 + t];
       DR_ALLOC_ONCE(h, rm, (size_t)K * esz);
-      hipLaunchKernelGGL(drs_rowmax_kernel<T>, dim3(256), dim3(256), 0, h->stream, (const T *)tab, K, (T *)rm);
+      if ((rc = LAUNCH(h, drs_rowmax_kernel<T>, dim3(256), dim3(256), 0, (const T *)tab, K, (T *)rm)) != DM_OK) return rc;
       void *&et = s->d_etabs[d * (d - 1) / 2 + t];
       DR_ALLOC_ONCE(h, et, ((size_t)K * K + 1024) * esz);
       HIPCHK(h, hipMemsetAsync((char *)et + (size_t)K * K * esz, 0, 1024 * esz, h->stream));
-      hipLaunchKernelGGL(drs_exptab_kernel<T>, dim3(1024), dim3(256), 0, h->stream, (const T *)tab, (const T *)rm, K, (T *)et);
-      HIPCHK(h, hipGetLastError());
+      if ((rc = LAUNCH(h, drs_exptab_kernel<T>, dim3(1024), dim3(256), 0, (const T *)tab, (const T *)rm, K, (T *)et)) != DM_OK) return rc;
     }
   }
   if (sizeof(T) == 4 && E % 64 == 0) {       // (the split GEMM stages 64-column tiles: a tile never straddles an embedding row)
     // split-fp16 history GEMM (dm_set_scorer_mode): scales from the largest magnitudes, W planes built once per set of weights
     if (!h->lazy.d_maxabs) ALLOC(h, h->lazy.d_maxabs, 8);
     HIPCHK(h, hipMemsetAsync(h->lazy.d_maxabs, 0, 8, h->stream));
-    hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, nullptr, n_emb, 0, h->lazy.d_maxabs);
-    hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(256), dim3(256), 0, h->stream, (const float *)s->d_wseq, nullptr, (int64_t)D * K * L * E, 0, h->lazy.d_maxabs + 1);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, (const float *)s->d_layer_emb, nullptr, n_emb, 0, h->lazy.d_maxabs)) != DM_OK ||
+        (rc = LAUNCH(h, dm_maxabs_kernel<false>, dim3(256), dim3(256), 0, (const float *)s->d_wseq, nullptr, (int64_t)D * K * L * E, 0, h->lazy.d_maxabs + 1)) != DM_OK)
+      return rc;
     unsigned mb[2];
     HIPCHK(h, hipMemcpyAsync(mb, h->lazy.d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     s->sh_a = split_shift(mb[0]); s->sh_b = split_shift(mb[1]);
     DR_ALLOC_ONCE(h, s->d_wseq_split, (size_t)2 * D * K * L * E * 2);
-    hipLaunchKernelGGL(dr_split_planes_kernel, dim3(1024), dim3(256), 0, h->stream, (const float *)s->d_wseq, (int64_t)D * K * L * E,
-                       ldexpf(1.0f, s->sh_b), (_Float16 *)s->d_wseq_split);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, dr_split_planes_kernel, dim3(1024), dim3(256), 0, (const float *)s->d_wseq, (int64_t)D * K * L * E, ldexpf(1.0f, s->sh_b),
+                     (_Float16 *)s->d_wseq_split)) != DM_OK) return rc;
   }
   if (sizeof(T) == 4 && s->d_wseq_split && L <= DR_X_MAXL) {
     // operands of the 256 x 256 history GEMM: a second copy of the embedding rows (4 E bytes per row, as the fp32 table) and of the
     // history columns, as 128-byte hi/lo records.  An optimisation, allocated after everything the model needs: when the memory is not
     // there the model keeps the 128 x 128 kernel for every batch size
-    { const char *e_ = getenv("DM_DR_GEMM_X_MIN_ROWS"); if (e_ && atoll(e_) > 0) s->x_min_rows = atoll(e_); }
-    const char *x_ = getenv("DM_DR_GEMM_X");                   // "0": keep the 128 x 128 kernel (and save the second table copy)
-    if (!(x_ && x_[0] == '0') && !s->x_refused) {
+    if (const long long v_ = env_int("DM_DR_GEMM_X_MIN_ROWS")) s->x_min_rows = v_;
+    if (!env_off("DM_DR_GEMM_X") && !s->x_refused) {      // "0": keep the 128 x 128 kernel (and save the second table copy)
       const std::string err0 = h->err;           // (an optimisation that does not fit leaves no trace, not even a last-error string)
       if ((!s->d_emb_stages && dm_alloc(h, &s->d_emb_stages, (size_t)n_emb * 4) != DM_OK) ||
           (!s->d_wseq_stages && dm_alloc(h, &s->d_wseq_stages, (size_t)D * K * L * E * 4) != DM_OK)) {
@@ -167,11 +160,10 @@ static int dr_derive(dm_ctx *h, dm_dr_state *s) {
         s->x_refused = true;                     // (a later derive of the same model does not try again)
         h->err = err0;
       } else {
-        hipLaunchKernelGGL(dr_split_rows_kernel, dim3(8192), dim3(256), 0, h->stream, (const float *)s->d_layer_emb, n_emb / E, E,
-                           ldexpf(1.0f, s->sh_a), (_Float16 *)s->d_emb_stages);
-        hipLaunchKernelGGL(dr_split_stages_kernel, dim3(1024), dim3(256), 0, h->stream, (const float *)s->d_wseq, D * K, L * E,
-                           ldexpf(1.0f, s->sh_b), (_Float16 *)s->d_wseq_stages);
-        HIPCHK(h, hipGetLastError());
+        if ((rc = LAUNCH(h, dr_split_rows_kernel, dim3(8192), dim3(256), 0, (const float *)s->d_layer_emb, n_emb / E, E, ldexpf(1.0f, s->sh_a),
+                         (_Float16 *)s->d_emb_stages)) != DM_OK ||
+            (rc = LAUNCH(h, dr_split_stages_kernel, dim3(1024), dim3(256), 0, (const float *)s->d_wseq, D * K, L * E, ldexpf(1.0f, s->sh_b),
+                         (_Float16 *)s->d_wseq_stages)) != DM_OK) return rc;
       }
     }
   }
@@ -195,9 +187,9 @@ static int dr_load_model_t(dm_ctx *h, const dm_dr_model *m) {
   const bool dev = m->on_device != 0;
   const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   s->dtype = m->dtype; s->E = E; s->L = L; s->K = K; s->D = D; s->num_item = m->num_item;
-  s->exact_only = getenv("DM_DR_EXACT_ONLY") != nullptr;
-  { const char *e_ = getenv("DM_DR_SLICED"); if (e_ && e_[0] == '0') s->sliced = false; }
-  { const char *e_ = getenv("DM_DR_SLICED_MIN_USERS"); if (e_ && atoll(e_) > 0) s->sliced_min = atoll(e_); }
+  s->exact_only = env_str("DM_DR_EXACT_ONLY") != nullptr;
+  if (env_off("DM_DR_SLICED")) s->sliced = false;
+  if (const long long v_ = env_int("DM_DR_SLICED_MIN_USERS")) s->sliced_min = v_;
   const size_t esz = sizeof(T);
   const int64_t n_emb = (m->num_item + (int64_t)K * (D - 1)) * E;    // LayerModel.scala:24
   // ---- copy-in: ONE vector holds the layer model, in the order Adam sees it; the table the search gathers from is its first section
@@ -323,8 +315,6 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
   const int n2 = dr_pow2_ge(beam);
   const size_t lds = dr_beam_lds((int)sizeof(T), K, D, n2);
   if (lds > 160 * 1024) return fail(h, DM_ERR_UNSUPPORTED, "dm_dr_beam_search: num_node / beam too large for LDS");
-  HIPCHK(h, hipFuncSetAttribute((const void *)dr_beam_kernel<T, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIPCHK(h, hipFuncSetAttribute((const void *)dr_beam_kernel<T, DR_MAXD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t chunk = 32768;
   int rc = s->S.reserve(h, ((size_t)(U < chunk ? U : chunk) * D * K + 64) * sizeof(T));      // + slack: the sliced search reads 8 columns at a time
   if (rc != DM_OK) return rc;
@@ -333,120 +323,106 @@ static int dr_beam_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int beam, i
   for (int64_t u0 = 0; u0 < U; u0 += chunk) {
     const int64_t n = U - u0 < chunk ? U - u0 : chunk;
     const bool detail = dr_time_launches();
-    LaunchTimer whole(h, EV_MAIN, !detail);          // the one pair around the whole search; stopped where either route ends
-    if (whole.rc != DM_OK) return whole.rc;
-    DrGemmParams<T> g{};
-    g.A = (const T *)s->d_layer_emb; g.lda = 0; g.gidx = d_seq + u0 * L; g.Lg = L; g.E = E;
-    g.B = (const T *)s->d_wseq; g.ldb = (int64_t)L * E; g.bias = (const T *)s->d_sbias; g.zero = (const T *)s->d_zero;
-    g.C = (T *)s->S.p; g.ldc = (int64_t)D * K; g.M = n; g.N = D * K; g.Kd = L * E;
-    if (sizeof(T) == 4 && s->d_wseq_split && h->scorer_mode != DM_SCORER_F32) {
-      DrGemmSplitParams q{};
-      q.emb = (const float *)s->d_layer_emb; q.gidx = g.gidx; q.Lg = L; q.E = E;
-      q.Bp = (const _Float16 *)s->d_wseq_split; q.bias = (const float *)s->d_sbias; q.zero = (const float *)s->d_zero;
-      q.C = (float *)s->S.p; q.ldc = g.ldc; q.M = n; q.N = D * K; q.Kd = L * E;
-      q.a_scale = ldexpf(1.0f, s->sh_a); q.c_unscale = ldexpf(1.0f, -(s->sh_a + s->sh_b));
-      q.embp = (const _Float16 *)s->d_emb_stages; q.Bt = (const _Float16 *)s->d_wseq_stages; q.zeroh = (const _Float16 *)s->d_zero;
-      const bool x = s->d_emb_stages && L <= DR_X_MAXL && (s->x_min_rows > 0 ? n >= s->x_min_rows : dr_gemm_x_pays(n, q.N, h->n_cu));
-      LaunchTimer tm(h, EV_MAIN, detail);
-      if (tm.rc != DM_OK) return tm.rc;
-      if (x) hipLaunchKernelGGL(dr_gemm_split_x_kernel, dim3(dr_gemm_x_grid(q.M, q.N)), dim3(512), 0, h->stream, q);
-      else {
-        dim3 grid((unsigned)((q.N + DR_TN - 1) / DR_TN), (unsigned)((q.M + DR_TM - 1) / DR_TM));
-        hipLaunchKernelGGL(dr_gemm_split_kernel, grid, dim3(256), 0, h->stream, q);
-      }
-      HIPCHK(h, hipGetLastError());
-      if ((rc = tm.stop()) != DM_OK) return rc;
-    } else if ((rc = dr_launch_gemm<T>(h, g, detail)) != DM_OK) return rc;
-    DrBeamParams<T> p{};
-    p.S = (const T *)s->S.p;
-    for (int i = 0; i < DR_MAXD * (DR_MAXD - 1) / 2; i++) p.tabs[i] = (const T *)s->d_tabs[i];
-    p.K = K; p.D = D; p.beam = beam; p.n2 = n2; p.U = n;
-    p.fast = dr_beam_fast_ok(K, n2) && !s->exact_only ? 1 : 0; p.nl = dr_beam_nl(K, n2);
-    p.slow_count = &h->d_ctr->dr_slow;
-    p.phase = h->d_phase;
-    p.out_paths = d_paths + u0 * beam * D; p.out_probs = d_probs + u0 * beam; p.out_counts = d_counts + u0;
-    const int64_t max_grid = (int64_t)h->n_cu * 8;
-    const unsigned grid = (unsigned)(n < max_grid ? n : max_grid);
-    if (s->sliced && p.fast && K <= DRS_W * DRS_NS && n2 <= 64 && D <= DR_MAXD && n >= s->sliced_min) {      // (small batches: one launch beats five)
-      // column-sliced search (dr_sliced.hip.inc): layer 0, then per layer a statistics launch over (user, path, slice) and a cut
-      // launch over users; state and partial statistics in one grow-only block
-      const size_t b_nodes = DevArena::up((size_t)n * beam * D * 4), b_prob = DevArena::up((size_t)n * beam * sizeof(T)), b_np = DevArena::up((size_t)n * 4);
-      const size_t b_smax = DevArena::up((size_t)n * D * sizeof(T)), b_ps = DevArena::up((size_t)n * beam * DRS_NS * sizeof(T)), b_pb = DevArena::up((size_t)n * beam * 64 * sizeof(T));
-      const size_t b_es = DevArena::up(((size_t)n * D * K + 64) * sizeof(T));
-      if ((rc = s->state.reserve(h, 2 * (b_nodes + b_prob + b_np) + b_smax + b_ps + b_pb + b_es + b_np)) != DM_OK) return rc;
-      char *w = (char *)s->state.p;
-      int32_t *nodes[2]; T *pprob[2]; int32_t *npv[2];
-      for (int i = 0; i < 2; i++) { nodes[i] = (int32_t *)w; w += b_nodes; pprob[i] = (T *)w; w += b_prob; npv[i] = (int32_t *)w; w += b_np; }
-      DrsParams<T> q{};
-      q.S = p.S; q.K = K; q.D = D; q.beam = beam; q.n2 = n2; q.nl = p.nl; q.U = n;
-      for (int i = 0; i < DR_MAXD * (DR_MAXD - 1) / 2; i++) { q.tabs[i] = (const T *)s->d_tabs[i]; q.rowmax[i] = (const T *)s->d_rowmax[i]; q.etabs[i] = (const T *)s->d_etabs[i]; }
-      q.smax = (T *)w; w += b_smax; q.part_s = (T *)w; w += b_ps; q.part_bmax = (T *)w; w += b_pb; q.ES = (T *)w; w += b_es; q.todo = (int32_t *)w;
-      q.out_paths = p.out_paths; q.out_probs = p.out_probs; q.out_counts = p.out_counts; q.slow_count = p.slow_count;
-      HIPCHK(h, hipFuncSetAttribute((const void *)drs_layer0_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      q.nodes_n = nodes[0]; q.pprob_n = pprob[0]; q.np_n = npv[0]; q.last = D == 1 ? 1 : 0;
-      // under DM_DR_TIME_LAUNCHES every launch gets its own event pair; dm_kernel_timing_get_kind: EV_DR_CUT = layer 0, EV_DR_STATS + 2 d =
-      // statistics of layer d, EV_DR_CUT + 2 d = its cut, EV_DR_BLOCK + 2 d = the block version's pass over the users the one-wave version
-      // flagged (the history GEMM is EV_MAIN, like the single kernel of the other route)
-      auto timed = [&](int kind, auto launch) -> int {
-        LaunchTimer tm(h, kind, detail);
-        if (tm.rc != DM_OK) return tm.rc;
-        launch();
-        HIPCHK(h, hipGetLastError());
-        return tm.stop();
-      };
-      {
-        const char *e_ = getenv("DM_DR_LAYER0_BLOCK");          // A/B switch: the block version (dr_beam_layer<T, 0>) for everybody
-        const bool wave0 = !(e_ && e_[0] == '1');
-        q.only_todo = 0;
-        if (wave0) {
-          HIPCHK(h, hipMemsetAsync(q.todo, 0, (size_t)n * 4, h->stream));
-          if ((rc = timed(EV_DR_CUT, [&]() { hipLaunchKernelGGL(drs_layer0_wave_kernel<T>, dim3((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)h->n_cu * 8)), dim3(256), 0, h->stream, q); })) != DM_OK) return rc;
-          q.only_todo = 1;                                      // the users the one-wave version flagged
+    rc = timed(h, EV_MAIN, !detail, [&]() -> int {      // the one pair around the whole search, whichever route it takes
+      DrGemmParams<T> g{};
+      g.A = (const T *)s->d_layer_emb; g.lda = 0; g.gidx = d_seq + u0 * L; g.Lg = L; g.E = E;
+      g.B = (const T *)s->d_wseq; g.ldb = (int64_t)L * E; g.bias = (const T *)s->d_sbias; g.zero = (const T *)s->d_zero;
+      g.C = (T *)s->S.p; g.ldc = (int64_t)D * K; g.M = n; g.N = D * K; g.Kd = L * E;
+      if (sizeof(T) == 4 && s->d_wseq_split && h->scorer_mode != DM_SCORER_F32) {
+        DrGemmSplitParams q{};
+        q.emb = (const float *)s->d_layer_emb; q.gidx = g.gidx; q.Lg = L; q.E = E;
+        q.Bp = (const _Float16 *)s->d_wseq_split; q.bias = (const float *)s->d_sbias; q.zero = (const float *)s->d_zero;
+        q.C = (float *)s->S.p; q.ldc = g.ldc; q.M = n; q.N = D * K; q.Kd = L * E;
+        q.a_scale = ldexpf(1.0f, s->sh_a); q.c_unscale = ldexpf(1.0f, -(s->sh_a + s->sh_b));
+        q.embp = (const _Float16 *)s->d_emb_stages; q.Bt = (const _Float16 *)s->d_wseq_stages; q.zeroh = (const _Float16 *)s->d_zero;
+        const bool x = s->d_emb_stages && L <= DR_X_MAXL && (s->x_min_rows > 0 ? n >= s->x_min_rows : dr_gemm_x_pays(n, q.N, h->n_cu));
+        const dim3 grid((unsigned)((q.N + DR_TN - 1) / DR_TN), (unsigned)((q.M + DR_TM - 1) / DR_TM));
+        rc = timed(h, EV_MAIN, detail, [&] {
+          return x ? LAUNCH(h, dr_gemm_split_x_kernel, dim3(dr_gemm_x_grid(q.M, q.N)), dim3(512), 0, q) : LAUNCH(h, dr_gemm_split_kernel, grid, dim3(256), 0, q);
+        });
+        if (rc != DM_OK) return rc;
+      } else if ((rc = dr_launch_gemm<T>(h, g, detail)) != DM_OK) return rc;
+      DrBeamParams<T> p{};
+      p.S = (const T *)s->S.p;
+      for (int i = 0; i < DR_MAXD * (DR_MAXD - 1) / 2; i++) p.tabs[i] = (const T *)s->d_tabs[i];
+      p.K = K; p.D = D; p.beam = beam; p.n2 = n2; p.U = n;
+      p.fast = dr_beam_fast_ok(K, n2) && !s->exact_only ? 1 : 0; p.nl = dr_beam_nl(K, n2);
+      p.slow_count = &h->d_ctr->dr_slow;
+      p.phase = h->d_phase;
+      p.out_paths = d_paths + u0 * beam * D; p.out_probs = d_probs + u0 * beam; p.out_counts = d_counts + u0;
+      const int64_t max_grid = (int64_t)h->n_cu * 8;
+      const unsigned grid = (unsigned)(n < max_grid ? n : max_grid);
+      if (s->sliced && p.fast && K <= DRS_W * DRS_NS && n2 <= 64 && D <= DR_MAXD && n >= s->sliced_min) {      // (small batches: one launch beats five)
+        // column-sliced search (dr_sliced.hip.inc): layer 0, then per layer a statistics launch over (user, path, slice) and a cut
+        // launch over users; state and partial statistics in one grow-only block
+        const size_t b_nodes = DevArena::up((size_t)n * beam * D * 4), b_prob = DevArena::up((size_t)n * beam * sizeof(T)), b_np = DevArena::up((size_t)n * 4);
+        const size_t b_smax = DevArena::up((size_t)n * D * sizeof(T)), b_ps = DevArena::up((size_t)n * beam * DRS_NS * sizeof(T)), b_pb = DevArena::up((size_t)n * beam * 64 * sizeof(T));
+        const size_t b_es = DevArena::up(((size_t)n * D * K + 64) * sizeof(T));
+        if ((rc = s->state.reserve(h, 2 * (b_nodes + b_prob + b_np) + b_smax + b_ps + b_pb + b_es + b_np)) != DM_OK) return rc;
+        char *w = (char *)s->state.p;
+        int32_t *nodes[2]; T *pprob[2]; int32_t *npv[2];
+        for (int i = 0; i < 2; i++) { nodes[i] = (int32_t *)w; w += b_nodes; pprob[i] = (T *)w; w += b_prob; npv[i] = (int32_t *)w; w += b_np; }
+        DrsParams<T> q{};
+        q.S = p.S; q.K = K; q.D = D; q.beam = beam; q.n2 = n2; q.nl = p.nl; q.U = n;
+        for (int i = 0; i < DR_MAXD * (DR_MAXD - 1) / 2; i++) { q.tabs[i] = (const T *)s->d_tabs[i]; q.rowmax[i] = (const T *)s->d_rowmax[i]; q.etabs[i] = (const T *)s->d_etabs[i]; }
+        q.smax = (T *)w; w += b_smax; q.part_s = (T *)w; w += b_ps; q.part_bmax = (T *)w; w += b_pb; q.ES = (T *)w; w += b_es; q.todo = (int32_t *)w;
+        q.out_paths = p.out_paths; q.out_probs = p.out_probs; q.out_counts = p.out_counts; q.slow_count = p.slow_count;
+        q.nodes_n = nodes[0]; q.pprob_n = pprob[0]; q.np_n = npv[0]; q.last = D == 1 ? 1 : 0;
+        // under DM_DR_TIME_LAUNCHES every launch gets its own event pair; dm_kernel_timing_get_kind: EV_DR_CUT = layer 0, EV_DR_STATS + 2 d =
+        // statistics of layer d, EV_DR_CUT + 2 d = its cut, EV_DR_BLOCK + 2 d = the block version's pass over the users the one-wave version
+        // flagged (the history GEMM is EV_MAIN, like the single kernel of the other route)
+        {
+          const bool wave0 = !env_on("DM_DR_LAYER0_BLOCK");       // A/B switch: the block version (dr_beam_layer<T, 0>) for everybody
+          q.only_todo = 0;
+          if (wave0) {
+            HIPCHK(h, hipMemsetAsync(q.todo, 0, (size_t)n * 4, h->stream));
+            if ((rc = timed(h, EV_DR_CUT, detail, [&] { return LAUNCH(h, drs_layer0_wave_kernel<T>, dim3((unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)h->n_cu * 8)), dim3(256), 0, q); })) != DM_OK) return rc;
+            q.only_todo = 1;                                      // the users the one-wave version flagged
+          }
+          HIPCHK(h, lds_opt_in(drs_layer0_kernel<T>, lds));      // (a host call: ahead of the event pair, not inside it)
+          if ((rc = timed(h, wave0 ? EV_DR_BLOCK : EV_DR_CUT, detail, [&] { return LAUNCH(h, drs_layer0_kernel<T>, dim3(grid), dim3(DR_NT), lds, p, q); })) != DM_OK) return rc;
+          q.only_todo = 0;
         }
-        if ((rc = timed(wave0 ? EV_DR_BLOCK : EV_DR_CUT, [&]() { hipLaunchKernelGGL(drs_layer0_kernel<T>, dim3(grid), dim3(DR_NT), lds, h->stream, p, q); })) != DM_OK) return rc;
-        q.only_todo = 0;
-      }
-      const size_t lds_sel = drs_select_lds((int)sizeof(T), D, n2, p.nl);
-      const unsigned g_stats = (unsigned)(DRS_NS * h->n_cu);
-      int cur = 0;
-      for (int d = 1; d < D; d++) {
-        q.nodes = nodes[cur]; q.pprob = pprob[cur]; q.np = npv[cur];
-        q.nodes_n = nodes[cur ^ 1]; q.pprob_n = pprob[cur ^ 1]; q.np_n = npv[cur ^ 1]; q.last = d == D - 1 ? 1 : 0;
-        // the cut: one wave per user when the block scores fit its registers (beam <= 64), the few users it flags redone by the block
-        // version; DM_DR_SELECT_BLOCK=1 keeps the block version for everybody (A/B switch)
-        const bool wave_cut = n2 <= 64 && !(getenv("DM_DR_SELECT_BLOCK") && getenv("DM_DR_SELECT_BLOCK")[0] == '1');
-        const size_t lds_selw = 4 * ((drs_selw_lds_per_wave((int)sizeof(T), D, n2, p.nl) + 15) & ~(size_t)15);
-        const unsigned g_selw = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)h->n_cu * 16);
-        if (wave_cut) HIPCHK(h, hipMemsetAsync(q.todo, 0, (size_t)n * 4, h->stream));
-#define DRS_LAYER(NT)                                                                                                                              \
-        do {                                                                                                                                       \
-          HIPCHK(h, hipFuncSetAttribute((const void *)(drs_select_kernel<T, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sel));      \
-          HIPCHK(h, hipFuncSetAttribute((const void *)(drs_select_wave_kernel<T, NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_selw)); \
-          if ((rc = timed(EV_DR_STATS + 2 * d, [&]() { hipLaunchKernelGGL((drs_stats_kernel<T, NT>), dim3(g_stats), dim3(256), 0, h->stream, q, d); })) != DM_OK) return rc; \
-          q.only_todo = 0;                                                                                                                         \
-          if (wave_cut) {                                                                                                                          \
-            if ((rc = timed(EV_DR_CUT + 2 * d, [&]() { hipLaunchKernelGGL((drs_select_wave_kernel<T, NT>), dim3(g_selw), dim3(256), lds_selw, h->stream, q, d); })) != DM_OK) return rc; \
-            q.only_todo = 1;                                                                                                                       \
-          }                                                                                                                                        \
-          if ((rc = timed((wave_cut ? EV_DR_BLOCK : EV_DR_CUT) + 2 * d, [&]() { hipLaunchKernelGGL((drs_select_kernel<T, NT>), dim3(grid), dim3(DR_NT), lds_sel, h->stream, q, d); })) != DM_OK) return rc; \
-        } while (0)
-        switch (d) {
-          case 1: DRS_LAYER(1); break;
-          case 2: DRS_LAYER(2); break;
-          default: DRS_LAYER(3); break;
-        }
+        const size_t lds_sel = drs_select_lds((int)sizeof(T), D, n2, p.nl);
+        const unsigned g_stats = (unsigned)(DRS_NS * h->n_cu);
+        int cur = 0;
+        for (int d = 1; d < D; d++) {
+          q.nodes = nodes[cur]; q.pprob = pprob[cur]; q.np = npv[cur];
+          q.nodes_n = nodes[cur ^ 1]; q.pprob_n = pprob[cur ^ 1]; q.np_n = npv[cur ^ 1]; q.last = d == D - 1 ? 1 : 0;
+          // the cut: one wave per user when the block scores fit its registers (beam <= 64), the few users it flags redone by the block
+          // version; DM_DR_SELECT_BLOCK=1 keeps the block version for everybody (A/B switch)
+          const bool wave_cut = n2 <= 64 && !env_on("DM_DR_SELECT_BLOCK");
+          const size_t lds_selw = 4 * ((drs_selw_lds_per_wave((int)sizeof(T), D, n2, p.nl) + 15) & ~(size_t)15);
+          const unsigned g_selw = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)h->n_cu * 16);
+          if (wave_cut) HIPCHK(h, hipMemsetAsync(q.todo, 0, (size_t)n * 4, h->stream));
+#define DRS_LAYER(NT) \
+          do { \
+            HIPCHK(h, lds_opt_in(drs_select_kernel<T, NT>, lds_sel)); \
+            if (wave_cut) HIPCHK(h, lds_opt_in(drs_select_wave_kernel<T, NT>, lds_selw)); \
+            if ((rc = timed(h, EV_DR_STATS + 2 * d, detail, [&] { return LAUNCH(h, (drs_stats_kernel<T, NT>), dim3(g_stats), dim3(256), 0, q, d); })) != DM_OK) return rc; \
+            q.only_todo = 0; \
+            if (wave_cut) { \
+              if ((rc = timed(h, EV_DR_CUT + 2 * d, detail, [&] { return LAUNCH(h, (drs_select_wave_kernel<T, NT>), dim3(g_selw), dim3(256), lds_selw, q, d); })) != DM_OK) return rc; \
+              q.only_todo = 1; \
+            } \
+            if ((rc = timed(h, (wave_cut ? EV_DR_BLOCK : EV_DR_CUT) + 2 * d, detail, [&] { return LAUNCH(h, (drs_select_kernel<T, NT>), dim3(grid), dim3(DR_NT), lds_sel, q, d); })) != DM_OK) return rc; \
+          } while (0)
+          switch (d) {
+            case 1: DRS_LAYER(1); break;
+            case 2: DRS_LAYER(2); break;
+            default: DRS_LAYER(3); break;
+          }
 #undef DRS_LAYER
-        cur ^= 1;
+          cur ^= 1;
+        }
+        return DM_OK;
       }
-      if ((rc = whole.stop()) != DM_OK) return rc;
-      continue;
-    }
-    LaunchTimer tm(h, EV_MAIN, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    if (D <= 3) hipLaunchKernelGGL((dr_beam_kernel<T, 3>), dim3(grid), dim3(DR_NT), lds, h->stream, p);
-    else hipLaunchKernelGGL((dr_beam_kernel<T, DR_MAXD>), dim3(grid), dim3(DR_NT), lds, h->stream, p);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK || (rc = whole.stop()) != DM_OK) return rc;
+      HIPCHK(h, D <= 3 ? lds_opt_in(dr_beam_kernel<T, 3>, lds) : lds_opt_in(dr_beam_kernel<T, DR_MAXD>, lds));
+      return timed(h, EV_MAIN, detail, [&] {
+        return D <= 3 ? LAUNCH(h, (dr_beam_kernel<T, 3>), dim3(grid), dim3(DR_NT), lds, p) : LAUNCH(h, (dr_beam_kernel<T, DR_MAXD>), dim3(grid), dim3(DR_NT), lds, p);
+      });
+    });
+    if (rc != DM_OK) return rc;
   }
   return DM_OK;
 }
@@ -517,7 +493,6 @@ static int dr_recommend_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int be
   const int n2k = dr_pow2_ge(topk);
   const size_t lds = dr_rerank_lds((int)sizeof(T), E, beam, n2k);
   if (lds > 160 * 1024) return fail(h, DM_ERR_UNSUPPORTED, "dm_dr_recommend: topk too large for LDS");
-  HIPCHK(h, hipFuncSetAttribute((const void *)dr_rerank_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t cap64 = (int64_t)beam * (s->max_bucket > 0 ? s->max_bucket : 1);
   if (cap64 > (1 << 24)) return fail(h, DM_ERR_UNSUPPORTED, "dm_dr_recommend: beam * largest path bucket exceeds 2^24 candidates");
   const int cap = (int)cap64;
@@ -531,11 +506,8 @@ static int dr_recommend_dev_t(dm_ctx *h, const int32_t *d_seq, int64_t U, int be
   p.K = s->K; p.D = s->D; p.E = E; p.beam = beam; p.topk = topk; p.n2k = n2k; p.cap = cap; p.U = U;
   p.cand = (int32_t *)s->cand.p; p.score = (T *)((char *)s->cand.p + DevArena::up((size_t)grid * cap * 4));
   p.out_ids = d_ids; p.out_scores = d_scores; p.out_counts = d_counts; p.out_ncand = nullptr;
-  LaunchTimer tm(h);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL(dr_rerank_kernel<T>, dim3((unsigned)grid), dim3(DR_NT), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  HIPCHK(h, lds_opt_in(dr_rerank_kernel<T>, lds));
+  return timed(h, EV_MAIN, true, [&] { return LAUNCH(h, dr_rerank_kernel<T>, dim3((unsigned)grid), dim3(DR_NT), lds, p); });
 }
 
 // scratch for the intermediate paths of a recommend call

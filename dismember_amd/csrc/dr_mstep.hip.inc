@@ -145,8 +145,7 @@ struct DrmResult {
 };
 
 static int64_t drm_chunk() {
-  const char *e = getenv("DM_DR_MSTEP_CHUNK");
-  if (e && atoll(e) > 0) return atoll(e);
+  if (const long long v_ = env_int("DM_DR_MSTEP_CHUNK")) return v_;
   return 4 * 32768;                                  // whole chunks of the search's own 32 768
 }
 
@@ -198,13 +197,6 @@ static int drm_run(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int64_
   uint32_t *tmp = ar.ptr<uint32_t>(o_tmp);
   long long *item_off = ar.ptr<long long>(o_off);
   unsigned long long *occ = ar.ptr<unsigned long long>(o_occ), *n_seg = ar.ptr<unsigned long long>(o_n), *n_live = n_seg + 1, *n_kept = n_seg + 2;
-  auto timed = [&](int kind, auto launch) -> int {
-    LaunchTimer tm(h, kind, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    launch();
-    HIPCHK(h, hipGetLastError());
-    return tm.stop();
-  };
   HIPCHK(h, hipMemsetAsync(occ, 0, (size_t)num_item * 8, h->stream));
   HIPCHK(h, hipMemsetAsync(n_seg, 0, 64, h->stream));
   // ---- the search, chunk by chunk, and the pairs of each chunk
@@ -212,75 +204,63 @@ static int drm_run(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int64_
     const int64_t n = std::min<int64_t>(chunk, N - i0);
     int32_t *paths = d_paths_all ? d_paths_all + i0 * C * D : ar.ptr<int32_t>(o_paths);
     if ((rc = dr_beam_dev_t<T>(h, d_seq + i0 * L, n, C, paths, prob + i0 * C, counts + i0)) != DM_OK) return rc;
-    if ((rc = timed(EV_DRM_PAIRS, [&] {
-           hipLaunchKernelGGL(drm_pairs_kernel, dim3(drt_blocks(h, n * C, 256)), dim3(256), 0, h->stream, (const int32_t *)paths, (const int32_t *)counts, d_tgt, i0, n, C, D, K,
-                              cbits, sentinel, kb[0], vb[0]);
-         })) != DM_OK) return rc;
+    rc = timed(h, EV_DRM_PAIRS, detail, [&] {
+      return LAUNCH(h, drm_pairs_kernel, dim3(drt_blocks(h, n * C, 256)), dim3(256), 0, paths, counts, d_tgt, i0, n, C, D, K, cbits, sentinel, kb[0], vb[0]);
+    });
+    if (rc != DM_OK) return rc;
   }
-  if ((rc = timed(EV_DRM_OCC, [&] { hipLaunchKernelGGL(drm_occ_kernel, dim3(drt_blocks(h, N, 256)), dim3(256), 0, h->stream, d_tgt, (const int32_t *)counts, N, occ, n_live); })) != DM_OK)
-    return rc;
+  if ((rc = timed(h, EV_DRM_OCC, detail, [&] { return LAUNCH(h, drm_occ_kernel, dim3(drt_blocks(h, N, 256)), dim3(256), 0, d_tgt, counts, N, occ, n_live); })) != DM_OK) return rc;
   // ---- (item, path) segments: one stable sort, the heads' positions
   int where = 0;
-  {
-    LaunchTimer tm(h, EV_DRM_SORT, detail);
-    if (tm.rc != DM_OK) return tm.rc;
+  rc = timed(h, EV_DRM_SORT, detail, [&]() -> int {
     HIPCHK(h, dev_radix_sort_pairs(h->stream, kb[0], vb[0], kb[1], vb[1], m, 0, ibits + cbits, tmp, &where));
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    return DM_OK;
+  });
+  if (rc != DM_OK) return rc;
   const unsigned long long *ks = kb[where];
   const int32_t *vs = vb[where];
   const int f0 = where ^ 1;                              // the pair the first sort left free; pair 2 is the other half of the next two sorts
-  {
-    LaunchTimer tm(h, EV_DRM_HEADS, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drm_heads_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, ks, m, sentinel, flag);
+  rc = timed(h, EV_DRM_HEADS, detail, [&]() -> int {
+    if ((rc = LAUNCH(h, drm_heads_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, ks, m, sentinel, flag)) != DM_OK) return rc;
     HIPCHK(h, (dev_select_flagged<int32_t>(h->stream, (const int32_t *)nullptr, (const char *)nullptr, (const uint8_t *)flag, seg_start, (char *)nullptr, n_seg, m, tmp)));
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    return DM_OK;
+  });
+  if (rc != DM_OK) return rc;
   // ---- the sums, in sample order
   {
     DrmSegParams p{};
     p.vs = vs; p.seg_start = seg_start; p.n_seg = n_seg; p.n_live = n_live; p.prob = prob; p.m = m;
     p.seg_score = seg_score; p.key2 = kb[f0]; p.val2 = vb[f0];
-    if ((rc = timed(EV_DRM_SEGSUM, [&] { hipLaunchKernelGGL(drm_seg_sum_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, p); })) != DM_OK) return rc;
+    if ((rc = timed(h, EV_DRM_SEGSUM, detail, [&] { return LAUNCH(h, drm_seg_sum_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, p); })) != DM_OK) return rc;
   }
   // ---- top C per item: stable by score descending, then stable by item -> (item, score descending, code ascending); rank < C survives
   int w2 = 0, w3 = 0;
-  {
-    LaunchTimer tm(h, EV_DRM_SCORE_SORT, detail);
-    if (tm.rc != DM_OK) return tm.rc;
+  rc = timed(h, EV_DRM_SCORE_SORT, detail, [&]() -> int {
     HIPCHK(h, dev_radix_sort_pairs(h->stream, kb[f0], vb[f0], kb[2], vb[2], m, 0, 63, tmp, &w2));
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    return DM_OK;
+  });
+  if (rc != DM_OK) return rc;
   const int a2 = w2 ? 2 : f0, b2 = w2 ? f0 : 2;
-  {
-    LaunchTimer tm(h, EV_DRM_ITEM_SORT, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drm_item_keys_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, (const int32_t *)vb[a2], ks, (const int32_t *)seg_start,
-                       (const unsigned long long *)n_seg, m, cbits, (unsigned long long)num_item, kb[a2]);
+  rc = timed(h, EV_DRM_ITEM_SORT, detail, [&]() -> int {
+    if ((rc = LAUNCH(h, drm_item_keys_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, vb[a2], ks, seg_start, n_seg, m, cbits, num_item, kb[a2])) != DM_OK) return rc;
     HIPCHK(h, dev_radix_sort_pairs(h->stream, kb[a2], vb[a2], kb[b2], vb[b2], m, 0, ibits, tmp, &w3));
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    return DM_OK;
+  });
+  if (rc != DM_OK) return rc;
   const int a3 = w3 ? b2 : a2, b3 = w3 ? a2 : b2;
-  {
-    LaunchTimer tm(h, EV_DRM_CUT, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drm_keep_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, (const unsigned long long *)kb[a3], m, C, (unsigned long long)num_item, flag);
+  rc = timed(h, EV_DRM_CUT, detail, [&]() -> int {
+    if ((rc = LAUNCH(h, drm_keep_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, kb[a3], m, C, num_item, flag)) != DM_OK) return rc;
     HIPCHK(h, (dev_select_flagged<unsigned long long, int32_t>(h->stream, (const unsigned long long *)kb[a3], (const int32_t *)vb[a3], (const uint8_t *)flag, kb[b3], vb[b3],
                                                                n_kept, m, tmp)));
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    return DM_OK;
+  });
+  if (rc != DM_OK) return rc;
   long long *out_codes = (long long *)kb[a3];             // (the cut's input is dead)
-  {
-    LaunchTimer tm(h, EV_DRM_EMIT, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drm_emit_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, (const int32_t *)vb[b3], (const unsigned long long *)n_kept, ks,
-                       (const int32_t *)seg_start, (const double *)seg_score, m, cmask, out_codes, out_scores);
-    hipLaunchKernelGGL(drm_offsets_kernel, dim3(drt_blocks(h, num_item + 1, 256)), dim3(256), 0, h->stream, (const unsigned long long *)kb[b3],
-                       (const unsigned long long *)n_kept, num_item, item_off);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+  rc = timed(h, EV_DRM_EMIT, detail, [&] {
+    const int r = LAUNCH(h, drm_emit_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, vb[b3], n_kept, ks, seg_start, seg_score, m, cmask, out_codes, out_scores);
+    return r != DM_OK ? r : LAUNCH(h, drm_offsets_kernel, dim3(drt_blocks(h, num_item + 1, 256)), dim3(256), 0, kb[b3], n_kept, num_item, item_off);
+  });
+  if (rc != DM_OK) return rc;
   unsigned long long total = 0;
   HIPCHK(h, hipMemcpyAsync(&total, n_kept, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));            // the call's one wait before its results move

@@ -342,25 +342,19 @@ static int drr_launch_sampler(dm_ctx *h, const int32_t *d_tgt, int64_t B, long l
   dm_dr_state *s = h->dr;
   DrrSampleParams sp{};
   sp.targets = d_tgt; sp.B = B; sp.S = s->rt->S; sp.num_item = s->num_item; sp.seed = s->rt->seed; sp.step = step; sp.out = out; sp.ld = ld;
-  hipLaunchKernelGGL(drr_sample_kernel, dim3(drt_blocks(h, B, 4)), dim3(256), 0, h->stream, sp);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, drr_sample_kernel, dim3(drt_blocks(h, B, 4)), dim3(256), 0, sp);
 }
 
 // rows x [L] ids -> U [rows x E] (RerankModel.forward; the same launch dm_dr_recommend makes for its user vectors)
 template <typename T>
-static int drr_user_vectors(dm_ctx *h, const int32_t *d_seq, int64_t rows, T *U, int kind, bool timed) {
+static int drr_user_vectors(dm_ctx *h, const int32_t *d_seq, int64_t rows, T *U, int kind, bool on) {
   dm_dr_state *s = h->dr;
   DrGemmParams<T> g{};
   g.A = (const T *)s->d_rr_emb; g.lda = 0; g.gidx = d_seq; g.Lg = s->L; g.E = s->E;
   g.B = (const T *)s->d_rr_w; g.ldb = (int64_t)s->L * s->E; g.bias = (const T *)s->d_rr_b; g.zero = (const T *)s->d_zero;
   g.C = U; g.ldc = s->E; g.M = rows; g.N = s->E; g.Kd = s->L * s->E;
   dim3 grid((unsigned)((g.N + DR_TN - 1) / DR_TN), (unsigned)((g.M + DR_TM - 1) / DR_TM));
-  LaunchTimer tm(h, kind, timed);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL(dr_gemm_kernel<T>, grid, dim3(256), 0, h->stream, g);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  return timed(h, kind, on, [&] { return LAUNCH(h, dr_gemm_kernel<T>, grid, dim3(256), 0, g); });
 }
 
 template <typename T>
@@ -395,26 +389,21 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
   // ---- zeroGradParameters of the graph: the rows the last batch reached (the dense blocks are overwritten below); the criterion's
   // gradient is cleared only when it does not accumulate
   if (t->g.prev_m > 0) {
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->g.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->g.prev.p, nullptr,
-                       t->g.prev_m, NI, nullptr, E, gg);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, (drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->g.prev_m, 4)), dim3(256), 0, (const unsigned long long *)t->g.prev.p, nullptr,
+                     t->g.prev_m, NI, nullptr, E, gg)) != DM_OK) return rc;
     t->g.forget();
   }
   if (t->c.prev_m > 0) {
-    hipLaunchKernelGGL((drr_seg_smx_kernel<T, 0>), dim3(drt_blocks(h, t->c.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->c.prev.p, nullptr,
-                       t->c.prev_m, NI, nullptr, nullptr, S1, E, sg, sg + NI * E);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, (drr_seg_smx_kernel<T, 0>), dim3(drt_blocks(h, t->c.prev_m, 4)), dim3(256), 0, (const unsigned long long *)t->c.prev.p, nullptr,
+                     t->c.prev_m, NI, nullptr, nullptr, S1, E, sg, sg + NI * E)) != DM_OK) return rc;
     t->c.forget();
   }
   // ---- the S + 1 classes of every row
-  {
-    LaunchTimer tm(h, EV_DRR_SAMPLE, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drr_items_kernel, dim3(drt_blocks(h, m2, 256)), dim3(256), 0, h->stream, d_tgt, d_neg, B, S, items);
-    HIPCHK(h, hipGetLastError());
-    if (!d_neg && (rc = drr_launch_sampler(h, d_tgt, B, (long long)t->fb_count, items + 1, S1)) != DM_OK) return rc;
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+  rc = timed(h, EV_DRR_SAMPLE, detail, [&] {
+    const int r = LAUNCH(h, drr_items_kernel, dim3(drt_blocks(h, m2, 256)), dim3(256), 0, d_tgt, d_neg, B, S, items);
+    return r != DM_OK || d_neg ? r : drr_launch_sampler(h, d_tgt, B, (long long)t->fb_count, items + 1, S1);
+  });
+  if (rc != DM_OK) return rc;
   t->fb_count += 1;
   // ---- forward: user vectors, then logits / softmax / G / dU / loss in one kernel
   if ((rc = drr_user_vectors<T>(h, d_seq, B, U, EV_DRR_FWD, detail)) != DM_OK) return rc;
@@ -427,28 +416,23 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
     sp.lg = lg;
     const int spw = 64 >> lg;
     const bool keep = E / 4 <= (1 << lg) && (S1 + spw - 1) / spw <= DRR_KEEP;
-    LaunchTimer tm(h, EV_DRR_SOFTMAX, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    if (keep) hipLaunchKernelGGL((drr_sampled_softmax_kernel<T, true>), dim3((unsigned)nb), dim3(256), 0, h->stream, sp);
-    else hipLaunchKernelGGL((drr_sampled_softmax_kernel<T, false>), dim3((unsigned)nb), dim3(256), 0, h->stream, sp);
-    hipLaunchKernelGGL(drt_loss_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)sp.partial, nb, 1, B, ar.ptr<double>(o_loss));
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    rc = timed(h, EV_DRR_SOFTMAX, detail, [&] {
+      const int r = keep ? LAUNCH(h, (drr_sampled_softmax_kernel<T, true>), dim3((unsigned)nb), dim3(256), 0, sp)
+                         : LAUNCH(h, (drr_sampled_softmax_kernel<T, false>), dim3((unsigned)nb), dim3(256), 0, sp);
+      return r != DM_OK ? r : LAUNCH(h, drt_loss_sum_kernel, dim3(1), dim3(64), 0, sp.partial, nb, 1, B, ar.ptr<double>(o_loss));
+    });
+    if (rc != DM_OK) return rc;
   }
   // ---- the softmax tables' gradient: sort the slots by item, one wave per item
-  {
-    LaunchTimer tm(h, EV_DRR_SMGRAD, detail);
-    if (tm.rc != DM_OK) return tm.rc;
+  rc = timed(h, EV_DRR_SMGRAD, detail, [&]() -> int {
     if ((rc = drt_sort_slots(h, items, m2, NI, sb, ks, vs)) != DM_OK) return rc;
-    if (t->accumulate)
-      hipLaunchKernelGGL((drr_seg_smx_kernel<T, 2>), dim3(drt_blocks(h, m2, 4)), dim3(256), 0, h->stream, ks, vs, m2, NI, (const T *)G, (const T *)U, S1, E, sg, sg + NI * E);
-    else
-      hipLaunchKernelGGL((drr_seg_smx_kernel<T, 1>), dim3(drt_blocks(h, m2, 4)), dim3(256), 0, h->stream, ks, vs, m2, NI, (const T *)G, (const T *)U, S1, E, sg, sg + NI * E);
-    HIPCHK(h, hipGetLastError());
+    rc = t->accumulate ? LAUNCH(h, (drr_seg_smx_kernel<T, 2>), dim3(drt_blocks(h, m2, 4)), dim3(256), 0, ks, vs, m2, NI, G, U, S1, E, sg, sg + NI * E)
+                       : LAUNCH(h, (drr_seg_smx_kernel<T, 1>), dim3(drt_blocks(h, m2, 4)), dim3(256), 0, ks, vs, m2, NI, G, U, S1, E, sg, sg + NI * E);
+    if (rc != DM_OK) return rc;
     if (!t->accumulate && (rc = t->c.remember(h, ks, m2)) != DM_OK) return rc;
-    if ((rc = t->c.mark_active(h, drt_blocks(h, m2, 256), items, m2)) != DM_OK) return rc;
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    return t->c.mark_active(h, drt_blocks(h, m2, 256), items, m2);
+  });
+  if (rc != DM_OK) return rc;
   // ---- the graph: dX = dU rerank_w, then dW / db over slabs of the batch
   {
     DrtGemmParams<T> g{};
@@ -461,23 +445,20 @@ static int drr_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, c
     q.B = (const T *)s->d_rr_emb; q.gidx = d_seq; q.Lg = L; q.E = E; q.gcols = cols;
     q.C = part; q.ldc = cols + 1; q.c_slab = (int64_t)E * (cols + 1); q.M = E; q.N = cols + 1; q.Kd = B; q.slab = DRT_SLAB;
     if ((rc = drt_launch_gemm<T>(h, q, EV_DRR_DW, detail)) != DM_OK) return rc;
-    LaunchTimer tm(h, EV_DRR_DW, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)E * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, E, cols,
-                       gg + NI * E, gg + NI * E + (int64_t)E * cols, (int64_t)cols);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    rc = timed(h, EV_DRR_DW, detail, [&] {
+      return LAUNCH(h, drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)E * (cols + 1), 256)), dim3(256), 0, part, (int)slabs, E, cols, gg + NI * E,
+                    gg + NI * E + (int64_t)E * cols, cols);
+    });
+    if (rc != DM_OK) return rc;
   }
   // ---- embedding gradient: sort the history slots by item, one wave per item
-  {
-    LaunchTimer tm(h, EV_DRR_EMB, detail);
-    if (tm.rc != DM_OK) return tm.rc;
+  rc = timed(h, EV_DRR_EMB, detail, [&]() -> int {
     if ((rc = drt_sort_slots(h, d_seq, m1, NI, sb, ks, vs)) != DM_OK) return rc;
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, false>), dim3(drt_blocks(h, m1, 4)), dim3(256), 0, h->stream, ks, vs, m1, NI, (const T *)dX, E, gg);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = t->g.remember(h, ks, m1)) != DM_OK || (rc = t->g.mark_active(h, drt_blocks(h, m1, 256), d_seq, m1)) != DM_OK) return rc;
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    if ((rc = LAUNCH(h, (drt_seg_rows_kernel<T, false>), dim3(drt_blocks(h, m1, 4)), dim3(256), 0, ks, vs, m1, NI, dX, E, gg)) != DM_OK) return rc;
+    if ((rc = t->g.remember(h, ks, m1)) != DM_OK) return rc;
+    return t->g.mark_active(h, drt_blocks(h, m1, 256), d_seq, m1);
+  });
+  if (rc != DM_OK) return rc;
   if (out_loss) HIPCHK(h, hipMemcpyAsync(out_loss, ar.ptr<double>(o_loss), 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DM_OK;
@@ -562,12 +543,12 @@ int dm_dr_rerank_adam_step(dm_handle_t h, float grad_scale) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const AdamPlan plan_g = t->g.plan_step(act[0]), plan_c = t->c.plan_step(act[1]);
   const bool f64 = s->dtype == DM_F64;
-  LaunchTimer tm(h, EV_DRR_ADAM, dr_time_launches());
-  if (tm.rc != DM_OK) return tm.rc;
-  if ((rc = adam_step(h, t->g, plan_g, s->d_rr_par, f64, false, grad_scale, false, 1024)) != DM_OK) return rc;
-  if ((rc = adam_step(h, t->c, plan_c, s->d_sm_par, f64, t->accumulate != 0, grad_scale, true, 256)) != DM_OK) return rc;
-  t->g.forget(); t->c.forget();      // the steps zeroed every gradient they visited (the accumulating criterion keeps no list)
-  return tm.stop();
+  rc = timed(h, EV_DRR_ADAM, dr_time_launches(), [&] {
+    const int r = adam_step(h, t->g, plan_g, s->d_rr_par, f64, false, grad_scale, false, 1024);
+    return r != DM_OK ? r : adam_step(h, t->c, plan_c, s->d_sm_par, f64, t->accumulate != 0, grad_scale, true, 256);
+  });
+  if (rc == DM_OK) { t->g.forget(); t->c.forget(); }      // the steps zeroed every gradient they visited (the accumulating criterion keeps no list)
+  return rc;
 }
 
 int dm_dr_rerank_download(dm_handle_t h, int vec, int what, void *out, int64_t n) {
@@ -596,7 +577,7 @@ static int drr_full_loss_t(dm_ctx *h, const int32_t *seq_ids, const int32_t *tar
   const int64_t NI = s->num_item;
   int64_t chunk = std::max<int64_t>(1, ((int64_t)256 << 20) / (NI * (int64_t)sizeof(T)));
   chunk = std::min<int64_t>(chunk, (int64_t)1 << 20);
-  { const char *e_ = getenv("DM_DR_FULL_LOSS_ROWS"); if (e_ && atoll(e_) > 0) chunk = std::min<int64_t>(atoll(e_), (int64_t)1 << 20); }
+  if (const long long v_ = env_int("DM_DR_FULL_LOSS_ROWS")) chunk = std::min<int64_t>(v_, (int64_t)1 << 20);
   chunk = std::min(chunk, B);
   const int nb = (int)std::min<int64_t>((chunk + 3) / 4, 1024);
   DevTemps tmp(h);
@@ -621,9 +602,8 @@ static int drr_full_loss_t(dm_ctx *h, const int32_t *seq_ids, const int32_t *tar
     if ((rc = dr_launch_gemm<T>(h, g, false)) != DM_OK) return rc;
     DrtSoftmaxParams<T> sp{};
     sp.Z = Z; sp.paths = d_tgt; sp.B = n; sp.K = (int)NI; sp.D = 1; sp.partial = lp;
-    hipLaunchKernelGGL(drt_softmax_ce_kernel<T>, dim3((unsigned)nbc, 1), dim3(256), 0, h->stream, sp);
-    hipLaunchKernelGGL(drt_loss_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)lp, nbc, 1, (int64_t)1, lp + nb);      // B = 1: the chunk's sum
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, drt_softmax_ce_kernel<T>, dim3((unsigned)nbc, 1), dim3(256), 0, sp)) != DM_OK ||
+        (rc = LAUNCH(h, drt_loss_sum_kernel, dim3(1), dim3(64), 0, lp, nbc, 1, 1, lp + nb)) != DM_OK) return rc;      // B = 1: the chunk's sum
     double part = 0;
     HIPCHK(h, hipMemcpyAsync(&part, lp + nb, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -314,8 +314,8 @@ static unsigned drt_blocks(dm_ctx *h, int64_t n, int per) { return (unsigned)std
 // The caller's segment kernel (one wave per destination) adds the slots' values; then TrainVec::remember and mark_active.
 struct DrtSortBufs { unsigned long long *k0, *k1; int32_t *v0, *v1; uint32_t *tmp; };
 static int drt_sort_slots(dm_ctx *h, const int32_t *ids, int64_t m, int64_t NR, const DrtSortBufs &b, const unsigned long long *&ks, const int32_t *&vs) {
-  hipLaunchKernelGGL(drt_pairs_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, ids, m, NR, b.k0, b.v0);
-  HIPCHK(h, hipGetLastError());
+  const int rc = LAUNCH(h, drt_pairs_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, ids, m, NR, b.k0, b.v0);
+  if (rc != DM_OK) return rc;
   int bits = 1;
   while (((int64_t)1 << bits) <= NR) bits++;                // NR itself (padding) sorts last
   int where = 0;
@@ -326,15 +326,11 @@ static int drt_sort_slots(dm_ctx *h, const int32_t *ids, int64_t m, int64_t NR, 
 }
 
 template <typename T>
-static int drt_launch_gemm(dm_ctx *h, const DrtGemmParams<T> &p, int kind, bool timed) {
+static int drt_launch_gemm(dm_ctx *h, const DrtGemmParams<T> &p, int kind, bool on) {
   if (p.M <= 0 || p.N <= 0 || p.Kd <= 0) return DM_OK;
   const int64_t slabs = (p.Kd + p.slab - 1) / p.slab;
   dim3 grid((unsigned)((p.N + DRT_T - 1) / DRT_T), (unsigned)((p.M + DRT_T - 1) / DRT_T), (unsigned)slabs);
-  LaunchTimer tm(h, kind, timed);
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL(drt_gemm_kernel<T>, grid, dim3(256), 0, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  return timed(h, kind, on, [&] { return LAUNCH(h, drt_gemm_kernel<T>, grid, dim3(256), 0, p); });
 }
 
 template <typename T>
@@ -365,17 +361,15 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
   if (s->wseq_stale && (rc = dr_refresh_wseq<T>(h, s)) != DM_OK) return rc;
   // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
   if (t->vec.prev_m > 0) {
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, h->stream, (const unsigned long long *)t->vec.prev.p, nullptr,
-                       t->vec.prev_m, NR, nullptr, E, grad);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, (drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, (const unsigned long long *)t->vec.prev.p, nullptr,
+                     t->vec.prev_m, NR, nullptr, E, grad)) != DM_OK) return rc;
     t->vec.forget();
   }
   // ---- inputs
   DrtIdxParams ip{};
   ip.seq = d_seq; ip.paths = d_paths; ip.B = B; ip.L = L; ip.D = D; ip.K = K; ip.num_item = s->num_item;
   for (int d = 0; d < D; d++) ip.idx[d] = ar.ptr<int32_t>(o_idx[d]);
-  hipLaunchKernelGGL(drt_build_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, h->stream, ip);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = LAUNCH(h, drt_build_idx_kernel, dim3(drt_blocks(h, m, 256)), dim3(256), 0, ip)) != DM_OK) return rc;
   // ---- forward
   for (int d = 0; d < D; d++) {
     DrGemmParams<T> g{};
@@ -383,22 +377,17 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
     g.B = (const T *)s->d_w[d]; g.ldb = (int64_t)(L + d) * E; g.bias = (const T *)s->d_b[d]; g.zero = (const T *)s->d_zero;
     g.C = Z + (int64_t)d * K; g.ldc = DK; g.M = B; g.N = K; g.Kd = (L + d) * E;
     dim3 grid((unsigned)((g.N + DR_TN - 1) / DR_TN), (unsigned)((g.M + DR_TM - 1) / DR_TM));
-    LaunchTimer tm(h, EV_DRT_FWD, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(dr_gemm_kernel<T>, grid, dim3(256), 0, h->stream, g);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    if ((rc = timed(h, EV_DRT_FWD, detail, [&] { return LAUNCH(h, dr_gemm_kernel<T>, grid, dim3(256), 0, g); })) != DM_OK) return rc;
   }
   // ---- softmax + cross-entropy: Z_d -> G_d
   {
     DrtSoftmaxParams<T> sp{};
     sp.Z = Z; sp.paths = d_paths; sp.B = B; sp.K = K; sp.D = D; sp.partial = ar.ptr<double>(o_lp);
-    LaunchTimer tm(h, EV_DRT_SOFTMAX, detail);
-    if (tm.rc != DM_OK) return tm.rc;
-    hipLaunchKernelGGL(drt_softmax_ce_kernel<T>, dim3((unsigned)nb, (unsigned)D), dim3(256), 0, h->stream, sp);
-    hipLaunchKernelGGL(drt_loss_sum_kernel, dim3(1), dim3(64), 0, h->stream, (const double *)sp.partial, nb, D, B, ar.ptr<double>(o_loss));
-    HIPCHK(h, hipGetLastError());
-    if ((rc = tm.stop()) != DM_OK) return rc;
+    rc = timed(h, EV_DRT_SOFTMAX, detail, [&] {
+      const int r = LAUNCH(h, drt_softmax_ce_kernel<T>, dim3((unsigned)nb, (unsigned)D), dim3(256), 0, sp);
+      return r != DM_OK ? r : LAUNCH(h, drt_loss_sum_kernel, dim3(1), dim3(64), 0, sp.partial, nb, D, B, ar.ptr<double>(o_loss));
+    });
+    if (rc != DM_OK) return rc;
   }
   // ---- dX: history columns of every layer in one product, then the node columns layer by layer (the last layer writes, the others add)
   {
@@ -426,29 +415,26 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
       g.B = (const T *)s->d_layer_emb; g.gidx = ip.idx[d]; g.Lg = L + d; g.E = E; g.gcols = cols;
       g.C = part; g.ldc = cols + 1; g.c_slab = (int64_t)K * (cols + 1); g.M = K; g.N = cols + 1; g.Kd = B; g.slab = DRT_SLAB;
       if ((rc = drt_launch_gemm<T>(h, g, EV_DRT_DW, detail)) != DM_OK) return rc;
-      LaunchTimer tm(h, EV_DRT_DW, detail);
-      if (tm.rc != DM_OK) return tm.rc;
-      hipLaunchKernelGGL(drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)K * (cols + 1), 256)), dim3(256), 0, h->stream, (const T *)part, (int)slabs, K, cols,
-                         grad + off, grad + off + (int64_t)K * cols, (int64_t)cols);
-      HIPCHK(h, hipGetLastError());
-      if ((rc = tm.stop()) != DM_OK) return rc;
+      rc = timed(h, EV_DRT_DW, detail, [&] {
+        return LAUNCH(h, drt_slab_sum_kernel<T>, dim3(drt_blocks(h, (int64_t)K * (cols + 1), 256)), dim3(256), 0, part, (int)slabs, K, cols, grad + off,
+                      grad + off + (int64_t)K * cols, cols);
+      });
+      if (rc != DM_OK) return rc;
       off += (int64_t)K * cols + K;
     }
   }
   // ---- embedding gradient: sort the slots by destination row, one wave per destination
-  {
-    LaunchTimer tm(h, EV_DRT_EMB, detail);
-    if (tm.rc != DM_OK) return tm.rc;
+  rc = timed(h, EV_DRT_EMB, detail, [&]() -> int {
     const DrtSortBufs sb{ar.ptr<unsigned long long>(o_k0), ar.ptr<unsigned long long>(o_k1), ar.ptr<int32_t>(o_v0), ar.ptr<int32_t>(o_v1), ar.ptr<uint32_t>(o_tmp)};
     const int32_t *full = ip.idx[D - 1];                    // [B x (L+D-1)]: every input position of the batch
     const unsigned long long *ks;
     const int32_t *vs;
     if ((rc = drt_sort_slots(h, full, m, NR, sb, ks, vs)) != DM_OK) return rc;
-    hipLaunchKernelGGL((drt_seg_rows_kernel<T, false>), dim3(drt_blocks(h, m, 4)), dim3(256), 0, h->stream, ks, vs, m, NR, (const T *)dX, E, grad);
-    HIPCHK(h, hipGetLastError());
-    if ((rc = t->vec.remember(h, ks, m)) != DM_OK || (rc = t->vec.mark_active(h, drt_blocks(h, m, 256), full, m)) != DM_OK) return rc;
-    if ((rc = tm.stop()) != DM_OK) return rc;
-  }
+    if ((rc = LAUNCH(h, (drt_seg_rows_kernel<T, false>), dim3(drt_blocks(h, m, 4)), dim3(256), 0, ks, vs, m, NR, dX, E, grad)) != DM_OK) return rc;
+    if ((rc = t->vec.remember(h, ks, m)) != DM_OK) return rc;
+    return t->vec.mark_active(h, drt_blocks(h, m, 256), full, m);
+  });
+  if (rc != DM_OK) return rc;
   if (out_loss) HIPCHK(h, hipMemcpyAsync(out_loss, ar.ptr<double>(o_loss), (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DM_OK;
@@ -498,11 +484,9 @@ int dm_dr_adam_step(dm_handle_t h, float grad_scale) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const AdamPlan plan = t->vec.plan_step(act);
   s->derived_stale = true; s->wseq_stale = true;      // before the first launch: a step that fails half-way has still moved weights
-  LaunchTimer tm(h, EV_DRT_ADAM, dr_time_launches());
-  if (tm.rc != DM_OK) return tm.rc;
-  if ((rc = adam_step(h, t->vec, plan, s->d_par, s->dtype == DM_F64, false, grad_scale, false, 1024)) != DM_OK) return rc;
-  t->vec.forget();                // the step zeroed every gradient it visited, and it visited every row a batch has reached
-  return tm.stop();
+  rc = timed(h, EV_DRT_ADAM, dr_time_launches(), [&] { return adam_step(h, t->vec, plan, s->d_par, s->dtype == DM_F64, false, grad_scale, false, 1024); });
+  if (rc == DM_OK) t->vec.forget();                // the step zeroed every gradient it visited, and it visited every row a batch has reached
+  return rc;
 }
 
 int dm_dr_train_param_count(dm_handle_t h, int64_t *n) {

@@ -76,6 +76,61 @@ struct LaunchTimer {
   int stop() { return (on && rc == DM_OK && hipEventRecord(e1, h->stream) != hipSuccess) ? fail(h, DM_ERR_HIP, "hipEventRecord failed") : rc; }
 };
 
+// ---- the one way a kernel is launched.  Every launch is followed by its own hipGetLastError(), so a refused launch (an empty grid, an
+// LDS request over the limit) is reported at its site and under its own name.  The kernel comes as a function pointer and the arguments
+// are converted to ITS parameter types (implicit conversions only, forwarded without a copy of their own): a wrong argument is a compile
+// error, and no call site casts to steer a deduction.
+//   launch_on(stream, kernel, grid, block, lds, args...)      -> hipError_t: for code that has a stream and no handle (dev_sort.hip.inc)
+//   launch_lds_on(...)                                        the same after opting the kernel in to `lds` bytes of dynamic LDS (not cached)
+//   lds_opt_in(kernel, lds)                                   the opt-in alone: ahead of timed(), so that the host call stays outside the pair, and
+//                                                             where an occupancy query or a loop of launches follows it
+//   LAUNCH(h, kernel, grid, block, lds, args...)              on h->stream -> DM_OK, or DM_ERR_HIP with the error and the site in h->err
+//   LAUNCH_LDS(h, ...)                                        LAUNCH with the opt-in
+//   LAUNCHCHK(h, ...)                                         LAUNCH, and the calling function returns the rc when it is not DM_OK
+//   timed(h, kind, on, body)                                  an event pair of `kind` (none when !on) around body(), which returns an rc;
+//                                                             a failing body leaves the pair open (dm_kernel_timing_get* skips those)
+template <typename... P, typename... A>
+static hipError_t launch_on(hipStream_t stream, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A &&...args) {
+  static_assert(sizeof...(P) == sizeof...(A), "launch: one argument per kernel parameter");
+  static_assert((std::is_convertible<A &&, P>::value && ...), "launch: an argument does not convert to its kernel parameter");
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<P>(std::forward<A>(args))...);
+  return hipGetLastError();
+}
+template <typename... P>
+static hipError_t lds_opt_in(void (*kernel)(P...), size_t lds) {
+  return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+template <typename... P, typename... A>
+static hipError_t launch_lds_on(hipStream_t stream, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, A &&...args) {
+  const hipError_t e = lds_opt_in(kernel, lds);
+  return e != hipSuccess ? e : launch_on(stream, kernel, grid, block, lds, std::forward<A>(args)...);
+}
+static int launch_rc(dm_ctx *h, hipError_t e, const char *what, const char *file, int line) {
+  if (e == hipSuccess) return DM_OK;
+  char b[512];
+  snprintf(b, sizeof b, "%s failed: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+  return fail(h, DM_ERR_HIP, b);
+}
+#define LAUNCH(h, kernel, ...) launch_rc(h, launch_on((h)->stream, kernel, __VA_ARGS__), "launch of " #kernel, __FILE__, __LINE__)
+#define LAUNCH_LDS(h, kernel, ...) launch_rc(h, launch_lds_on((h)->stream, kernel, __VA_ARGS__), "launch of " #kernel, __FILE__, __LINE__)
+#define LAUNCHCHK(h, ...) do { const int rc_ = LAUNCH(h, __VA_ARGS__); if (rc_ != DM_OK) return rc_; } while (0)      // as HIPCHK: returns from the caller
+
+template <typename Body>
+static int timed(dm_ctx *h, int kind, bool on, Body body) {
+  LaunchTimer tm(h, kind, on);
+  if (tm.rc != DM_OK) return tm.rc;
+  const int rc = body();
+  return rc != DM_OK ? rc : tm.stop();
+}
+
+// ---- environment switches.  A reader reads the environment when it is called: a site that reads once per process keeps the result in a
+// function-local static, every other site reads per call (the tests flip switches inside one process).  "On" is a first character '1',
+// "off" a first character '0'; env_int is 0 when the variable is unset or not positive.
+static inline const char *env_str(const char *name) { return getenv(name); }
+static inline bool env_on(const char *name) { const char *e = env_str(name); return e && e[0] == '1'; }
+static inline bool env_off(const char *name) { const char *e = env_str(name); return e && e[0] == '0'; }
+static inline long long env_int(const char *name) { const char *e = env_str(name); const long long v = e ? atoll(e) : 0; return v > 0 ? v : 0; }
+
 // ---- request arena: the device buffers of one host-buffer request, laid out in h->req (grow only, by half again: no hipMalloc /
 // hipFree on the request path once the handle has seen its largest request).  add() every buffer, commit(), then ptr<T>(offset).
 struct ReqArena : DevArena {

@@ -141,7 +141,7 @@ __global__ void dm_jtm_sum_kernel(const int64_t *row_off, int64_t R0, int64_t n_
 // DM_JTM_MAX_PAIRS=<positive integer>: scored rows per chunk of the child-weight loops, read per call like DM_JTM_REBALANCE (tests: chunk
 // boundaries at catalogue sizes a test can afford); unset or invalid: the caller's default
 static int64_t jtm_max_pairs(int64_t dflt) {
-  const char *e = getenv("DM_JTM_MAX_PAIRS");
+  const char *e = env_str("DM_JTM_MAX_PAIRS");
   if (!e || !*e) return dflt;
   char *end = nullptr;
   const long long v = strtoll(e, &end, 10);
@@ -193,9 +193,8 @@ static int jtm_child_weights_impl(dm_ctx *h, int scorer, const int64_t *row_off,
     dm_release(h->d_jtm_rseq, h->d_jtm_rmask);
     if ((rc = dm_alloc(h, (void **)&h->d_jtm_rseq, (size_t)(Rall > 0 ? Rall : 1) * L * 4)) != DM_OK ||
         (rc = dm_alloc(h, (void **)&h->d_jtm_rmask, (size_t)(Rall > 0 ? Rall : 1) * 4)) != DM_OK) return rc;
-    if (Rall > 0)
-      hipLaunchKernelGGL(dm_jtm_rowseq_kernel, dim3((unsigned)((Rall + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->d_jtm_rids, Rall, L,
-                         (const int32_t *)h->d_id_to_code, h->non_leaf_offset, h->max_code, h->num_index, h->d_jtm_rseq, h->d_jtm_rmask, d_bad);
+    if (Rall > 0 && (rc = LAUNCH(h, dm_jtm_rowseq_kernel, dim3((unsigned)((Rall + 255) / 256)), dim3(256), 0, h->d_jtm_rids, Rall, L, h->d_id_to_code, h->non_leaf_offset,
+                                 h->max_code, h->num_index, h->d_jtm_rseq, h->d_jtm_rmask, d_bad)) != DM_OK) return rc;
     h->jtm_rseq_ids_epoch = h->ids_epoch; h->jtm_rseq_num_index = h->num_index;
   }
   if (cached && n_items > 0 && (i_lo < h->jtm_i_lo || i_lo + n_items > h->jtm_i_hi))
@@ -249,8 +248,8 @@ static int jtm_child_weights_impl(dm_ctx *h, int scorer, const int64_t *row_off,
     float *d_w_use = resident ? d_weights_all + i0 * nchild : d_w;
     if (e != hipSuccess) return fail(h, DM_ERR_HIP, "dm_jtm_child_weights: upload failed");
     if (pairs > 0 && per_row) {
-      hipLaunchKernelGGL(dm_jtm_codes_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream, (const int64_t *)d_off, (const int32_t *)d_ritem,
-                         (int32_t)(i_lo + i0), d_node_use, R0, nrows, gap, d_codes);
+      rc = LAUNCH(h, dm_jtm_codes_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, d_off, d_ritem, (int32_t)(i_lo + i0), d_node_use, R0, nrows, gap, d_codes);
+      if (rc != DM_OK) return rc;
       rc = scorer == DM_KIND_DEEPFM ? dfm_pairs_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, pairs, L, d_out, nchain)
                                     : din_rows_dev(h, d_codes, h->d_jtm_rseq + (R0 - Rb) * L, use_mask ? h->d_jtm_rmask + (R0 - Rb) : nullptr, pairs, L, d_out, nchain);
       if (rc != DM_OK) return rc;
@@ -262,12 +261,12 @@ static int jtm_child_weights_impl(dm_ctx *h, int scorer, const int64_t *row_off,
       p.hierarchical = hierarchical; p.min_level = min_level; p.use_mask = use_mask;
       p.non_leaf_offset = h->non_leaf_offset; p.max_code = h->max_code;
       p.codes = d_codes; p.seqs = d_seqs; p.rmask = d_mask; p.bad = d_bad;
-      hipLaunchKernelGGL(dm_jtm_expand_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, h->stream, p);
+      if ((rc = LAUNCH(h, dm_jtm_expand_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, p)) != DM_OK) return rc;
       // (hierarchical: the histories differ per chain depth, so the DeepFM set-up runs once per pair here)
       rc = scorer == DM_KIND_DEEPFM ? dfm_pairs_dev(h, d_codes, d_seqs, pairs, L, d_out, 1) : din_rows_dev(h, d_codes, d_seqs, d_mask, pairs, L, d_out);
       if (rc != DM_OK) return rc;
     }
-    hipLaunchKernelGGL(dm_jtm_sum_kernel, dim3((unsigned)((ni * nchild + 255) / 256)), dim3(256), 0, h->stream, d_off, R0, ni, gap, d_out, d_w_use);
+    if ((rc = LAUNCH(h, dm_jtm_sum_kernel, dim3((unsigned)((ni * nchild + 255) / 256)), dim3(256), 0, d_off, R0, ni, gap, d_out, d_w_use)) != DM_OK) return rc;
     e = resident ? hipSuccess : hipMemcpyAsync(weights + i0 * nchild, d_w, (size_t)ni * nchild * 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);       // row_item (host staging) is reused by the next chunk
     if (e != hipSuccess) return fail(h, DM_ERR_HIP, std::string("dm_jtm_child_weights: ") + hipGetErrorString(e));
@@ -678,7 +677,7 @@ static int jtm_rebalance_all_t(dm_ctx *h, const W *weights, const int32_t *old_n
 
 // the device version (jtm_rebalance_dev.hip.inc) on host arrays: upload, run, download.  DM_JTM_REBALANCE=host keeps the host logic.
 static bool jtm_rebalance_on_device(const dm_ctx *h, int64_t n, int old_level, int level) {
-  const char *e = getenv("DM_JTM_REBALANCE");
+  const char *e = env_str("DM_JTM_REBALANCE");
   if (e && !strcmp(e, "host")) return false;
   (void)h;
   return n >= 4096 && level - old_level <= 8 && old_level <= 24 && n < ((int64_t)1 << 31);

@@ -236,8 +236,8 @@ static int jtm_rebalance_all_dev(dm_ctx *h, const W *d_w, const int32_t *d_old_n
   const unsigned GB = 2048, TB = 256;
   hipError_t e = hipMemsetAsync(s.processed, 0, (size_t)s.P * s.PW * 4, h->stream);
   if (e != hipSuccess) return fin(fail(h, DM_ERR_HIP, "dm_jtm_rebalance_all: memset failed"));
-  if (C <= 32) hipLaunchKernelGGL((jtm_rb_init_kernel<W, 32>), dim3(GB), dim3(TB), 0, h->stream, s, ord[0]);
-  else hipLaunchKernelGGL((jtm_rb_init_kernel<W, 256>), dim3(GB), dim3(TB), 0, h->stream, s, ord[0]);
+  rc = C <= 32 ? LAUNCH(h, (jtm_rb_init_kernel<W, 32>), dim3(GB), dim3(TB), 0, s, ord[0]) : LAUNCH(h, (jtm_rb_init_kernel<W, 256>), dim3(GB), dim3(TB), 0, s, ord[0]);
+  if (rc != DM_OK) return fin(rc);
   const int end_bit = 33 + (old_level > 0 ? old_level : 1);
   int curo = 0;
   hipError_t ce = hipSuccess;          // first error of a select / sort pass
@@ -245,10 +245,10 @@ static int jtm_rebalance_all_dev(dm_ctx *h, const W *d_w, const int32_t *d_old_n
   for (int round = 0; round <= C; round++) {
     (void)hipMemsetAsync(s.sizes, 0, (size_t)s.P * C * 4, h->stream);
     (void)hipMemsetAsync(s.counters, 0, 24, h->stream);
-    if (s.P * C <= 8192) hipLaunchKernelGGL(jtm_rb_sizes_small_kernel<W>, dim3(512), dim3(TB), (size_t)s.P * C * 4, h->stream, s);
-    else hipLaunchKernelGGL(jtm_rb_sizes_kernel<W>, dim3(GB), dim3(TB), 0, h->stream, s);
-    hipLaunchKernelGGL(jtm_rb_choose_kernel<W>, dim3((unsigned)std::min<int64_t>((s.P + TB - 1) / TB, 4096)), dim3(TB), 0, h->stream, s);
-    hipLaunchKernelGGL(jtm_rb_flag_kernel<W>, dim3(GB), dim3(TB), 0, h->stream, s, (const int32_t *)ord[curo], flag, key);
+    rc = s.P * C <= 8192 ? LAUNCH(h, jtm_rb_sizes_small_kernel<W>, dim3(512), dim3(TB), (size_t)s.P * C * 4, s) : LAUNCH(h, jtm_rb_sizes_kernel<W>, dim3(GB), dim3(TB), 0, s);
+    if (rc != DM_OK) return fin(rc);
+    if ((rc = LAUNCH(h, jtm_rb_choose_kernel<W>, dim3((unsigned)std::min<int64_t>((s.P + TB - 1) / TB, 4096)), dim3(TB), 0, s)) != DM_OK) return fin(rc);
+    if ((rc = LAUNCH(h, jtm_rb_flag_kernel<W>, dim3(GB), dim3(TB), 0, s, ord[curo], flag, key)) != DM_OK) return fin(rc);
     ck(dev_select_flagged<int32_t, unsigned long long>(h->stream, ord[curo], key, flag, citem, ckey, s.counters + 1, n, tmp));      // items and keys in one pass
     unsigned long long hc[2] = {0, 0};
     if (hipMemcpyAsync(hc, s.counters, 16, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
@@ -266,15 +266,15 @@ static int jtm_rebalance_all_dev(dm_ctx *h, const W *d_w, const int32_t *d_old_n
       // `key` (the uncompacted keys) is dead after the compaction and serves as the second pass's key buffer
       ck(dev_radix_sort_pairs(h->stream, ckey, citem, skey, sitem, m, 0, 64, tmp, &wh));
       if (wh == 0) { std::swap(ckey, skey); std::swap(citem, sitem); }
-      hipLaunchKernelGGL(jtm_rb_key2_kernel<W>, dim3(GB), dim3(TB), 0, h->stream, s, (const int32_t *)sitem, m, key);
+      if ((rc = LAUNCH(h, jtm_rb_key2_kernel<W>, dim3(GB), dim3(TB), 0, s, sitem, m, key)) != DM_OK) return fin(rc);
       ck(dev_radix_sort_pairs(h->stream, key, sitem, skey, citem, m, 32, end_bit, tmp, &wh));
       if (wh == 0) { std::swap(key, skey); } else { std::swap(citem, sitem); }
     }
-    hipLaunchKernelGGL(jtm_rb_segstart_kernel, dim3(GB), dim3(TB), 0, h->stream, (const unsigned long long *)skey, m, seg);
+    if ((rc = LAUNCH(h, jtm_rb_segstart_kernel, dim3(GB), dim3(TB), 0, skey, m, seg)) != DM_OK) return fin(rc);
     (void)hipMemsetAsync(stay, 1, (size_t)n, h->stream);
-    hipLaunchKernelGGL(jtm_rb_cut_kernel<W>, dim3(GB), dim3(TB), 0, h->stream, s, (const unsigned long long *)skey, (const int32_t *)sitem, m, (const int64_t *)seg, oflag, stay);
+    if ((rc = LAUNCH(h, jtm_rb_cut_kernel<W>, dim3(GB), dim3(TB), 0, s, skey, sitem, m, seg, oflag, stay)) != DM_OK) return fin(rc);
     // new list order: everything that stayed (previous order), then the overflow in sorted order
-    hipLaunchKernelGGL(jtm_rb_stayflag_kernel, dim3(GB), dim3(TB), 0, h->stream, (const int32_t *)ord[curo], (const uint8_t *)stay, n, flag);
+    if ((rc = LAUNCH(h, jtm_rb_stayflag_kernel, dim3(GB), dim3(TB), 0, ord[curo], stay, n, flag)) != DM_OK) return fin(rc);
     ck(dev_select_flagged<int32_t>(h->stream, ord[curo], (const char *)nullptr, flag, ord[curo ^ 1], (char *)nullptr, s.counters + 1, n, tmp));
     ck(dev_select_flagged<int32_t>(h->stream, sitem, (const char *)nullptr, oflag, ovf, (char *)nullptr, s.counters + 2, m, tmp));
     unsigned long long hk[3] = {0, 0, 0};
@@ -286,7 +286,5 @@ static int jtm_rebalance_all_dev(dm_ctx *h, const W *d_w, const int32_t *d_old_n
       return fin(fail(h, DM_ERR_HIP, "dm_jtm_rebalance_all: copy failed"));
     curo ^= 1;
   }
-  hipLaunchKernelGGL(jtm_rb_out_kernel<W>, dim3(GB), dim3(TB), 0, h->stream, s, d_out);
-  if (hipGetLastError() != hipSuccess) rc = fail(h, DM_ERR_HIP, "dm_jtm_rebalance_all: kernel launch failed");
-  return fin(rc);
+  return fin(LAUNCH(h, jtm_rb_out_kernel<W>, dim3(GB), dim3(TB), 0, s, d_out));
 }

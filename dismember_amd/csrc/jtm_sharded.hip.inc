@@ -152,11 +152,11 @@ static int jtm_optimize_impl(dm_ctx *h, int scorer, const int32_t *item_code, in
     const int level = std::min(max_level, old_level + gap);
     const int C = 1 << (level - old_level);
     const int max_assign = 1 << (max_level - level);             // TreeLearning.scala:56
-    hipLaunchKernelGGL(jtm_ancestor_kernel, dim3(2048), dim3(256), 0, h->stream, (const int32_t *)d_code, n_items, level, d_old);
+    rc = LAUNCH(h, jtm_ancestor_kernel, dim3(2048), dim3(256), 0, d_code, n_items, level, d_old);      // (a failure reaches the agreement below)
     // ---- (a) scoring: this rank's contiguous item range, into its slice of the weight matrix
     if (W > 1) jtm_shard_range(n_items, rank, W, &lo, &hi);
     const auto t0 = clk::now();
-    if (hi > lo)
+    if (rc == DM_OK && hi > lo)
       rc = jtm_child_weights_impl(h, scorer, h->jtm_off.data() + lo, nullptr, true, lo, nullptr, hi - lo, h->jtm_L, old_level, level, hierarchical, min_level,
                                   use_mask, nullptr, d_proj + lo, d_w + lo * C);
     const auto t1 = clk::now();
@@ -184,13 +184,13 @@ static int jtm_optimize_impl(dm_ctx *h, int scorer, const int32_t *item_code, in
     } else {
       int64_t p_lo, p_hi;
       jtm_shard_range(P, rank, W, &p_lo, &p_hi);
-      hipLaunchKernelGGL(jtm_owner_flag_kernel, dim3(2048), dim3(256), 0, h->stream, (const int32_t *)d_proj, n_items, (int32_t)(P - 1), p_lo, p_hi, d_flag);
-      hipError_t e = dev_select_flagged<int32_t>(h->stream, (const int32_t *)nullptr, (const char *)nullptr, (const uint8_t *)d_flag, d_pack, (char *)nullptr, d_cnt,
-                                                  n_items, (uint32_t *)d_tmp);      // the item indices themselves, in order
-      unsigned long long hm = 0;
       // (rank-local failures up to the projection exchange are collected in lrc: the peers are told before anybody enters the all-gather)
-      int lrc = DM_OK;
-      if (e != hipSuccess || hipMemcpyAsync(&hm, d_cnt, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+      int lrc = LAUNCH(h, jtm_owner_flag_kernel, dim3(2048), dim3(256), 0, d_proj, n_items, (int32_t)(P - 1), p_lo, p_hi, d_flag);
+      unsigned long long hm = 0;
+      if (lrc == DM_OK &&
+          (dev_select_flagged<int32_t>(h->stream, (const int32_t *)nullptr, (const char *)nullptr, (const uint8_t *)d_flag, d_pack, (char *)nullptr, d_cnt, n_items,
+                                       (uint32_t *)d_tmp) != hipSuccess ||      // the item indices themselves, in order
+           hipMemcpyAsync(&hm, d_cnt, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess))
         lrc = fail(h, DM_ERR_HIP, "dm_jtm_optimize_cached: item selection failed");
       const int64_t m = lrc == DM_OK ? (int64_t)hm : 0;
       if (lrc == DM_OK && m > 0) {
@@ -199,9 +199,8 @@ static int jtm_optimize_impl(dm_ctx *h, int scorer, const int32_t *item_code, in
         if (lrc == DM_OK) {
           float *c_w = (float *)B;
           int32_t *c_old = (int32_t *)(B + DevArena::up((size_t)m * C * 4)), *c_node = (int32_t *)(B + DevArena::up((size_t)m * C * 4) + DevArena::up((size_t)m * 4));
-          hipLaunchKernelGGL(jtm_compact_kernel, dim3(2048), dim3(256), 0, h->stream, (const int32_t *)d_pack, m, C, (const float *)d_w, (const int32_t *)d_old,
-                             (const int32_t *)d_proj, c_w, c_old, c_node);
-          lrc = jtm_rebalance_all_dev(h, c_w, c_old, c_node, m, old_level, level, max_assign, d_pack + m);
+          lrc = LAUNCH(h, jtm_compact_kernel, dim3(2048), dim3(256), 0, d_pack, m, C, d_w, d_old, d_proj, c_w, c_old, c_node);
+          if (lrc == DM_OK) lrc = jtm_rebalance_all_dev(h, c_w, c_old, c_node, m, old_level, level, max_assign, d_pack + m);
           if (lrc == DM_ERR_UNSUPPORTED) lrc = fail(h, DM_ERR_STATE, "dm_jtm_optimize_cached: device re-balance refused a shape it was planned for");
         }
       }
@@ -216,10 +215,11 @@ static int jtm_optimize_impl(dm_ctx *h, int scorer, const int32_t *item_code, in
       uint64_t o = 0;
       for (int r = 0; r < W; r++) {
         const int64_t mr = (int64_t)(sizes[r] / 8);
-        if (mr) hipLaunchKernelGGL(jtm_scatter_kernel, dim3(1024), dim3(256), 0, h->stream, (const int32_t *)(d_all + o), (const int32_t *)(d_all + o + mr), mr, d_next);
+        if (mr && (rc = LAUNCH(h, jtm_scatter_kernel, dim3(1024), dim3(256), 0, d_all + o, d_all + o + mr, mr, d_next)) != DM_OK) break;
         o += 2 * (uint64_t)mr;
         st.proj_bytes += sizes[r];
       }
+      if (rc != DM_OK) break;
       if (hipStreamSynchronize(h->stream) != hipSuccess) { rc = fail(h, DM_ERR_HIP, "dm_jtm_optimize_cached: projection exchange failed"); break; }
       t_ex += secs(t3, clk::now());
       st.steps_node_sharded++;

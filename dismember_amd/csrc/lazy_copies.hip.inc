@@ -179,12 +179,10 @@ static int ensure_split_scales(dm_ctx *h) {
   for (;;) {
     HIPCHK(h, hipMemsetAsync(z.d_maxabs, 0, 8, h->stream));
     if (patch) {
-      if (z.active_rows_host)
-        hipLaunchKernelGGL(dm_maxabs_kernel<true>, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->train.active_list, (int64_t)z.active_rows_host * E, E, z.d_maxabs);
+      if (z.active_rows_host) LAUNCHCHK(h, dm_maxabs_kernel<true>, dim3(1024), dim3(256), 0, h->d_emb32, h->train.active_list, (int64_t)z.active_rows_host * E, E, z.d_maxabs);
     } else
-      hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, h->stream, h->d_emb32, nullptr, h->num_index * (int64_t)E, E, z.d_maxabs);
-    hipLaunchKernelGGL(dm_maxabs_kernel<false>, dim3(16), dim3(256), 0, h->stream, (const float *)h->d_wfrag, nullptr, (int64_t)E * E, E, z.d_maxabs + 1);
-    HIPCHK(h, hipGetLastError());
+      LAUNCHCHK(h, dm_maxabs_kernel<false>, dim3(4096), dim3(256), 0, h->d_emb32, nullptr, h->num_index * (int64_t)E, E, z.d_maxabs);
+    LAUNCHCHK(h, dm_maxabs_kernel<false>, dim3(16), dim3(256), 0, (const float *)h->d_wfrag, nullptr, (int64_t)E * E, E, z.d_maxabs + 1);
     HIPCHK(h, hipMemcpyAsync(mb, z.d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (patch && mb[0] != 0 && split_shift(mb[0]) < z.sh_e) { patch = false; continue; }    // an active row outgrew the scale: full scan
@@ -196,9 +194,7 @@ static int ensure_split_scales(dm_ctx *h) {
   }
   z.emb_split_patch = patch;
   z.sh_w = split_shift(mb[1]);
-  hipLaunchKernelGGL(dm_build_wsplit_kernel, dim3(64), dim3(256), 0, h->stream, (const float *)h->d_wfrag, E, ldexpf(1.0f, z.sh_w),
-                     (_Float16 *)z.d_wsplit);
-  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h, dm_build_wsplit_kernel, dim3(64), dim3(256), 0, (const float *)h->d_wfrag, E, ldexpf(1.0f, z.sh_w), (_Float16 *)z.d_wsplit);
   z.split_dirty = false; z.emb_split_dirty = true; z.rows_split_dirty = true;      // the table's and the rows planes' turn
   return DM_OK;
 }
@@ -221,14 +217,12 @@ static int ensure_split(dm_ctx *h) {
     z.emb_split_need_full = true;
   }
   if (z.emb_split_need_full || !z.emb_split_patch) {
-    hipLaunchKernelGGL(dm_build_emb_split_kernel<false>, dim3(8192), dim3(256), 0, h->stream, h->d_emb32, nullptr, h->num_index, E, ldexpf(1.0f, z.sh_e),
-                       (_Float16 *)z.d_emb_split);
+    LAUNCHCHK(h, dm_build_emb_split_kernel<false>, dim3(8192), dim3(256), 0, h->d_emb32, nullptr, h->num_index, E, ldexpf(1.0f, z.sh_e), (_Float16 *)z.d_emb_split);
     z.emb_split_need_full = false;
   } else if (z.active_rows_host) {
-    hipLaunchKernelGGL(dm_build_emb_split_kernel<true>, dim3(1024), dim3(256), 0, h->stream, h->d_emb32, h->train.active_list, (int64_t)z.active_rows_host,
-                       E, ldexpf(1.0f, z.sh_e), (_Float16 *)z.d_emb_split);
+    LAUNCHCHK(h, dm_build_emb_split_kernel<true>, dim3(1024), dim3(256), 0, h->d_emb32, h->train.active_list, (int64_t)z.active_rows_host, E, ldexpf(1.0f, z.sh_e),
+              (_Float16 *)z.d_emb_split);
   }
-  HIPCHK(h, hipGetLastError());
   z.emb_split_dirty = false;
   return DM_OK;
 }
@@ -252,10 +246,8 @@ static int ensure_g_table(dm_ctx *h) {
   const int64_t waves = (h->num_index + 15) / 16, blocks = (waves + DMW_NWAVES - 1) / DMW_NWAVES;
   const int grid = (int)std::min<int64_t>(blocks, (int64_t)h->n_cu * 8);
   rc = dispatch_E<32>(h, E, "the setup table needs an embedding size of 32, 64 or 128", [&](auto e) {
-    hipLaunchKernelGGL((dm_build_g_table_kernel<decltype(e)::value>), dim3(grid), dim3(DMW_BLOCK), 0, h->stream, (const float *)h->d_emb32,
-                       (const f32x4 *)h->d_afrag, (const f32x4 *)h->d_bfrag, h->num_index, z.d_g_table);
-    HIPCHK(h, hipGetLastError());
-    return DM_OK;
+    return LAUNCH(h, dm_build_g_table_kernel<decltype(e)::value>, dim3(grid), dim3(DMW_BLOCK), 0, h->d_emb32, (const f32x4 *)h->d_afrag, (const f32x4 *)h->d_bfrag, h->num_index,
+                  z.d_g_table);
   });
   if (rc != DM_OK) return rc;
   z.g_table_dirty = false;
@@ -268,8 +260,7 @@ static int ensure_g_table(dm_ctx *h) {
 // quarter of the free device memory (remembered until the next load).  A clone reads its owner's table, built on the owner's stream.
 static int g_table_for_search(dm_ctx *h, const float **table) {
   *table = nullptr;
-  const char *e_ = getenv("DM_G_TABLE");
-  const int knob = (e_ && e_[0] == '0') ? 0 : (e_ && e_[0] == '1') ? 1 : -1;
+  const int knob = env_off("DM_G_TABLE") ? 0 : env_on("DM_G_TABLE") ? 1 : -1;
   if (knob == 0) return DM_OK;
   dm_ctx *o = h->parent ? h->parent : h;
   std::lock_guard<std::recursive_mutex> lk_(o->mu);
@@ -308,16 +299,13 @@ static int ensure_rows_split(dm_ctx *h) {
   if (!z.d_rows_split) ALLOC(h, z.d_rows_split, plane_bytes + (size_t)E * E * 4);
   float *Mbuf = (float *)((char *)z.d_rows_split + plane_bytes);
   HIPCHK(h, hipMemsetAsync(z.d_maxabs, 0, 8, h->stream));
-  hipLaunchKernelGGL(dm_rows_m_kernel, dim3(64), dim3(256), 0, h->stream, h->d_attA, h->d_w1aA, h->d_w1bA, E, Mbuf, z.d_maxabs);
-  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h, dm_rows_m_kernel, dim3(64), dim3(256), 0, h->d_attA, h->d_w1aA, h->d_w1bA, E, Mbuf, z.d_maxabs);
   unsigned mb[2];
   HIPCHK(h, hipMemcpyAsync(mb, z.d_maxabs, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   model_changed(h);
   z.sh_r = split_shift(mb[0] > mb[1] ? mb[0] : mb[1]);
-  hipLaunchKernelGGL(dm_build_rows_planes_kernel, dim3(64), dim3(256), 0, h->stream, h->d_w1aA, (const float *)Mbuf, E, ldexpf(1.0f, z.sh_r),
-                     (_Float16 *)z.d_rows_split);
-  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h, dm_build_rows_planes_kernel, dim3(64), dim3(256), 0, h->d_w1aA, Mbuf, E, ldexpf(1.0f, z.sh_r), (_Float16 *)z.d_rows_split);
   z.rows_split_dirty = false;
   return DM_OK;
 }
@@ -334,8 +322,7 @@ static int ensure_frags64(dm_ctx *h) {
   const double *base = (const double *)h->d_compact;
   const double *att_w = base + h->num_index * E, *l1_w = att_w + n;
   double *f = (double *)z.d_frag64;
-  hipLaunchKernelGGL(dm_build_frags64_kernel, dim3(64), dim3(256), 0, h->stream, att_w, l1_w, E, f, f + n, f + 2 * n);
-  HIPCHK(h, hipGetLastError());
+  LAUNCHCHK(h, dm_build_frags64_kernel, dim3(64), dim3(256), 0, att_w, l1_w, E, f, f + n, f + 2 * n);
   HIPCHK(h, hipMemcpyAsync(&z.b2_64, l1_w + 2 * n + 2 * E, 8, hipMemcpyDeviceToHost, h->stream));      // l2.b: a kernel argument
   HIPCHK(h, hipStreamSynchronize(h->stream));
   z.frag64_dirty = false;

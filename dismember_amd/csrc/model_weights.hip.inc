@@ -21,27 +21,21 @@ static int derive_small(dm_ctx *h, int what) {
       double *const f = (double *)h->d_tr64, *const no = nullptr;      // six E x E blocks: A fragments of att.W, W1a, W1b, then of their transposes
       auto blk = [&](int i) { return f ? f + i * n2 : no; };
       const int rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) {
-        hipLaunchKernelGGL((dm_refresh_fragments_kernel<double, decltype(e)::value>), dim3(64), dim3(256), 0, h->stream, tail, tail + n2, no, no, no,
-                           blk(0), blk(1), blk(2), blk(3), blk(4), blk(5), (double *)h->d_att_wT_t, (double *)h->d_l1T_t);
-        HIPCHK(h, hipGetLastError());
-        return DM_OK;
+        return LAUNCH(h, (dm_refresh_fragments_kernel<double, decltype(e)::value>), dim3(64), dim3(256), 0, tail, tail + n2, no, no, no, blk(0), blk(1), blk(2), blk(3), blk(4),
+                      blk(5), (double *)h->d_att_wT_t, (double *)h->d_l1T_t);
       });
       if (rc != DM_OK) return rc;
     }
     if (!(what & DERIVE_F32_MIRROR)) return DM_OK;
-    hipLaunchKernelGGL(dm_f64_to_f32_kernel, dim3(64), dim3(256), 0, h->stream, tail, (float *)h->d_tail32, 3 * n2 + 2 * E + 1);
-    HIPCHK(h, hipGetLastError());
+    LAUNCHCHK(h, dm_f64_to_f32_kernel, dim3(64), dim3(256), 0, tail, (float *)h->d_tail32, 3 * n2 + 2 * E + 1);
     tail32 = (const float *)h->d_tail32;
   }
   // the transposed fragments and the plain transposes are in the model's own type: not part of an f64 model's f32 mirror
   float *const no = nullptr;
   const int rc = dispatch_E(h, E, "unsupported embed size", [&](auto e) {
-    hipLaunchKernelGGL((dm_refresh_fragments_kernel<float, decltype(e)::value>), dim3(64), dim3(256), 0, h->stream, tail32, tail32 + n2,
-                       (float *)h->d_wfrag, (float *)h->d_afrag, (float *)h->d_bfrag, (float *)h->d_attA, (float *)h->d_w1aA, (float *)h->d_w1bA,
-                       f64 ? no : (float *)h->d_attTA, f64 ? no : (float *)h->d_w1aTA, f64 ? no : (float *)h->d_w1bTA,
-                       f64 ? no : (float *)h->d_att_wT_t, f64 ? no : (float *)h->d_l1T_t);
-    HIPCHK(h, hipGetLastError());
-    return DM_OK;
+    return LAUNCH(h, (dm_refresh_fragments_kernel<float, decltype(e)::value>), dim3(64), dim3(256), 0, tail32, tail32 + n2, (float *)h->d_wfrag, (float *)h->d_afrag,
+                  (float *)h->d_bfrag, (float *)h->d_attA, (float *)h->d_w1aA, (float *)h->d_w1bA, f64 ? no : (float *)h->d_attTA, f64 ? no : (float *)h->d_w1aTA,
+                  f64 ? no : (float *)h->d_w1bTA, f64 ? no : (float *)h->d_att_wT_t, f64 ? no : (float *)h->d_l1T_t);
   });
   if (rc != DM_OK) return rc;
   const float *b = tail32 + 3 * n2;      // l1.b ; l2.W ; l2.b
@@ -54,9 +48,7 @@ static int derive_small(dm_ctx *h, int what) {
 
 // f64 model: the f32 table the throughput beam kernels read
 static int mirror_table32(dm_ctx *h) {
-  hipLaunchKernelGGL(dm_f64_to_f32_kernel, dim3(4096), dim3(256), 0, h->stream, (const double *)h->d_compact, h->d_emb32, h->num_index * (int64_t)h->embed);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, dm_f64_to_f32_kernel, dim3(4096), dim3(256), 0, (const double *)h->d_compact, h->d_emb32, h->num_index * (int64_t)h->embed);
 }
 
 // The handle takes ownership of a device-resident compact vector of `dtype` with the kernels' embed size E (E_model: the model's own,

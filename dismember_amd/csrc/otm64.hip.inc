@@ -168,11 +168,8 @@ __global__ __launch_bounds__(256) void otm64_attn_kernel(Otm64Attn<T> p) {
 template <typename T, int NE>
 static int otm_pl_launch_attn_ne(dm_ctx *h, const Otm64Attn<T> &a) {
   const size_t lds = otm_pl_attn_lds(a.L, a.E, sizeof(T));
-  HIPCHK(h, hipFuncSetAttribute((const void *)otm64_attn_kernel<T, NE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t blocks = a.U * ((a.n + OTM_PL_ROWS - 1) / OTM_PL_ROWS);
-  hipLaunchKernelGGL((otm64_attn_kernel<T, NE>), dim3((unsigned)blocks), dim3(256), lds, h->stream, a);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH_LDS(h, (otm64_attn_kernel<T, NE>), dim3((unsigned)blocks), dim3(256), lds, a);
 }
 template <typename T>
 static int otm_pl_launch_attn(dm_ctx *h, const Otm64Attn<T> &a) {
@@ -229,14 +226,12 @@ __global__ void otm64_emit_kernel(Otm64Out<T> p) {
 // outgrow LDS, for searches with no level to score, and as a cross-check (DM_OTM64_PIPELINE=1 in the environment)
 template <int E, int KQ, int KT = 1>
 static int launch_beam64_EK(dm_ctx *h, const Beam64Params &p, int grid, int lds) {
-  HIPCHK(h, hipFuncSetAttribute((const void *)dm_beam64_kernel<E, KQ, KT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   if (KT == 1) snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam64_kernel<%d, %d>", E, KQ);
   else snprintf(h->last_kernel, sizeof(h->last_kernel), "dm_beam64_kernel<%d, %d, %d>", E, KQ, KT);
-  LaunchTimer tm(h, EV_MAIN, !(p.host_direct && !h->time_direct));       // single-request path: the launch and nothing else
-  if (tm.rc != DM_OK) return tm.rc;
-  hipLaunchKernelGGL((dm_beam64_kernel<E, KQ, KT>), dim3(grid), dim3(DM64_BLOCK), lds, h->stream, p);
-  HIPCHK(h, hipGetLastError());
-  return tm.stop();
+  HIPCHK(h, lds_opt_in(dm_beam64_kernel<E, KQ, KT>, lds));
+  return timed(h, EV_MAIN, !(p.host_direct && !h->time_direct), [&] {      // single-request path: the launch and nothing else
+    return LAUNCH(h, (dm_beam64_kernel<E, KQ, KT>), dim3(grid), dim3(DM64_BLOCK), lds, p);
+  });
 }
 template <int E>
 static int launch_beam64_E(dm_ctx *h, const Beam64Params &p, int grid, int lds) {
@@ -254,12 +249,12 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
                              double *d_sc64, float *d_sc32, int32_t *d_counts, int max_levels, int cap, int32_t *d_tc,
                              double *d_ts64, float *d_ts32, int32_t *d_tn, bool *done, bool host_direct = false) {
   *done = false;
-  { const char *e_ = getenv("DM_OTM64_PIPELINE"); if (e_ && e_[0] == '1') return DM_OK; }
+  if (env_on("DM_OTM64_PIPELINE")) return DM_OK;
   int start, level0;
   level_start_int(beam, &start, &level0);
   if (leaf_level <= level0) return DM_OK;
   if (L > DM_PIPE_MAXL) return DM_OK;
-  { const char *e_ = getenv("DM_LONG_PIPELINE"); if (L > DM_MAXL && e_ && e_[0] == '1') return DM_OK; }      // (A/B: 17 .. 32 positions on the per-level pipeline)
+  if (L > DM_MAXL && env_on("DM_LONG_PIPELINE")) return DM_OK;      // (A/B: 17 .. 32 positions on the per-level pipeline)
   const int kt = L > DM_MAXL ? 2 : 1;         // key tiles of 16 history positions
   const int E = h->embed;
   int fcap, pcap;
@@ -270,8 +265,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   // slots (beam <= 256): twelve one-wave teams again — no team barriers, no split of a level's tiles, twelve users in flight per CU — with the
   // beam's codes AND the candidates' scores in the team's global scratch (L2), which leaves 1.2 KB of LDS per team; then six two-wave teams
   // (codes in the scratch), then 4 / 2 / 1 teams with everything in LDS.
-  const char *e12_ = getenv("DM_OTM64_NO12G"), *e6_ = getenv("DM_OTM64_NO6");
-  const bool no12 = e12_ && e12_[0] == '1', no6 = e6_ && e6_[0] == '1';
+  const bool no12 = env_on("DM_OTM64_NO12G"), no6 = env_on("DM_OTM64_NO6");
   const int cands[6][3] = {{12, 0, 0}, {12, 1, 1}, {6, 1, 0}, {4, 0, 0}, {2, 0, 0}, {1, 0, 0}};
   for (int ci = 0; ci < 6; ci++) {
     if (ci == 0 && pcap > 128) continue;
@@ -297,7 +291,7 @@ static int beam64_search_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, 
   p.b_global = b_global; p.v_global = v_global;
   p.host_direct = (host_direct && p.static_users) ? 1 : 0;
   if (host_direct && !p.host_direct) return DM_OK;      // (the caller falls back to the staged path)
-  { const char *e_ = getenv("DM_OTM64_LDS_SORT"); p.force_lds_sort = (e_ && e_[0] == '1') ? 1 : 0; }
+  p.force_lds_sort = env_on("DM_OTM64_LDS_SORT") ? 1 : 0;
   p.sm_scale = sm_scale64(h);
   p.phase_cycles = h->d_phase;
   if (!p.static_users || U > 64) HIPCHK(h, reset_search_counters(h, false));
@@ -349,7 +343,7 @@ static int otm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, i
   while (pcap < stride) pcap <<= 1;
   const size_t lds_prune = (size_t)pcap * 12;
   if (lds_prune > 160 * 1024) return fail(h, DM_ERR_UNSUPPORTED, "fp64 OTM beam search: beam too large for the LDS sort");
-  HIPCHK(h, hipFuncSetAttribute((const void *)otm64_prune_expand_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prune));
+  HIPCHK(h, lds_opt_in(otm64_prune_expand_kernel<T>, lds_prune));          // once for the launches of every level below
   for (int64_t u0 = 0; u0 < U; u0 += Uc) {
     const int64_t Un = U - u0 < Uc ? U - u0 : Uc;
     const int32_t *seq = d_seq + u0 * L;
@@ -360,16 +354,14 @@ static int otm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, i
     if ((rc = dr_launch_gemm<T>(h, g)) != DM_OK) return rc;
     g.A = T1; g.gidx = nullptr; g.B = l1_w + E; g.ldb = 2 * E; g.bias = l1_b; g.C = G;
     if ((rc = dr_launch_gemm<T>(h, g)) != DM_OK) return rc;
-    hipLaunchKernelGGL(otm64_init_kernel<T>, dim3(256), dim3(256), 0, h->stream, c0, sc, Un, stride, start);
-    HIPCHK(h, hipGetLastError());
+    LAUNCHCHK(h, otm64_init_kernel<T>, dim3(256), dim3(256), 0, c0, sc, Un, stride, start);
     int n = start + 1;
     int32_t *cur = c0, *nxt = c1;
     for (int level = level0; level < leaf_level; level++) {
       const bool first = level == level0;
       const int nb = first ? n : (n < beam ? n : beam);
       Otm64Prune<T> pp{cur, sc, nxt, n, nb, first ? 1 : 0, stride, Un, pcap};
-      hipLaunchKernelGGL(otm64_prune_expand_kernel<T>, dim3((unsigned)Un), dim3(256), first ? 0 : lds_prune, h->stream, pp);
-      HIPCHK(h, hipGetLastError());
+      LAUNCHCHK(h, otm64_prune_expand_kernel<T>, dim3((unsigned)Un), dim3(256), first ? 0 : lds_prune, pp);
       n = 2 * nb;
       std::swap(cur, nxt);
       // H1 = Q W1a^T over the Un * n candidate rows.  Rows are addressed [u][stride]: one GEMM per user block would waste
@@ -393,16 +385,14 @@ static int otm_pipeline_dev(dm_ctx *h, const int32_t *d_seq, int64_t U, int L, i
         o.codes = cur; o.scores = sc; o.stride = stride; o.n = n; o.U = Un; o.u0 = u0;
         if (last) { o.out_ids = d_ids; o.out_sc64 = d_sc64; o.out_sc32 = d_sc32; o.out_cnt = d_counts; o.out_stride = 2 * beam; }
         if (d_tn && it < max_levels) { o.tr_codes = d_tc; o.tr_sc64 = d_ts64; o.tr_sc32 = d_ts32; o.tr_cnt = d_tn; o.tr_levels = max_levels; o.tr_cap = cap; o.level = it; }
-        hipLaunchKernelGGL(otm64_emit_kernel<T>, dim3(512), dim3(256), 0, h->stream, o);
-        HIPCHK(h, hipGetLastError());
+        LAUNCHCHK(h, otm64_emit_kernel<T>, dim3(512), dim3(256), 0, o);
       }
     }
     if (leaf_level <= level0) {     // no level to score: the initial frontier is the answer (scores 0), as in the reference
       Otm64Out<T> o{};
       o.codes = cur; o.scores = sc; o.stride = stride; o.n = n; o.U = Un; o.u0 = u0;
       o.out_ids = d_ids; o.out_sc64 = d_sc64; o.out_sc32 = d_sc32; o.out_cnt = d_counts; o.out_stride = 2 * beam;
-      hipLaunchKernelGGL(otm64_emit_kernel<T>, dim3(512), dim3(256), 0, h->stream, o);
-      HIPCHK(h, hipGetLastError());
+      LAUNCHCHK(h, otm64_emit_kernel<T>, dim3(512), dim3(256), 0, o);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));      // the workspace is reused by the next pass
   }

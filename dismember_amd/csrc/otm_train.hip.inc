@@ -175,16 +175,14 @@ static int otm_targets_dev(dm_ctx *h, char *A, const OtmTgtArena &a, const int32
   HIPCHK(h, hipMemcpyAsync(d_seq, seq_codes, (size_t)U * L * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_toff, target_off, (size_t)(U + 1) * 8, hipMemcpyHostToDevice, h->stream));
   if (NT > 0) HIPCHK(h, hipMemcpyAsync(d_tin, target_nodes, (size_t)NT * 4, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(otm_umask_kernel, dim3(GU), dim3(256), 0, h->stream, (const int32_t *)d_seq, U, L, o->use_mask, d_umask);
-  hipLaunchKernelGGL(otm_tgt_leaf_kernel, dim3(GU), dim3(256), 0, h->stream, (const int64_t *)d_toff, (const int32_t *)d_tin, U,
-                     a.tnode(A, levels - 1), a.tlab(A, levels - 1), a.tcnt(A, levels - 1));
+  LAUNCHCHK(h, otm_umask_kernel, dim3(GU), dim3(256), 0, d_seq, U, L, o->use_mask, d_umask);
+  LAUNCHCHK(h, otm_tgt_leaf_kernel, dim3(GU), dim3(256), 0, d_toff, d_tin, U, a.tnode(A, levels - 1), a.tlab(A, levels - 1), a.tcnt(A, levels - 1));
   for (int li = levels - 1; li >= 1; li--) {
     if (o->target_mode == 1) {
-      hipLaunchKernelGGL(otm_tgt_normal_kernel, dim3(GU), dim3(256), 0, h->stream, (const int64_t *)d_toff, U, (const int32_t *)a.tnode(A, li),
-                         (const int32_t *)a.tcnt(A, li), a.tnode(A, li - 1), a.tlab(A, li - 1), a.tcnt(A, li - 1));
+      LAUNCHCHK(h, otm_tgt_normal_kernel, dim3(GU), dim3(256), 0, d_toff, U, a.tnode(A, li), a.tcnt(A, li), a.tnode(A, li - 1), a.tlab(A, li - 1), a.tcnt(A, li - 1));
       continue;
     }
-    hipLaunchKernelGGL(otm_scan_kernel, dim3(1), dim3(64), 0, h->stream, (const int32_t *)a.tcnt(A, li), U, d_coff);
+    LAUNCHCHK(h, otm_scan_kernel, dim3(1), dim3(64), 0, a.tcnt(A, li), U, d_coff);
     int64_t total = 0;
     HIPCHK(h, hipMemcpyAsync(&total, d_coff + U, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -194,7 +192,7 @@ static int otm_targets_dev(dm_ctx *h, char *A, const OtmTgtArena &a, const int32
     p.codes = (int32_t *)(A + a.o_ccodes); p.rseq = (int32_t *)(A + a.o_cseq); p.rmask = (unsigned *)(A + a.o_cmask); p.negl = (double *)(A + a.o_negl);
     p.pred = A + a.o_pred; p.pnode = a.tnode(A, li - 1); p.plab = a.tlab(A, li - 1); p.pcnt = a.tcnt(A, li - 1);
     if (total > 0 && !dfm) {
-      hipLaunchKernelGGL(otm_tgt_rows_kernel, dim3(GU), dim3(256), 0, h->stream, p);
+      LAUNCHCHK(h, otm_tgt_rows_kernel, dim3(GU), dim3(256), 0, p);
       // computePreds (:167-172): posPreds and negPreds as one launch (a row's value does not depend on its batch)
       // (f32 histories of 17 .. 32 positions: the general forward — the MFMA rows kernel holds one 16-position score tile)
       const int rc = f64 ? (rows_fwd64_available(h, L) ? rows_fwd64(h, p.codes, p.rseq, p.rmask, 2 * total, L, (double *)(A + a.o_pred))      // (the matrix-pipe forward while training state exists)
@@ -204,10 +202,9 @@ static int otm_targets_dev(dm_ctx *h, char *A, const OtmTgtArena &a, const int32
       if (rc != DM_OK) return rc;
       if (fwd_rows) *fwd_rows += (uint64_t)(2 * total);
     }
-    if (f64) hipLaunchKernelGGL(otm_tgt_reduce_kernel<double>, dim3(GU), dim3(256), 0, h->stream, p);
-    else hipLaunchKernelGGL(otm_tgt_reduce_kernel<float>, dim3(GU), dim3(256), 0, h->stream, p);
+    if (f64) LAUNCHCHK(h, otm_tgt_reduce_kernel<double>, dim3(GU), dim3(256), 0, p);
+    else LAUNCHCHK(h, otm_tgt_reduce_kernel<float>, dim3(GU), dim3(256), 0, p);
   }
-  HIPCHK(h, hipGetLastError());
   return DM_OK;
 }
 
@@ -312,10 +309,8 @@ static int otm_train_batch_impl(dm_ctx *h, bool dfm, const int32_t *seq_codes, i
     const int nl = n_lv[(size_t)it];
     const int64_t B = U * nl;
     const auto ta = clk::now();
-    hipLaunchKernelGGL(otm_batch_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 8192)), dim3(256), 0, h->stream, (const int32_t *)d_seq,
-                       (const unsigned *)d_umask, (const int64_t *)d_toff, U, L, (const int32_t *)d_tc, (const int32_t *)d_tnn, levels, cap, it, nl,
-                       (const int32_t *)tn_(it), (const double *)tl_(it), (const int32_t *)tc_(it), b_codes, grouped ? (int32_t *)nullptr : b_seq,
-                       grouped ? (unsigned *)nullptr : b_mask, b_lab);
+    LAUNCHCHK(h, otm_batch_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 8192)), dim3(256), 0, d_seq, d_umask, d_toff, U, L, d_tc, d_tnn, levels, cap, it, nl, tn_(it),
+              tl_(it), tc_(it), b_codes, grouped ? (int32_t *)nullptr : b_seq, grouped ? (unsigned *)nullptr : b_mask, b_lab);
     float lf = 0.f;
     double ld = 0.0;
     if (dfm && grouped) rc = dfm_train_fb_grouped_dev(h, d_seq, nullptr, b_codes, b_lab, U, nl, 0, &ld);

@@ -286,20 +286,15 @@ static int sample_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int
   p.max_code = h->max_code; p.lv_codes = h->d_lv_codes; p.lv_cdf = h->d_lv_cdf; p.lv_start = h->d_lv_start;
   p.codes = d_codes; p.seqs = d_seqs; p.rowmask = d_rowmask; p.labels = d_labels; p.cap = cap;
   if (T > 0) {
-    hipLaunchKernelGGL(dm_sample_plan_kernel, dim3((unsigned)((T + 255) / 256 < 1024 ? (T + 255) / 256 : 1024)), dim3(256), 0, h->stream, p, d_cnt);
-    hipLaunchKernelGGL(dm_sample_scan_kernel, dim3(1), dim3(1024), 0, h->stream, (const int64_t *)d_cnt, p.row_off, T);
-    HIPCHK(h, hipGetLastError());
+    LAUNCHCHK(h, dm_sample_plan_kernel, dim3((unsigned)((T + 255) / 256 < 1024 ? (T + 255) / 256 : 1024)), dim3(256), 0, p, d_cnt);
+    LAUNCHCHK(h, dm_sample_scan_kernel, dim3(1), dim3(1024), 0, d_cnt, p.row_off, T);
     const int64_t items = T * (h->max_level - o->start_level + 1);
     int64_t blocks = (items + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     const size_t lds = (size_t)4 * (negmax + 64) * 4;
-    if (blocks > 0) {
-      hipLaunchKernelGGL(dm_sample_kernel, dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-      HIPCHK(h, hipGetLastError());
-    }
+    if (blocks > 0) LAUNCHCHK(h, dm_sample_kernel, dim3((unsigned)blocks), dim3(256), lds, p);
     if (d_seq_codes) {
-      hipLaunchKernelGGL(dm_sample_hist_kernel, dim3((unsigned)std::min<int64_t>((T * L + 255) / 256, 1024)), dim3(256), 0, h->stream, p, d_seq_codes);
-      HIPCHK(h, hipGetLastError());
+      LAUNCHCHK(h, dm_sample_hist_kernel, dim3((unsigned)std::min<int64_t>((T * L + 255) / 256, 1024)), dim3(256), 0, p, d_seq_codes);
       HIPCHK(h, hipMemcpyAsync(d_row_off, p.row_off, (size_t)(T + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
     }
     long long total = 0;

@@ -300,12 +300,11 @@ static int tdm_pl_fold(dm_ctx *h, TdmPlScorer &scorer, const int32_t *d_seq, int
   if ((rc = scorer.attach(h, ar)) != DM_OK) return rc;
   HIPCHK(h, reset_search_counters(h, false));
   const size_t lds_step = (size_t)stride * 16;
-  HIPCHK(h, hipFuncSetAttribute((const void *)tdm_pl_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_step));
+  HIPCHK(h, lds_opt_in(tdm_pl_step_kernel, lds_step));          // once for the launches of every level below
   TdmPlTree t{h->d_exists, h->d_leaf, h->d_node_id, h->d_id_to_code, h->n_slots, h->num_index, h->non_leaf_offset, h->max_code};
   for (int64_t u0 = 0; u0 < U; u0 += Uc) {
     const int64_t Un = U - u0 < Uc ? U - u0 : Uc;
-    hipLaunchKernelGGL(tdm_pl_keys_kernel, dim3(256), dim3(256), 0, h->stream, d_seq + u0 * L, Un * L, t, kcode);
-    HIPCHK(h, hipGetLastError());
+    LAUNCHCHK(h, tdm_pl_keys_kernel, dim3(256), dim3(256), 0, d_seq + u0 * L, Un * L, t, kcode);
     if ((rc = scorer.setup(h, kcode, Un)) != DM_OK) return rc;
     TdmPlStep sp{};
     sp.t = t; sp.lf_code = lf_code; sp.lf_score = lf_score; sp.lf_pos = lf_pos; sp.lf_n = lf_n;
@@ -314,28 +313,23 @@ static int tdm_pl_fold(dm_ctx *h, TdmPlScorer &scorer, const int32_t *d_seq, int
     sp.scored_rows = &h->d_ctr->rows;
     int32_t *cur = c0, *nxt = c1, *ncur = n0, *nnxt = n1;
     sp.init = 1; sp.next = cur; sp.next_cnt = ncur; sp.sc = sc;
-    hipLaunchKernelGGL(tdm_pl_step_kernel, dim3((unsigned)Un), dim3(256), lds_step, h->stream, sp);
-    HIPCHK(h, hipGetLastError());
+    LAUNCHCHK(h, tdm_pl_step_kernel, dim3((unsigned)Un), dim3(256), lds_step, sp);
     HIPCHK(h, hipMemsetAsync(sc, 0, (size_t)Un * stride * 4, h->stream));
     sp.init = 0;
     for (int it = 0; it < n_iter; it++) {
       sp.it = it; sp.cur = cur; sp.cnt = ncur; sp.next = nxt; sp.next_cnt = nnxt;
-      hipLaunchKernelGGL(tdm_pl_step_kernel, dim3((unsigned)Un), dim3(256), lds_step, h->stream, sp);
-      HIPCHK(h, hipGetLastError());
+      LAUNCHCHK(h, tdm_pl_step_kernel, dim3((unsigned)Un), dim3(256), lds_step, sp);
       std::swap(cur, nxt); std::swap(ncur, nnxt);
       if ((rc = scorer.score(h, cur, ncur, sc, Un)) != DM_OK) return rc;
       if (d_tn && it < trace_levels) {
-        hipLaunchKernelGGL(tdm_pl_trace_kernel, dim3(512), dim3(256), 0, h->stream, (const int32_t *)cur, (const float *)sc, (const int32_t *)ncur,
-                           stride, Un, u0, it, trace_levels, cap, d_tc, d_ts, d_tn);
-        HIPCHK(h, hipGetLastError());
+        LAUNCHCHK(h, tdm_pl_trace_kernel, dim3(512), dim3(256), 0, cur, sc, ncur, stride, Un, u0, it, trace_levels, cap, d_tc, d_ts, d_tn);
       }
     }
     TdmPlFinal f{};
     f.node_id = h->d_node_id; f.lf_code = lf_code; f.lf_score = lf_score; f.lf_pos = lf_pos; f.lf_n = lf_n; f.lf_key = lf_key;
     f.consumed_off = d_coff; f.consumed_ids = d_cids; f.out_ids = d_ids; f.out_scores = d_scores; f.out_counts = d_counts;
     f.lcap = lcap; f.topk = o->topk; f.U = Un; f.u0 = u0;
-    hipLaunchKernelGGL(tdm_pl_final_kernel, dim3((unsigned)Un), dim3(256), 0, h->stream, f);
-    HIPCHK(h, hipGetLastError());
+    LAUNCHCHK(h, tdm_pl_final_kernel, dim3((unsigned)Un), dim3(256), 0, f);
     HIPCHK(h, hipStreamSynchronize(h->stream));      // the workspace is reused by the next pass
   }
   return DM_OK;

@@ -3,8 +3,7 @@
 // MiniBatch.transformWithMask (T/dataset/MiniBatch.scala:129-147).
 
 static bool tg_enabled() {
-  const char *e = getenv("DM_TRAIN_GROUPED");       // DM_TRAIN_GROUPED=0: the grouped entry point expands to plain rows (A/B, tests)
-  return !(e && e[0] == '0');
+  return !env_off("DM_TRAIN_GROUPED");       // DM_TRAIN_GROUPED=0: the grouped entry point expands to plain rows (A/B, tests)
 }
 
 static size_t tg_up(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -38,17 +37,10 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
   double *grad = (double *)h->train.grad;
   // every launch gets an event pair (dm_kernel_timing_get_kind: EV_TG_SETUP = per-user setup, EV_TG_ROWS = the row kernel, EV_TG_WGRAD_A = dW1a +
   // per-user sums, EV_TG_USER_BWD = per-user backward, EV_TG_WGRAD_B = dW1b / datt.W): bench.py prices the row kernel against the fp64 matrix peak from these
-  auto timed = [&](int kind, auto launch) -> int {
-    LaunchTimer tm(h, kind);
-    if (tm.rc != DM_OK) return tm.rc;
-    launch();
-    HIPCHK(h, hipGetLastError());
-    return tm.stop();
-  };
   // ---- per-user setup
   TgSetupParams sp{};
   sp.emb = base; sp.num_index = h->num_index; sp.attA = f64f + n2; sp.w1bB = f64f + 2 * n2; sp.b1 = b1; sp.seq = d_seq; sp.U = U; sp.L = L; sp.b = bufs;
-  if ((rc = timed(EV_TG_SETUP, [&] { hipLaunchKernelGGL((tg_setup_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, sp); })) != DM_OK) return rc;
+  if ((rc = timed(h, EV_TG_SETUP, true, [&] { return LAUNCH(h, tg_setup_kernel<E>, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, sp); })) != DM_OK) return rc;
   // ---- rows: forward + backward
   TgRowsParams rp{};
   rp.emb = base; rp.num_index = h->num_index; rp.l1_w = l1_w; rp.w2 = w2; rp.b2 = h->lazy.b2_64;
@@ -71,9 +63,9 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     const int64_t items = U * rp.chunks_per_user;
     int64_t blocks = (items + TG_NWAVES - 1) / TG_NWAVES;
     if (blocks > h->n_cu) blocks = h->n_cu;
-    auto go = [&](auto kern) -> int {
-      HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-      return timed(EV_TG_ROWS, [&] { hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(TG_BLOCK), lds, h->stream, rp); });
+    auto go = [&](void (*tg_rows_kernel_E_KQ)(TgRowsParams)) -> int {      // (the parameter's name is what LAUNCH puts into an error message)
+      HIPCHK(h, lds_opt_in(tg_rows_kernel_E_KQ, lds));
+      return timed(h, EV_TG_ROWS, true, [&] { return LAUNCH(h, tg_rows_kernel_E_KQ, dim3((unsigned)blocks), dim3(TG_BLOCK), lds, rp); });
     };
     switch ((L + 3) / 4) {
       case 1: rc = go(tg_rows_kernel<E, 1>); break;
@@ -84,8 +76,8 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     if (rc != DM_OK) return rc;
   }
   double *g_l2b = grad + h->num_index * E + 3 * (int64_t)n2 + 2 * E;
-  hipLaunchKernelGGL(tg_loss_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 1024)), dim3(256), 0, h->stream, (const double *)rp.logits,
-                     (const double *)rp.GL, d_labels, B, (double *)h->d_loss, g_l2b);
+  if ((rc = LAUNCH(h, tg_loss_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 1024)), dim3(256), 0, rp.logits, rp.GL, d_labels, B, (double *)h->d_loss, g_l2b)) != DM_OK)
+    return rc;
   // ---- dW1a + the per-user sums dG, dK + l1.b / l2.W gradients
   TgWgradParams wp{};
   wp.emb = base; wp.num_index = h->num_index; wp.codes = d_codes; wp.Z = rp.Z; wp.P = rp.P; wp.DS = rp.DS; wp.GL = rp.GL; wp.w2 = w2;
@@ -95,13 +87,13 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     const int64_t want = std::max<int64_t>(1, (int64_t)h->n_cu * 8 / NBq);     // two waves per SIMD, a few chunks per slot
     wp.users_per_chunk = (int)std::max<int64_t>(1, (U + 4 * want - 1) / (4 * want));
     const unsigned chunks = (unsigned)((U + wp.users_per_chunk - 1) / wp.users_per_chunk);
-    if ((rc = timed(EV_TG_WGRAD_A, [&] { hipLaunchKernelGGL((tg_wgrad_kernel<E>), dim3(1, chunks), dim3(64 * NBq), 0, h->stream, wp); })) != DM_OK) return rc;
+    if ((rc = timed(h, EV_TG_WGRAD_A, true, [&] { return LAUNCH(h, tg_wgrad_kernel<E>, dim3(1, chunks), dim3(64 * NBq), 0, wp); })) != DM_OK) return rc;
   }
   // ---- per-user backward, then dW1b / datt.W over the U x 16 per-user rows
   TgUserBwdParams up{};
   up.attTA = (const f64x4 *)(tr + 3 * n2); up.w1bTA = (const f64x4 *)(tr + 5 * n2); up.seq = d_seq; up.U = U; up.L = L; up.num_index = h->num_index;
   up.b = bufs; up.grad = grad;
-  if ((rc = timed(EV_TG_USER_BWD, [&] { hipLaunchKernelGGL((tg_user_bwd_kernel<E>), dim3((unsigned)((U + 3) / 4)), dim3(256), 0, h->stream, up); })) != DM_OK) return rc;
+  if ((rc = timed(h, EV_TG_USER_BWD, true, [&] { return LAUNCH(h, tg_user_bwd_kernel<E>, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, up); })) != DM_OK) return rc;
   WGradParamsT<double> wg{};
   wg.emb = base; wg.codes = nullptr; wg.DZ = bufs.dGrows; wg.AT = bufs.T1rows; wg.DA = bufs.dTrows; wg.CB = bufs.Krows;
   wg.B = U * 16; wg.num_index = h->num_index; wg.grad = grad; wg.mat_base = 1;
@@ -109,9 +101,8 @@ static int tg_launch_E(dm_ctx *h, const int32_t *d_seq, const unsigned *d_umask,
     const int64_t want = std::max<int64_t>(1, (int64_t)h->n_cu * 16 / (2 * NBq));
     wg.chunk = std::max<int64_t>(128, (((wg.B + want - 1) / want) + 7) / 8 * 8);
     const int chunks = (int)((wg.B + wg.chunk - 1) / wg.chunk);
-    if ((rc = timed(EV_TG_WGRAD_B, [&] { hipLaunchKernelGGL((dm_wgrad_kernel<double, E>), dim3(2 * NBq, chunks), dim3(64), 0, h->stream, wg); })) != DM_OK) return rc;
+    if ((rc = timed(h, EV_TG_WGRAD_B, true, [&] { return LAUNCH(h, (dm_wgrad_kernel<double, E>), dim3(2 * NBq, chunks), dim3(64), 0, wg); })) != DM_OK) return rc;
   }
-  HIPCHK(h, hipGetLastError());
   return DM_OK;
 }
 
@@ -127,9 +118,9 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
     int rc = t.alloc(rseq, (size_t)B * L * 4);
     if (rc == DM_OK) rc = t.alloc(rmask, (size_t)B * 4);
     if (rc == DM_OK) {
-      hipLaunchKernelGGL(tg_expand_rows_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 8192)), dim3(256), 0, h->stream, d_seq, d_umask, U, n, L, rseq, rmask);
+      rc = LAUNCH(h, tg_expand_rows_kernel, dim3((unsigned)std::min<int64_t>((B + 255) / 256, 8192)), dim3(256), 0, d_seq, d_umask, U, n, L, rseq, rmask);
       float lf = 0.f;
-      rc = train_fb_dev(h, d_codes, rseq, rmask, d_labels, B, L, &lf);      // (synchronises: the loss is read back)
+      if (rc == DM_OK) rc = train_fb_dev(h, d_codes, rseq, rmask, d_labels, B, L, &lf);      // (synchronises: the loss is read back)
       if (loss) *loss = lf;
     }
     if (hipStreamSynchronize(h->stream) != hipSuccess && rc == DM_OK) rc = fail(h, DM_ERR_HIP, "train_fb_grouped_dev: kernel failed");
@@ -157,11 +148,9 @@ static int train_fb_grouped_dev(dm_ctx *h, const int32_t *d_seq, const unsigned 
                       [&](auto e) { return tg_launch_E<decltype(e)::value>(h, d_seq, d_umask, d_codes, d_labels, U, n, L); });
   if (rc != DM_OK) return rc;
   // rows the gradient reached: the candidates and the users' histories (each history once, not once per row)
-  hipLaunchKernelGGL(dm_mark_touched_kernel, dim3(256), dim3(256), 0, h->stream, d_codes, (const int32_t *)nullptr, B, 0, h->d_touch_bits,
-                     h->d_touch_list, h->d_touch_cnt, (unsigned long long)h->touch_cap, h->num_index);
-  hipLaunchKernelGGL(dm_mark_touched_kernel, dim3(64), dim3(256), 0, h->stream, d_seq, (const int32_t *)nullptr, U * L, 0, h->d_touch_bits,
-                     h->d_touch_list, h->d_touch_cnt, (unsigned long long)h->touch_cap, h->num_index);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = LAUNCH(h, dm_mark_touched_kernel, dim3(256), dim3(256), 0, d_codes, nullptr, B, 0, h->d_touch_bits, h->d_touch_list, h->d_touch_cnt, h->touch_cap, h->num_index)) != DM_OK ||
+      (rc = LAUNCH(h, dm_mark_touched_kernel, dim3(64), dim3(256), 0, d_seq, nullptr, U * L, 0, h->d_touch_bits, h->d_touch_list, h->d_touch_cnt, h->touch_cap, h->num_index)) != DM_OK)
+    return rc;
   if ((rc = h->train.mark_active(h, 256, d_codes, B, d_seq, U * L)) != DM_OK) return rc;
   if (loss) {
     double acc[2];

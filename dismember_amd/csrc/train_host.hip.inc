@@ -62,23 +62,16 @@ static int launch_train_E(dm_ctx *h, TrainParamsT<T> &p, const WGradParamsT<T> &
   int64_t tiles = (p.B + 15) / 16, blocks = (tiles + nw - 1) / nw;
   const int64_t max_blocks = h->n_cu;
   if (blocks > max_blocks) blocks = max_blocks;
-  if (p.L <= DM_MAXL) {
-    if (lds) HIPCHK(h, hipFuncSetAttribute((const void *)dm_train_rows_kernel<T, E, DM_MAXL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((dm_train_rows_kernel<T, E, DM_MAXL>), dim3((unsigned)blocks), dim3(block), lds, h->stream, p);
-  } else {      // histories of 17 .. 32 positions
-    if (lds) HIPCHK(h, hipFuncSetAttribute((const void *)dm_train_rows_kernel<T, E, DM_PIPE_MAXL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((dm_train_rows_kernel<T, E, DM_PIPE_MAXL>), dim3((unsigned)blocks), dim3(block), lds, h->stream, p);
-  }
-  HIPCHK(h, hipGetLastError());
+  const int rc = p.L <= DM_MAXL ? LAUNCH_LDS(h, (dm_train_rows_kernel<T, E, DM_MAXL>), dim3((unsigned)blocks), dim3(block), lds, p)
+                                : LAUNCH_LDS(h, (dm_train_rows_kernel<T, E, DM_PIPE_MAXL>), dim3((unsigned)blocks), dim3(block), lds, p);      // histories of 17 .. 32 positions
+  if (rc != DM_OK) return rc;
   // weight gradients: 3 matrices x (NT / RT)^2 output blocks x row chunks, ~8 one-wave workgroups per SIMD, at least 128 rows each
   constexpr int NT = E / 16, RT = NT < 4 ? NT : 4, NBLK = 3 * (NT / RT) * (NT / RT);
   WGradParamsT<T> wq = wg;
   const int64_t want = std::max<int64_t>(1, (int64_t)h->n_cu * 32 / NBLK);
   wq.chunk = std::max<int64_t>(128, (((wq.B + want - 1) / want) + 7) / 8 * 8);
   const int chunks = (int)((wq.B + wq.chunk - 1) / wq.chunk);
-  hipLaunchKernelGGL((dm_wgrad_kernel<T, E>), dim3(NBLK, chunks), dim3(64), 0, h->stream, wq);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return LAUNCH(h, (dm_wgrad_kernel<T, E>), dim3(NBLK, chunks), dim3(64), 0, wq);
 }
 
 template <typename T>
@@ -128,15 +121,8 @@ static int rows_fwd64_E(dm_ctx *h, TrainParamsT<double> &p) {
   const int lds = E * E * 8 + 4 * ml * 16 * 2 * 8 + (ml > 16 ? 0 : 4 * ml * 16 * 4);
   int64_t tiles = (p.B + 15) / 16, blocks = (tiles + 3) / 4;
   if (blocks > h->n_cu) blocks = h->n_cu;
-  if (p.L <= DM_MAXL) {
-    HIPCHK(h, hipFuncSetAttribute((const void *)dm_train_rows_kernel<double, E, DM_MAXL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((dm_train_rows_kernel<double, E, DM_MAXL, true>), dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-  } else {
-    HIPCHK(h, hipFuncSetAttribute((const void *)dm_train_rows_kernel<double, E, DM_PIPE_MAXL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((dm_train_rows_kernel<double, E, DM_PIPE_MAXL, true>), dim3((unsigned)blocks), dim3(256), lds, h->stream, p);
-  }
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return p.L <= DM_MAXL ? LAUNCH_LDS(h, (dm_train_rows_kernel<double, E, DM_MAXL, true>), dim3((unsigned)blocks), dim3(256), lds, p)
+                        : LAUNCH_LDS(h, (dm_train_rows_kernel<double, E, DM_PIPE_MAXL, true>), dim3((unsigned)blocks), dim3(256), lds, p);
 }
 static bool rows_fwd64_available(const dm_ctx *h, int L) { return h->dtype == DM_F64 && h->d_tr64 && L >= 1 && L <= DM_PIPE_MAXL; }
 // ... and on a handle WITHOUT training state: the fragments are built on first use (freed with the weights they were made from:
@@ -201,9 +187,8 @@ static int train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs
   rc = h->dtype == DM_F64 ? train_fb_launch<double>(h, d_codes, d_seqs, d_rowmask, d_labels, B, L)
                           : train_fb_launch<float>(h, d_codes, d_seqs, d_rowmask, d_labels, B, L);
   if (rc != DM_OK) return rc;
-  hipLaunchKernelGGL(dm_mark_touched_kernel, dim3(256), dim3(256), 0, h->stream, d_codes, d_seqs, B, L, h->d_touch_bits,
-                     h->d_touch_list, h->d_touch_cnt, (unsigned long long)h->touch_cap, h->num_index);
-  HIPCHK(h, hipGetLastError());
+  if ((rc = LAUNCH(h, dm_mark_touched_kernel, dim3(256), dim3(256), 0, d_codes, d_seqs, B, L, h->d_touch_bits, h->d_touch_list, h->d_touch_cnt, h->touch_cap,
+                   h->num_index)) != DM_OK) return rc;
   if ((rc = h->train.mark_active(h, 256, d_codes, B, d_seqs, B * L)) != DM_OK) return rc;
   if (loss) {
     if (h->dtype == DM_F64) {
@@ -259,7 +244,7 @@ int dm_train_forward_backward(dm_handle_t h, const int32_t *codes, const int32_t
   if (n_pad > 0) {
     if ((rc = t.alloc(d_pad, n_pad * 4)) != DM_OK) return rc;
     if (hipMemcpyAsync(d_pad, pad_flat_idx, n_pad * 4, hipMemcpyHostToDevice, h->stream) != hipSuccess) return fail(h, DM_ERR_HIP, "upload failed");
-    hipLaunchKernelGGL(dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, h->stream, d_pad, n_pad, L, d_mask);
+    if ((rc = LAUNCH(h, dm_pad_rowmask_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, d_pad, n_pad, L, d_mask)) != DM_OK) return rc;
   }
   float l = 0.f;
   rc = train_fb_dev(h, d_codes, d_seqs, d_mask, d_lab, B, L, &l);
@@ -288,8 +273,7 @@ int dm_adam_step(dm_handle_t h, float grad_scale) {
   if ((rc = adam_step(h, h->train, plan, h->d_compact, h->dtype == DM_F64, false, grad_scale, false, 64)) != DM_OK) return rc;
   // forget which rows were touched in this step
   if (cnt > 0 && h->d_touch_list) {
-    hipLaunchKernelGGL(dm_clear_touched_kernel, dim3(256), dim3(256), 0, h->stream, h->d_touch_list, (int64_t)cnt, h->d_touch_bits);
-    HIPCHK(h, hipGetLastError());
+    if ((rc = LAUNCH(h, dm_clear_touched_kernel, dim3(256), dim3(256), 0, h->d_touch_list, cnt, h->d_touch_bits)) != DM_OK) return rc;
   }
   HIPCHK(h, hipMemsetAsync(h->d_touch_cnt, 0, 8, h->stream));
   h->touch_ub = 0;
@@ -354,22 +338,15 @@ __global__ void dm_add_rows_kernel(T *grad, const int32_t *rows, const T *g, int
   }
 }
 static int launch_gather_rows(dm_ctx *h, int64_t cnt, int32_t *d_rows, void *d_grads) {
-  if (h->dtype == DM_F64)
-    hipLaunchKernelGGL(dm_gather_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (const double *)h->train.grad, h->d_touch_list, cnt, h->embed, d_rows, (double *)d_grads);
-  else
-    hipLaunchKernelGGL(dm_gather_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (const float *)h->train.grad, h->d_touch_list, cnt, h->embed, d_rows, (float *)d_grads);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return h->dtype == DM_F64
+             ? LAUNCH(h, dm_gather_rows_kernel<double>, dim3(1024), dim3(256), 0, (const double *)h->train.grad, h->d_touch_list, cnt, h->embed, d_rows, (double *)d_grads)
+             : LAUNCH(h, dm_gather_rows_kernel<float>, dim3(1024), dim3(256), 0, (const float *)h->train.grad, h->d_touch_list, cnt, h->embed, d_rows, (float *)d_grads);
 }
 static int launch_add_rows(dm_ctx *h, const int32_t *d_rows, const void *d_grads, int64_t n) {
   const int rc = h->train.mark_active(h, 256, d_rows, n);
   if (rc != DM_OK) return rc;
-  if (h->dtype == DM_F64)
-    hipLaunchKernelGGL(dm_add_rows_kernel<double>, dim3(1024), dim3(256), 0, h->stream, (double *)h->train.grad, d_rows, (const double *)d_grads, n, h->embed, h->num_index);
-  else
-    hipLaunchKernelGGL(dm_add_rows_kernel<float>, dim3(1024), dim3(256), 0, h->stream, (float *)h->train.grad, d_rows, (const float *)d_grads, n, h->embed, h->num_index);
-  HIPCHK(h, hipGetLastError());
-  return DM_OK;
+  return h->dtype == DM_F64 ? LAUNCH(h, dm_add_rows_kernel<double>, dim3(1024), dim3(256), 0, (double *)h->train.grad, d_rows, (const double *)d_grads, n, h->embed, h->num_index)
+                            : LAUNCH(h, dm_add_rows_kernel<float>, dim3(1024), dim3(256), 0, (float *)h->train.grad, d_rows, (const float *)d_grads, n, h->embed, h->num_index);
 }
 
 int dm_train_export_rows(dm_handle_t h, int32_t *d_rows, void *d_grads, int64_t cap, int64_t *n) {
