@@ -16,7 +16,10 @@ struct TrainVec {
   unsigned long long *active_cnt = nullptr;
   dm_adam_opts opts{};
   int t = 0;
-  DevGrow prev;                                          // the sorted destination rows of the last batch (zeroed by the next); DIN: unused
+  DevGrow prev;                                          // the sorted destination rows of the last batch (zeroed by the next); DIN: unused.
+                                                         // After dm_deepfm_train_sync_gradients: every rank's unique rows, rank after rank (a
+                                                         // union with repeats, sorted only inside a rank) - enough for drt_seg_rows_kernel<T, true>,
+                                                         // which clears at every change of key, and clearing a row twice changes nothing
   int64_t prev_m = 0;
 
   int init(dm_ctx *h, int64_t rows_, int E_, int64_t n_, size_t elem_size, const dm_adam_opts &o);

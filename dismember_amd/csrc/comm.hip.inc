@@ -593,6 +593,32 @@ int dm_allreduce_grads(dm_handle_t *hs, int n) {
   return sync_gradients_impl(hs, n);
 }
 
+// The payload half of dm_comm_all_gather_dev, for a caller that already knows every rank's size (all[r], total = their sum): the only
+// transport-specific code of a device all-gather.  Ordered after the work queued on the handle's stream and complete on return; d_send
+// may be this rank's place inside d_recv.  *syncs (optional) += the times the host waited for the stream.
+static int comm_all_gather_dev_payload(dm_ctx *h, dm_comm *c, const void *d_send, size_t bytes, void *d_recv, const std::vector<uint64_t> &all, size_t total, int *syncs) {
+  int rc;
+  if (c->kind == DM_COMM_RCCL) {
+    rc = rccl_all_gather_v_dev(c, d_send, d_recv, all, h->stream);
+    if (rc != DM_OK) return fail(h, rc, c->err);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (syncs) *syncs += 1;
+    return DM_OK;
+  }
+  std::vector<char> sendbuf(bytes), recv;
+  std::vector<uint64_t> sz;
+  if (bytes) HIPCHK(h, hipMemcpyAsync(sendbuf.data(), d_send, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (syncs) *syncs += 1;
+  rc = comm_all_gather_v_host(c, sendbuf.data(), bytes, recv, sz);
+  if (rc != DM_OK) return fail(h, rc, c->err);
+  if (recv.size() != total) return fail(h, DM_ERR_STATE, "dm_comm_all_gather_dev: the blocks received do not add up to the announced sizes");
+  if (total) HIPCHK(h, hipMemcpyAsync(d_recv, recv.data(), total, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));      // recv is read by the copy
+  if (syncs) *syncs += 1;
+  return DM_OK;
+}
+
 // var-size all-gather of DEVICE buffers on the handle's stream (JTM weight blocks, result lists): d_recv receives the blocks
 // in rank order; sizes[r] (host) are filled for every rank.  d_recv == NULL: size query only.
 int dm_comm_all_gather_dev(dm_handle_t h, const void *d_send, size_t bytes, void *d_recv, size_t recv_cap, uint64_t *sizes) {
@@ -610,16 +636,5 @@ int dm_comm_all_gather_dev(dm_handle_t h, const void *d_send, size_t bytes, void
   for (int r = 0; r < c->nranks; r++) { sizes[r] = all[r]; total += all[r]; }
   if (!d_recv) return DM_OK;
   if (total > recv_cap) return fail(h, DM_ERR_INVALID, "dm_comm_all_gather_dev: receive buffer too small");
-  if (c->kind == DM_COMM_RCCL) {
-    rc = rccl_all_gather_v_dev(c, d_send, d_recv, all, h->stream);
-    if (rc != DM_OK) return fail(h, rc, c->err);
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DM_OK;
-  }
-  std::vector<char> sendbuf(bytes), recv;
-  if (bytes) HIPCHK(h, hipMemcpy(sendbuf.data(), d_send, bytes, hipMemcpyDeviceToHost));
-  rc = comm_all_gather_v_host(c, sendbuf.data(), bytes, recv, sz);
-  if (rc != DM_OK) return fail(h, rc, c->err);
-  if (total) HIPCHK(h, hipMemcpy(d_recv, recv.data(), total, hipMemcpyHostToDevice));
-  return DM_OK;
+  return comm_all_gather_dev_payload(h, c, d_send, bytes, d_recv, all, total, nullptr);
 }

@@ -31,6 +31,8 @@ struct dm_dfm_train {
   TrainVec vec;                              // over d_compact in its padded layout: rows = num_index, E = embed
   float *fragF = nullptr, *fragB = nullptr;  // l1.W in the two fragment orders of dfm_train_rows_kernel (dfm_train_derive_kernel)
   DevGrow ws, io;
+  DevGrow sync;                              // staging of dm_deepfm_train_sync_gradients (dfm_train_sync.hip.inc): all ranks' blocks, their tails
+  bool exchanged = false;                    // vec.grad holds the sum over ranks: until the next forward/backward or Adam step
 };
 
 static void dfm_train_release(dm_ctx *h) {
@@ -38,7 +40,7 @@ static void dfm_train_release(dm_ctx *h) {
   if (!t) return;
   t->vec.release();
   dm_release(t->fragF, t->fragB);
-  for (DevGrow *g : {&t->ws, &t->io}) g->release();
+  for (DevGrow *g : {&t->ws, &t->io, &t->sync}) g->release();
   delete t;
   h->dfm_tr = nullptr;
 }
@@ -369,8 +371,11 @@ int dm_deepfm_train_free(dm_handle_t h) {
 }
 
 // ---- what the row step and the user-grouped step (dfm_train_grouped.hip.inc) share on the host
-// zeroGradParameters for the table: the rows the last batch reached, of either step (the dense blocks are overwritten by every step)
+// zeroGradParameters for the table: the rows the last batch reached, of either step (the dense blocks are overwritten by every step).
+// After a gradient exchange `prev` is the concatenation of every rank's rows, not sorted and with repeats: the kernel clears at every
+// change of key, so a row may be cleared more than once, which changes nothing
 static int dfm_train_clear_prev(dm_ctx *h, dm_dfm_train *t) {
+  t->exchanged = false;
   if (t->vec.prev_m <= 0) return DM_OK;
   const int rc = LAUNCH(h, (drt_seg_rows_kernel<float, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, (const unsigned long long *)t->vec.prev.p, nullptr,
                         t->vec.prev_m, h->num_index, nullptr, h->embed, (float *)t->vec.grad);
@@ -510,6 +515,7 @@ int dm_deepfm_adam_step(dm_handle_t h, float grad_scale) {
   rc = timed(h, EV_DFT_ADAM, dfm_time_launches(), [&] { return adam_step(h, t->vec, plan, h->d_compact, false, false, grad_scale, false, 1024); });
   if (rc != DM_OK) return rc;
   t->vec.forget();                  // the step zeroed every gradient it visited, and it visited every row a batch has reached
+  t->exchanged = false;
   if ((rc = dfm_rederive(h)) != DM_OK) return rc;
   model_changed(h);
   return DM_OK;

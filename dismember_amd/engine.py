@@ -1057,6 +1057,12 @@ class Engine:
     def deepfm_adam_step(self, grad_scale=1.0):
         self._chk(N.lib().dm_deepfm_adam_step(self._h, float(grad_scale)))
 
+    def deepfm_train_sync_gradients(self):
+        """LocalOptimizer.syncGradients for a DeepFM model over the attached communicator (dm_deepfm_train_sync_gradients, DESIGN.md
+        §19; collective: every rank calls it, a rank whose batch was empty included).  Afterwards every replica's gradient is the
+        rank-ordered fp32 sum of the ranks' gradients; deepfm_adam_step(1 / world) follows.  train_sync_stats() says what it moved."""
+        self._chk(N.lib().dm_deepfm_train_sync_gradients(self._h))
+
     def deepfm_train_param_count(self):
         n = C.c_int64(0)
         self._chk(N.lib().dm_deepfm_train_param_count(self._h, C.byref(n)))
@@ -1195,7 +1201,9 @@ class Engine:
         DM_DR_TIME_LAUNCHES=1 the Deep-Retrieval training step: 50 = forward GEMMs, 51 = softmax + cross-entropy, 52 = dX products,
         53 = dW / db products and slab sums, 54 = embedding gradient (pairs, sort, segment sums), 55 = Adam; and the M-step's path scores:
         80 = pairs of a chunk, 81 = the (item, path) sort, 82 = segment heads, 83 = segment sums, 84 = sort by score, 85 = sort by item,
-        86 = the cut at C, 87 = codes / scores / offsets, 88 = occurrences"""
+        86 = the cut at C, 87 = codes / scores / offsets, 88 = occurrences; under DM_DFM_TIME_LAUNCHES=1 the DeepFM training step
+        (70 .. 76) and its gradient exchange across ranks: 77 = this rank's unique rows and block, 78 = the rank-ordered sums after
+        the all-gather"""
         n, ms = C.c_int(0), C.c_double(0)
         self._chk(N.lib().dm_kernel_timing_get_kind(self._h, int(kind), C.byref(n), C.byref(ms)))
         return n.value, ms.value

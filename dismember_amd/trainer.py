@@ -1,4 +1,4 @@
-"""Training of the node scorer (DIN data-parallel; DeepFM on one device): mirror of the reference's LocalOptimizer
+"""Training of the node scorer (DIN and DeepFM, data-parallel): mirror of the reference's LocalOptimizer
 (tdm/src/main/scala/com/mass/tdm/optim/LocalOptimizer.scala:58-187) with one worker per GPU.
 
 Reference: N worker threads, each with a model clone sharing the weights and a private gradient buffer;
@@ -7,7 +7,9 @@ then ONE Adam step updates the shared weights.  Here a worker is a process with 
 weights); `Engine.train_sync_gradients()` (dm_train_sync_gradients: RCCL all-reduce of the dense block + all-gather of
 the touched embedding rows, re-summed in rank order, inside the library) makes every replica hold the same summed
 gradient, and every replica applies the same Adam step, so replicas stay bit-identical without a parameter broadcast
-(never a ring over the 17 GB table).
+(never a ring over the 17 GB table).  A DeepFM engine does the same through `Engine.deepfm_train_sync_gradients()`
+(dm_deepfm_train_sync_gradients, DESIGN.md §19: one var-size all-gather of [touched rows | their gradients | dense blocks], everything
+re-summed in rank order on either transport) and `Engine.deepfm_adam_step(1 / world)`.
 """
 import os
 
@@ -20,7 +22,8 @@ class TDMTrainer:
     comm: dismember_amd.comm.Comm (or None for a single worker).  sampler: "device" draws the negatives on the GPU
     (dm_tdm_sample_train_batch_dev; rows never visit the host), "host" uses dm_tdm_make_train_batch.
     An engine that holds a DeepFM model is driven through its own entry points (Engine.deepfm_*), without a mask — the graph has none,
-    tdm/.../model/TDM.scala:26-29 — and without a communicator: gradient exchange for DeepFM is not built.
+    tdm/.../model/TDM.scala:26-29.  With a communicator every step is local step -> Engine.deepfm_train_sync_gradients ->
+    deepfm_adam_step(1 / world), whichever form the local step takes; a rank whose sampler drew no rows still takes part in the exchange.
     grouped (DeepFM with the device sampler only; a DIN engine ignores it, the host sampler keeps the row step): True trains with the
     ragged user-grouped step (Engine.deepfm_train_step_sampled(grouped=True): a target's history is read once, not once per row;
     other summation orders than the row step's, so not its bytes), False with the row step, None reads DM_DFM_TRAIN_GROUPED ("1" = on)
@@ -35,10 +38,10 @@ class TDMTrainer:
         self.deepfm = engine.scorer == "deepfm"
         self.grouped = (os.environ.get("DM_DFM_TRAIN_GROUPED") == "1") if grouped is None else bool(grouped)
         if self.deepfm:
-            if comm is not None:
-                raise ValueError("TDMTrainer: gradient exchange for a DeepFM model is not built (comm must be None)")
             self.use_mask = False
             engine.deepfm_train_init(lr=lr)
+            if comm is not None:
+                engine.attach_comm(comm)
             return
         engine.train_init(lr=lr)
         if comm is not None:
@@ -57,8 +60,15 @@ class TDMTrainer:
                 codes, seqs, y = self.e.deepfm_make_train_batch(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
                                                                 with_prob=self.with_prob, tolerance=self.tolerance)
                 loss = self.e.deepfm_train_forward_backward(codes, seqs, y) if codes.size else 0.0
-            self.e.deepfm_adam_step(1.0)
+            if self.comm is not None:
+                import time
+                t0 = time.perf_counter()
+                self.e.deepfm_train_sync_gradients()      # syncGradients, LocalOptimizer.scala:164-187
+                self.sync_s += time.perf_counter() - t0; self.sync_calls += 1
+            self.e.deepfm_adam_step(1.0 / world)          # ... / realParallelism, folded into the Adam kernel
             self.it += 1
+            if self.comm is not None:
+                loss = self.comm.allreduce(float(loss)) / world       # lossSum / realParallelism, LocalOptimizer.scala:161
             return loss
         if self.sampler == "device":
             loss = self.e.train_step_sampled(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,

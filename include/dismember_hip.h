@@ -645,6 +645,18 @@ int dm_deepfm_train_forward_backward_csr_dev(dm_handle_t h, const int32_t *d_seq
  * the dense blocks, or the whole vector when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 - the same bytes
  * either way.  Rebuilds every copy the searches read and tells the clones: serving continues with the new weights. */
 int dm_deepfm_adam_step(dm_handle_t h, float grad_scale);
+/* LocalOptimizer.syncGradients (T/optim/LocalOptimizer.scala:164-187) minus the division, which dm_deepfm_adam_step(1 / N) folds in, over the
+ * communicator attached with dm_comm_attach: after any of the three steps above, every replica holds for every table
+ * row any rank reached ((0 + g_0) + g_1) + ... in rank order (ranks that did not reach the row are skipped) and the rank-ordered sum of the
+ * dense blocks, on BOTH transports: the fp32 sum of the ranks' local gradients bit for bit, no floating-point atomics.  One var-size
+ * all-gather of [row ids | gradient rows | dense blocks] through the path of dm_comm_all_gather_dev; the table never moves.  A rank that
+ * ran no step since its last Adam step (its sampler drew no rows) takes part with no rows and a zero dense part.  Collective: every rank
+ * calls it.  Ranks that train different shapes (num_index, padded embed size, seq_len) ALL return DM_ERR_STATE before any gradient
+ * moves.  Before any collective, with the handle left usable: DM_ERR_STATE without a communicator, without dm_deepfm_train_init, on a clone,
+ * on a DIN model, and for a second exchange with no forward/backward or Adam step in between (it would sum a sum).  A one-rank
+ * communicator: DM_OK, nothing moves.  dm_train_sync_stats reports what the call moved (host synchronisations: waits on the handle's
+ * stream). */
+int dm_deepfm_train_sync_gradients(dm_handle_t h);
 int dm_deepfm_train_param_count(dm_handle_t h, int64_t *n);             /* of the model's own (unpadded) layout */
 /* what: 0 weights (needs no training state), 1 gradient, 2 first moment, 3 second moment, in the model's own layout; n must be the
  * parameter count (DM_ERR_INVALID) */

@@ -4,7 +4,10 @@ host transport (RCCL refuses two ranks per device; same entry point and kernels,
 TDMTrainer steps (device-side negative sampling, sync, Adam) every replica must hold bit-identical weights, and they
 must equal a single worker that sees all W slices with the gradient formed in rank order.
 Prints one JSON line; the driver-side copy is kept as profiles/<round>_dp_train_check.json.
-  usage: python tools/dp_train_check.py [workers]"""
+  usage: python tools/dp_train_check.py [workers] [--deepfm]
+--deepfm: the same check through the DeepFM trainer (dm_deepfm_train_sync_gradients).  A DeepFM step REPLACES the
+gradient, so a single worker cannot accumulate the W slices; instead every worker also hands back its local and its exchanged gradient
+of every step, and the exchanged one must equal the float32 numpy sum of the local ones in rank order, bit for bit."""
 import json, multiprocessing as mp, os, socket, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,12 +26,46 @@ def data(world):
     return t, seqs, tgt
 
 
-def engine(t):
+def deepfm_weights():
+    rng = np.random.default_rng(5)
+    n = 8191 * 16 + 11 * 11 * 16 + 2 * 11 + 1
+    return (rng.standard_normal(n) * 0.05).astype(np.float32)
+
+
+def engine(t, deepfm=False):
     from dismember_amd import Engine
     e = Engine(0)
     e.load_tree(t["codes"], t["ids"], t["is_leaf"], int(t["max_level"])); e.load_id_maps(t["leaf_ids"], t["leaf_codes"])
+    if deepfm:
+        e.load_weights_deepfm(deepfm_weights(), 16, 10, 8191)
+        return e
     e.load_weights_din(np.load(os.path.join(GOLDEN, "din_f32.npy")) * np.float32(0.3), 16, 8191)
     return e
+
+
+def deepfm_worker(rank, world, port, q):
+    """TDMTrainer.step taken apart so that the gradients can be read: local step, exchange, Adam"""
+    from dismember_amd import sharding
+    from dismember_amd.comm import Comm
+    from dismember_amd.trainer import TDMTrainer
+    t, seqs, tgt = data(world)
+    eng = engine(t, deepfm=True)
+    comm = Comm(world, rank, "127.0.0.1", port, transport="host")
+    tr = TDMTrainer(eng, NEG, lr=1e-3, comm=comm, seed=77, sampler="device")
+    lo, hi = sharding.shard_range(len(seqs), rank, world)
+    losses, grads = [], []
+    for it in range(STEPS):
+        loss = eng.deepfm_train_step_sampled(seqs[lo:hi], tgt[lo:hi], NEG, 1, seed=77 + 1000003 * it + rank)
+        local = eng.deepfm_train_download("grad")
+        eng.deepfm_train_sync_gradients()
+        grads.append((local, eng.deepfm_train_download("grad")))
+        eng.deepfm_adam_step(1.0 / world)
+        losses.append(comm.allreduce(float(loss)) / world)
+    # ... and the trainer's own step on top, so that its wiring runs too
+    losses.append(float(tr.step(seqs[lo:hi], tgt[lo:hi])))
+    q.put((rank, losses, eng.deepfm_train_download("weights"), grads))
+    comm.barrier()
+    eng.close(); comm.close()
 
 
 def worker(rank, world, port, q):
@@ -47,15 +84,29 @@ def worker(rank, world, port, q):
 
 
 def main():
-    world = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+    args = [v for v in sys.argv[1:] if v != "--deepfm"]
+    deepfm = "--deepfm" in sys.argv[1:]
+    world = int(args[0]) if args else 2
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=deepfm_worker if deepfm else worker, args=(r, world, port, q)) for r in range(world)]
     [p.start() for p in procs]
     out = sorted((q.get(timeout=600) for _ in range(world)), key=lambda x: x[0])
     [p.join(120) for p in procs]
     w0 = out[0][2]
+    if deepfm:
+        exact = True
+        for it in range(STEPS):
+            want = np.zeros_like(out[0][3][it][0])
+            for r in range(world):
+                want = want + out[r][3][it][0]          # float32, rank order
+            exact = exact and all(np.array_equal(out[r][3][it][1], want) for r in range(world))
+        print(json.dumps({"workers": world, "steps": STEPS + 1, "scorer": "deepfm", "transport": "host (W processes on one GPU)",
+                          "replicas_bit_identical": bool(all(np.array_equal(w0, o[2]) for o in out[1:])),
+                          "exchange_equals_rank_ordered_numpy_sum": bool(exact), "losses_per_worker": [o[1] for o in out],
+                          "weights_changed": bool(not np.array_equal(w0, deepfm_weights())), "exit_codes": [p.exitcode for p in procs]}))
+        return
     rec = {"workers": world, "steps": STEPS, "transport": "host (W processes on one GPU)",
            "replicas_bit_identical": bool(all(np.array_equal(w0, o[2]) for o in out[1:])),
            "losses_per_worker": [o[1] for o in out],
