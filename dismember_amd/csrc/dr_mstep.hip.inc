@@ -150,8 +150,7 @@ static int64_t drm_chunk() {
 }
 
 // every refusal of the two entry points that needs neither the arrays' contents nor memory
-static int drm_check(dm_ctx *h, bool ptrs_ok, int64_t N, int C, const void *tp, const void *tpr, const void *tc) {
-  const char *who = "dm_dr_mstep_path_scores";
+static int drm_check(dm_ctx *h, bool ptrs_ok, int64_t N, int C, const void *tp, const void *tpr, const void *tc, const char *who = "dm_dr_mstep_path_scores") {
   dm_dr_state *s = h->dr;
   if (!s || !s->loaded) return fail(h, DM_ERR_STATE, std::string(who) + ": Deep-Retrieval model not loaded");
   if (C < 1 || C > 2048) return fail(h, DM_ERR_INVALID, std::string(who) + ": num_candidate_path must be in [1, 2048]");
@@ -272,8 +271,8 @@ static int drm_run(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int64_
 static int drm_run_any(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int64_t N, int C, int32_t *d_paths_all, DrmResult *res) {
   return h->dr->dtype == DM_F32 ? drm_run<float>(h, d_seq, d_tgt, N, C, d_paths_all, res) : drm_run<double>(h, d_seq, d_tgt, N, C, d_paths_all, res);
 }
-static int drm_short_cap(dm_ctx *h, int64_t cap, int64_t need) {
-  return fail(h, DM_ERR_INVALID, "dm_dr_mstep_path_scores: cap " + std::to_string(cap) + " is too small, " + std::to_string(need) + " entries are needed (out_total)");
+static int drm_short_cap(dm_ctx *h, int64_t cap, int64_t need, const char *who = "dm_dr_mstep_path_scores") {
+  return fail(h, DM_ERR_INVALID, std::string(who) + ": cap " + std::to_string(cap) + " is too small, " + std::to_string(need) + " entries are needed (out_total)");
 }
 
 int dm_dr_mstep_path_scores_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_targets, int64_t N, int num_candidate_path, int64_t cap, int64_t *d_out_item_off,

@@ -49,6 +49,9 @@ enum EvKind {
   // codes / scores / offsets, occurrences.  The searches of the chunks are EV_MAIN, as everywhere
   EV_DRM_PAIRS = 80, EV_DRM_SORT = 81, EV_DRM_HEADS = 82, EV_DRM_SEGSUM = 83, EV_DRM_SCORE_SORT = 84, EV_DRM_ITEM_SORT = 85, EV_DRM_CUT = 86, EV_DRM_EMIT = 87,
   EV_DRM_OCC = 88,
+  // its streaming mode (dr_mstep_stream.hip.inc), under the same switch: path codes of a chunk, the order of the samples by item (sort, runs,
+  // queue sort), the per-item fold, the compaction into the CSR
+  EV_DMS_CODES = 89, EV_DMS_ORDER = 90, EV_DMS_FOLD = 91, EV_DMS_EMIT = 92,
 };
 
 // the next pair of the handle's pool, recorded as `kind`

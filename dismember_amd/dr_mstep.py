@@ -3,7 +3,9 @@
 
 The expensive part — one beam search with `beam = numCandidatePath` per training sample (:143-147, :181-186) — is ONE
 batched `dm_dr_beam_search` call per chunk; per-item aggregation is a sort + segmented sum over 64-bit path codes, on the host
-(`batch_path_scores`) or without the candidates leaving the device (`batch_path_scores_dev`, `optimize(path_scores="device")`).  The greedy,
+(`batch_path_scores`) or without the candidates leaving the device (`batch_path_scores_dev`, `optimize(path_scores="device")`); the
+streaming mode's decayed running scores likewise (`streaming_path_scores` on the host, `streaming_path_scores_dev` /
+`optimize(train_mode="streaming", path_scores="device_streaming")` on the device).  The greedy,
 penalised path choice is inherently sequential over items (a shared path-size table), as in the reference, and stays on the host.
 Orders the reference takes from hash maps are fixed here: ties between equal path scores resolve to the smaller path code
 (ascending node tuple), items are visited in ascending id."""
@@ -103,6 +105,18 @@ def streaming_path_scores(engine, sequences, targets, num_candidate_path, decay_
     return scores
 
 
+def streaming_path_scores_dev(engine, sequences, targets, num_candidate_path, decay_factor=0.999, with_occurrence=False):
+    """streaming_path_scores on the device (Engine.dr_mstep_streaming_path_scores): search, the per-item fold in ascending
+    sample index and the cut at C without the candidates leaving the device.  -> the dict streaming_path_scores returns (and, with
+    with_occurrence, {item: number of samples})."""
+    off, codes, scores, occ = engine.dr_mstep_streaming_path_scores(sequences, targets, num_candidate_path, decay_factor)
+    hit = np.flatnonzero(occ)
+    out = {int(v): (codes[off[v]:off[v + 1]], scores[off[v]:off[v + 1]]) for v in hit}
+    if not with_occurrence:
+        return out
+    return out, dict(zip(hit.tolist(), occ[hit].tolist()))
+
+
 def penalty_func(path_size, poly_order):
     f = lambda s: math.pow(s, poly_order) / poly_order
     return f(path_size + 1) - f(path_size)
@@ -146,13 +160,22 @@ def assign_paths(item_path_scores, item_occurrence, all_items, num_iteration, nu
 def optimize(engine, sequences, targets, all_items, num_candidate_path, num_path_per_item, num_iteration=3, train_mode="batch",
              decay_factor=0.999, batch_size=8192, seed=0, penalty_factor=3e-6, penalty_poly_order=4, path_scores="host"):
     """CoordinateDescent.optimize(model, trainMode) -> item -> paths (internal ids).  path_scores="device" (batch mode only) aggregates the
-    candidates on the device (batch_path_scores_dev) and takes the item occurrences from the same call."""
+    candidates on the device (batch_path_scores_dev) and takes the item occurrences from the same call; path_scores="device_streaming"
+    (streaming mode only) does the same for the decayed running scores (streaming_path_scores_dev)."""
     K, D = engine.dr_dims["K"], engine.dr_dims["D"]
-    if path_scores not in ("host", "device"):
+    if path_scores not in ("host", "device", "device_streaming"):
         raise ValueError(path_scores)
+    if path_scores == "device_streaming":
+        if train_mode != "streaming":
+            raise ValueError("path_scores=\"device_streaming\" serves train_mode=\"streaming\" only")
+        sc, occ = streaming_path_scores_dev(engine, sequences, targets, num_candidate_path, decay_factor, with_occurrence=True)
+        return assign_paths(sc, occ, sorted(int(i) for i in all_items), num_iteration, num_path_per_item, K, D, seed,
+                            penalty_factor, penalty_poly_order)
     if path_scores == "device":
+        # two spellings, one per mode: tests/test_gpu_dr_mstep.py pins that "device" with train_mode="streaming" raises, so the streaming
+        # route is "device_streaming"; folding the two into one is left to whoever edits that test
         if train_mode != "batch":
-            raise ValueError("path_scores=\"device\" serves train_mode=\"batch\" only")
+            raise ValueError("path_scores=\"device\" serves train_mode=\"batch\" only (streaming: \"device_streaming\")")
         sc, occ = batch_path_scores_dev(engine, sequences, targets, num_candidate_path, with_occurrence=True)
         return assign_paths(sc, occ, sorted(int(i) for i in all_items), num_iteration, num_path_per_item, K, D, seed,
                             penalty_factor, penalty_poly_order)

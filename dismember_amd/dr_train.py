@@ -18,6 +18,9 @@ One E-step / M-step round on an engine that holds a Deep-Retrieval model (`Engin
                                   path_scores="device")                                # the candidates never leave the device
     trainer.set_item_paths(np.array([new_paths[i] for i in range(num_item)]))
 
+The streaming M-step (`cd.train_mode streaming`, configs/c5_dr_10m.conf) has its own device route: `train_mode="streaming",
+decay_factor=0.999, path_scores="device_streaming"` folds every item's decayed running scores on the device.
+
 The first search after a step rebuilds the search's derived copies of the weights; steps in between do not.
 
 Both halves, served end to end:

@@ -781,6 +781,44 @@ class Engine:
                                                       d_scores, d_occurrence, _p(total, N.i64p), d_trace[0], d_trace[1], d_trace[2]))
         return int(total[0])
 
+    # ---- Deep-Retrieval M-step, streaming mode: decayed running path scores
+    def dr_mstep_streaming_path_scores(self, seqs, targets, num_candidate_path, decay_factor=0.999, trace=False, cap=None):
+        """dm_dr_mstep_streaming_path_scores: the arguments and the result of dr_mstep_path_scores; item v's entries are its running list
+        after its last sample (streamingPathScore, folded in ascending sample index): descending by score, ties in ascending path code —
+        except for an item with one sample, which keeps that sample's beam as it is."""
+        d = self.dr_dims
+        seq = _i32(seqs).reshape(-1, d["L"])
+        tg = _i32(targets).reshape(-1)
+        assert len(seq) == len(tg)
+        n, c = len(seq), int(num_candidate_path)
+        if cap is None:
+            cap = min(n, d["num_item"]) * max(c, 0)
+        f64p = C.POINTER(C.c_double)
+        off = np.empty(d["num_item"] + 1, np.int64)
+        occ = np.empty(d["num_item"], np.int64)
+        codes = np.empty(max(cap, 1), np.int64)
+        scores = np.empty(max(cap, 1), np.float64)
+        total = np.zeros(1, np.int64)
+        tr = None
+        if trace:
+            tr = (np.empty((n, max(c, 0), d["D"]), np.int32), np.empty((n, max(c, 0)), np.float64), np.empty(n, np.int32))
+        self._chk(N.lib().dm_dr_mstep_streaming_path_scores(self._h, _p(seq, N.i32p), _p(tg, N.i32p), n, c, float(decay_factor), int(cap), _p(off, N.i64p),
+                                                            _p(codes, N.i64p), _p(scores, f64p), _p(occ, N.i64p), _p(total, N.i64p),
+                                                            _p(tr[0], N.i32p) if trace else None, _p(tr[1], f64p) if trace else None,
+                                                            _p(tr[2], N.i32p) if trace else None))
+        t = int(total[0])
+        out = (off, codes[:t].copy(), scores[:t].copy(), occ)
+        return out + tr if trace else out
+
+    def dr_mstep_streaming_path_scores_dev(self, d_seq, d_targets, n, num_candidate_path, cap, d_item_off, d_codes, d_scores, d_occurrence=None,
+                                           d_trace=(None, None, None), decay_factor=0.999):
+        """the same on device arrays (ids not range-checked) -> total"""
+        total = np.zeros(1, np.int64)
+        self._chk(N.lib().dm_dr_mstep_streaming_path_scores_dev(self._h, d_seq, d_targets, int(n), int(num_candidate_path), float(decay_factor), int(cap),
+                                                                d_item_off, d_codes, d_scores, d_occurrence, _p(total, N.i64p), d_trace[0], d_trace[1],
+                                                                d_trace[2]))
+        return int(total[0])
+
     # ---- Deep-Retrieval E-step: the layer model's training step (DESIGN.md §10)
     def dr_train_init(self, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
         o = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)

@@ -606,6 +606,26 @@ int dm_dr_mstep_path_scores_dev(dm_handle_t h, const int32_t *d_seq_ids, const i
                                 int64_t *d_out_occurrence, int64_t *out_total,
                                 int32_t *d_trace_paths, double *d_trace_probs, int32_t *d_trace_counts);
 
+/* ---- Deep-Retrieval M-step, streaming mode: decayed running path scores folded on the device ----
+ * CoordinateDescent.streamingPathScore (D/optim/CoordinateDescent.scala:162-212): one beam search with beam = num_candidate_path (C) per
+ * sample; per target item a running list of at most C (path code, score) entries, updated with the item's samples in ASCENDING SAMPLE
+ * INDEX.  The first sample's beam is the list as it stands.  Every later sample merges its beam into the list: with m = the smallest score
+ * of the list, a path in both scores decay_factor * old + new, a path of the beam only decay_factor * m + new, a path of the list only
+ * decay_factor * old; fp64, each product and each sum rounded on its own; the new list is the first C of the union by (score descending,
+ * path code ascending).  The reference's mini-batches do not enter the result.  Arguments, the CSR result, cap / out_total, the trace
+ * arrays, the chunked search and every refusal are those of dm_dr_mstep_path_scores; in addition decay_factor must be finite and in [0, 1]
+ * (DM_ERR_INVALID).  An item with one sample keeps that sample's beam in the beam's order; every other list is descending by score, equal
+ * scores in ascending path code.  The same inputs give the same bytes.  The handle stays usable after every refusal. */
+int dm_dr_mstep_streaming_path_scores(dm_handle_t h, const int32_t *seq_ids, const int32_t *targets, int64_t N, int num_candidate_path,
+                                      double decay_factor, int64_t cap, int64_t *out_item_off, int64_t *out_codes, double *out_scores,
+                                      int64_t *out_occurrence, int64_t *out_total,
+                                      int32_t *trace_paths, double *trace_probs, int32_t *trace_counts);
+/* the same with device arrays (ids are NOT range-checked); out_total stays a host pointer; returns when the results are in place */
+int dm_dr_mstep_streaming_path_scores_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_targets, int64_t N,
+                                          int num_candidate_path, double decay_factor, int64_t cap, int64_t *d_out_item_off,
+                                          int64_t *d_out_codes, double *d_out_scores, int64_t *d_out_occurrence, int64_t *out_total,
+                                          int32_t *d_trace_paths, double *d_trace_probs, int32_t *d_trace_counts);
+
 /* ---- DeepFM: one training step on the device ----
  * LocalOptimizer.trainBatch with the DeepFM graph (T/optim/LocalOptimizer.scala:139-162, useMask = false; T/model/DeepFM.scala:11-45;
  * S/nn/FM.scala:24-71, S/nn/Linear.scala, S/nn/BCECriterionWithLogits.scala:27-64 averaged over the batch; S/optim/Adam.scala:19-73).
