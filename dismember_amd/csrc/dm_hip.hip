@@ -1598,6 +1598,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "deepfm.hip.inc"
 #include "dfm_train.hip.inc"
 #include "dfm_train_grouped.hip.inc"
+#include "train_grouped_csr.hip.inc"
 #include "comm.hip.inc"
 #include "dfm_train_sync.hip.inc"
 #include "dfm_jtm.hip.inc"

@@ -56,11 +56,19 @@ __device__ __forceinline__ int32_t dm_sample_hist_code(const SampleParams &p, in
   const int32_t tt = (int32_t)((uint32_t)id - (uint32_t)p.non_leaf_offset);
   return tt > p.max_code ? -1 : tt;
 }
-// the CSR twin's histories: every target's, once, whether it yields rows or not
-__global__ void dm_sample_hist_kernel(SampleParams p, int32_t *seq_codes) {
+// the CSR twin's histories: every target's, once, whether it yields rows or not; umask (or null) [T]: the rowmask word dm_sample_kernel
+// gives the target's rows (bit j = position j is padding, 0 without use_mask)
+__global__ void dm_sample_hist_kernel(SampleParams p, int32_t *seq_codes, uint32_t *umask) {
   const int64_t n = p.T * p.L;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     seq_codes[i] = dm_sample_hist_code(p, p.seq_ids[i]);
+  if (!umask) return;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < p.T; t += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t w = 0;
+    if (p.use_mask)
+      for (int j = 0; j < p.L; j++) w |= (dm_sample_hist_code(p, p.seq_ids[t * p.L + j]) == -1 ? 1u : 0u) << j;
+    umask[t] = w;
+  }
 }
 
 // target ids -> codes and row counts (pathNodes of an unknown / padding target is empty: no rows)
@@ -260,10 +268,10 @@ static int sample_check(dm_ctx *h, int kind, int64_t T, int L, const int32_t *ne
 }
 
 // all request / output pointers are device pointers; *n_rows = rows produced (a host sync).  d_seq_codes / d_row_off (both or neither; then
-// d_seqs is null): the CSR form, histories [T][L] once per target and the plan's offsets [T + 1]
+// d_seqs is null): the CSR form, histories [T][L] once per target and the plan's offsets [T + 1]; d_umask (with them, or null): [T] mask words
 static int sample_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int64_t T, int L, const int32_t *neg_counts,
                       const dm_sample_opts *o, int32_t *d_codes, int32_t *d_seqs, uint32_t *d_rowmask, float *d_labels, int64_t cap,
-                      int64_t *n_rows, int32_t *d_seq_codes = nullptr, int64_t *d_row_off = nullptr) {
+                      int64_t *n_rows, int32_t *d_seq_codes = nullptr, int64_t *d_row_off = nullptr, uint32_t *d_umask = nullptr) {
   const int nl = h->max_level + 1;
   std::vector<int32_t> neg(nl), lvl_off(nl + 1, 0);
   int negmax = 1;
@@ -294,7 +302,7 @@ static int sample_dev(dm_ctx *h, const int32_t *d_seq, const int32_t *d_tgt, int
     const size_t lds = (size_t)4 * (negmax + 64) * 4;
     if (blocks > 0) LAUNCHCHK(h, dm_sample_kernel, dim3((unsigned)blocks), dim3(256), lds, p);
     if (d_seq_codes) {
-      LAUNCHCHK(h, dm_sample_hist_kernel, dim3((unsigned)std::min<int64_t>((T * L + 255) / 256, 1024)), dim3(256), 0, p, d_seq_codes);
+      LAUNCHCHK(h, dm_sample_hist_kernel, dim3((unsigned)std::min<int64_t>((T * L + 255) / 256, 1024)), dim3(256), 0, p, d_seq_codes, d_umask);
       HIPCHK(h, hipMemcpyAsync(d_row_off, p.row_off, (size_t)(T + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
     }
     long long total = 0;
@@ -321,6 +329,21 @@ int dm_tdm_sample_train_batch_dev(dm_handle_t h, const int32_t *d_seq_item_ids, 
     return fail(h, DM_ERR_INVALID, "dm_tdm_sample_train_batch_dev: output buffers too small");
   HIPCHK(h, hipSetDevice(h->device));
   return sample_dev(h, d_seq_item_ids, d_target_item_ids, T, L, neg_counts, opts, d_codes, d_seqs, d_rowmask, d_labels, cap, n_rows);
+}
+
+int dm_tdm_sample_train_batch_csr_dev(dm_handle_t h, const int32_t *d_seq_item_ids, const int32_t *d_target_item_ids, int64_t T, int L,
+                                      const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *d_codes,
+                                      int32_t *d_seq_codes, uint32_t *d_umask, int64_t *d_row_off, float *d_labels, int64_t cap, int64_t *n_rows) {
+  if (!h || !n_rows) return DM_ERR_INVALID;
+  int64_t per = 0;
+  int rc = sample_check(h, DM_KIND_DIN, T, L, neg_counts, n_counts, opts, &per);
+  if (rc != DM_OK) return rc;
+  *n_rows = T * per;
+  if (!d_codes) return DM_OK;                        // size query: an upper bound, the row twin's
+  if (!d_seq_item_ids || !d_target_item_ids || !d_seq_codes || !d_umask || !d_row_off || !d_labels || cap < T * per)
+    return fail(h, DM_ERR_INVALID, "dm_tdm_sample_train_batch_csr_dev: output buffers too small");
+  HIPCHK(h, hipSetDevice(h->device));
+  return sample_dev(h, d_seq_item_ids, d_target_item_ids, T, L, neg_counts, opts, d_codes, nullptr, nullptr, d_labels, cap, n_rows, d_seq_codes, d_row_off, d_umask);
 }
 
 int dm_tdm_make_train_batch(dm_handle_t h, const int32_t *seq_item_ids, const int32_t *target_item_ids, int64_t T, int L,

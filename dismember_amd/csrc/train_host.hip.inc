@@ -157,6 +157,26 @@ static int rows_fwd64(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, 
   return dispatch_E(h, E, "unsupported embed size", [&](auto e) { return rows_fwd64_E<decltype(e)::value>(h, p); });
 }
 
+// The touched-row list keeps growing until the next Adam step (gradients accumulate across calls): keep a host-side upper bound of its
+// length and grow the list, PRESERVING its entries, before a call that may add `more` rows could overflow it.
+static int train_touch_reserve(dm_ctx *h, size_t more) {
+  h->touch_ub += more;
+  if (h->touch_ub > (size_t)h->num_index) h->touch_ub = (size_t)h->num_index;
+  if (h->touch_ub > h->touch_cap) {
+    size_t cap = h->touch_cap * 2 > h->touch_ub ? h->touch_cap * 2 : h->touch_ub;
+    if (cap > (size_t)h->num_index) cap = (size_t)h->num_index;
+    int32_t *nl = nullptr;
+    ALLOC(h, nl, cap * 4);
+    if (h->d_touch_list && h->touch_cap)
+      HIPCHK(h, hipMemcpyAsync(nl, h->d_touch_list, h->touch_cap * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    dm_release(h->d_touch_list);
+    h->d_touch_list = nl;
+    h->touch_cap = cap;
+  }
+  return DM_OK;
+}
+
 // all pointers device; accumulates this batch's gradients (mean BCE over the B rows) into the handle's gradient
 static int train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs, const unsigned *d_rowmask,
                         const float *d_labels, int64_t B, int L, float *loss) {
@@ -165,24 +185,7 @@ static int train_fb_dev(dm_ctx *h, const int32_t *d_codes, const int32_t *d_seqs
   const size_t vec = (size_t)B * E * es;
   int rc = ensure_ws(h, 4 * vec + (size_t)B * es);
   if (rc != DM_OK) return rc;
-  {
-    // The touched-row list keeps growing until the next Adam step (gradients accumulate across calls): keep a host-side
-    // upper bound of its length and grow the list, PRESERVING its entries, before a call could overflow it.
-    h->touch_ub += (size_t)B * (1 + L);
-    if (h->touch_ub > (size_t)h->num_index) h->touch_ub = (size_t)h->num_index;
-    if (h->touch_ub > h->touch_cap) {
-      size_t cap = h->touch_cap * 2 > h->touch_ub ? h->touch_cap * 2 : h->touch_ub;
-      if (cap > (size_t)h->num_index) cap = (size_t)h->num_index;
-      int32_t *nl = nullptr;
-      ALLOC(h, nl, cap * 4);
-      if (h->d_touch_list && h->touch_cap)
-        HIPCHK(h, hipMemcpyAsync(nl, h->d_touch_list, h->touch_cap * 4, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      dm_release(h->d_touch_list);
-      h->d_touch_list = nl;
-      h->touch_cap = cap;
-    }
-  }
+  if ((rc = train_touch_reserve(h, (size_t)B * (1 + L))) != DM_OK) return rc;
   HIPCHK(h, hipMemsetAsync(h->d_loss, 0, 16, h->stream));
   rc = h->dtype == DM_F64 ? train_fb_launch<double>(h, d_codes, d_seqs, d_rowmask, d_labels, B, L)
                           : train_fb_launch<float>(h, d_codes, d_seqs, d_rowmask, d_labels, B, L);

@@ -517,10 +517,15 @@ class Engine:
         return codes[:R], seqs[:R], mask[:R], lab[:R]
 
     def train_step_sampled(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, use_mask=True, with_prob=False,
-                           tolerance=20):
+                           tolerance=20, grouped=False):
         """convertBatch + trainBatch with the rows resident in HBM: targets and histories are uploaded (40 B per target),
         dm_tdm_sample_train_batch_dev expands them on the device straight into the buffers of
-        dm_train_forward_backward_dev.  Returns the mean BCE loss of the expanded rows."""
+        dm_train_forward_backward_dev.  Returns the mean BCE loss of the expanded rows.
+        grouped (f32 models, L <= 16): dm_tdm_sample_train_batch_csr_dev into the buffers of dm_train_forward_backward_csr_dev instead
+         — the same rows from the same seed, every target's history and mask written and read once; no [R][L] row
+        histories are carved."""
+        if grouped:
+            return self._train_step_sampled_csr(seq_item_ids, target_item_ids, neg_counts, start_level, seed, use_mask, with_prob, tolerance)
         seq = _i32(seq_item_ids)
         tgt = _i32(target_item_ids).ravel()
         T, L = seq.shape
@@ -550,6 +555,104 @@ class Engine:
             return 0.0
         loss = C.c_float(0)
         self._chk(N.lib().dm_train_forward_backward_dev(self._h, d_codes, d_seqs, d_mask, d_lab, n.value, L, C.byref(loss)))
+        return loss.value
+
+    def _sample_csr_carve(self, T, L, R):
+        """the sampler's CSR buffers inside the engine's grow-only sampling buffer: ids, targets, codes, seq codes, masks, offsets, labels"""
+        al = lambda v: (v + 255) & ~255
+        need = 2 * al(T * L * 4) + 2 * al(T * 4) + 2 * al(R * 4) + al((T + 1) * 8)        # the seven sub-buffers as carved below: no [R][L]
+        if getattr(self, "_samp_bytes", 0) < need:
+            if getattr(self, "_samp_buf", None):
+                self.dev_free(self._samp_buf)
+            self._samp_buf, self._samp_bytes = self.dev_alloc(need + need // 2), need + need // 2
+        base = self._samp_buf.value
+        out = []
+        for nbytes in (T * L * 4, T * 4, R * 4, T * L * 4, T * 4, (T + 1) * 8, R * 4):
+            out.append(C.c_void_p(base)); base += al(nbytes)
+        return out
+
+    def _sample_csr_dev(self, seq_item_ids, target_item_ids, neg_counts, start_level, seed, use_mask, with_prob, tolerance):
+        """dm_tdm_sample_train_batch_csr_dev into the sampling buffer -> (T, L, R, d_codes, d_sc, d_um, d_off, d_lab)"""
+        seq = _i32(seq_item_ids)
+        tgt = _i32(target_item_ids).ravel()
+        T, L = seq.shape
+        neg = _i32(neg_counts)
+        o = N.SampleOpts(int(start_level), int(bool(with_prob)), int(tolerance), int(bool(use_mask)), int(seed))
+        n = C.c_int64(0)
+        self._chk(N.lib().dm_tdm_sample_train_batch_csr_dev(self._h, None, None, T, L, _p(neg, N.i32p), neg.size, C.byref(o), None, None, None,
+                                                            None, None, 0, C.byref(n)))
+        R = max(n.value, 1)
+        d_seq, d_tgt, d_codes, d_sc, d_um, d_off, d_lab = self._sample_csr_carve(T, L, R)
+        if T:
+            self.h2d(d_seq, seq); self.h2d(d_tgt, tgt)
+        self._chk(N.lib().dm_tdm_sample_train_batch_csr_dev(self._h, d_seq, d_tgt, T, L, _p(neg, N.i32p), neg.size, C.byref(o), d_codes, d_sc,
+                                                            d_um, d_off, d_lab, R, C.byref(n)))
+        return T, L, n.value, d_codes, d_sc, d_um, d_off, d_lab
+
+    def _train_step_sampled_csr(self, seq_item_ids, target_item_ids, neg_counts, start_level, seed, use_mask, with_prob, tolerance):
+        T, L, R, d_codes, d_sc, d_um, d_off, d_lab = self._sample_csr_dev(seq_item_ids, target_item_ids, neg_counts, start_level, seed,
+                                                                           use_mask, with_prob, tolerance)
+        if R == 0:
+            return 0.0
+        return self.train_forward_backward_csr_dev(d_sc, d_um, d_off, d_codes, d_lab, T, R, L)
+
+    def sample_train_batch_csr(self, seq_item_ids, target_item_ids, neg_counts, start_level=1, seed=0, use_mask=True, with_prob=False,
+                               tolerance=20):
+        """dm_tdm_sample_train_batch_csr_dev, downloaded (for the tests): (codes [R], labels [R], seq_codes [T, L], user_mask [T],
+        row_off [T + 1])."""
+        T, L, R, d_codes, d_sc, d_um, d_off, d_lab = self._sample_csr_dev(seq_item_ids, target_item_ids, neg_counts, start_level, seed,
+                                                                           use_mask, with_prob, tolerance)
+        codes = np.empty(R, np.int32); lab = np.empty(R, np.float32); sc = np.empty((T, L), np.int32)
+        um = np.empty(T, np.uint32); off = np.empty(T + 1, np.int64)
+        if R:
+            self.d2h(codes, d_codes); self.d2h(lab, d_lab)
+        self.d2h(off, d_off)
+        if T:
+            self.d2h(sc, d_sc); self.d2h(um, d_um)
+        return codes, lab, sc, um, off
+
+    def train_forward_backward_csr(self, seq_codes, user_mask, row_off, codes, labels):
+        """One forward/backward of an f32 DIN model over a ragged user-grouped batch (dm_train_forward_backward_csr_dev):
+        seq_codes [U][L], user_mask [U] (bit j: position j masked) or None, row_off [U + 1] (int64), codes / labels [B] — rows
+        row_off[u] .. row_off[u + 1] are user u's and share its history and mask; a user may have none.  ADDS to the gradient, like
+        train_forward_backward.  Checks the offsets here (ValueError), uploads and calls the device entry, which checks them again on
+        the device (ids are not range-checked: one outside [0, num_index) reads as -1); -> the mean loss."""
+        seq = _i32(seq_codes)
+        U, L = seq.shape if seq.ndim == 2 else (0, 1)
+        off = np.ascontiguousarray(row_off, np.int64).ravel()
+        codes = _i32(codes).ravel()
+        B = codes.size
+        lab = np.ascontiguousarray(labels, np.float32).ravel()
+        um = None if user_mask is None else np.ascontiguousarray(user_mask, np.uint32).ravel()
+        if off.size != U + 1 or lab.size != B or (um is not None and um.size != U):
+            raise ValueError("train_forward_backward_csr: row_off must hold U + 1 offsets, user_mask U words and labels one value per row")
+        if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != B:
+            bad = 0 if off[0] != 0 else int(np.flatnonzero(np.diff(off) < 0)[0]) if (np.diff(off) < 0).any() else U
+            raise ValueError("train_forward_backward_csr: row_off must start at 0, never decrease and end at B = %d "
+                             "(first offending user %d)" % (B, bad))
+        al = lambda v: (v + 255) & ~255
+        buf = self.dev_alloc(al(U * L * 4) + al(U * 4) + al((U + 1) * 8) + 2 * al(B * 4) + 256)
+        try:
+            d_seq = C.c_void_p(buf.value)
+            d_um = C.c_void_p(d_seq.value + al(U * L * 4))
+            d_off = C.c_void_p(d_um.value + al(U * 4))
+            d_codes = C.c_void_p(d_off.value + al((U + 1) * 8))
+            d_lab = C.c_void_p(d_codes.value + al(B * 4))
+            if U:
+                self.h2d(d_seq, seq); self.h2d(d_off, off)
+                if um is not None:
+                    self.h2d(d_um, um)
+            if B:
+                self.h2d(d_codes, codes); self.h2d(d_lab, lab)
+            return self.train_forward_backward_csr_dev(d_seq, d_um if um is not None else None, d_off, d_codes, d_lab, U, B, L)
+        finally:
+            self.dev_free(buf)
+
+    def train_forward_backward_csr_dev(self, d_seq_codes, d_user_mask, d_row_off, d_codes, d_labels, U, B, L):
+        """the same on device arrays: d_seq_codes [U][L], d_user_mask [U] or None, d_row_off [U + 1] int64, d_codes / d_labels [B] -> the mean loss"""
+        loss = C.c_float(0)
+        self._chk(N.lib().dm_train_forward_backward_csr_dev(self._h, d_seq_codes, d_user_mask, d_row_off, d_codes, d_labels, int(U), int(B), int(L),
+                                                            C.byref(loss)))
         return loss.value
 
     def train_forward_backward_grouped(self, seq_codes, user_mask, codes, labels):
@@ -1241,7 +1344,8 @@ class Engine:
         80 = pairs of a chunk, 81 = the (item, path) sort, 82 = segment heads, 83 = segment sums, 84 = sort by score, 85 = sort by item,
         86 = the cut at C, 87 = codes / scores / offsets, 88 = occurrences; under DM_DFM_TIME_LAUNCHES=1 the DeepFM training step
         (70 .. 76) and its gradient exchange across ranks: 77 = this rank's unique rows and block, 78 = the rank-ordered sums after
-        the all-gather"""
+        the all-gather; under DM_TRAIN_TIME_LAUNCHES=1 the ragged user-grouped DIN training step: 56 = per-user set-up, 57 = rows kernel,
+        58 = per-user backward, 59 = dense gradients (column sums, three products and their slab sums), 68 = table gradient"""
         n, ms = C.c_int(0), C.c_double(0)
         self._chk(N.lib().dm_kernel_timing_get_kind(self._h, int(kind), C.byref(n), C.byref(ms)))
         return n.value, ms.value

@@ -124,6 +124,7 @@ def tdm_train_deep_model(conf_path, quiet=True, engine=None, seed=2024, max_iter
     start = p["start_sample_level"]
     per = int(sum(1 + int(neg[l]) for l in range(start, depth + 1)))                # rows one target expands to (MiniBatch.scala:23-38)
     T = max(1, p["total_batch_size"] // per)                                       # expandBatch = true
+    # (the row step, unless DM_DFM_TRAIN_GROUPED=1 / DM_DIN_TRAIN_GROUPED=1 asks the trainer for a model's ragged user-grouped step)
     tr = TDMTrainer(eng, neg, start_level=start, use_mask=p["use_mask"], lr=p["learning_rate"], seed=seed,
                     with_prob=p["sample_with_probability"], tolerance=p["sample_tolerance"])
     rng = np.random.default_rng(seed)

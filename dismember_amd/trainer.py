@@ -27,16 +27,24 @@ class TDMTrainer:
     grouped (DeepFM with the device sampler only; a DIN engine ignores it, the host sampler keeps the row step): True trains with the
     ragged user-grouped step (Engine.deepfm_train_step_sampled(grouped=True): a target's history is read once, not once per row;
     other summation orders than the row step's, so not its bytes), False with the row step, None reads DM_DFM_TRAIN_GROUPED ("1" = on)
-    once, here."""
+    once, here.
+    din_grouped (an f32 DIN engine with the device sampler only; anything else keeps the row step, decided here): True trains with the
+    ragged user-grouped DIN step (Engine.train_step_sampled(grouped=True), DESIGN.md §21: deterministic, a target's history read once,
+    the mask honoured), False with the row step, None reads DM_DIN_TRAIN_GROUPED ("1" = on) once, here.  A batch whose histories are
+    longer than 16 positions takes the row step."""
 
     def __init__(self, engine, neg_counts, start_level=1, use_mask=True, lr=1e-3, comm=None, seed=0, sampler="device",
-                 with_prob=False, tolerance=20, grouped=None):
+                 with_prob=False, tolerance=20, grouped=None, din_grouped=None):
         self.e, self.neg, self.start, self.use_mask = engine, np.asarray(neg_counts, np.int32), start_level, use_mask
         self.comm, self.seed, self.it, self.sampler, self.with_prob = comm, seed, 0, sampler, bool(with_prob)
         self.tolerance = int(tolerance)                   # model.sample_tolerance (NegativeSampler.scala:116-145)
         self.sync_s, self.sync_calls = 0.0, 0             # wall time spent in the gradient exchange (bench.py reports it)
         self.deepfm = engine.scorer == "deepfm"
         self.grouped = (os.environ.get("DM_DFM_TRAIN_GROUPED") == "1") if grouped is None else bool(grouped)
+        want_din = (os.environ.get("DM_DIN_TRAIN_GROUPED") == "1") if din_grouped is None else bool(din_grouped)
+        # True: the steps MAY take the grouped DIN route (engine, dtype and sampler allow it); a batch whose histories are longer than 16
+        # positions still takes the row step, which only step() can see
+        self.din_grouped = bool(want_din and not self.deepfm and sampler == "device" and np.dtype(engine.dtype) == np.float32)
         if self.deepfm:
             self.use_mask = False
             engine.deepfm_train_init(lr=lr)
@@ -72,7 +80,8 @@ class TDMTrainer:
             return loss
         if self.sampler == "device":
             loss = self.e.train_step_sampled(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
-                                             use_mask=self.use_mask, with_prob=self.with_prob, tolerance=self.tolerance)
+                                             use_mask=self.use_mask, with_prob=self.with_prob, tolerance=self.tolerance,
+                                             grouped=self.din_grouped and np.asarray(seq_item_ids).shape[-1] <= 16)
         else:
             codes, seqs, mask, y = self.e.make_train_batch(seq_item_ids, target_item_ids, self.neg, self.start, seed=seed,
                                                             use_mask=self.use_mask, with_prob=self.with_prob, tolerance=self.tolerance)

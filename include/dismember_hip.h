@@ -512,6 +512,27 @@ int dm_train_forward_backward_dev(dm_handle_t h, const int32_t *d_codes, const i
  * kernels (train_grouped_f64.hip.inc), anything else is expanded to plain rows.  Ids are not range-checked. */
 int dm_train_forward_backward_grouped_dev(dm_handle_t h, const int32_t *d_seq_codes, const uint32_t *d_user_mask, const int32_t *d_codes,
                                           const float *d_labels, int64_t U, int rows_per_user, int L, float *loss);
+/* the DIN step of an f32 model on a ragged user-grouped batch (T/dataset/MiniBatch.scala:129-147 replicates one
+ * history over a target's sampled nodes, T/optim/LocalOptimizer.scala:139-162 is the step): rows d_row_off[u] .. d_row_off[u + 1] of
+ * d_codes / d_labels [B] belong to user u and read d_seq_codes[u] [L] with the mask word d_umask[u] (bit j = position j masked, as
+ * dm_train_forward_backward_dev's rowmask; d_umask may be NULL); a user may have no rows.  ADDS the batch's gradient (mean BCE over the B
+ * rows) into the handle's gradient like dm_train_forward_backward_dev, with which it may be mixed before one dm_adam_step; *loss (host, or
+ * NULL) and dm_train_last_loss give the loss.  No floating-point atomics: the same batch gives the same bytes, whatever the grid
+ * (DM_DIN_TRAIN_GRID=n forces one).  The offsets are validated on the device before anything is read through them or added to the
+ * gradient: d_row_off[0] == 0, non-decreasing, d_row_off[U] == B, else DM_ERR_INVALID naming the first offending user.  Device arrays, ids
+ * NOT range-checked (an id outside [0, num_index) is read as -1).  U <= 0, B <= 0, a null array other than d_umask, L outside 1 .. 32:
+ * DM_ERR_INVALID; L = 17 .. 32 (histories longer than 16 keep the row step), an f64 model (it keeps dm_train_forward_backward_grouped_dev),
+ * B > 4 194 240, U > 2 097 120 or B + U L >= 2^31: DM_ERR_UNSUPPORTED; no weights / no dm_train_init: DM_ERR_STATE. */
+int dm_train_forward_backward_csr_dev(dm_handle_t h, const int32_t *d_seq_codes, const uint32_t *d_umask, const int64_t *d_row_off, const int32_t *d_codes,
+                                      const float *d_labels, int64_t U, int64_t B, int L, float *loss);
+/* dm_tdm_sample_train_batch_dev in the form dm_train_forward_backward_csr_dev reads (NegativeSampler.scala:76-158, MiniBatch.scala:129-147):
+ * the same d_codes / d_labels bytes and row order from the same seed and options, d_seq_codes [T][L] = every target's history as codes,
+ * written once per target (also for a target that yields no rows), d_umask [T] = the rowmask word the row sampler gives the target's rows
+ * (0 when opts->use_mask is 0), d_row_off [T + 1] = the first row of every target.  No [cap][L] histories are written.  Size query
+ * (d_codes == NULL), checks and refusals: the row twin's. */
+int dm_tdm_sample_train_batch_csr_dev(dm_handle_t h, const int32_t *d_seq_item_ids, const int32_t *d_target_item_ids, int64_t T, int L,
+                                      const int32_t *neg_counts, int n_counts, const dm_sample_opts *opts, int32_t *d_codes,
+                                      int32_t *d_seq_codes, uint32_t *d_umask, int64_t *d_row_off, float *d_labels, int64_t cap, int64_t *n_rows);
 int dm_memcpy_d2d(dm_handle_t h, void *dst, const void *src, size_t bytes);
 
 /* ---- device-resident variants (bench: inputs already in HBM when the clock starts) ---- */

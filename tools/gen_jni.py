@@ -125,6 +125,8 @@ EXTENTS = {
     "dm_tdm_make_train_batch": {"seq_item_ids": "T * L", "target_item_ids": "T", "neg_counts": "n_counts", "out_codes": "cap",
                                 "out_seqs": "cap * L", "out_rowmask": "cap", "out_labels": "cap", "n_rows": "1"},
     "dm_tdm_sample_train_batch_dev": {"neg_counts": "n_counts", "n_rows": "1"},
+    "dm_tdm_sample_train_batch_csr_dev": {"neg_counts": "n_counts", "n_rows": "1"},
+    "dm_train_forward_backward_csr_dev": {"loss": "1"},
     "dm_deepfm_train_forward_backward": {"codes": "B", "seqs": "B * L", "labels": "B", "out_loss": "1"},
     "dm_deepfm_train_forward_backward_dev": {"out_loss": "1"},
     "dm_deepfm_train_forward_backward_grouped_dev": {"out_loss": "1"},
