@@ -91,6 +91,7 @@ SIGNATURES = {
                                                            C.POINTER(C.c_double)]),
     "dm_deepfm_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
     "dm_deepfm_train_sync_gradients": (C.c_int, [C.c_void_p]),
+    "dm_dr_train_sync_gradients": (C.c_int, [C.c_void_p]),
     "dm_deepfm_train_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dm_deepfm_train_download": (C.c_int, [C.c_void_p, C.c_int, f32p, C.c_int64]),
     "dm_deepfm_make_train_batch": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, i32p, C.c_int, C.POINTER(SampleOpts),

@@ -17,7 +17,7 @@ struct TrainVec {
   dm_adam_opts opts{};
   int t = 0;
   DevGrow prev;                                          // the sorted destination rows of the last batch (zeroed by the next); DIN: unused.
-                                                         // After dm_deepfm_train_sync_gradients: every rank's unique rows, rank after rank (a
+                                                         // After a gradient exchange (rows_sync): every rank's unique rows, rank after rank (a
                                                          // union with repeats, sorted only inside a rank) - enough for drt_seg_rows_kernel<T, true>,
                                                          // which clears at every change of key, and clearing a row twice changes nothing
   int64_t prev_m = 0;

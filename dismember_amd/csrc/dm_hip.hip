@@ -1600,7 +1600,9 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "dfm_train_grouped.hip.inc"
 #include "train_grouped_csr.hip.inc"
 #include "comm.hip.inc"
+#include "rows_sync.hip.inc"
 #include "dfm_train_sync.hip.inc"
+#include "dr_train_sync.hip.inc"
 #include "dfm_jtm.hip.inc"
 #include "jtm_sharded.hip.inc"
 #include "train_grouped_host.hip.inc"

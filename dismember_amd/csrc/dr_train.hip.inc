@@ -27,13 +27,15 @@
 struct dm_dr_train {
   TrainVec vec;              // over d_par: [layer_emb ; W_0 ; b_0 ; ...], rows = the embedding table's
   DevGrow ws, io;
+  DevGrow sync;                              // staging of dm_dr_train_sync_gradients (dr_train_sync.hip.inc): all ranks' blocks, their tails
+  bool exchanged = false;                    // vec.grad holds the sum over ranks: until the next forward/backward or Adam step
 };
 
 static void dr_train_release(dm_dr_state *s) {
   dm_dr_train *t = s->tr;
   if (!t) return;
   t->vec.release();
-  for (DevGrow *g : {&t->ws, &t->io}) g->release();
+  for (DevGrow *g : {&t->ws, &t->io, &t->sync}) g->release();
   delete t;
   s->tr = nullptr;
 }
@@ -359,7 +361,10 @@ static int dr_train_fb_dev_t(dm_ctx *h, const int32_t *d_seq, const int32_t *d_p
   T *Z = ar.ptr<T>(o_z), *dX = ar.ptr<T>(o_dx), *part = ar.ptr<T>(o_part);
   T *grad = (T *)t->vec.grad;
   if (s->wseq_stale && (rc = dr_refresh_wseq<T>(h, s)) != DM_OK) return rc;
-  // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below)
+  // ---- zeroGradParameters: the rows the last batch reached (the dense blocks are overwritten below).  After a gradient exchange `prev`
+  // is the concatenation of every rank's rows, sorted only inside a rank: the kernel clears at every change of key, so a row may be
+  // cleared more than once, which changes nothing
+  t->exchanged = false;
   if (t->vec.prev_m > 0) {
     if ((rc = LAUNCH(h, (drt_seg_rows_kernel<T, true>), dim3(drt_blocks(h, t->vec.prev_m, 4)), dim3(256), 0, (const unsigned long long *)t->vec.prev.p, nullptr,
                      t->vec.prev_m, NR, nullptr, E, grad)) != DM_OK) return rc;
@@ -484,6 +489,7 @@ int dm_dr_adam_step(dm_handle_t h, float grad_scale) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const AdamPlan plan = t->vec.plan_step(act);
   s->derived_stale = true; s->wseq_stale = true;      // before the first launch: a step that fails half-way has still moved weights
+  t->exchanged = false;
   rc = timed(h, EV_DRT_ADAM, dr_time_launches(), [&] { return adam_step(h, t->vec, plan, s->d_par, s->dtype == DM_F64, false, grad_scale, false, 1024); });
   if (rc == DM_OK) t->vec.forget();                // the step zeroed every gradient it visited, and it visited every row a batch has reached
   return rc;

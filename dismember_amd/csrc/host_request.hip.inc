@@ -43,6 +43,8 @@ enum EvKind {
   // its gradient exchange across ranks (dfm_train_sync.hip.inc): this rank's unique rows and its block; after the all-gather, the tails'
   // and the rows' rank-ordered sums with their bookkeeping
   EV_DFT_SYNC_PACK = 77, EV_DFT_SYNC_SUM = 78,
+  // the Deep-Retrieval layer model's gradient exchange (dr_train_sync.hip.inc) under DM_DR_TIME_LAUNCHES=1: the same two brackets
+  EV_DRT_SYNC_PACK = 79, EV_DRT_SYNC_SUM = 93,
   EV_DRR_FWD = 60, EV_DRR_SAMPLE = 61, EV_DRR_SOFTMAX = 62, EV_DRR_SMGRAD = 63, EV_DRR_DX = 64, EV_DRR_DW = 65, EV_DRR_EMB = 66, EV_DRR_ADAM = 67,
   // the Deep-Retrieval M-step's path scores under DM_DR_TIME_LAUNCHES=1 (dr_mstep.hip.inc): pairs of a chunk, the (item, path) sort, segment
   // heads (flags + compaction), segment sums, the sort by score, the sort by item (with its key kernel), the cut at C (flags + compaction),

@@ -23,6 +23,12 @@ decay_factor=0.999, path_scores="device_streaming"` folds every item's decayed r
 
 The first search after a step rebuilds the search's derived copies of the weights; steps in between do not.
 
+Data-parallel: every rank holds a replica and passes the SAME global batch to `step`; the trainer slices it as
+LocalOptimizer.trainLayerBatch does, exchanges the layer model's gradients (`Engine.dr_train_sync_gradients`) and steps with 1 / P:
+
+    trainer = DRTrainer(engine, item_paths, lr=1e-3, comm=Comm.from_env())
+    trainer.step(seqs, targets)                                  # the mean loss over the workers, the same on every rank
+
 Both halves, served end to end:
 
     trainer = DRTrainer(engine, item_paths, lr=1e-3, rerank=True, num_sampled=20, seed=1)
@@ -64,6 +70,13 @@ def expand_batch(seqs, targets, item_paths):
     return np.repeat(seqs, J, axis=0), np.ascontiguousarray(item_paths[tg].reshape(len(tg) * J, -1), np.int32)
 
 
+def layer_slices(B, W):
+    """LocalOptimizer.trainLayerBatch (LocalOptimizer.scala:135-166): how a mini-batch of B samples is split over W workers ->
+    ([(offset, length)] per worker, P = the workers that get a sample: W, or B when B < W)"""
+    task, extra = B // W, B % W
+    return [(i * task + min(i, extra), task + (1 if i < extra else 0)) for i in range(W)], (extra if task == 0 else W)
+
+
 def init_rerank_weights(num_item, L, E, rng, dtype=np.float64):
     """The five rerank arrays as the reference's modules initialise them: Embedding and Linear weights and softmaxWeights N(0, 0.05)
     (scalann nn/Embedding.scala:20, nn/Linear.scala:12, RerankModel.scala:15), the Linear bias and softmaxBiases zero (Linear.scala:13,
@@ -93,11 +106,21 @@ class DRTrainer:
     on the device from `seed`; accumulate=True is the reference's never-cleared softmax-table gradient, False clears it per
     batch; rerank_epochs: the reference's reRankStoppingEpoch — the rerank step runs while `epoch` (1-based, advanced by next_epoch())
     is <= rerank_epochs (None: always).  `rerank_losses` collects its loss per step (NaN once stopped).  The rerank optimizer takes the
-    layer optimizer's options (one learning rate in the reference's conf); its softmax tables take the criterion's own (eps 1e-7, no decay)."""
+    layer optimizer's options (one learning rate in the reference's conf); its softmax tables take the criterion's own (eps 1e-7, no decay).
+
+    comm (a dismember_amd.comm.Comm, None: one worker): data-parallel training of the LAYER model.  Every rank passes the same global
+    (seqs, targets) to step(); rank i trains its slice (layer_slices), the gradients are exchanged (Engine.dr_train_sync_gradients: the
+    rank-ordered sum, so the replicas stay bit-identical) and the Adam step divides by P, the number of ranks that had a sample.  step()
+    returns the mean of those ranks' losses (LocalOptimizer.scala:164-165).  The RERANK model is not split: as in the reference every
+    step trains it on the whole batch, here on every rank with the same seed — deterministic step and sampler keep those replicas
+    identical too, and this half does not get faster with more ranks.  All ranks must pass the same seed (ValueError otherwise).
+    sync_s / sync_calls: wall time spent in the exchange and the number of exchanges."""
 
     def __init__(self, engine, item_paths, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8, rerank=False, num_sampled=None, seed=0,
-                 accumulate=True, rerank_epochs=None):
+                 accumulate=True, rerank_epochs=None, comm=None):
         self.engine = engine
+        self.comm = comm
+        self.sync_s, self.sync_calls = 0.0, 0
         self.set_item_paths(item_paths)
         self.losses = []
         self.rerank = bool(rerank)
@@ -108,7 +131,15 @@ class DRTrainer:
         if self.rerank:
             if num_sampled is None:
                 raise ValueError("rerank=True needs num_sampled")
+            if comm is not None:          # (a collective: every rank raises, or none)
+                # the sampler's seed is 64 bits wide and the allreduce carries doubles: compare the two 32-bit halves, each exact
+                halves = np.array([int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF], np.float64)
+                hi, lo = comm.allreduce(halves, "max"), -comm.allreduce(-halves, "max")
+                if not np.array_equal(hi, lo):
+                    raise ValueError("DRTrainer: every rank must pass the same seed with rerank=True (the rerank replicas draw the same negatives)")
             engine.dr_rerank_train_init(num_sampled, seed=seed, accumulate=accumulate, lr=lr, lr_decay=lr_decay, beta1=beta1, beta2=beta2, eps=eps)
+        if comm is not None:
+            engine.attach_comm(comm)
 
     def set_item_paths(self, item_paths):
         p = np.ascontiguousarray(item_paths, np.int32)
@@ -120,9 +151,12 @@ class DRTrainer:
     def step(self, seqs, targets):
         """one batch: expand by the targets' paths, forward/backward, Adam -> per-layer losses [D]; with rerank=True the rerank step
         follows on the unexpanded batch -> (per-layer losses [D], sampled-softmax loss)"""
-        seq, paths = expand_batch(seqs, targets, self.item_paths)
-        loss = self.engine.dr_train_forward_backward(seq, paths)
-        self.engine.dr_adam_step(1.0)
+        if self.comm is None:
+            seq, paths = expand_batch(seqs, targets, self.item_paths)
+            loss = self.engine.dr_train_forward_backward(seq, paths)
+            self.engine.dr_adam_step(1.0)
+        else:
+            loss = self._layer_step_parallel(seqs, targets)
         self.losses.append(loss)
         if not self.rerank:
             return loss
@@ -132,6 +166,24 @@ class DRTrainer:
             self.engine.dr_rerank_adam_step(1.0)
         self.rerank_losses.append(rr)
         return loss, rr
+
+    def _layer_step_parallel(self, seqs, targets):
+        """trainLayerBatch + syncGradients: this rank's slice, the exchange, Adam with 1 / P -> the mean loss of the P working ranks"""
+        import time
+        seqs, targets = np.asarray(seqs), np.asarray(targets)
+        slices, P = layer_slices(len(targets), self.comm.world)
+        if P == 0:
+            raise ValueError("DRTrainer.step: empty batch")
+        lo, n = slices[self.comm.rank]
+        loss = np.zeros(self.engine.dr_dims["D"], np.float64)
+        if n > 0:                         # (a rank past P runs no step: it enters the exchange with no rows and a zero dense part)
+            seq, paths = expand_batch(seqs[lo:lo + n], targets[lo:lo + n], self.item_paths)
+            loss = self.engine.dr_train_forward_backward(seq, paths)
+        t0 = time.perf_counter()
+        self.engine.dr_train_sync_gradients()
+        self.sync_s += time.perf_counter() - t0; self.sync_calls += 1
+        self.engine.dr_adam_step(1.0 / P)
+        return self.comm.allreduce(loss) / P
 
     def next_epoch(self):
         self.epoch += 1

@@ -951,6 +951,12 @@ class Engine:
     def dr_adam_step(self, grad_scale=1.0):
         self._chk(N.lib().dm_dr_adam_step(self._h, float(grad_scale)))
 
+    def dr_train_sync_gradients(self):
+        """LocalOptimizer.syncGradients for the Deep-Retrieval layer model over the attached communicator (dm_dr_train_sync_gradients,
+        DESIGN.md §22; collective: every rank calls it, a rank that ran no step included).  Afterwards every replica's gradient is the
+        rank-ordered sum, in the model's dtype, of the ranks' gradients; dr_adam_step(1 / P) follows.  train_sync_stats() says what it moved."""
+        self._chk(N.lib().dm_dr_train_sync_gradients(self._h))
+
     def dr_train_param_count(self):
         n = C.c_int64(0)
         self._chk(N.lib().dm_dr_train_param_count(self._h, C.byref(n)))

@@ -743,6 +743,17 @@ int dm_dr_train_forward_backward_dev(dm_handle_t h, const int32_t *d_seq_ids, co
  * when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 — the same bytes either way.  Marks the search's derived
  * copies (history columns, node tables, split planes) stale: the next search rebuilds them, not every step. */
 int dm_dr_adam_step(dm_handle_t h, float grad_scale);
+/* LocalOptimizer.syncGradients (D/optim/LocalOptimizer.scala:167-194) minus the division, which dm_dr_adam_step(1 / P) folds in, over the
+ * communicator attached with dm_comm_attach: after dm_dr_train_forward_backward on each rank's slice, every replica
+ * holds for every embedding row any rank reached ((0 + g_0) + g_1) + ... in rank order (ranks that did not reach the row are skipped) and
+ * the rank-ordered sum of the dense blocks [W_0 ; b_0 ; ...], in the model's dtype and on BOTH transports: the sum of the ranks' local
+ * gradients bit for bit, no floating-point atomics.  One var-size all-gather of [row ids | gradient rows | dense blocks]; the table
+ * never moves.  A rank that ran no step since dm_dr_train_init or its last Adam step takes part with no rows and a zero dense part.
+ * Collective: every rank calls it.  Ranks that train different shapes or dtypes ALL return DM_ERR_STATE before any gradient moves.
+ * Before any collective, with the handle left usable: DM_ERR_STATE without a Deep-Retrieval model, without dm_dr_train_init, on a clone,
+ * without a communicator, and for a second exchange with no forward/backward or Adam step in between (it would sum a sum).  A one-rank
+ * communicator: DM_OK, nothing moves.  dm_train_sync_stats reports what the call moved. */
+int dm_dr_train_sync_gradients(dm_handle_t h);
 int dm_dr_train_param_count(dm_handle_t h, int64_t *n);
 /* what: 0 weights (needs no training state), 1 gradient, 2 first moment, 3 second moment; n must be the parameter count (DM_ERR_INVALID) */
 int dm_dr_train_download(dm_handle_t h, int what, void *out, int64_t n);
