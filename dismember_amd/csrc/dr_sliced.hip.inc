@@ -339,9 +339,26 @@ __device__ __forceinline__ DrsLds<T> drs_carve(char *base, int D, int n2, int nl
   return l;
 }
 
-template <typename T> struct DrsTol;        // relative margin of the cut; smallest score it is trusted at
-template <> struct DrsTol<float> { static constexpr float rel = 1e-3f, floor_ = 1e-30f; };
-template <> struct DrsTol<double> { static constexpr double rel = 1e-9, floor_ = 1e-290; };
+// Relative margin of the cut; smallest score it is trusted at; and the two limits below which the PRODUCTS exp(l - Mhat) are no longer
+// trusted.  Mhat is an upper bound, so a path's products can all sit in the underflow range while its scores cp * product (cp = parent
+// probability / sum) look perfectly normal — floor_ never sees that.  With tiny = numeric_limits<T>::min(): a product of <= 4 tabulated
+// factors, each <= 1, is off by at most 4 tiny absolutely once a factor or a partial product is subnormal or flushed to zero.
+//   * pmax_min: a path's sum s has K <= 1024 terms, so |s - true| <= 4096 tiny, and s >= the path's largest product pmax.  For a
+//     relative error of rel / 4:  pmax >= 4 * 4096 tiny / rel.
+//   * prod_min: a candidate at the cut has the product thr / cp; for a relative error of rel / 8:  thr / cp >= 8 * 4 tiny / rel.
+// Together with the rounding of normal products (1e-6 in f32, 1e-15 in fp64) every score at or above the cut is then within rel / 2 of
+// the true one, which is what thr = tau (1 - rel) allows for (tau <= (1 + rel / 2) true beam-th, a winner's score >= (1 - rel / 2) of it);
+// and a survivor's exp(l - Mhat) >= prod_min is a normal number divided by an accurate sum.  A user-layer with a live path outside
+// either limit takes the exact path.  (f32: 1.9e-31 = exp(-70.7), 3.8e-34;  fp64: 3.6e-295 = exp(-677.7), 7.1e-298.)
+template <typename T> struct DrsTol;
+template <> struct DrsTol<float> {
+  static constexpr float rel = 1e-3f, floor_ = 1e-30f;
+  static constexpr float pmax_min = 16384.f * std::numeric_limits<float>::min() / rel, prod_min = 32.f * std::numeric_limits<float>::min() / rel;
+};
+template <> struct DrsTol<double> {
+  static constexpr double rel = 1e-9, floor_ = 1e-290;
+  static constexpr double pmax_min = 16384. * std::numeric_limits<double>::min() / rel, prod_min = 32. * std::numeric_limits<double>::min() / rel;
+};
 
 template <typename T, int NTAB>
 __global__ __launch_bounds__(DR_NT, 4) void drs_select_kernel(DrsParams<T> p, int d) {
@@ -357,7 +374,7 @@ __global__ __launch_bounds__(DR_NT, 4) void drs_select_kernel(DrsParams<T> p, in
     const T *Srow = p.S + u * ((int64_t)D * K) + (int64_t)d * K;
     const T *ESrow = p.ES + u * ((int64_t)D * K) + (int64_t)d * K;
     for (int i = tid; i < np * D; i += DR_NT) L.nodes[i] = p.nodes[u * p.beam * D + i];
-    if (tid == 0) L.cnt[2] = 0;
+    if (tid == 0) { L.cnt[2] = 0; L.cnt[3] = 0; }
     __syncthreads();
     // per path: Mhat, the sum in slice order, c = log(parent prob) - Mhat - log(sum); then every block's log-space maximum
     for (int q = tid; q < np; q += DR_NT) {
@@ -377,7 +394,12 @@ __global__ __launch_bounds__(DR_NT, 4) void drs_select_kernel(DrsParams<T> p, in
     }
     __syncthreads();
     const int nb = np * 64;
-    for (int b = tid; b < nb; b += DR_NT) L.bmax[b] = p.part_bmax[u * p.beam * 64 + b] * L.cp[b >> 6];
+    for (int b = tid; b < nb; b += DR_NT) {           // a wave holds the 64 blocks of ONE path (nb = 64 np, DR_NT = 4 x 64)
+      const T raw = p.part_bmax[u * p.beam * 64 + b];
+      L.bmax[b] = raw * L.cp[b >> 6];
+      // the path's largest product below DrsTol::pmax_min: its sum has lost terms or bits to underflow, exact path (as for s == 0)
+      if (__ballot(raw >= DrsTol<T>::pmax_min) == 0ull && lane == 0) atomicOr(L.cnt + 2, 1);
+    }
     __syncthreads();
     const bool degenerate = L.cnt[2] != 0;
     const long long n = (long long)np * K;
@@ -395,8 +417,10 @@ __global__ __launch_bounds__(DR_NT, 4) void drs_select_kernel(DrsParams<T> p, in
       const T tau = DrKey<T>::dec(L.st->pre_hi);
       const T thr = tau * ((T)1 - DrsTol<T>::rel);
       if (tid == 0) { L.cnt[0] = 0; L.cnt[1] = 0; }
+      // the cut in product space, thr / cp, of some path below DrsTol::prod_min: candidates next to it may have lost bits
+      for (int q = tid; q < np; q += DR_NT) if (!(thr >= DrsTol<T>::prod_min * L.cp[q])) atomicOr(L.cnt + 3, 1);
       __syncthreads();
-      const bool usable = (tau == tau) && thr >= DrsTol<T>::floor_ && thr < (T)INFINITY;    // uniform
+      const bool usable = (tau == tau) && thr >= DrsTol<T>::floor_ && thr < (T)INFINITY && L.cnt[3] == 0;    // uniform
       if (usable) {
         for (int b = tid; b < nb; b += DR_NT)
           if (L.bmax[b] >= thr) { const int sl = atomicAdd(L.cnt + 1, 1); if (sl < p.nl) L.blist[sl] = b; }
@@ -519,7 +543,9 @@ __global__ __launch_bounds__(DR_NT, 4) void drs_select_kernel(DrsParams<T> p, in
 // block score by bisection on the leading 24 bits of the (positive, float-rounded) scores — one wave-wide count per bit —, candidate blocks and
 // surviving elements compacted with ballots, the winners rank-sorted.  Twenty waves per CU each carry their own user; the block
 // version's 0.8 ms per layer was barrier and atomic latency (120 k cycles per user and workgroup).  Users whose lists overflow, whose
-// scores sit in the underflow range or whose sums degenerated are flagged in todo[] and redone by drs_select_kernel.
+// scores sit in the underflow range, whose sums degenerated or whose products sit below the limits of DrsTol are flagged in todo[] and
+// redone by drs_select_kernel.  Reason bytes of dm_debug_dr_wave_fallbacks: 1 sum zero / non-finite, 2 score floor, 3 too many blocks,
+// 4 too few survivors, 5 too many survivors, 6 products in the underflow range (pmax_min, prod_min).
 __host__ __device__ static inline size_t drs_selw_lds_per_wave(int esz, int D, int n2, int nl) {
   return (size_t)n2 * esz * 4 + (size_t)n2 * D * 4 + (size_t)nl * (esz + 4) + (size_t)nl * 4 + 32;
 }
@@ -571,14 +597,17 @@ __global__ __launch_bounds__(256, DRS_SELW_WPS) void drs_select_wave_kernel(DrsP
     // block scores: lane holds blocks lane + 64 i, i.e. block `lane` of path i — as FLOATS rounded toward zero (64 registers; the
     // cut needs a lower bound of the kb-th largest score and a superset of the blocks above it, not the scores themselves)
     float sc[64];
+    bool thin = false;                                  // (uniform) a path whose largest product is below DrsTol::pmax_min: its sum is not trusted
 #pragma unroll
     for (int i = 0; i < 64; i++) {
-      const T v = i < np ? p.part_bmax[(u * p.beam + i) * 64 + lane] * Lcp[i] : (T)0;
+      const T raw = i < np ? p.part_bmax[(u * p.beam + i) * 64 + lane] : (T)0;
+      const T v = i < np ? raw * Lcp[i] : (T)0;
       if (!(v >= (T)0)) bad = true;                     // NaN
+      if (i < np && __ballot(raw >= DrsTol<T>::pmax_min) == 0ull) thin = true;
       sc[i] = sizeof(T) == 8 ? __double2float_rz((double)v) : (float)v;
     }
-    bool fallback = __ballot(bad) != 0ull;
-    int nc = 0, why = fallback ? 1 : 0;
+    bool fallback = __ballot(bad) != 0ull || thin;
+    int nc = 0, why = __ballot(bad) != 0ull ? 1 : (thin ? 6 : 0);
     if (!fallback) {
       // bisection on the float bits (sign 0; exponent and 16 mantissa bits: tau within 2^-16 below the kb-th largest).  The count of a
       // candidate is 64 compares whose lane masks are popcounted on the SCALAR unit (v_cmp + s_bcnt1): no per-lane adds, no wave reduction
@@ -595,6 +624,8 @@ __global__ __launch_bounds__(256, DRS_SELW_WPS) void drs_select_wave_kernel(DrsP
       // blocks whose (exact) score reaches thr: the float is at most one ulp below the score
       const float thr_f = (float)((double)thr * (1.0 - 1.2e-7));
       if (!(thr >= DrsTol<T>::floor_) || !(thr < (T)INFINITY) || !(tau >= (T)1e-30)) { fallback = true; why = 2; }         // uniform
+      // the cut in product space, thr / cp, of some path below DrsTol::prod_min (np <= 64: one path per lane)
+      else if (__ballot(lane < np && !(thr >= DrsTol<T>::prod_min * Lcp[lane < np ? lane : 0])) != 0ull) { fallback = true; why = 6; }
       if (!fallback) {
         int nblk = 0;
 #pragma unroll

@@ -840,6 +840,20 @@ class Engine:
                                           sc.ctypes.data_as(C.POINTER(C.c_double)), _p(cnt, N.i32p)))
         return ids, sc, cnt
 
+    def dr_search_counters(self, reset=True):
+        """(exact_layers, wave_fallbacks, reasons[8]) since the last reset: user-layers of the Deep-Retrieval beam search that took the
+        exact radix-select path (either route, layer 0 included), user-layers the sliced route's one-wave cut handed to the block
+        kernel, and that count by reason (one byte each, so it wraps at 256): [1] sum zero / non-finite, [2] score floor, [3] too many
+        blocks, [4] too few survivors, [5] too many survivors, [6] products in the underflow range."""
+        slow = C.c_ulonglong(0)
+        two = (C.c_ulonglong * 2)()
+        lib = N.lib()
+        lib.dm_debug_dr_slow_layers.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+        lib.dm_debug_dr_wave_fallbacks.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int]
+        self._chk(lib.dm_debug_dr_slow_layers(self._h, C.byref(slow), int(bool(reset))))
+        self._chk(lib.dm_debug_dr_wave_fallbacks(self._h, two, int(bool(reset))))
+        return int(slow.value), int(two[0]), [(int(two[1]) >> (8 * i)) & 0xFF for i in range(8)]
+
     def dr_beam_search_dev(self, d_seq, U, beam, d_paths, d_probs, d_counts):
         self._chk(N.lib().dm_dr_beam_search_dev(self._h, d_seq, U, int(beam), d_paths, d_probs, d_counts))
 

@@ -76,7 +76,7 @@ def main():
         two = (C.c_ulonglong * 2)()
         N.lib().dm_debug_dr_wave_fallbacks(eng._h, two, 1)
         out["beam_search"]["wave_cut_fallback_layers_per_user"] = two[0] / float(U * (a.steps + 1))
-        out["beam_search"]["wave_cut_fallback_reasons_hex"] = hex(two[1])      # bytes: [1] degenerate sums, [2] score floor, [3] blocks, [4] too few, [5] too many
+        out["beam_search"]["wave_cut_fallback_reasons_hex"] = hex(two[1])      # bytes: [1] degenerate sums, [2] score floor, [3] blocks, [4] too few, [5] too many, [6] products in the underflow range
     except AttributeError:
         pass
     if a.rerank:
