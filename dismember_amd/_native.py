@@ -192,6 +192,12 @@ SIGNATURES = {
                                                     i64p, i64p, i32p, C.POINTER(C.c_double), i32p]),
     "dm_dr_mstep_streaming_path_scores_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int64, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, i64p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dm_dr_mstep_assign_paths": (C.c_int, [C.c_void_p, i64p, i64p, C.POINTER(C.c_double), i64p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_double, C.c_int, C.c_uint64, i64p, i64p, i32p, i64p, i32p, C.POINTER(C.c_double)]),
+    "dm_dr_mstep_assign_paths_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, i64p, C.c_void_p, C.c_void_p]),
+    "dm_dr_mstep_optimize": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64,
+                                       i64p]),
     "dm_memcpy_d2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "dm_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "dm_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -189,6 +189,7 @@ struct dm_ctx {
   dm_jtm_stats jtm_stats{};
   dm_otm_stats otm_stats{};
   DevGrow sync;
+  DevGrow dra, dra_io;           // the M-step's path assignment (dr_mstep_assign.hip.inc): every array of a call; the host entries' uploads and results
 };
 
 static std::string g_create_err;
@@ -514,7 +515,7 @@ int dm_destroy(dm_handle_t h) {
   if (h->parent) { clone_forget(h); h->parent->n_clones.fetch_sub(1); h->parent = nullptr; }
   free_tree(h); free_weights(h); dm_dr_free(h->dr);
   dm_release(h->d_id_to_code, h->d_ctr, h->d_phase);
-  for (DevGrow *g : {&h->ws, &h->req, &h->sync, &h->samp, &h->defer, &h->scratch64, &h->dfm_jtm_ws}) g->release();
+  for (DevGrow *g : {&h->ws, &h->req, &h->sync, &h->samp, &h->defer, &h->scratch64, &h->dfm_jtm_ws, &h->dra, &h->dra_io}) g->release();
   if (h->h_stage) (void)hipHostFree(h->h_stage);
   jtm_drop_cache(h);
   for (auto &pr : h->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
@@ -1593,6 +1594,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "dr_rerank_train.hip.inc"
 #include "dr_mstep.hip.inc"
 #include "dr_mstep_stream.hip.inc"
+#include "dr_mstep_assign.hip.inc"
 #include "otm64.hip.inc"
 #include "tdm_pipeline.hip.inc"
 #include "deepfm.hip.inc"

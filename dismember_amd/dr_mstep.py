@@ -6,7 +6,9 @@ batched `dm_dr_beam_search` call per chunk; per-item aggregation is a sort + seg
 (`batch_path_scores`) or without the candidates leaving the device (`batch_path_scores_dev`, `optimize(path_scores="device")`); the
 streaming mode's decayed running scores likewise (`streaming_path_scores` on the host, `streaming_path_scores_dev` /
 `optimize(train_mode="streaming", path_scores="device_streaming")` on the device).  The greedy,
-penalised path choice is inherently sequential over items (a shared path-size table), as in the reference, and stays on the host.
+penalised path choice is inherently sequential over items (a shared path-size table), as in the reference: `assign_paths` is the host
+loop, `assign_paths_dev` / `optimize(assign="device")` the same chain as one wave on the device (Engine.dr_mstep_assign_paths,
+Engine.dr_mstep_optimize).
 Orders the reference takes from hash maps are fixed here: ties between equal path scores resolve to the smaller path code
 (ascending node tuple), items are visited in ascending id."""
 import math
@@ -157,14 +159,100 @@ def assign_paths(item_path_scores, item_occurrence, all_items, num_iteration, nu
     return {v: [_decode(c, K, D) for c in codes] for v, codes in mapping.items()}
 
 
+def decode_codes(codes, K, D):
+    """path codes [...] -> node ids [..., D] (code = sum_d node_d * K^(D-1-d)), vectorised"""
+    c = np.array(codes, np.int64)
+    out = np.empty(c.shape + (D,), np.int64)
+    for d in range(D - 1, -1, -1):
+        out[..., d] = c % K
+        c //= K
+    return out
+
+
+def pack_csr(item_path_scores, item_occurrence, num_item):
+    """the dicts of the host routes -> the CSR of the device routes: (item_off [num_item + 1], codes, scores, occurrence [num_item])"""
+    cnt = np.zeros(num_item, np.int64)
+    occ = np.zeros(num_item, np.int64)
+    items = sorted(int(v) for v in item_path_scores)
+    for v in items:
+        cnt[v] = len(item_path_scores[v][0])
+    for v, n in item_occurrence.items():
+        occ[int(v)] = n
+    off = np.zeros(num_item + 1, np.int64)
+    np.cumsum(cnt, out=off[1:])
+    codes = np.concatenate([np.asarray(item_path_scores[v][0], np.int64) for v in items]) if items else np.zeros(0, np.int64)
+    scores = np.concatenate([np.asarray(item_path_scores[v][1], np.float64) for v in items]) if items else np.zeros(0, np.float64)
+    return off, codes, scores, occ
+
+
+def _as_mapping(out_codes, K, D, items=None):
+    """[num_item, J] codes -> {item: [J path tuples]} for `items` (None: every item); the decode is one vectorised pass"""
+    J = out_codes.shape[1]
+    flat = list(map(tuple, decode_codes(out_codes, K, D).reshape(-1, D).tolist()))
+    items = range(out_codes.shape[0]) if items is None else items
+    return {int(v): flat[int(v) * J:(int(v) + 1) * J] for v in items}
+
+
+def assign_paths_dev(engine, item_off, codes, scores, occurrence, num_iteration, num_path_per_item, K, D, seed=0, penalty_factor=3e-6,
+                     penalty_poly_order=4, all_items=None, as_array=False):
+    """assign_paths on the device (Engine.dr_mstep_assign_paths) over the CSR the device path-score routes return.  The hit
+    items get what assign_paths gives them (up to the last bits of log1p where two gains nearly tie); the items that never occur draw
+    from the library's own counter-based stream, not numpy's.  all_items (None: every item): an item outside it is not visited and its
+    row is not handed out.  -> {item: [J path tuples]}, or with as_array=True the codes [num_item, J] int64."""
+    occ = np.array(occurrence, np.int64)
+    items = None
+    if all_items is not None:
+        items = np.unique(np.asarray(list(all_items), np.int64))
+        if len(items) != len(occ):
+            keep = np.zeros(len(occ), bool)
+            keep[items] = True
+            occ[~keep] = 0
+        else:
+            items = None
+    out = engine.dr_mstep_assign_paths(item_off, codes, scores, occ, K, D, num_path_per_item, num_iteration, penalty_factor, penalty_poly_order, seed)
+    return out if as_array else _as_mapping(out, K, D, items)
+
+
 def optimize(engine, sequences, targets, all_items, num_candidate_path, num_path_per_item, num_iteration=3, train_mode="batch",
-             decay_factor=0.999, batch_size=8192, seed=0, penalty_factor=3e-6, penalty_poly_order=4, path_scores="host"):
+             decay_factor=0.999, batch_size=8192, seed=0, penalty_factor=3e-6, penalty_poly_order=4, path_scores="host", assign="host",
+             as_array=False):
     """CoordinateDescent.optimize(model, trainMode) -> item -> paths (internal ids).  path_scores="device" (batch mode only) aggregates the
     candidates on the device (batch_path_scores_dev) and takes the item occurrences from the same call; path_scores="device_streaming"
-    (streaming mode only) does the same for the decayed running scores (streaming_path_scores_dev)."""
+    (streaming mode only) does the same for the decayed running scores (streaming_path_scores_dev).  assign="device" runs the greedy
+    assignment on the device too (assign_paths_dev): with a device path_scores and all_items = every item it is ONE call
+    (Engine.dr_mstep_optimize), nothing but the result leaves the device; as_array=True (assign="device" only) returns the codes
+    [num_item, J] instead of the dict."""
     K, D = engine.dr_dims["K"], engine.dr_dims["D"]
     if path_scores not in ("host", "device", "device_streaming"):
         raise ValueError(path_scores)
+    if assign not in ("host", "device"):
+        raise ValueError(assign)
+    if as_array and assign != "device":
+        raise ValueError("as_array=True needs assign=\"device\"")
+    if assign == "device":
+        if path_scores == "device_streaming" and train_mode != "streaming":
+            raise ValueError("path_scores=\"device_streaming\" serves train_mode=\"streaming\" only")
+        if path_scores == "device" and train_mode != "batch":
+            raise ValueError("path_scores=\"device\" serves train_mode=\"batch\" only (streaming: \"device_streaming\")")
+        if train_mode not in ("batch", "streaming"):
+            raise ValueError(train_mode)
+        num_item = engine.dr_dims["num_item"]
+        items = np.unique(np.asarray(list(all_items), np.int64))
+        every = len(items) == num_item
+        kw = dict(seed=seed, penalty_factor=penalty_factor, penalty_poly_order=penalty_poly_order)
+        if path_scores != "host" and every:
+            out = engine.dr_mstep_optimize(sequences, targets, num_candidate_path, num_path_per_item, num_iteration, train_mode, decay_factor, **kw)
+            return out if as_array else _as_mapping(out, K, D)
+        if path_scores == "host":
+            sc = (batch_path_scores(engine, sequences, targets, num_candidate_path) if train_mode == "batch" else
+                  streaming_path_scores(engine, sequences, targets, num_candidate_path, decay_factor, batch_size))
+            tg, cnt = np.unique(np.asarray(targets), return_counts=True)
+            csr = pack_csr(sc, dict(zip(tg.tolist(), cnt.tolist())), num_item)
+        elif path_scores == "device":
+            csr = engine.dr_mstep_path_scores(sequences, targets, num_candidate_path)
+        else:
+            csr = engine.dr_mstep_streaming_path_scores(sequences, targets, num_candidate_path, decay_factor)
+        return assign_paths_dev(engine, *csr, num_iteration, num_path_per_item, K, D, all_items=None if every else items, as_array=as_array, **kw)
     if path_scores == "device_streaming":
         if train_mode != "streaming":
             raise ValueError("path_scores=\"device_streaming\" serves train_mode=\"streaming\" only")

@@ -185,6 +185,18 @@ class DRTrainer:
         self.engine.dr_adam_step(1.0 / P)
         return self.comm.allreduce(loss) / P
 
+    def mstep(self, seqs, targets, num_candidate_path, num_iteration=3, assign="host", **kw):
+        """the M-step of one E/M round: dr_mstep.optimize over every item with the trained weights (the number of paths per item stays),
+        and the new mapping becomes the trainer's.  assign="device" runs the greedy assignment on the device as well (DESIGN.md §23);
+        kw: optimize's other arguments (train_mode, path_scores, decay_factor, seed, penalty_factor, penalty_poly_order).
+        -> the new item_paths [num_item, J, D]"""
+        from dismember_amd import dr_mstep
+        d = self.engine.dr_dims
+        m = dr_mstep.optimize(self.engine, seqs, targets, range(d["num_item"]), num_candidate_path, self.item_paths.shape[1], num_iteration,
+                              assign=assign, **kw)
+        self.set_item_paths(np.array([m[i] for i in range(d["num_item"])], np.int32))
+        return self.item_paths
+
     def next_epoch(self):
         self.epoch += 1
 

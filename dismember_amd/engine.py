@@ -936,6 +936,64 @@ class Engine:
                                                                 d_trace[2]))
         return int(total[0])
 
+    # ---- Deep-Retrieval M-step: the greedy penalised path assignment
+    def dr_mstep_assign_paths(self, item_off, codes, scores, occurrence, num_node, num_layer, num_path_per_item, num_iteration=3, penalty_factor=3e-6,
+                              penalty_poly_order=4, seed=0, with_paths=False, trace=False):
+        """dm_dr_mstep_assign_paths on the CSR dr_mstep_path_scores returns (needs no model) -> out_codes [num_item, J] int64: the J path
+        codes of every item (an item with occurrence 0: random paths from `seed`).  with_paths=True appends (path_codes [P] ascending,
+        path_sizes [P] int32): the distinct codes of the CSR and their final sizes; trace=True appends (trace_sel [T, n_hit, J] int32,
+        trace_gain [T, n_hit, J]): the chosen candidate position and the computed gain of every decision, hit items in ascending id."""
+        off = np.ascontiguousarray(item_off, np.int64).reshape(-1)
+        cd = np.ascontiguousarray(codes, np.int64).reshape(-1)
+        sc = np.ascontiguousarray(scores, np.float64).reshape(-1)
+        oc = np.ascontiguousarray(occurrence, np.int64).reshape(-1)
+        ni, total, j, t = len(oc), len(cd), int(num_path_per_item), int(num_iteration)
+        assert len(off) == ni + 1 and len(sc) == total
+        f64p = C.POINTER(C.c_double)
+        out = np.empty((ni, max(j, 0)), np.int64)
+        pc = ps = npaths = ts = tg = None
+        if with_paths:
+            pc, ps, npaths = np.empty(max(total, 1), np.int64), np.empty(max(total, 1), np.int32), np.zeros(1, np.int64)
+        if trace:
+            nh = int((oc > 0).sum())
+            ts, tg = np.zeros((max(t, 0), nh, max(j, 0)), np.int32), np.zeros((max(t, 0), nh, max(j, 0)), np.float64)
+        opt = lambda a, ty: _p(a, ty) if a is not None else None
+        self._chk(N.lib().dm_dr_mstep_assign_paths(self._h, _p(off, N.i64p), _p(cd, N.i64p), _p(sc, f64p), _p(oc, N.i64p), ni, total, int(num_node), int(num_layer),
+                                                   j, t, float(penalty_factor), int(penalty_poly_order), int(seed), _p(out, N.i64p), opt(pc, N.i64p), opt(ps, N.i32p),
+                                                   opt(npaths, N.i64p), opt(ts, N.i32p), opt(tg, f64p)))
+        res = (out,)
+        if with_paths:
+            res += (pc[:int(npaths[0])].copy(), ps[:int(npaths[0])].copy())
+        if trace:
+            res += (ts, tg)
+        return res[0] if len(res) == 1 else res
+
+    def dr_mstep_assign_paths_dev(self, d_item_off, d_codes, d_scores, d_occurrence, num_item, total, num_node, num_layer, num_path_per_item, d_out_codes,
+                                  num_iteration=3, penalty_factor=3e-6, penalty_poly_order=4, seed=0, d_paths=(None, None), d_trace=(None, None)):
+        """the same on device arrays -> the number of distinct paths (None without d_paths = (d_path_codes, d_path_sizes))"""
+        npaths = np.zeros(1, np.int64)
+        self._chk(N.lib().dm_dr_mstep_assign_paths_dev(self._h, d_item_off, d_codes, d_scores, d_occurrence, int(num_item), int(total), int(num_node), int(num_layer),
+                                                       int(num_path_per_item), int(num_iteration), float(penalty_factor), int(penalty_poly_order), int(seed),
+                                                       d_out_codes, d_paths[0], d_paths[1], _p(npaths, N.i64p) if d_paths[0] is not None else None,
+                                                       d_trace[0], d_trace[1]))
+        return int(npaths[0]) if d_paths[0] is not None else None
+
+    def dr_mstep_optimize(self, seqs, targets, num_candidate_path, num_path_per_item, num_iteration=3, train_mode="batch", decay_factor=0.999,
+                          penalty_factor=3e-6, penalty_poly_order=4, seed=0):
+        """dm_dr_mstep_optimize: the path scores of dr_mstep_path_scores (train_mode "batch") or dr_mstep_streaming_path_scores ("streaming")
+        and the assignment on them in one call, nothing but the result leaves the device -> out_codes [num_item, J] int64"""
+        if train_mode not in ("batch", "streaming"):
+            raise ValueError(train_mode)
+        d = self.dr_dims
+        seq = _i32(seqs).reshape(-1, d["L"])
+        tg = _i32(targets).reshape(-1)
+        assert len(seq) == len(tg)
+        out = np.empty((d["num_item"], max(int(num_path_per_item), 0)), np.int64)
+        self._chk(N.lib().dm_dr_mstep_optimize(self._h, _p(seq, N.i32p), _p(tg, N.i32p), len(seq), int(num_candidate_path), int(train_mode == "streaming"),
+                                               float(decay_factor), int(num_path_per_item), int(num_iteration), float(penalty_factor), int(penalty_poly_order),
+                                               int(seed), _p(out, N.i64p)))
+        return out
+
     # ---- Deep-Retrieval E-step: the layer model's training step (DESIGN.md §10)
     def dr_train_init(self, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
         o = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)

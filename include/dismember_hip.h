@@ -647,6 +647,44 @@ int dm_dr_mstep_streaming_path_scores_dev(dm_handle_t h, const int32_t *d_seq_id
                                           int64_t *d_out_codes, double *d_out_scores, int64_t *d_out_occurrence, int64_t *out_total,
                                           int32_t *d_trace_paths, double *d_trace_probs, int32_t *d_trace_counts);
 
+/* ---- Deep-Retrieval M-step: the greedy penalised path assignment on the device ----
+ * The coordinate-descent loop of CoordinateDescent.optimize (D/optim/CoordinateDescent.scala:48-82; penaltyFunc :112-115) over the per-item
+ * CSR of dm_dr_mstep_path_scores / dm_dr_mstep_streaming_path_scores: item_off [num_item + 1], codes / scores [total], occurrence
+ * [num_item].  For t = 1 .. num_iteration, over the items v with occurrence[v] > 0 in ascending id, for j = J - 1 down to 0: (t > 1) the
+ * path slot j held gives its place back (size - 1); every candidate c of v not yet chosen in this visit scores
+ *   g = nv (log1p(prob_c + partial) - log1p(partial)) - penalty_factor ((s + 1)^p / p - s^p / p),  s = size[code_c], nv = occurrence[v], fp64;
+ * the largest g wins, among equal g the lowest CSR position (maxBy :62-70); size[best] + 1; partial += g (the GAIN, :76); out[v][j] = best.
+ * An item with occurrence 0 gets J random paths (generateRandomPath, :52): node d of path j uniform in [0, num_node) from a counter-based
+ * splitmix64 keyed by (seed, v, j, d) — the reference draws from an unseeded Random, so the stream is this library's own.
+ * out_codes [num_item x J].  out_path_codes / out_path_sizes / out_num_paths: all NULL or all set; they receive the distinct codes of the CSR
+ * in ascending order (at most total), their final sizes (int32) and their number.  trace_sel (int32) / trace_gain [num_iteration x n_hit x J]
+ * (n_hit = items with occurrence > 0, in ascending id): both NULL or both set; the chosen candidate position inside the item's range and the
+ * gain as computed, for every decision.  Needs a handle, not a model.
+ * Refused before anything is read or allocated (DM_ERR_INVALID): J < 1, num_iteration < 1, penalty_poly_order outside [1, 8], penalty_factor
+ * not finite or negative, num_node^num_layer not below 2^62, a null required array, a partly given optional group; DM_ERR_UNSUPPORTED:
+ * total >= 2^31 or num_item * J >= 2^31.  Checked on the device before the loop runs (DM_ERR_INVALID, the first offending item in the
+ * message, nothing written): offsets that decrease or leave [0, total] (item_off[0] = 0, item_off[num_item] = total), a hit item with fewer
+ * than J or more than 2048 candidates, a code outside [0, num_node^num_layer), a score that is not finite or is negative, a path listed twice
+ * by a hit item.  partial <= -1 or a winning gain that is not finite stops the loop: DM_ERR_INVALID with the item in the message (where
+ * math.log1p raises on the host route).  num_item == 0 or no hit item: DM_OK.  The same inputs give the same bytes; the handle stays usable. */
+int dm_dr_mstep_assign_paths(dm_handle_t h, const int64_t *item_off, const int64_t *codes, const double *scores, const int64_t *occurrence,
+                             int64_t num_item, int64_t total, int num_node, int num_layer, int num_path_per_item, int num_iteration,
+                             double penalty_factor, int penalty_poly_order, uint64_t seed, int64_t *out_codes, int64_t *out_path_codes,
+                             int32_t *out_path_sizes, int64_t *out_num_paths, int32_t *trace_sel, double *trace_gain);
+/* the same with device arrays; out_num_paths stays a host pointer; returns when the results are in place */
+int dm_dr_mstep_assign_paths_dev(dm_handle_t h, const int64_t *d_item_off, const int64_t *d_codes, const double *d_scores,
+                                 const int64_t *d_occurrence, int64_t num_item, int64_t total, int num_node, int num_layer,
+                                 int num_path_per_item, int num_iteration, double penalty_factor, int penalty_poly_order, uint64_t seed,
+                                 int64_t *d_out_codes, int64_t *d_out_path_codes, int32_t *d_out_path_sizes, int64_t *out_num_paths,
+                                 int32_t *d_trace_sel, double *d_trace_gain);
+/* CoordinateDescent.optimize (:29-83) in one call: the path scores of dm_dr_mstep_path_scores (mode 0) or
+ * dm_dr_mstep_streaming_path_scores (mode 1, with decay_factor) and the assignment above on them; the candidates and the CSR never leave the
+ * device.  Host arrays in, out_codes [num_item x J] out; num_node / num_layer are the loaded model's.  Every check of
+ * dm_dr_mstep_path_scores holds as it is, then those of the assignment; mode outside {0, 1}: DM_ERR_INVALID. */
+int dm_dr_mstep_optimize(dm_handle_t h, const int32_t *seq_ids, const int32_t *targets, int64_t N, int num_candidate_path, int mode,
+                         double decay_factor, int num_path_per_item, int num_iteration, double penalty_factor, int penalty_poly_order,
+                         uint64_t seed, int64_t *out_codes);
+
 /* ---- DeepFM: one training step on the device ----
  * LocalOptimizer.trainBatch with the DeepFM graph (T/optim/LocalOptimizer.scala:139-162, useMask = false; T/model/DeepFM.scala:11-45;
  * S/nn/FM.scala:24-71, S/nn/Linear.scala, S/nn/BCECriterionWithLogits.scala:27-64 averaged over the batch; S/optim/Adam.scala:19-73).
