@@ -173,6 +173,9 @@ SIGNATURES = {
     "dm_dr_train_free": (C.c_int, [C.c_void_p]),
     "dm_dr_train_forward_backward": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.POINTER(C.c_double)]),
     "dm_dr_train_forward_backward_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]),
+    "dm_dr_train_forward_backward_grouped": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
+    "dm_dr_train_forward_backward_grouped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
+    "dm_dr_layer_loss": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
     "dm_dr_adam_step": (C.c_int, [C.c_void_p, C.c_float]),
     "dm_dr_train_param_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "dm_dr_train_download": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

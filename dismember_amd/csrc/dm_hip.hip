@@ -1591,6 +1591,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "sampler.hip.inc"
 #include "dr_host.hip.inc"
 #include "dr_train.hip.inc"
+#include "dr_train_grouped.hip.inc"
 #include "dr_rerank_train.hip.inc"
 #include "dr_mstep.hip.inc"
 #include "dr_mstep_stream.hip.inc"

@@ -29,6 +29,13 @@ LocalOptimizer.trainLayerBatch does, exchanges the layer model's gradients (`Eng
     trainer = DRTrainer(engine, item_paths, lr=1e-3, comm=Comm.from_env())
     trainer.step(seqs, targets)                                  # the mean loss over the workers, the same on every rank
 
+The sample-grouped layer step takes every sample once with its J paths instead of the expanded batch: the same
+gradient re-associated, each history product computed once per sample (opt-in, also by DM_DR_TRAIN_GROUPED=1).  The evaluation losses:
+
+    trainer = DRTrainer(engine, item_paths, lr=1e-3, grouped=True)
+    trainer.evaluate_layer(eval_seqs, eval_targets)              # Evaluator.evaluateLayerModel: per-layer cross-entropy [D]
+    evaluation.evaluate_dr(engine, eval_seqs, labels, users, consumed, topk, beam, loss_fn=trainer.eval_loss_fn(eval_seqs, eval_targets))
+
 Both halves, served end to end:
 
     trainer = DRTrainer(engine, item_paths, lr=1e-3, rerank=True, num_sampled=20, seed=1)
@@ -37,6 +44,8 @@ Both halves, served end to end:
     print(trainer.evaluate_rerank(eval_seqs, eval_targets))      # Evaluator.evaluateReRankModel: the full softmax
     engine.dr_recommend(user_seqs, beam, topk)                   # reads the trained rerank arrays in place
 """
+import os
+
 import numpy as np
 
 
@@ -114,12 +123,17 @@ class DRTrainer:
     returns the mean of those ranks' losses (LocalOptimizer.scala:164-165).  The RERANK model is not split: as in the reference every
     step trains it on the whole batch, here on every rank with the same seed — deterministic step and sampler keep those replicas
     identical too, and this half does not get faster with more ranks.  All ranks must pass the same seed (ValueError otherwise).
-    sync_s / sync_calls: wall time spent in the exchange and the number of exchanges."""
+    sync_s / sync_calls: wall time spent in the exchange and the number of exchanges.
+
+    grouped (None: DM_DR_TRAIN_GROUPED=1 in the environment, otherwise False): the layer step takes every sample once with its J paths
+    (Engine.dr_train_forward_backward_grouped) instead of the batch expanded by np.repeat: the same gradient re-associated,
+    each history product computed once per sample.  Losses, the exchange and 1 / P are as in the row step."""
 
     def __init__(self, engine, item_paths, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8, rerank=False, num_sampled=None, seed=0,
-                 accumulate=True, rerank_epochs=None, comm=None):
+                 accumulate=True, rerank_epochs=None, comm=None, grouped=None):
         self.engine = engine
         self.comm = comm
+        self.grouped = os.environ.get("DM_DR_TRAIN_GROUPED") == "1" if grouped is None else bool(grouped)
         self.sync_s, self.sync_calls = 0.0, 0
         self.set_item_paths(item_paths)
         self.losses = []
@@ -152,8 +166,7 @@ class DRTrainer:
         """one batch: expand by the targets' paths, forward/backward, Adam -> per-layer losses [D]; with rerank=True the rerank step
         follows on the unexpanded batch -> (per-layer losses [D], sampled-softmax loss)"""
         if self.comm is None:
-            seq, paths = expand_batch(seqs, targets, self.item_paths)
-            loss = self.engine.dr_train_forward_backward(seq, paths)
+            loss = self._forward_backward(seqs, targets)
             self.engine.dr_adam_step(1.0)
         else:
             loss = self._layer_step_parallel(seqs, targets)
@@ -167,6 +180,13 @@ class DRTrainer:
         self.rerank_losses.append(rr)
         return loss, rr
 
+    def _forward_backward(self, seqs, targets):
+        """the layer model's forward/backward on (seqs, targets): grouped, every sample once with the [J, D] paths of its target; otherwise
+        the batch expanded to one row per path"""
+        if self.grouped:
+            return self.engine.dr_train_forward_backward_grouped(seqs, self.item_paths[np.asarray(targets, np.int64)])
+        return self.engine.dr_train_forward_backward(*expand_batch(seqs, targets, self.item_paths))
+
     def _layer_step_parallel(self, seqs, targets):
         """trainLayerBatch + syncGradients: this rank's slice, the exchange, Adam with 1 / P -> the mean loss of the P working ranks"""
         import time
@@ -177,8 +197,7 @@ class DRTrainer:
         lo, n = slices[self.comm.rank]
         loss = np.zeros(self.engine.dr_dims["D"], np.float64)
         if n > 0:                         # (a rank past P runs no step: it enters the exchange with no rows and a zero dense part)
-            seq, paths = expand_batch(seqs[lo:lo + n], targets[lo:lo + n], self.item_paths)
-            loss = self.engine.dr_train_forward_backward(seq, paths)
+            loss = self._forward_backward(seqs[lo:lo + n], targets[lo:lo + n])
         t0 = time.perf_counter()
         self.engine.dr_train_sync_gradients()
         self.sync_s += time.perf_counter() - t0; self.sync_calls += 1
@@ -203,6 +222,20 @@ class DRTrainer:
     def evaluate_rerank(self, seqs, targets):
         """Evaluator.evaluateReRankModel: the full-softmax loss of the rerank model on (seqs, targets)"""
         return self.engine.dr_rerank_full_loss(seqs, targets)
+
+    def evaluate_layer(self, seqs, targets):
+        """Evaluator.evaluateLayerModel: the per-layer cross-entropy [D] of (seqs, targets) under the current item -> paths mapping"""
+        return self.engine.dr_layer_loss(seqs, self.item_paths[np.asarray(targets, np.int64)])
+
+    def eval_loss_fn(self, eval_seqs, eval_targets):
+        """-> the loss_fn(off, n) evaluation.evaluate_dr takes: (layer losses [D], rerank loss) of eval samples [off, off + n); the rerank
+        loss is the full softmax's when the trainer trains the rerank model, otherwise 0"""
+        seqs, targets = np.asarray(eval_seqs), np.asarray(eval_targets)
+
+        def loss_fn(off, n):
+            s, t = seqs[off:off + n], targets[off:off + n]
+            return self.evaluate_layer(s, t).tolist(), (self.evaluate_rerank(s, t) if self.rerank else 0.0)
+        return loss_fn
 
     def rerank_weights(self):
         """the five rerank arrays as dr_load_model takes them"""

@@ -1020,6 +1020,36 @@ class Engine:
         self._chk(N.lib().dm_dr_train_forward_backward_dev(self._h, d_seq, d_paths, int(B), loss.ctypes.data_as(C.POINTER(C.c_double))))
         return loss
 
+    def _dr_grouped_args(self, seq_ids, paths):
+        d = self.dr_dims
+        seq = _i32(seq_ids).reshape(-1, d["L"])
+        pa = _i32(paths)
+        if pa.ndim != 3 or pa.shape[0] != len(seq) or pa.shape[2] != d["D"]:
+            raise ValueError("paths must be [S, J, D] with one entry per row of seq_ids")
+        return seq, pa, np.empty(d["D"], np.float64)
+
+    def dr_train_forward_backward_grouped(self, seq_ids, paths):
+        """seq_ids [S, L] internal ids (-1 = padding), paths [S, J, D] nodes: every sample once, with the J paths of its target item
+        (DESIGN.md §24).  The gradient of dr_train_forward_backward on the expanded batch (np.repeat(seq_ids, J), paths.reshape(-1, D)),
+        each history product computed once per sample; -> per-layer losses [D] (float64), the mean over the S J rows."""
+        seq, pa, loss = self._dr_grouped_args(seq_ids, paths)
+        self._chk(N.lib().dm_dr_train_forward_backward_grouped(self._h, _p(seq, N.i32p), _p(pa, N.i32p), len(seq), pa.shape[1],
+                                                               loss.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss
+
+    def dr_train_forward_backward_grouped_dev(self, d_seq, d_paths, S, J):
+        """the same on device arrays [S, L] and [S, J, D] (not range-checked) -> per-layer losses [D]"""
+        loss = np.empty(self.dr_dims["D"], np.float64)
+        self._chk(N.lib().dm_dr_train_forward_backward_grouped_dev(self._h, d_seq, d_paths, int(S), int(J), loss.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss
+
+    def dr_layer_loss(self, seq_ids, paths):
+        """Evaluator.evaluateLayerModel: the per-layer cross-entropy [D] of seq_ids [S, L] with paths [S, J, D], the mean over the S J
+        rows.  Forward only; needs no dr_train_init and leaves gradient and optimizer state alone."""
+        seq, pa, loss = self._dr_grouped_args(seq_ids, paths)
+        self._chk(N.lib().dm_dr_layer_loss(self._h, _p(seq, N.i32p), _p(pa, N.i32p), len(seq), pa.shape[1], loss.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss
+
     def dr_adam_step(self, grad_scale=1.0):
         self._chk(N.lib().dm_dr_adam_step(self._h, float(grad_scale)))
 

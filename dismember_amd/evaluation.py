@@ -221,9 +221,9 @@ def evaluate_dr(engine, sequences, labels, users, user_consumed, topk, beam_size
     stable over the same candidate order).  Ids are the model's internal item ids (MappingOp.itemIdMapping), as in the reference's
     data set.
 
-    The two loss columns (evaluateLayerModel :75-85, evaluateReRankModel :87-97) belong to Deep-Retrieval TRAINING, which is out
-    of scope here (config 5 is serving-only): `loss_fn(off, n) -> (layer_losses, rerank_loss)` supplies them when
-    a caller has the training-side modules, otherwise they are reported as 0 over `num_layer` layers."""
+    The two loss columns (evaluateLayerModel :75-85, evaluateReRankModel :87-97) come from `loss_fn(off, n) -> (layer_losses,
+    rerank_loss)`: `DRTrainer.eval_loss_fn(eval_seqs, eval_targets)` (dismember_amd/dr_train.py) computes both on the device
+    (Engine.dr_layer_loss, Engine.dr_rerank_full_loss).  Without a loss_fn they are reported as 0 over `num_layer` layers."""
     seqs = np.ascontiguousarray(sequences, np.int32)
     N = seqs.shape[0]
     total = None

@@ -776,6 +776,21 @@ int dm_dr_train_free(dm_handle_t h);                                /* the model
 int dm_dr_train_forward_backward(dm_handle_t h, const int32_t *seq_ids, const int32_t *paths, int64_t B, double *out_loss);
 /* the same on device arrays, NOT range-checked; out_loss is still a host pointer (the call synchronizes) */
 int dm_dr_train_forward_backward_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_paths, int64_t B, double *out_loss);
+/* The same step on a sample-grouped batch: S samples, seq_ids [S x L], each with J >= 1 paths, paths [S x J x D];
+ * row r = s J + j, R = S J, every mean over R.  The value of dm_dr_train_forward_backward on the expanded batch (each history repeated
+ * J times), re-associated: every history product runs once per sample instead of once per row.  Fixed summation order, no floating-point
+ * atomics; the handle is left as the row call leaves it, so dm_dr_adam_step and dm_dr_train_sync_gradients follow either.  Range-checks
+ * ids and nodes before anything is uploaded (DM_ERR_INDEX); S <= 0, J <= 0 or a null array DM_ERR_INVALID; DM_ERR_STATE before
+ * dm_dr_load_model / dm_dr_train_init and on a clone; S J > 4 194 240 or S L + S J (D - 1) >= 2^31 DM_ERR_UNSUPPORTED. */
+int dm_dr_train_forward_backward_grouped(dm_handle_t h, const int32_t *seq_ids, const int32_t *paths, int64_t S, int64_t J, double *out_loss);
+/* the same on device arrays, NOT range-checked; out_loss is still a host pointer (the call synchronizes) */
+int dm_dr_train_forward_backward_grouped_dev(dm_handle_t h, const int32_t *d_seq_ids, const int32_t *d_paths, int64_t S, int64_t J, double *out_loss);
+/* Evaluator.evaluateLayerModel (D/evaluation/Evaluator.scala): the per-layer cross-entropy out_loss [D] of the grouped batch, the mean
+ * over its S J rows; forward only, in chunks of samples (DM_DR_LAYER_LOSS_ROWS in the environment forces a chunk size), chunk sums added in
+ * chunk order.  Needs a loaded model and no training state; gradient, remembered rows and optimizer state are neither read nor written.
+ * Host arrays, range-checked (DM_ERR_INDEX); S <= 0, J <= 0 or a null argument DM_ERR_INVALID; J > 4 194 240 DM_ERR_UNSUPPORTED; a clone
+ * DM_ERR_STATE. */
+int dm_dr_layer_loss(dm_handle_t h, const int32_t *seq_ids, const int32_t *paths, int64_t S, int64_t J, double *out_loss);
 /* Adam.optimize (scalann/.../optim/Adam.scala:19-73) over the vector with dm_adam_step's kernels and rules (lr_decay, bias correction,
  * gradient scaled by grad_scale and zeroed): the embedding rows a gradient has ever reached plus the dense blocks, or the whole vector
  * when eps == 0, when a quarter of the rows is active or under DM_ADAM_DENSE=1 — the same bytes either way.  Marks the search's derived
