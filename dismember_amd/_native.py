@@ -201,6 +201,18 @@ SIGNATURES = {
                                                C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, i64p, C.c_void_p, C.c_void_p]),
     "dm_dr_mstep_optimize": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64,
                                        i64p]),
+    "dm_dr_set_item_paths": (C.c_int, [C.c_void_p, i32p, C.c_int]),
+    "dm_dr_path_items_size": (C.c_int, [C.c_void_p, i64p, i64p]),
+    "dm_dr_path_items_download": (C.c_int, [C.c_void_p, i64p, i64p, i32p]),
+    "dm_dr_item_paths_download": (C.c_int, [C.c_void_p, i32p, C.c_int64]),
+    "dm_dr_train_set_load": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64]),
+    "dm_dr_train_set_free": (C.c_int, [C.c_void_p]),
+    "dm_dr_train_set_size": (C.c_int, [C.c_void_p, i64p, i32p]),
+    "dm_dr_train_set_shuffle": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64]),
+    "dm_dr_train_set_order_download": (C.c_int, [C.c_void_p, i32p]),
+    "dm_dr_train_set_forward_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_double)]),
+    "dm_dr_train_set_rerank_forward_backward": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_double)]),
+    "dm_dr_train_set_mstep": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_uint64, i64p]),
     "dm_memcpy_d2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "dm_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "dm_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),

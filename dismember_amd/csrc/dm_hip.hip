@@ -1596,6 +1596,7 @@ int dm_tdm_bruteforce_topk(dm_handle_t h, const int32_t *seq_item_ids, int64_t U
 #include "dr_mstep.hip.inc"
 #include "dr_mstep_stream.hip.inc"
 #include "dr_mstep_assign.hip.inc"
+#include "dr_train_set.hip.inc"
 #include "otm64.hip.inc"
 #include "tdm_pipeline.hip.inc"
 #include "deepfm.hip.inc"

@@ -46,6 +46,13 @@ struct dm_dr_state {
   long long *d_codes = nullptr;
   int64_t *d_item_off = nullptr;
   int32_t *d_items = nullptr;
+  int64_t n_path_items = 0;                         // entries of d_items (dm_dr_path_items_size)
+  // the resident item -> paths table [num_item x J x D] and training set (dr_train_set.hip.inc): seq [N x L], targets [N], order [N]
+  int J = 0;
+  int32_t *d_item_paths = nullptr;
+  int64_t ts_N = 0;
+  int32_t *d_ts_seq = nullptr, *d_ts_tgt = nullptr, *d_ts_order = nullptr;
+  DevGrow ts_ws;                                    // the sorts of the CSR build and of the shuffle
   // scratch (grow only)
   DevGrow S, UV, io, cand;                          // io: seq ids + paths + probs + counts + outputs of one chunk
   DevGrow ms, ms_io;                                // the M-step's path scores (dr_mstep.hip.inc): every array of a call; the host entry's uploads
@@ -61,7 +68,8 @@ static void dm_dr_free(dm_dr_state *s) {
     for (auto &t : *v) dm_release(t);
   s->d_rr_emb = s->d_rr_w = s->d_rr_b = s->d_sm_w = s->d_sm_b = nullptr;
   dm_release(s->d_rr_par, s->d_sm_par, s->d_codes, s->d_item_off, s->d_items);
-  for (DevGrow *g : {&s->state, &s->S, &s->UV, &s->io, &s->cand, &s->ms, &s->ms_io}) g->release();
+  dm_release(s->d_item_paths, s->d_ts_seq, s->d_ts_tgt, s->d_ts_order);
+  for (DevGrow *g : {&s->state, &s->S, &s->UV, &s->io, &s->cand, &s->ms, &s->ms_io, &s->ts_ws}) g->release();
   delete s;
 }
 
@@ -300,7 +308,7 @@ int dm_dr_load_path_items(dm_handle_t h, const int32_t *path_nodes, int64_t n_pa
   HIPCHK(h, hipMemcpy(s->d_codes, codes.data(), (size_t)n_paths * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(s->d_item_off, off.data(), ((size_t)n_paths + 1) * 8, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(s->d_items, its.data(), (size_t)n_items * 4, hipMemcpyHostToDevice));
-  s->P = n_paths; s->max_bucket = (int)mb; s->paths_loaded = true;
+  s->P = n_paths; s->n_path_items = n_items; s->max_bucket = (int)mb; s->paths_loaded = true;
   return DM_OK;
 }
 

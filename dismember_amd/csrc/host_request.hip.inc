@@ -57,6 +57,9 @@ enum EvKind {
   // its greedy path assignment (dr_mstep_assign.hip.inc), under the same switch: dense path indices (sort, heads, ranks), validation + hit list,
   // the chain (one launch per iteration), random paths + the decode of the chosen positions.  (90 .. 93 were taken when these were added.)
   EV_DRA_INDEX = 94, EV_DRA_CHECK = 95, EV_DRA_CHAIN = 96, EV_DRA_RANDOM = 97,
+  // the resident mapping and training set (dr_train_set.hip.inc), under the same switch: the path -> items CSR built from the table (codes,
+  // sort, flags, compactions, offsets), the shuffle (keys + sort), the gather of one range of samples
+  EV_DTS_CSR = 98, EV_DTS_SHUFFLE = 99, EV_DTS_GATHER = 100,
   // the ragged user-grouped DIN training step under DM_TRAIN_TIME_LAUNCHES=1 (train_grouped_csr.hip.inc): per-user set-up, the rows kernel, the
   // per-user backward, the dense gradients (column sums, three products with their slab sums), the table gradient (pairs, sort, segment sums)
   EV_DTC_SETUP = 56, EV_DTC_ROWS = 57, EV_DTC_USER_BWD = 58, EV_DTC_DW = 59, EV_DTC_EMB = 68,

@@ -95,6 +95,14 @@ def init_rerank_weights(num_item, L, E, rng, dtype=np.float64):
                 softmax_w=n(num_item, E), softmax_b=np.zeros(num_item, dtype))
 
 
+def init_layer_weights(num_item, L, K, D, E, rng, dtype=np.float64):
+    """The layer model's arrays as LayerModel.scala:22-39 initialises them: the shared embedding table [(num_item + K (D - 1)) x E] and
+    every Linear weight [K x (L + d) E] N(0, 0.05) (scalann nn/EmbeddingShare.scala:21, nn/Linear.scala:12), the Linear biases zero
+    (Linear.scala:13).  rng: a numpy Generator."""
+    n = lambda *shape: (rng.standard_normal(shape) * 0.05).astype(dtype)
+    return dict(layer_emb=n(num_item + K * (D - 1), E), layer_w=[n(K, (L + d) * E) for d in range(D)], layer_b=[np.zeros(K, dtype) for _ in range(D)])
+
+
 def split_rerank(graph, softmax, E, L, num_item):
     """the two trainable vectors [rerank_emb ; rerank_w ; rerank_b] and [softmax_w ; softmax_b] -> the five arrays of dr_load_model"""
     a, b = num_item * E, num_item * E + E * L * E
@@ -130,9 +138,10 @@ class DRTrainer:
     each history product computed once per sample.  Losses, the exchange and 1 / P are as in the row step."""
 
     def __init__(self, engine, item_paths, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8, rerank=False, num_sampled=None, seed=0,
-                 accumulate=True, rerank_epochs=None, comm=None, grouped=None):
+                 accumulate=True, rerank_epochs=None, comm=None, grouped=None, resident=False):
         self.engine = engine
         self.comm = comm
+        self.resident = bool(resident)
         self.grouped = os.environ.get("DM_DR_TRAIN_GROUPED") == "1" if grouped is None else bool(grouped)
         self.sync_s, self.sync_calls = 0.0, 0
         self.set_item_paths(item_paths)
@@ -161,21 +170,66 @@ class DRTrainer:
         if p.ndim != 3 or p.shape[0] != d["num_item"] or p.shape[2] != d["D"]:
             raise ValueError("item_paths must be [num_item, J, D]")
         self.item_paths = p
+        if self.resident:
+            self.engine.dr_set_item_paths(p)
+
+    def load_set(self, seqs, targets):
+        """resident=True: the training set goes to the device once (Engine.dr_train_set_load); step_range() trains on ranges of it"""
+        self._need_resident("load_set")
+        self.engine.dr_train_set_load(seqs, targets)
+        self.set_size = len(np.asarray(targets).reshape(-1))
+
+    def shuffle(self, seed):
+        """the order of the trainer's current epoch (Engine.dr_train_set_shuffle(seed, epoch))"""
+        self._need_resident("shuffle")
+        self.engine.dr_train_set_shuffle(seed, self.epoch)
+
+    def _need_resident(self, what):
+        if not self.resident:
+            raise ValueError("DRTrainer.%s needs resident=True" % what)
+
+    def step_range(self, offset, length):
+        """step() on samples order[offset : offset + length] of the resident set: nothing but the range goes to the device.  With a
+        communicator the range is sliced by layer_slices, exchanged and stepped with 1 / P as step() does with its batch."""
+        self._need_resident("step_range")
+        return self._step(length, lambda lo, n: self.engine.dr_train_set_forward_backward(offset + lo, n, grouped=self.grouped),
+                          lambda: self.engine.dr_train_set_rerank_forward_backward(offset, length), "step_range")
 
     def step(self, seqs, targets):
         """one batch: expand by the targets' paths, forward/backward, Adam -> per-layer losses [D]; with rerank=True the rerank step
         follows on the unexpanded batch -> (per-layer losses [D], sampled-softmax loss)"""
+        if self.comm is not None:
+            seqs, targets = np.asarray(seqs), np.asarray(targets)
+        return self._step(len(targets), lambda lo, n: self._forward_backward(seqs[lo:lo + n], targets[lo:lo + n]),
+                          lambda: self.engine.dr_rerank_forward_backward(seqs, targets), "step")
+
+    def _step(self, B, layer_fb, rerank_fb, who):
+        """what step() and step_range() share.  layer_fb(lo, n): the layer model's forward/backward on samples [lo, lo + n) of the B
+        of this step; rerank_fb(): the rerank model's on all of them.  One worker: the whole batch and Adam.  With a communicator,
+        trainLayerBatch + syncGradients: this rank's slice, the exchange, Adam with 1 / P -> the mean loss of the P working ranks."""
         if self.comm is None:
-            loss = self._forward_backward(seqs, targets)
+            loss = layer_fb(0, B)
             self.engine.dr_adam_step(1.0)
         else:
-            loss = self._layer_step_parallel(seqs, targets)
+            import time
+            slices, P = layer_slices(B, self.comm.world)
+            if P == 0:
+                raise ValueError("DRTrainer.%s: empty batch" % who)
+            lo, n = slices[self.comm.rank]
+            loss = np.zeros(self.engine.dr_dims["D"], np.float64)
+            if n > 0:                     # (a rank past P runs no step: it enters the exchange with no rows and a zero dense part)
+                loss = layer_fb(lo, n)
+            t0 = time.perf_counter()
+            self.engine.dr_train_sync_gradients()
+            self.sync_s += time.perf_counter() - t0; self.sync_calls += 1
+            self.engine.dr_adam_step(1.0 / P)
+            loss = self.comm.allreduce(loss) / P
         self.losses.append(loss)
         if not self.rerank:
             return loss
         rr = float("nan")
         if self.rerank_epochs is None or self.epoch <= self.rerank_epochs:
-            rr = self.engine.dr_rerank_forward_backward(seqs, targets)
+            rr = rerank_fb()
             self.engine.dr_rerank_adam_step(1.0)
         self.rerank_losses.append(rr)
         return loss, rr
@@ -187,33 +241,38 @@ class DRTrainer:
             return self.engine.dr_train_forward_backward_grouped(seqs, self.item_paths[np.asarray(targets, np.int64)])
         return self.engine.dr_train_forward_backward(*expand_batch(seqs, targets, self.item_paths))
 
-    def _layer_step_parallel(self, seqs, targets):
-        """trainLayerBatch + syncGradients: this rank's slice, the exchange, Adam with 1 / P -> the mean loss of the P working ranks"""
-        import time
-        seqs, targets = np.asarray(seqs), np.asarray(targets)
-        slices, P = layer_slices(len(targets), self.comm.world)
-        if P == 0:
-            raise ValueError("DRTrainer.step: empty batch")
-        lo, n = slices[self.comm.rank]
-        loss = np.zeros(self.engine.dr_dims["D"], np.float64)
-        if n > 0:                         # (a rank past P runs no step: it enters the exchange with no rows and a zero dense part)
-            loss = self._forward_backward(seqs[lo:lo + n], targets[lo:lo + n])
-        t0 = time.perf_counter()
-        self.engine.dr_train_sync_gradients()
-        self.sync_s += time.perf_counter() - t0; self.sync_calls += 1
-        self.engine.dr_adam_step(1.0 / P)
-        return self.comm.allreduce(loss) / P
-
     def mstep(self, seqs, targets, num_candidate_path, num_iteration=3, assign="host", **kw):
         """the M-step of one E/M round: dr_mstep.optimize over every item with the trained weights (the number of paths per item stays),
         and the new mapping becomes the trainer's.  assign="device" runs the greedy assignment on the device as well (DESIGN.md §23);
         kw: optimize's other arguments (train_mode, path_scores, decay_factor, seed, penalty_factor, penalty_poly_order).
-        -> the new item_paths [num_item, J, D]"""
+        -> the new item_paths [num_item, J, D]
+
+        resident=True: Engine.dr_train_set_mstep over the RESIDENT set in storage order, both halves on the device.  seqs and targets
+        must then be None (the set is the one load_set uploaded), assign is not looked at, and kw may hold train_mode, decay_factor,
+        seed, penalty_factor and penalty_poly_order only (path_scores has no meaning there): anything else is a ValueError."""
         from dismember_amd import dr_mstep
         d = self.engine.dr_dims
+        if self.resident:
+            if seqs is not None or targets is not None:
+                raise ValueError("DRTrainer.mstep with resident=True runs over the set load_set uploaded: pass seqs=None, targets=None")
+            extra = set(kw) - {"train_mode", "decay_factor", "seed", "penalty_factor", "penalty_poly_order"}
+            if extra:
+                raise ValueError("DRTrainer.mstep with resident=True does not take %s" % ", ".join(sorted(extra)))
+            return self._mstep_resident(num_candidate_path, num_iteration, **kw)
         m = dr_mstep.optimize(self.engine, seqs, targets, range(d["num_item"]), num_candidate_path, self.item_paths.shape[1], num_iteration,
                               assign=assign, **kw)
         self.set_item_paths(np.array([m[i] for i in range(d["num_item"])], np.int32))
+        return self.item_paths
+
+    def _mstep_resident(self, num_candidate_path, num_iteration, train_mode="batch", decay_factor=0.999, penalty_factor=3e-6, penalty_poly_order=4, seed=0):
+        """Engine.dr_train_set_mstep over the resident set (storage order): table and CSR follow on the device, the host copy from its codes"""
+        d = self.engine.dr_dims
+        codes = self.engine.dr_train_set_mstep(num_candidate_path, num_iteration, train_mode, decay_factor, penalty_factor, penalty_poly_order, seed)
+        p = np.empty(codes.shape + (d["D"],), np.int32)
+        for k in range(d["D"] - 1, -1, -1):
+            p[..., k] = codes % d["K"]
+            codes = codes // d["K"]
+        self.item_paths = p
         return self.item_paths
 
     def next_epoch(self):

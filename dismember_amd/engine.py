@@ -994,6 +994,80 @@ class Engine:
                                                int(seed), _p(out, N.i64p)))
         return out
 
+    # ---- Deep-Retrieval: the mapping and the training set resident on the device
+    def dr_set_item_paths(self, item_paths):
+        """item_paths [num_item, J, D] nodes: the table stays on the device and the path -> items CSR is built from it there - what
+        dr_load_path_items(*synth.dr_path_items(item_paths)) leaves behind, without the host inversion"""
+        d = self.dr_dims
+        p = _i32(item_paths)
+        if p.ndim != 3 or p.shape[0] != d["num_item"] or p.shape[2] != d["D"]:
+            raise ValueError("item_paths must be [num_item, J, D]")
+        self._chk(N.lib().dm_dr_set_item_paths(self._h, _p(p, N.i32p), p.shape[1]))
+
+    def dr_train_set_size(self):
+        """-> (samples of the resident set, paths per item of the resident table), 0 for what the handle does not hold: the extents of
+        the downloads below, asked of the library rather than remembered here"""
+        n, j = C.c_int64(0), C.c_int32(0)
+        self._chk(N.lib().dm_dr_train_set_size(self._h, C.byref(n), C.byref(j)))
+        return int(n.value), int(j.value)
+
+    def dr_path_items_download(self):
+        """the path -> items CSR after either loader -> (codes [P] int64 ascending, item_off [P + 1] int64, items [n] int32)"""
+        n_paths, n_items = C.c_int64(0), C.c_int64(0)
+        self._chk(N.lib().dm_dr_path_items_size(self._h, C.byref(n_paths), C.byref(n_items)))
+        codes, off, items = np.empty(n_paths.value, np.int64), np.empty(n_paths.value + 1, np.int64), np.empty(n_items.value, np.int32)
+        self._chk(N.lib().dm_dr_path_items_download(self._h, _p(codes, N.i64p), _p(off, N.i64p), _p(items, N.i32p)))
+        return codes, off, items
+
+    def dr_item_paths_download(self):
+        """the resident item -> paths table [num_item, J, D]"""
+        d = self.dr_dims
+        out = np.empty((d["num_item"], max(self.dr_train_set_size()[1], 1), d["D"]), np.int32)      # (no table: one row, and the library refuses)
+        self._chk(N.lib().dm_dr_item_paths_download(self._h, _p(out, N.i32p), out.size))
+        return out
+
+    def dr_train_set_load(self, seqs, targets):
+        """seqs [N, L] internal ids (-1 = padding), targets [N]: uploaded once; the order is the identity until dr_train_set_shuffle"""
+        seq = _i32(seqs).reshape(-1, self.dr_dims["L"])
+        tg = _i32(targets).reshape(-1)
+        assert len(seq) == len(tg)
+        self._chk(N.lib().dm_dr_train_set_load(self._h, _p(seq, N.i32p), _p(tg, N.i32p), len(tg)))
+
+    def dr_train_set_free(self):
+        self._chk(N.lib().dm_dr_train_set_free(self._h))
+
+    def dr_train_set_shuffle(self, seed, epoch):
+        """the order of an epoch: sample indices sorted (stable) by splitmix(splitmix(seed ^ splitmix(epoch)) + i)"""
+        self._chk(N.lib().dm_dr_train_set_shuffle(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch)))
+
+    def dr_train_set_order(self):
+        out = np.empty(max(self.dr_train_set_size()[0], 1), np.int32)                              # (no set: the library refuses)
+        self._chk(N.lib().dm_dr_train_set_order_download(self._h, _p(out, N.i32p)))
+        return out
+
+    def dr_train_set_forward_backward(self, offset, length, grouped=False):
+        """the layer step (grouped: the sample-grouped one) on samples order[offset : offset + length] of the resident set, gathered on
+        the device with their targets' paths -> per-layer losses [D]; dr_adam_step / dr_train_sync_gradients follow"""
+        loss = np.empty(self.dr_dims["D"], np.float64)
+        self._chk(N.lib().dm_dr_train_set_forward_backward(self._h, int(offset), int(length), int(bool(grouped)), loss.ctypes.data_as(C.POINTER(C.c_double))))
+        return loss
+
+    def dr_train_set_rerank_forward_backward(self, offset, length):
+        """the rerank step on the same range, negatives drawn on the device -> the sampled-softmax loss"""
+        loss = C.c_double(0.0)
+        self._chk(N.lib().dm_dr_train_set_rerank_forward_backward(self._h, int(offset), int(length), C.byref(loss)))
+        return float(loss.value)
+
+    def dr_train_set_mstep(self, num_candidate_path, num_iteration=3, train_mode="batch", decay_factor=0.999, penalty_factor=3e-6, penalty_poly_order=4, seed=0):
+        """dr_mstep_optimize over the resident set in storage order, J the resident table's; the table and the CSR follow the new codes
+        on the device -> out_codes [num_item, J] int64"""
+        if train_mode not in ("batch", "streaming"):
+            raise ValueError(train_mode)
+        out = np.empty((self.dr_dims["num_item"], self.dr_train_set_size()[1]), np.int64)
+        self._chk(N.lib().dm_dr_train_set_mstep(self._h, int(num_candidate_path), int(train_mode == "streaming"), float(decay_factor), int(num_iteration),
+                                                float(penalty_factor), int(penalty_poly_order), int(seed), _p(out, N.i64p)))
+        return out
+
     # ---- Deep-Retrieval E-step: the layer model's training step (DESIGN.md §10)
     def dr_train_init(self, lr=1e-3, lr_decay=0.0, beta1=0.9, beta2=0.999, eps=1e-8):
         o = N.AdamOpts(lr, lr_decay, beta1, beta2, eps)

@@ -4,6 +4,7 @@
     python -m dismember_amd.tasks TDMTrainDeepModel --tdmConfFile configs/c1_tdm_movielens.conf [--quiet]
     python -m dismember_amd.tasks JTMTreeLearning   --jtmConfFile <file>
     python -m dismember_amd.tasks OTMTrainDeepModel --otmConfFile <file>     (then OTMConstructTree on the same file)
+    python -m dismember_amd.tasks DRTrainDeepModel  --drConfFile <file>      (then DRCoordinateDescent on the same file)
 
 Each function is the body of the reference's `CommandApp` of the same name (examples/src/main/scala/com/mass/retrieval/):
 the conf file is read by dismember_amd.conf (same keys, same defaults, same "failed to find <key>" stop), the steps are the
@@ -20,6 +21,9 @@ carried over: Java serialisation (the model file is `dm_save_model`'s flat check
   jtm_tree_learning     jtm/JTMTreeLearning.scala:17-48    -> JTM.optimize (jtm/.../optim/JTM.scala:26-73), TreeUtil.writeTree
   otm_train_deep_model  otm/OTMTrainDeepModel.scala:20-75  -> LocalDataSet (dismember_amd/otm_data.py), LocalOptimizer.optimize, OTM.saveModel
   otm_construct_tree    otm/OTMConstructTree.scala:17-45   -> TreeConstruction.run, Serialization.saveMapping
+  dr_train_deep_model   dr/DRTrainDeepModel.scala:20-85    -> LocalDataSet (dismember_amd/dr_data.py), LocalOptimizer.optimize over the resident
+                        training set, the model file (dismember_amd/dr_io.py: this project's own format)
+  dr_coordinate_descent dr/DRCoordinateDescent.scala:20-63 -> CoordinateDescent.optimize (Engine.dr_train_set_mstep), MappingOp.writeMapping
 """
 import os
 import sys
@@ -355,6 +359,139 @@ def otm_construct_tree(conf_path, quiet=True, engine=None, deepfm=False):
     return dict(mapping=result, old_mapping=mapping, seconds=dt, params=p, engine=eng)
 
 
+def _dr_dataset(p, task, seed):
+    """LocalDataSet of the two Deep-Retrieval tasks (dismember_amd/dr_data.py)"""
+    from .dr_data import DRDataSet
+    if p["data_path"] == "synthetic":
+        raise ValueError("%s: data_path synthetic is a bench-only config (configs/c5_dr_10m.conf is measured by bench.py and tools/dr_*_bench.py); "
+                         "there is no synthetic generator behind the conf task" % task)
+    sample = _read_interactions(p["data_path"])
+    return DRDataSet(sample, p["num_layer"], p["num_node"], p["num_path_per_item"], p["train_batch_size"], p["eval_batch_size"], p["seq_len"],
+                     p["min_seq_len"], p["split_ratio"], initialize_mapping=p["initialize_mapping"], mapping_path=p["mapping_path"],
+                     rng=np.random.default_rng(seed))
+
+
+def dr_train_deep_model(conf_path, quiet=True, engine=None, seed=2024, max_iterations=None, time_recommend=True, resident=True):
+    """DRTrainDeepModel (examples/.../dr/DRTrainDeepModel.scala:20-85): LocalDataSet, LayerModel + RerankModel in fp64 (the reference's
+    type), LocalOptimizer.optimize (deep-retrieval/.../optim/LocalOptimizer.scala:58-133: per epoch a shuffle and batches of
+    max(1, train_batch_size / num_path_per_item) targets, both models on every batch; the evaluator every show_progress_interval
+    iterations and at each epoch's end), the model file (dr_io.save_model: this project's own format), the timed recommend call.
+    resident=True keeps the training set and the item -> paths table on the device; False feeds host batches.
+    Like the reference's task it writes no mapping file: the result carries item_id_map and item_paths.
+    -> dict(losses [(layer losses, rerank loss)], eval [(epoch, iteration, DrEvalResult)], recommendation, item_id_map, item_paths, params)"""
+    from . import dr_io, synth
+    from .dr_train import DRTrainer, init_layer_weights, init_rerank_weights
+    from .engine import Engine
+    from .facade import DeepRetrieval
+    p = C.task_params("DRTrainDeepModel", conf_path)
+    if not quiet:
+        print("\n".join("%s: %s" % kv for kv in sorted(p.items())))
+    ds = _dr_dataset(p, "DRTrainDeepModel", seed)
+    L, E, K, D, ni = p["seq_len"], p["embed_size"], p["num_node"], p["num_layer"], ds.num_item
+    rng = np.random.default_rng(seed + 1)
+    w = init_layer_weights(ni, L, K, D, E, rng, np.float64)
+    w.update(init_rerank_weights(ni, L, E, rng, np.float64))
+    eng = engine or Engine(0)
+    eng.dr_load_model(w, E, L, K, D, ni, dtype=np.float64)
+    tr = DRTrainer(eng, ds.item_paths, lr=p["learning_rate"], rerank=True, num_sampled=p["num_sampled"], seed=seed, resident=resident)
+    N, T = ds.train_size, ds.num_targets_per_batch
+    if N < 1:
+        raise ValueError("DRTrainDeepModel: the data set has no training sample")
+    if resident:
+        tr.load_set(ds.train_seqs, ds.train_targets)
+    else:
+        eng.dr_load_path_items(*synth.dr_path_items_fast(ds.item_paths, K))
+    loss_fn = tr.eval_loss_fn(ds.eval_seqs, ds.eval_targets)
+    interval = p["show_progress_interval"]
+    n_batch = (N + T - 1) // T
+    losses, evals, done = [], [], 0
+    for epoch in range(1, p["epoch_num"] + 1):
+        if resident:
+            tr.shuffle(seed)
+        else:
+            order = np.random.default_rng([seed, epoch]).permutation(N)
+        for it in range(1, n_batch + 1):
+            off, n = (it - 1) * T, min(T, N - (it - 1) * T)
+            t0 = time.perf_counter()
+            if resident:
+                layer, rr = tr.step_range(off, n)
+            else:
+                layer, rr = tr.step(ds.train_seqs[order[off:off + n]], ds.train_targets[order[off:off + n]])
+            dt = time.perf_counter() - t0
+            losses.append(([float(x) for x in layer], float(rr)))
+            done += 1
+            if (it == n_batch or (interval > 0 and it % interval == 0)) and len(ds.eval_seqs):
+                res = ev.evaluate_dr(eng, ds.eval_seqs, ds.eval_labels, ds.eval_users, ds.user_consumed, p["topk_number"], p["beam_size"],
+                                     batch_size=ds.num_eval_targets_per_batch, loss_fn=loss_fn)
+                evals.append((epoch, it, res))
+                if not quiet:
+                    print("Epoch %d Iteration %d/%d Train time %.4fs layer loss %s rerank loss %.4f\n\t%s" % (epoch, it, n_batch, dt, losses[-1][0], rr, res))
+            if max_iterations is not None and done >= max_iterations:
+                break
+        tr.next_epoch()
+        if max_iterations is not None and done >= max_iterations:
+            break
+    _mkdir_for(p["model_path"])
+    dr_io.save_model(p["model_path"], eng)
+    dr = DeepRetrieval(eng, ds.item_id_map)
+    query = [0, 0, 2126, 204, 3257, 3439, 996, 1681, 3438, 1882]
+    query = query[-L:] if L <= 10 else [0] * (L - 10) + query
+    out = dict(losses=losses, eval=evals, params=p, engine=eng, item_id_map=ds.item_id_map, item_paths=tr.item_paths, n_train=N, n_eval=len(ds.eval_seqs))
+    out["recommendation"] = dr.recommend(query, 3, 20)
+    if not quiet:
+        print("Recommendation result: %s" % (out["recommendation"],))
+    if time_recommend:                                                 # dr/package.scala:102-112
+        for _ in range(10):
+            dr.recommend(query, 10, 20)
+        t0 = time.perf_counter()
+        for _ in range(100):
+            dr.recommend(query, 10, 20)
+        out["recommend_ms"] = (time.perf_counter() - t0) * 10
+        if not quiet:
+            print("Average recommend time: %.4fms" % out["recommend_ms"])
+    return out
+
+
+def dr_coordinate_descent(conf_path, quiet=True, engine=None, seed=2024):
+    """DRCoordinateDescent (examples/.../dr/DRCoordinateDescent.scala:20-63): LocalDataSet, the model file of DRTrainDeepModel,
+    CoordinateDescent.optimize in the conf's train_mode over the training set resident on the device (Engine.dr_train_set_mstep), and
+    the mapping file (MappingOp.writeMapping) at mapping_path.  -> dict(item_paths [num_item, J, D], item_id_map, seconds, params)"""
+    from . import dr_io
+    from .engine import DismemberError, Engine
+    p = C.task_params("DRCoordinateDescent", conf_path)
+    if p["train_mode"] not in ("batch", "streaming"):
+        raise ValueError("train_mode must be batch or streaming")
+    if not quiet:
+        print("\n".join("%s: %s" % kv for kv in sorted(p.items())))
+    ds = _dr_dataset(p, "DRCoordinateDescent", seed)
+    eng = engine or Engine(0)
+    d = dr_io.load_model(eng, p["model_path"])
+    if (d["L"], d["K"], d["D"], d["num_item"]) != (p["seq_len"], p["num_node"], p["num_layer"], ds.num_item):
+        raise ValueError("DRCoordinateDescent: %s holds a model of other sizes than the conf and the data set give" % p["model_path"])
+    eng.dr_set_item_paths(ds.item_paths)
+    eng.dr_train_set_load(ds.train_seqs, ds.train_targets)
+    t0 = time.perf_counter()
+    try:
+        eng.dr_train_set_mstep(p["candidate_path_num"], p["iteration_num"], p["train_mode"], p["decay_factor"], p["penalty_factor"], p["penalty_poly_order"], seed)
+    except DismemberError as e:
+        if "log1p" not in str(e):
+            raise
+        # CoordinateDescent.scala:76 accumulates the GAIN, penalty included: once a crowded path's penalty takes it to -1 or below the
+        # reference goes on with a NaN; the library refuses (DESIGN.md section 23), and the user can act on it
+        raise ValueError("DRCoordinateDescent: %s.  The penalty of the paths this item can take outweighs its scores (penalty_factor %g, "
+                         "penalty_poly_order %d, train_mode %s): lower cd.penalty_factor or cd.penalty_poly_order, set cd.train_mode streaming, "
+                         "or train the model further (known limitation: DESIGN.md section 25)" % (e, p["penalty_factor"], p["penalty_poly_order"], p["train_mode"]))
+    dt = time.perf_counter() - t0
+    if not quiet:
+        print("coordinate descent time: %.4fs" % dt)
+    paths = eng.dr_item_paths_download()
+    eng.dr_train_set_free()
+    items = sorted(ds.item_id_map, key=ds.item_id_map.get)
+    _mkdir_for(p["mapping_path"])
+    dr_io.write_mapping(p["mapping_path"], items, [ds.item_id_map[i] for i in items], paths)
+    return dict(item_paths=paths, item_id_map=ds.item_id_map, seconds=dt, params=p, engine=eng)
+
+
 from .cluster import tdm_cluster_tree  # noqa: E402,F401  (reachable as tasks.tdm_cluster_tree; not in TASK_FUNCS: see README.md)
 
 
@@ -368,6 +505,7 @@ TASK_FUNCS = {
     "TDMTrainDeepModel": tdm_train_deep_model, "JTMTrainDeepModel": tdm_train_deep_model,
     "JTMTreeLearning": jtm_tree_learning,
     "OTMTrainDeepModel": otm_train_deep_model, "OTMConstructTree": _otm_construct_tree_cli,
+    "DRTrainDeepModel": dr_train_deep_model, "DRCoordinateDescent": dr_coordinate_descent,
 }
 
 

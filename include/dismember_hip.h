@@ -685,6 +685,48 @@ int dm_dr_mstep_optimize(dm_handle_t h, const int32_t *seq_ids, const int32_t *t
                          double decay_factor, int num_path_per_item, int num_iteration, double penalty_factor, int penalty_poly_order,
                          uint64_t seed, int64_t *out_codes);
 
+/* ---- Deep-Retrieval: the mapping and the training set resident on the device ----
+ * All of it is state of the loaded model: dm_dr_load_model drops it, every entry point below is refused on a clone and without a model
+ * (DM_ERR_STATE), and every refusal leaves the handle usable and allocates nothing.
+ *
+ * MappingOp.itemPathMapping: item_paths [num_item x J x D] nodes (host).  The table stays on the device, and the path -> items CSR is built
+ * from it there (no host sort): exactly what dm_dr_load_path_items leaves behind for the host inversion of the same table - distinct path
+ * codes sum_d node_d K^(D-1-d) ascending, the items of a path in ascending id, an item that lists one path twice counted once.  A node
+ * outside [0, num_node): DM_ERR_INDEX; J < 1 or a null array: DM_ERR_INVALID; num_item J >= 2^31 or num_node^num_layer >= 2^62: DM_ERR_UNSUPPORTED. */
+int dm_dr_set_item_paths(dm_handle_t h, const int32_t *item_paths, int J);
+/* the CSR after either loader: sizes, then codes [n_paths], item_off [n_paths + 1], items [n_items] (host).  DM_ERR_STATE before a loader. */
+int dm_dr_path_items_size(dm_handle_t h, int64_t *n_paths, int64_t *n_items);
+int dm_dr_path_items_download(dm_handle_t h, int64_t *codes, int64_t *item_off, int32_t *items);
+/* the resident table [num_item x J x D]; n must be that product (DM_ERR_INVALID); DM_ERR_STATE before dm_dr_set_item_paths */
+int dm_dr_item_paths_download(dm_handle_t h, int32_t *out, int64_t n);
+/* the training set: seq_ids [N x L] internal ids (-1 = padding), targets [N]; uploaded once, the order set to the identity.  An id outside
+ * [-1, num_item) or a target outside [0, num_item): DM_ERR_INDEX; N < 1 or a null array: DM_ERR_INVALID; N >= 2^31: DM_ERR_UNSUPPORTED. */
+int dm_dr_train_set_load(dm_handle_t h, const int32_t *seq_ids, const int32_t *targets, int64_t N);
+int dm_dr_train_set_free(dm_handle_t h);                            /* the model, the mapping and the training state stay */
+/* what the handle holds: the samples of the resident set (0: none) and the paths per item of the resident table (0: none) - the extents of
+ * dm_dr_train_set_order_download's out [N], dm_dr_item_paths_download's n and dm_dr_train_set_mstep's out_codes [num_item x J] */
+int dm_dr_train_set_size(dm_handle_t h, int64_t *n_samples, int32_t *n_paths_per_item);
+/* The order of an epoch: the sample indices sorted (stable) ascending by the 64-bit key splitmix(splitmix(seed ^ splitmix(epoch)) + i).
+ * LocalDataSet.scala shuffles with an unseeded Random, so this stream is the library's own, as the rerank sampler's is.  DM_ERR_STATE
+ * without a set. */
+int dm_dr_train_set_shuffle(dm_handle_t h, uint64_t seed, int64_t epoch);
+int dm_dr_train_set_order_download(dm_handle_t h, int32_t *out);   /* out [N] */
+/* One layer step on the samples order[offset .. offset + length): their histories and the [J x D] paths of their targets are gathered on
+ * the device, then dm_dr_train_forward_backward_grouped_dev (grouped != 0) or dm_dr_train_forward_backward_dev on the expanded batch of
+ * transformLayerData (grouped == 0) runs as it is; out_loss [D] (host, or NULL).  No Adam step and no exchange: dm_dr_adam_step and
+ * dm_dr_train_sync_gradients follow as after the host-batch calls.  DM_ERR_STATE without a set, a mapping or dm_dr_train_init;
+ * length < 1 or a range outside [0, N]: DM_ERR_INVALID; the row limits of the step it runs: DM_ERR_UNSUPPORTED. */
+int dm_dr_train_set_forward_backward(dm_handle_t h, int64_t offset, int64_t length, int grouped, double *out_loss);
+/* the rerank step on the same range: dm_dr_rerank_forward_backward_dev with the negatives drawn on the device.  DM_ERR_STATE without a set
+ * or dm_dr_rerank_train_init; the range as above; that step's row limits and 2 num_sampled > num_item: DM_ERR_UNSUPPORTED. */
+int dm_dr_train_set_rerank_forward_backward(dm_handle_t h, int64_t offset, int64_t length, double *out_loss);
+/* dm_dr_mstep_optimize over the resident set, always in STORAGE order (the streaming fold depends on the order of the samples; a shuffle
+ * does not change the result); the number of paths per item is the resident table's.  The new codes are decoded on the device into the
+ * table and the CSR is rebuilt from it; out_codes [num_item x J] (host) may be NULL.  DM_ERR_STATE without a set or a mapping; every other
+ * check of dm_dr_mstep_optimize holds. */
+int dm_dr_train_set_mstep(dm_handle_t h, int num_candidate_path, int mode, double decay_factor, int num_iteration, double penalty_factor,
+                          int penalty_poly_order, uint64_t seed, int64_t *out_codes);
+
 /* ---- DeepFM: one training step on the device ----
  * LocalOptimizer.trainBatch with the DeepFM graph (T/optim/LocalOptimizer.scala:139-162, useMask = false; T/model/DeepFM.scala:11-45;
  * S/nn/FM.scala:24-71, S/nn/Linear.scala, S/nn/BCECriterionWithLogits.scala:27-64 averaged over the batch; S/optim/Adam.scala:19-73).

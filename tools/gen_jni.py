@@ -143,6 +143,11 @@ EXTENTS = {
     "dm_dr_rerank_sample": {"targets": "B"},
     "dm_dr_rerank_download": {"out": "n"},
     "dm_dr_rerank_full_loss": {"targets": "B", "out": "1"},
+    "dm_dr_path_items_size": {"n_paths": "1", "n_items": "1"},
+    "dm_dr_item_paths_download": {"out": "n"},
+    "dm_dr_train_set_load": {"targets": "N"},
+    "dm_dr_train_set_size": {"n_samples": "1", "n_paths_per_item": "1"},
+    "dm_dr_train_set_rerank_forward_backward": {"out_loss": "1"},
     "dm_allreduce_grads": {"hs": "n"},
     "dm_cluster_tree": {"emb": "n * E", "codes_out": "n", "stats": "8"},
     "dm_cluster_tree_model": {"item_ids": "n", "codes_out": "n", "stats": "8"},
